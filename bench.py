@@ -15,6 +15,12 @@ N > 1    : image tiles (64x64) are sharded round-robin over the ranks (weak in n
            every rank holds a full scene replica; ONE RCCL reduce of the PixelData framebuffer to rank 0 closes the timed
            region (tiles are disjoint up to film-edge jitter, so the sum is the gather).
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+--full        : also the figures that take runs of their own: the untimed GPU counting batch (visits per ray, lane utilisation), the
+                roofline blocks built on it and the committed counter profile, and the CPU baseline (unless --no-cpu-baseline).
+--dump-outputs DIR : after the timed steps rank 0 writes what the timed path computed, DIR/pixel_data.npy (float32 (h, w, 7):
+                rgb, rgbSplat, weightSum of the frame), or a fixed seeded sample of its pixels when the frame exceeds 64 MB.
 """
 import argparse
 import json
@@ -291,7 +297,9 @@ def main():
     ap.add_argument("--instances", type=int, default=2000)
     ap.add_argument("--subdiv", type=int, default=4)
     ap.add_argument("--hard-scale", default="full", choices=["full", "small"], help="synthetic-sm-hard: 8.4 M (full) or 0.5 M (small) terrain triangles")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--full", action="store_true", help="also the counting batch, the roofline blocks and the CPU baseline (runs of their own, outside the timed region)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 writes the frame of the timed path as DIR/pixel_data.npy (float32; a seeded pixel sample above 64 MB)")
     ap.add_argument("--scene", default=None, metavar="FILE.xml", help="render a Mitsuba-0.5 scene file (ParseMitsubaScene) instead of a built-in workload")
     ap.add_argument("--via-loader", action="store_true", help="write the synthetic workload as a Mitsuba scene and load it through ctl_parse_mitsuba_scene")
     ap.add_argument("--tracer-param", action="append", default=[], metavar="KEY=VALUE")
@@ -329,7 +337,7 @@ def main():
         import torch.distributed as dist
         if share_gpu:
             local_rank = 0
-        if torch.cuda.is_available():
+        if torch.cuda.is_available() and not args.launch_only:     # --launch-only runs without a device, also on a box that has fewer than N
             torch.cuda.set_device(local_rank)   # torch.cuda.synchronize() in sync() then waits on this rank's own GPU instead of opening a context on device 0
         dist.init_process_group(backend="gloo")
         if args.launch_only:
@@ -482,9 +490,13 @@ def main():
         r = torch.tensor([rays], dtype=torch.float64); dist.all_reduce(r, op=dist.ReduceOp.SUM); rays = float(r.item())
 
     out = None
+    frame = img.getPixelData() if rank == 0 and (args.dump_frame or args.dump_outputs) else None     # before --full's counting batch adds to the image
     if rank == 0 and args.dump_frame:
-        np.save(args.dump_frame, img.getPixelData())
-    if rank == 0:
+        np.save(args.dump_frame, frame)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, frame)
+    roof = roof_shade = cpu = None
+    if rank == 0 and args.full:
         # traversal statistics of the SAME rays on the GPU (one extra, untimed batch in counting mode, as many passes per launch as the timed region had — a single
         # pass per launch is mostly ramp and drain and reports a lane utilisation the timed launches do not have): lane utilisation, visited nodes
         tr.setCounting(True)
@@ -586,6 +598,7 @@ def main():
         elif st.ms_shade > 0:
             roof_shade = {"bound": "unprofiled", "kernel_build": SHADE_BUILD, "vertices": n_closest, "ms": round(st.ms_shade, 3),
                           "note": "no counter profile of this workload with these shade sources in profiles/roofline_traffic.json (tools/profile_round.sh writes one)"}
+    if rank == 0:
         out = {
             "metric": "Mrays/s at %dx%d, %d spp (steps), depth-%d; achieved HBM GB/s vs peak" % (args.width, args.height, args.steps, args.depth),
             "value": round(rays / elapsed / 1e6, 3), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -599,8 +612,9 @@ def main():
                        "rough_transmittance": "per-material 1-D reduction (CTL_SCENE_REDUCED_ROUGH_TRANSMITTANCE: equal to the reference's lookup up to fp32 rounding)" if args.reduced_rough_transmittance else "the reference's 3-D lookup on every call (bit-equal frames)",
                        "parallelism": "image tiles 64x64 round-robin over %d GPU(s), 1 gather of the framebuffer per render" % world, "framebuffer_reduce": reduce_kind,
                        "rays_per_step": int(rays / args.steps), "scene_build_s": round(t_build, 2)},
-            "roofline": roof,
         }
+        if roof:
+            out["roofline"] = roof
         if roof_shade:
             out["roofline_shade"] = roof_shade
         if multi:
@@ -615,6 +629,25 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     return out
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(directory, frame):
+    """--dump-outputs: the frame the timed path computed (Image::getPixelData, (h, w, 7) float32) as DIR/pixel_data.npy.  A frame above 64 MB is written as a fixed
+    sample of its pixels instead (seed 0: the same pixels for the same frame size): DIR/pixel_data_sample.npy (n, 7) float32 and their row-major pixel indices,
+    DIR/pixel_data_sample_index.npy (n,) float64"""
+    os.makedirs(directory, exist_ok=True)
+    frame = np.ascontiguousarray(frame, np.float32)
+    if frame.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(directory, "pixel_data.npy"), frame)
+        return
+    px = frame.reshape(-1, frame.shape[-1])
+    n = (DUMP_LIMIT_BYTES - 4096) // (px.itemsize * px.shape[1] + 8)      # (less room for the two .npy headers)
+    idx = np.sort(np.random.default_rng(0).choice(len(px), n, replace=False))
+    np.save(os.path.join(directory, "pixel_data_sample.npy"), px[idx])
+    np.save(os.path.join(directory, "pixel_data_sample_index.npy"), idx.astype(np.float64))
 
 
 def _instanced_tris(desc):

@@ -71,3 +71,23 @@ def test_watchdog_ends_the_others_when_a_rank_dies():
     p = _run(["--gpus", "2", "--launch-only", "--launch-timeout", "120"], {"CTL_BENCH_TEST_RANK_FAULT": "die:1"}, timeout=120)
     assert p.returncode != 0 and p.stdout.strip() == ""
     assert "rank(s) [1] failed" in p.stderr and "7" in p.stderr
+
+
+def test_dump_outputs_samples_a_frame_above_64_mb(tmp_path):
+    """--dump-outputs writes a frame of at most 64 MB whole; a larger one as a fixed seeded sample of its pixels with their indices (float64), the same pixels every time"""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
+    small = np.random.RandomState(1).rand(64, 96, 7).astype(np.float32)
+    b.dump_outputs(str(tmp_path / "small"), small)
+    assert sorted(os.listdir(tmp_path / "small")) == ["pixel_data.npy"] and np.array_equal(np.load(tmp_path / "small" / "pixel_data.npy"), small)
+    big = np.arange(1600 * 1500 * 7, dtype=np.float32).reshape(1600, 1500, 7)      # 67.2 MB
+    for d in ("big0", "big1"):
+        b.dump_outputs(str(tmp_path / d), big)
+        assert sorted(os.listdir(tmp_path / d)) == ["pixel_data_sample.npy", "pixel_data_sample_index.npy"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= 64_000_000
+    px, idx = np.load(tmp_path / "big0" / "pixel_data_sample.npy"), np.load(tmp_path / "big0" / "pixel_data_sample_index.npy")
+    assert px.dtype == np.float32 and idx.dtype == np.float64 and len(px) == len(idx) > 1_000_000
+    assert np.array_equal(px, big.reshape(-1, 7)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "big1" / "pixel_data_sample_index.npy"))

@@ -50,7 +50,7 @@ def test_tile_ownership_partitions_the_film():
 
 
 def test_two_rank_gloo_reduce_reproduces_single_rank_frame(tmp_path):
-    import torch.multiprocessing as mp
+    import multiprocessing as mp      # the standard library's spawn: torch (and the HIP / RCCL libraries it bundles) stays out of the test process
     w, h = 192, 128   # 3 x 2 tiles
     out = str(tmp_path / "fb.npy")
     port = _free_port()
@@ -96,7 +96,7 @@ def _worker_progressive(rank, world, port, w, h, out_path):
 def test_per_pass_gathers_end_with_the_frame_of_one_final_reduce(tmp_path):
     """progressive display (north_star: a gather of the framebuffer at the end of each pass): K out-of-place per-pass gathers (ctl_image_reduce_to's contract) show the
     cumulative frame after every pass and end, bit for bit, with what ONE end-of-render in-place reduce gives — and with the one-rank frame"""
-    import torch.multiprocessing as mp
+    import multiprocessing as mp
     w, h = 192, 128
     out = str(tmp_path / "prog.npy")
     port = _free_port()
@@ -157,7 +157,7 @@ def test_gather_of_packed_tiles_equals_the_reduce(tmp_path, world, w, h):
     """north_star's exchange — a gather of the framebuffer — on 2 and 3 ranks over gloo: uneven tile counts (9 tiles / 2 ranks, 10 tiles / 3 ranks: the last slot of
     some ranks is padding), clipped border tiles, and samples a rank accumulated one pixel inside ANOTHER rank's tile (they travel in the slot's halo and are added on the
     root); the gathered frame == the reduced frame == the one-rank frame, bit for bit (integer-valued data: every sum is exact); a repeat gives the same frame"""
-    import torch.multiprocessing as mp
+    import multiprocessing as mp
     import tile_shards as parallel
     nt = ((w + 63) // 64) * ((h + 63) // 64)
     assert nt % world != 0 or h % 64 != 0

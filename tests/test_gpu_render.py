@@ -845,3 +845,34 @@ def test_bench_rccl_branch_runs_with_one_rank(gpu, tmp_path):
     assert "ncclReduce" in lines[2]["config"]["framebuffer_reduce"] and "CTL_BENCH_NO_GATHER" in lines[2]["config"]["framebuffer_reduce"]
     assert lines[0]["n_gpus"] == lines[1]["n_gpus"] == 1 and "rank_ms" not in lines[0]
     assert np.array_equal(frames[0].view(np.uint32), frames[1].view(np.uint32)) and np.array_equal(frames[0].view(np.uint32), frames[2].view(np.uint32))
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_its_outputs_and_full_adds_the_rest(gpu, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times K steps and prints the headline line without the roofline blocks; --dump-outputs DIR writes the frame of
+    the timed path (DIR/pixel_data.npy, float32: the --dump-frame array), the same bits from run to run with the same arguments; --full adds the roofline (its counting
+    batch runs after the dump, so the dumped frame is the plain run's)."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    common = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--width", "320", "--height", "192", "--instances", "60", "--subdiv", "2", "--no-cpu-baseline", "--no-cache"]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "CTL_BENCH_SHARE_GPU", "CTL_BENCH_COMM_WORLD1")}
+    lines, dumps = [], []
+    for k, extra in enumerate(([], [], ["--full"])):
+        d = tmp_path / ("out%d" % k)
+        args = common + extra + ["--dump-outputs", str(d)] + (["--dump-frame", str(tmp_path / "frame.npy")] if k == 0 else [])
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args, env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        js = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(js) == 1
+        lines.append(json.loads(js[0]))
+        assert sorted(os.listdir(d)) == ["pixel_data.npy"]
+        dumps.append(np.load(d / "pixel_data.npy"))
+    for b in lines:
+        assert b["steps"] == 3 and b["warmup"] == 1 and b["ms_per_step"] > 0 and b["value"] > 0 and b["unit"] == "Mrays/s" and b["higher_is_better"] is True
+        assert b["metric"] == lines[0]["metric"] and b["dtype"] == "f32"
+    assert "roofline" not in lines[0] and "roofline" not in lines[1] and "cpu_baseline" not in lines[0]
+    assert lines[2]["roofline"]["counting_passes"] == 3 and "per_ray" in lines[2]["roofline"]
+    a = dumps[0]
+    assert a.dtype == np.float32 and a.shape == (192, 320, 7) and a[..., 6].sum() > 0
+    assert np.array_equal(a.view(np.uint32), np.load(tmp_path / "frame.npy").view(np.uint32))
+    assert all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for b in dumps[1:])

@@ -4,7 +4,7 @@
 TAG=${1:-exp}; OUT=gpurun_out/$TAG; mkdir -p "$OUT"
 export TMPDIR=/tmp
 if [ "${SKIP_TESTS:-0}" != "1" ]; then timeout 1500 python -m pytest tests -m gpu -x -q > "$OUT/pytest.log" 2>&1; tail -5 "$OUT/pytest.log"; fi
-ARGS=${BENCH_ARGS:---steps 32 --warmup 2 --no-cpu-baseline}
+ARGS=${BENCH_ARGS:---full --steps 32 --warmup 2 --no-cpu-baseline}
 while read -r line; do
   [ -z "$line" ] && continue
   echo "== $line" | tee -a "$OUT/runs.jsonl"

@@ -5,7 +5,7 @@ set -u
 TAG=$1; shift
 OUT=gpurun_out/$TAG; mkdir -p "$OUT"
 export TMPDIR=/tmp
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline ${BENCH_ARGS:-}"
+ARGS="--full --steps 20 --warmup 5 --no-cpu-baseline ${BENCH_ARGS:-}"
 for v in "$@"; do
   export CTL_AMD_LIB=$PWD/cudatracerlib_amd/libctl_$v.so
   python bench.py $ARGS > "$OUT/$v.json" 2> "$OUT/$v.err"

@@ -1,7 +1,7 @@
 #!/bin/bash
 # one extra PMC pass over a bench run: tools/pmc_once.sh <tag> "<counters>" [bench args]; prints per-kernel sums of each counter
 TAG=$1; CTRS=$2; shift 2; OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
-timeout 600 rocprofv3 --pmc $CTRS --kernel-trace --output-format csv -d $OUT/pmc -o p -- python bench.py "$@" --no-cpu-baseline > $OUT/pmc.log 2>&1
+timeout 600 rocprofv3 --pmc $CTRS --kernel-trace --output-format csv -d $OUT/pmc -o p -- python bench.py --full "$@" --no-cpu-baseline > $OUT/pmc.log 2>&1
 python - "$OUT" <<'PY'
 import csv, glob, sys, collections
 acc = collections.defaultdict(lambda: collections.defaultdict(float))

@@ -7,7 +7,7 @@ TAG=${1:-pmc}; shift
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-ARGS="--steps 16 --warmup 2 --no-cpu-baseline $*"
+ARGS="--full --steps 16 --warmup 2 --no-cpu-baseline $*"
 python bench.py $ARGS > "$OUT/bench.json" 2> "$OUT/bench.err"     # also warms the geometry cache
 run() { local name=$1; shift; timeout 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d "$OUT/$name" -o p -- python bench.py $ARGS > "$OUT/$name.log" 2>&1; }
 run sqA SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY

@@ -9,8 +9,8 @@ OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 RUN=${*:---steps 20 --warmup 5}
-timeout 900 python bench.py $RUN > "$OUT/bench.json" 2> "$OUT/bench.err"
-ARGS="$RUN --no-cpu-baseline"
+timeout 900 python bench.py --full $RUN > "$OUT/bench.json" 2> "$OUT/bench.err"
+ARGS="--full $RUN --no-cpu-baseline"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o p -- python bench.py $ARGS > "$OUT/stats.log" 2>&1
 pmc() { local name=$1; shift; timeout 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d "$OUT/pmc_$name" -o p -- python bench.py $ARGS > "$OUT/pmc_$name.log" 2>&1; }
 pmc FETCH_SIZE FETCH_SIZE

@@ -9,21 +9,21 @@ if [ "${SKIP_PROFILE:-0}" != "1" ]; then
   bash tools/profile_round.sh ${TAG}bath --steps 20 --warmup 5 --workload synthetic-bathroom > $OUT/profile_bath.log 2>&1
   bash tools/profile_round.sh ${TAG}hard --steps 20 --warmup 5 --workload synthetic-sm-hard > $OUT/profile_hard.log 2>&1
 fi
-python bench.py > $OUT/bench_64spp.json 2>$OUT/e1
-python bench.py --steps 20 --warmup 5 > $OUT/bench_final.json 2>$OUT/e0
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --workload synthetic-bathroom > $OUT/bench_bathroom.json 2>$OUT/e2
-python bench.py --steps 128 --warmup 5 --no-cpu-baseline --workload synthetic-bathroom > $OUT/bench_bathroom_128spp.json 2>$OUT/e2b
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --workload synthetic-bathroom --reduced-rough-transmittance > $OUT/bench_bathroom_reduced.json 2>$OUT/e2c
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --workload cornell-glass --width 1024 --height 1024 > $OUT/bench_cornell.json 2>$OUT/e3
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --via-loader > $OUT/bench_loader.json 2>$OUT/e4
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --tracer-param PathSemantics=1 > $OUT/bench_wavefront_rules.json 2>$OUT/e5
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --workload synthetic-sm-hard > $OUT/bench_sm_hard.json 2>$OUT/e6
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --flat-format q8 > $OUT/bench_q8.json 2>$OUT/e7
+python bench.py --full > $OUT/bench_64spp.json 2>$OUT/e1
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_final.json 2>$OUT/e0
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --workload synthetic-bathroom > $OUT/bench_bathroom.json 2>$OUT/e2
+python bench.py --full --steps 128 --warmup 5 --no-cpu-baseline --workload synthetic-bathroom > $OUT/bench_bathroom_128spp.json 2>$OUT/e2b
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --workload synthetic-bathroom --reduced-rough-transmittance > $OUT/bench_bathroom_reduced.json 2>$OUT/e2c
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --workload cornell-glass --width 1024 --height 1024 > $OUT/bench_cornell.json 2>$OUT/e3
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --via-loader > $OUT/bench_loader.json 2>$OUT/e4
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --tracer-param PathSemantics=1 > $OUT/bench_wavefront_rules.json 2>$OUT/e5
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --workload synthetic-sm-hard > $OUT/bench_sm_hard.json 2>$OUT/e6
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --flat-format q8 > $OUT/bench_q8.json 2>$OUT/e7
 python tools/plugin_compare.py > $OUT/plugin_compare.txt 2>&1
 for P in 20 64 256; do PASSES=$P FUSE=1 python tools/shard_time_probe.py 1 2 4 8 >> $OUT/shard_time_probe.txt 2>&1; done
-CTL_BENCH_SHARE_GPU=1 timeout 900 python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_2ranks_shared_gpu.json 2>$OUT/e8
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --dump-frame $OUT/frame1.npy > /dev/null 2>&1
-CTL_BENCH_SHARE_GPU=1 timeout 1200 python bench.py --gpus 8 --steps 20 --warmup 5 --no-cpu-baseline --dump-frame $OUT/frame8.npy > $OUT/bench_8ranks_shared_gpu.json 2>$OUT/e9
+CTL_BENCH_SHARE_GPU=1 timeout 900 python bench.py --full --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_2ranks_shared_gpu.json 2>$OUT/e8
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --dump-frame $OUT/frame1.npy > /dev/null 2>&1
+CTL_BENCH_SHARE_GPU=1 timeout 1200 python bench.py --full --gpus 8 --steps 20 --warmup 5 --no-cpu-baseline --dump-frame $OUT/frame8.npy > $OUT/bench_8ranks_shared_gpu.json 2>$OUT/e9
 python - <<PY > $OUT/frames_8_vs_1.txt 2>&1
 import numpy as np
 a, b = np.load("$OUT/frame1.npy"), np.load("$OUT/frame8.npy")

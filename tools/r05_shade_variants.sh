@@ -5,7 +5,7 @@ out=gpurun_out/${1:-r05s}; mkdir -p $out; L=$PWD/cudatracerlib_amd; export PROBE
 for rep in 1 2; do for v in amd ${VARIANTS}; do CTL_AMD_LIB=$L/libctl_$v.so timeout 300 python tools/shade_basic_probe.py 2>>$out/err.log | grep "^{" | tee -a $out/probe.jsonl; done; done
 if [ "${SKIP_PMC:-0}" != "1" ]; then
 for v in amd ${VARIANTS}; do
-  CTL_AMD_LIB=$L/libctl_$v.so timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS --kernel-trace --output-format csv -d $out/pmc_$v -o p -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/pmc_$v.log 2>&1
+  CTL_AMD_LIB=$L/libctl_$v.so timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS --kernel-trace --output-format csv -d $out/pmc_$v -o p -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/pmc_$v.log 2>&1
   python - "$out/pmc_$v" "$v" <<'PY' | tee -a $out/pmc_sums.txt
 import csv, glob, sys, collections
 acc = collections.defaultdict(lambda: collections.defaultdict(float)); dur = collections.defaultdict(float)

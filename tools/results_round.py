@@ -20,7 +20,7 @@ sys.path.insert(0, ROOT)
 
 
 def bench(args, timeout=1500):
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=timeout)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + args, capture_output=True, text=True, timeout=timeout)
     for line in p.stdout.splitlines():
         if line.startswith("{"):
             return json.loads(line)

@@ -3,7 +3,7 @@
 set -u
 TAG=${1:-r03s}; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
-ARGS="${*:---steps 20 --warmup 5} --no-cpu-baseline"
+ARGS="--full ${*:---steps 20 --warmup 5} --no-cpu-baseline"
 python bench.py $ARGS > $OUT/bench.json 2> $OUT/bench.err
 run() { local name=$1; shift; timeout 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d "$OUT/$name" -o p -- python bench.py $ARGS > "$OUT/$name.log" 2>&1; }
 run sqA SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY
