@@ -77,6 +77,7 @@ def load(shared_math=False):
     o.orc_texture_eval.argtypes = [C.c_void_p, C.c_void_p, f32, f32, C.c_void_p]
     o.orc_set_block_counts.argtypes = [C.c_void_p, u32]
     o.orc_set_zero_stop_image.argtypes = [C.c_void_p]; o.orc_set_zero_stop_image.restype = None
+    o.orc_set_ray_count_image.argtypes = [C.c_void_p]; o.orc_set_ray_count_image.restype = None
     o.orc_image_add_samples.argtypes = [C.c_void_p, u32, u32, C.c_int, C.c_void_p]; o.orc_image_add_samples.restype = None
     o.orc_sample_normal_map.argtypes = [C.c_void_p, C.c_void_p, f32, f32, C.c_void_p, C.c_void_p]
     o.orc_alpha_test.argtypes = [C.c_void_p, C.c_void_p, f32, f32]
@@ -151,7 +152,7 @@ class Oracle:
         return hits
 
     def render(self, desc, width, height, n_passes=1, tables=None, direct=True, max_path_length=8, rr_start=5, threads=8, rows=None, half_host_quirk=False, alpha_test=False, block_counts=None,
-               flat=None, counts=None, partials=False, regularization=False, wavefront_rules=False, u16_barycentrics=False, omit_last_nee=False, zero_stop=None):
+               flat=None, counts=None, partials=False, regularization=False, wavefront_rules=False, u16_barycentrics=False, omit_last_nee=False, zero_stop=None, pixel_rays=None):
         """pathKernel2<DIRECT,false> over all pixels (Integrators/PathTracer.cu:182-194). tables = list of (t1, t2) per pass or None.
         alpha_test: traceRay<USE_ALPHA> when the scene has alpha maps (what the reference's single-ray path does; its wavefront
         intersectKernel has no alpha test).
@@ -163,6 +164,7 @@ class Oracle:
         counts: a dict that receives the traversal statistics of this render (path_rays, path_inner, path_tri, path_inst, occ_rays, ...).
         zero_stop: a float32 array (h, w, 7), added to: the samples the reference drops as NaN / infinite AFTER the path's throughput had become exactly zero, each as the
             radiance collected up to that vertex (what the product's kernels, which end such a path at once, count) — kernels' frame == returned frame + zero_stop.
+        pixel_rays: a uint32 array (h, w), added to: the rays each pixel traced (path and shadow rays).
         Returns (pixel_data (h, w, 7), rays)."""
         img = np.zeros((height, width, 7), np.float32)
         y0, y1 = (0, height) if rows is None else rows
@@ -180,6 +182,9 @@ class Oracle:
         if zero_stop is not None:
             assert zero_stop.dtype == np.float32 and zero_stop.shape == (height, width, 7) and zero_stop.flags["C_CONTIGUOUS"]
             self.lib.orc_set_zero_stop_image(zero_stop.ctypes.data)
+        if pixel_rays is not None:
+            assert pixel_rays.dtype == np.uint32 and pixel_rays.shape == (height, width) and pixel_rays.flags["C_CONTIGUOUS"]
+            self.lib.orc_set_ray_count_image(pixel_rays.ctypes.data)
         if counts is not None:
             self.lib.orc_render_counting(1)
         try:
@@ -188,6 +193,7 @@ class Oracle:
         finally:
             self.lib.orc_set_flat_bvh(None)
             self.lib.orc_set_zero_stop_image(None)
+            self.lib.orc_set_ray_count_image(None)
             if counts is not None:
                 c8 = (u64 * 8)()
                 self.lib.orc_render_counts(c8)

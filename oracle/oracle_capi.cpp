@@ -310,6 +310,10 @@ void orc_set_block_counts(const uint8_t* counts, uint32_t blocks_x) { g_block_co
 // zero-throughput path at once and count that radiance: their frame = the oracle's frame + this image, weights included (tests/test_gpu_fuzz.py).
 static ctl_pixel_data* g_zero_stop_img = nullptr;
 void orc_set_zero_stop_image(ctl_pixel_data* img) { g_zero_stop_img = img; }
+// per-pixel ray counts of the following orc_render calls (W x H counters, added to; NULL = none): the rays each pixel's paths traced, shadow rays included —
+// what the reference's g_RayTracedCounter counts around one pathKernel2 thread (tests/golden/pathtrace.npz)
+static uint32_t* g_ray_count_img = nullptr;
+void orc_set_ray_count_image(uint32_t* counts) { g_ray_count_img = counts; }
 // counting mode of orc_render: traversal statistics of every ray the following renders trace.  out8 = {path rays, n_inner, n_tri, n_inst,
 // occlusion rays, n_inner, n_tri, n_inst}; orc_render_counts(NULL) switches counting off, a non-NULL call reads and resets the totals.
 static bool g_count_render = false; static uint64_t g_render_counts[8] = {};
@@ -365,6 +369,7 @@ uint64_t orc_render(const ctl_scene_desc* desc, uint32_t W, uint32_t H, uint32_t
                 for (uint32_t x = xa; x < xb; x++)
                 for (uint32_t smp = 0, n_smp = g_block_counts ? g_block_counts[(y / 64) * g_blocks_x + x / 64] : 1u; smp < n_smp; smp++) {
                     // BlockSamplerBuffer::getNumSamplesPerPixel (WavefrontPathTracer.cu:31-36): the samples of a pixel in one pass continue one sampler
+                    const uint64_t rays_before = rays;
                     Sampler rng(t1, t2, y * W + x);   // TracerBase::getPixelIndex
                     rng.d2 = 2 * smp;
                     V2 j = rng.randomFloat2();
@@ -382,6 +387,7 @@ uint64_t orc_render(const ctl_scene_desc* desc, uint32_t W, uint32_t H, uint32_t
                     else
                     col = pathTrace(S, direct != 0, o, d, rng, maxPathLength, rrStart, &rays, partials ? &diff : nullptr, omitLastNEE);   // imp == 1 (Sensor.cu:127)
                     addSample(img, (int)W, (int)H, pX.x, pX.y, col);
+                    if (g_ray_count_img) g_ray_count_img[(size_t)y * W + x] += (uint32_t)(rays - rays_before);
                     if (g_zero_stop_img && zeroStop().have) {
                         const Spec c = V3(fmax2(0.0f, col.x), fmax2(0.0f, col.y), fmax2(0.0f, col.z));
                         const bool dropped = std::isnan(c.x) || std::isnan(c.y) || std::isnan(c.z) || std::isinf(c.x) || std::isinf(c.y) || std::isinf(c.z);

@@ -10,6 +10,7 @@
 // lets the reference's constructor / Update() derive what it derives (fdrInt, invEta2, sampling weights, ...), and calls sample / f / pdf in a frame whose
 // shading normal is +z.
 #include <SceneTypes/BSDF.h>
+#include <SceneTypes/Texture.h>
 #include "../include/ctl_amd.h"
 #include <cstdint>
 #include <cstring>
@@ -22,25 +23,30 @@ static Texture tex_of(const ctl_texture& t) {
     Texture r;
     if (t.type == CTL_TEX_CHECKER) { CheckerboardTexture c(spec3(t.value), spec3(t.value1), TextureMapping2D(t.uv_scale[0], t.uv_scale[1], t.uv_offset[0], t.uv_offset[1])); r.SetData(c); }
     else if (t.type == CTL_TEX_CONSTANT) { ConstantTexture c(spec3(t.value)); r.SetData(c); }
-    else throw std::runtime_error("ref_bsdf_driver: only constant and checkerboard textures");
+    else if (t.type == CTL_TEX_IMAGE) { ImageTexture it(TextureMapping2D(t.uv_scale[0], t.uv_scale[1], t.uv_offset[0], t.uv_offset[1]), std::string(), spec3(t.value)); it.tex_idx = t.image; r.SetData(it); }   // reads g_SceneData's images (ref_bind_scene)
+    else throw std::runtime_error("ref_bsdf_driver: texture kind not driven");
     return r;
+}
+// builds the reference BSDF of one of the simple models from the flat material and hands it to `put` (which stores it in a BSDFFirst or a BSDFALL)
+template <class P> static void visit_simple(const ctl_material& M, P&& put) {
+    switch (M.bsdf_type) {
+    case CTL_BSDF_DIFFUSE: { diffuse d(tex_of(M.tex[0])); d.m_combinedType = M.combined_type; put(d); break; }   // (the loader's `transmission` flag lives in m_combinedType)
+    case CTL_BSDF_ROUGHDIFFUSE: { roughdiffuse d(tex_of(M.tex[0]), tex_of(M.tex[1])); d.m_useFastApprox = M.u[0] != 0; put(d); break; }
+    case CTL_BSDF_DIELECTRIC: { dielectric d(M.f[0], tex_of(M.tex[1]), tex_of(M.tex[0])); d.eta_f.SetData(DispersionCauchy(M.f[0], M.f[1])); put(d); break; }
+    case CTL_BSDF_THINDIELECTRIC: { thindielectric d(M.f[0], tex_of(M.tex[1]), tex_of(M.tex[0])); put(d); break; }
+    case CTL_BSDF_ROUGHDIELECTRIC: { roughdielectric d((MicrofacetDistribution::EType)M.u[0], M.f[0], tex_of(M.tex[2]), tex_of(M.tex[3]), tex_of(M.tex[1]), tex_of(M.tex[0])); d.m_sampleVisible = M.u[1] != 0; put(d); break; }
+    case CTL_BSDF_CONDUCTOR: { conductor d(spec3(M.f), spec3(M.f + 3), tex_of(M.tex[0])); put(d); break; }
+    case CTL_BSDF_ROUGHCONDUCTOR: { roughconductor d((MicrofacetDistribution::EType)M.u[0], spec3(M.f), spec3(M.f + 3), tex_of(M.tex[1]), tex_of(M.tex[2]), tex_of(M.tex[0])); d.m_sampleVisible = M.u[1] != 0; put(d); break; }
+    case CTL_BSDF_PLASTIC: { plastic d(M.f[2], tex_of(M.tex[0]), tex_of(M.tex[1]), M.u[0] != 0); put(d); break; }
+    case CTL_BSDF_PHONG: { phong d(tex_of(M.tex[0]), tex_of(M.tex[1]), tex_of(M.tex[2])); put(d); break; }
+    case CTL_BSDF_ROUGHPLASTIC: { Texture a = tex_of(M.tex[2]), d0 = tex_of(M.tex[0]), s0 = tex_of(M.tex[1]); roughplastic d((MicrofacetDistribution::EType)M.u[2], M.f[0], a, d0, s0, M.u[0] != 0); put(d); break; }
+    case CTL_BSDF_WARD: { ward d((ward::EModelVariant)M.u[0], tex_of(M.tex[0]), tex_of(M.tex[1]), tex_of(M.tex[2]), tex_of(M.tex[3])); put(d); break; }
+    default: throw std::runtime_error("ref_bsdf_driver: model not driven");
+    }
 }
 static BSDFFirst simple_of(const ctl_material& M) {
     BSDFFirst b;
-    switch (M.bsdf_type) {
-    case CTL_BSDF_DIFFUSE: { diffuse d(tex_of(M.tex[0])); d.m_combinedType = M.combined_type; b.SetData(d); break; }   // (the loader's `transmission` flag lives in m_combinedType)
-    case CTL_BSDF_ROUGHDIFFUSE: { roughdiffuse d(tex_of(M.tex[0]), tex_of(M.tex[1])); d.m_useFastApprox = M.u[0] != 0; b.SetData(d); break; }
-    case CTL_BSDF_DIELECTRIC: { dielectric d(M.f[0], tex_of(M.tex[1]), tex_of(M.tex[0])); d.eta_f.SetData(DispersionCauchy(M.f[0], M.f[1])); b.SetData(d); break; }
-    case CTL_BSDF_THINDIELECTRIC: { thindielectric d(M.f[0], tex_of(M.tex[1]), tex_of(M.tex[0])); b.SetData(d); break; }
-    case CTL_BSDF_ROUGHDIELECTRIC: { roughdielectric d((MicrofacetDistribution::EType)M.u[0], M.f[0], tex_of(M.tex[2]), tex_of(M.tex[3]), tex_of(M.tex[1]), tex_of(M.tex[0])); d.m_sampleVisible = M.u[1] != 0; b.SetData(d); break; }
-    case CTL_BSDF_CONDUCTOR: { conductor d(spec3(M.f), spec3(M.f + 3), tex_of(M.tex[0])); b.SetData(d); break; }
-    case CTL_BSDF_ROUGHCONDUCTOR: { roughconductor d((MicrofacetDistribution::EType)M.u[0], spec3(M.f), spec3(M.f + 3), tex_of(M.tex[1]), tex_of(M.tex[2]), tex_of(M.tex[0])); d.m_sampleVisible = M.u[1] != 0; b.SetData(d); break; }
-    case CTL_BSDF_PLASTIC: { plastic d(M.f[2], tex_of(M.tex[0]), tex_of(M.tex[1]), M.u[0] != 0); b.SetData(d); break; }
-    case CTL_BSDF_PHONG: { phong d(tex_of(M.tex[0]), tex_of(M.tex[1]), tex_of(M.tex[2])); b.SetData(d); break; }
-    case CTL_BSDF_ROUGHPLASTIC: { Texture a = tex_of(M.tex[2]), d0 = tex_of(M.tex[0]), s0 = tex_of(M.tex[1]); roughplastic d((MicrofacetDistribution::EType)M.u[2], M.f[0], a, d0, s0, M.u[0] != 0); b.SetData(d); break; }
-    case CTL_BSDF_WARD: { ward d((ward::EModelVariant)M.u[0], tex_of(M.tex[0]), tex_of(M.tex[1]), tex_of(M.tex[2]), tex_of(M.tex[3])); b.SetData(d); break; }
-    default: throw std::runtime_error("ref_bsdf_driver: model not driven");
-    }
+    visit_simple(M, [&](const auto& d) { b.SetData(d); });
     b.As()->m_enableTwoSided = M.two_sided != 0;
     return b;
 }
@@ -66,6 +72,16 @@ template <class B> static void run(const B& bsdf, int mode, unsigned typeMask, i
             o[0] = cr; o[1] = cg; o[2] = cb; o[3] = bsdf.pdf(r, m); o[4] = o[5] = o[6] = o[7] = o[8] = 0.0f;
         }
     }
+}
+
+// Material::bsdf of mats[idx], any model (ref_pathtrace_driver.cpp builds the scene's materials with it)
+void ref_bsdf_all_of(const ctl_material* mats, uint32_t idx, BSDFALL& out) {
+    const ctl_material& M = mats[idx];
+    if (M.bsdf_type == CTL_BSDF_COATING) out.SetData(coating(simple_of(mats[M.u[2]]), M.f[0], M.f[2], tex_of(M.tex[0]), tex_of(M.tex[1])));
+    else if (M.bsdf_type == CTL_BSDF_ROUGHCOATING) out.SetData(roughcoating((MicrofacetDistribution::EType)M.u[0], simple_of(mats[M.u[2]]), M.f[0], M.f[2], tex_of(M.tex[0]), tex_of(M.tex[2]), tex_of(M.tex[1])));
+    else if (M.bsdf_type == CTL_BSDF_BLEND) out.SetData(blend(simple_of(mats[M.u[2]]), simple_of(mats[M.u[3]]), tex_of(M.tex[0])));
+    else visit_simple(M, [&](const auto& d) { out.SetData(d); });
+    out.As()->m_enableTwoSided = M.two_sided != 0;
 }
 
 extern "C" {

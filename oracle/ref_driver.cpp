@@ -9,10 +9,11 @@
 //
 // Further reference code is driven by ref_mipmap_driver.cpp (KernelMIPMap), ref_bsdf_driver.cpp (BSDF_Simple.cu, BSDF_Complex.cu) and ref_light_driver.cpp
 // (Light.cu) — files whose host-compilable part `make ref` extracts at build time.
-// What could NOT be built from the reference here (needs curand_kernel.h from the CUDA toolkit, nvcc's ::min / ::max, the global g_SceneData declared behind
-// curand, or un-vendored boost / pugixml / FreeImage): Math/Spline.cu (rough transmittance), Engine/ShapeSet.cu (area-light sampling), the two environment-map
-// sampling functions of Light.cu, KernelDynamicScene.cu, TraceHelper.cu, TraceAlgorithms.cu, PathTracer.cu, Sampler / CudaRandom, DynamicScene, the Mitsuba
-// loader.  See DESIGN.md "Oracle".
+// The path-tracing loop (PathTracer.cu, TraceAlgorithms.cu, TraceResult.cu, the host traceRay of TraceHelper.cu, the rest of KernelDynamicScene.cu it calls) is driven by
+// ref_pathtrace_driver.cpp through one generated unit with curand-free shadow copies of three Kernel/ headers.
+// What could NOT be built from the reference here (needs curand_kernel.h from the CUDA toolkit, the CUDA runtime, or un-vendored boost / pugixml / FreeImage):
+// CudaRandom / RandomSampler and cuRAND seeding (curand_kernel.h), the volume media and phase functions (not needed without volumes), the device traversal kernels and
+// texture bindings of TraceHelper.cu (CUDA runtime), the wavefront integrators, DynamicScene and the Mitsuba loader.  See DESIGN.md "Oracle".
 #include <Engine/TriIntersectorData.h>
 #include <Engine/TriangleData.h>
 #include <Engine/DifferentialGeometry.h>

@@ -19,18 +19,26 @@ static_assert(sizeof(image_layout) == sizeof(Image), "member layout of Image");
 static_assert(sizeof(PixelData) == 28, "PixelData is seven floats");
 }  // namespace
 
+// an Image over `pixels` laid out in `raw` (at least sizeof(Image) bytes, 16-aligned), or NULL when the raw layout does not answer the class's accessors
+Image* ref_image_view(void* raw, size_t raw_size, void* pixels, int w, int h) {
+    if (raw_size < sizeof(Image) || w < 2 || h < 1) return nullptr;
+    image_layout L; std::memset(&L, 0, sizeof L);
+    L.location = DataLocation::Synchronized; L.xres = w; L.yres = h;
+    L.pixels.location = DataLocation::Synchronized; L.pixels.length = (unsigned)(w * h); L.pixels.host = pixels;
+    std::memcpy(raw, &L, sizeof L);
+    Image* img = reinterpret_cast<Image*>(raw);
+    if ((int)img->getWidth() != w || (int)img->getHeight() != h || &img->getPixelData(1, h - 1) != (PixelData*)pixels + ((h - 1) * w + 1)) return nullptr;
+    return img;
+}
+
 extern "C" {
 
 // pixels: w x h PixelData (rgb[3], rgbSplat[3], weightSum), added to; samples: n x {sx, sy, r, g, b}.  Returns 0, or -2 when the raw layout does not answer the class's accessors.
 int ref_image_add_samples(void* pixels, int w, int h, int n, const float* samples) {
     if (w < 2 || h < 1) return -1;
     alignas(16) unsigned char raw[sizeof(Image)];
-    image_layout L; std::memset(&L, 0, sizeof L);
-    L.location = DataLocation::Synchronized; L.xres = w; L.yres = h;
-    L.pixels.location = DataLocation::Synchronized; L.pixels.length = (unsigned)(w * h); L.pixels.host = pixels;
-    std::memcpy(raw, &L, sizeof L);
-    Image* img = reinterpret_cast<Image*>(raw);
-    if ((int)img->getWidth() != w || (int)img->getHeight() != h || &img->getPixelData(1, h - 1) != (PixelData*)pixels + ((h - 1) * w + 1)) return -2;
+    Image* img = ref_image_view(raw, sizeof raw, pixels, w, h);
+    if (!img) return -2;
     for (int i = 0; i < n; i++) img->AddSample(samples[5 * i], samples[5 * i + 1], Spectrum(samples[5 * i + 2], samples[5 * i + 3], samples[5 * i + 4]));
     return 0;
 }

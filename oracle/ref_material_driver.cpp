@@ -40,6 +40,8 @@ Material material_of(const ctl_material& M) {
 }
 }  // namespace
 
+Material ref_material_of(const ctl_material& M) { return material_of(M); }   // for ref_pathtrace_driver.cpp (which then sets the material's own BSDF)
+
 extern "C" {
 
 // Material::SampleNormalMap(dg, wi).  q: 20 floats per query = uv(2), sys.s(3), sys.t(3), sys.n(3), geometric n(3), dpdu(3), dpdv(3); out: 10 floats = used, s(3), t(3), n(3)

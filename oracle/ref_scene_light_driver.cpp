@@ -19,6 +19,7 @@
 #include <cstdint>
 #include <cstring>
 #include <vector>
+#include <stdexcept>
 
 namespace CudaTracerLib { extern KernelDynamicScene g_SceneDataHost; }   // (declared by the generated unit from TraceHelper.h:15; repeated here only to name it)
 using namespace CudaTracerLib;
@@ -93,6 +94,29 @@ template <class LT> void pdf_direct(const LT& light, int n, const float* q, floa
 }  // namespace
 
 void ref_bind_scene(const ctl_scene_desc* d) { bind_scene(d); }   // for ref_material_driver.cpp: the same binding of g_SceneData
+
+// the scene's light L as the reference's Light aggregate (ref_pathtrace_driver.cpp).  Point / spot / distant lights take the descriptor's fields member by member
+// (SceneTypes/Light.h:34-37,147-151,228-233): the frame and the derived cosines are the builder's, as the restatement reads them.
+void ref_light_of(const ctl_scene_desc* d, const ctl_light& L, Light& out) {
+    const Frame F(NormalizedT<Vec3f>(L.to_world[0], L.to_world[1], L.to_world[2]), NormalizedT<Vec3f>(L.to_world[4], L.to_world[5], L.to_world[6]),
+                  NormalizedT<Vec3f>(L.to_world[8], L.to_world[9], L.to_world[10]));
+    switch (L.type) {
+    case CTL_LIGHT_POINT: out.SetData(PointLight(Vec3f(L.position[0], L.position[1], L.position[2]), spec3(L.radiance))); break;
+    case CTL_LIGHT_DIFFUSE: out.SetData(area_of(L)); break;
+    case CTL_LIGHT_INFINITE: out.SetData(env_of(d, L)); break;
+    case CTL_LIGHT_SPOT: {
+        SpotLight s; s.m_intensity = spec3(L.radiance); s.m_beamWidth = L.beam_width; s.m_cutoffAngle = L.cutoff_angle; s.m_cosBeamWidth = L.cos_beam_width;
+        s.m_cosCutoffAngle = L.cos_cutoff_angle; s.m_invTransitionWidth = L.inv_transition_width; s.ToWorld = F;
+        s.Position = Vec3f(L.position[0], L.position[1], L.position[2]); s.Target = s.Position + Vec3f(L.direction[0], L.direction[1], L.direction[2]);
+        out.SetData(s); break;
+    }
+    case CTL_LIGHT_DISTANT: {
+        DistantLight t; t.m_normalIrradiance = spec3(L.radiance); t.ToWorld = F; t.radius = L.bsphere_radius; t.m_invSurfaceArea = 1.0f / (PI * t.radius * t.radius);
+        out.SetData(t); break;
+    }
+    default: throw std::runtime_error("ref_light_of: light type not driven");
+    }
+}
 
 extern "C" {
 

@@ -833,8 +833,66 @@ def gen_image(r):
     np.savez_compressed(os.path.join(HERE, "image.npz"), width=np.int32(W), height=np.int32(H), samples=s, pixels=px)
 
 
+def pathtrace_cases():
+    """the path-tracing fixture's cases: (key, scene builder, width, height, passes, DIRECT, regularization, alpha test).  Max path length 8, RR start 5.
+    Image-textured area lights are left out: their value is undefined in the reference itself (hasUVPartials is never set, SceneTypes/Light.cu:76,126)."""
+    from cudatracerlib_amd import scenes
+    return [("cornell_1spp_direct", lambda: scenes.cornell_box(128, 128), 128, 128, 1, True, False, False),
+            ("cornell_1spp_nodirect", lambda: scenes.cornell_box(128, 128), 128, 128, 1, False, False, False),
+            ("cornell_16spp_direct", lambda: scenes.cornell_box(128, 128), 128, 128, 16, True, False, False),
+            ("cornell_16spp_nodirect", lambda: scenes.cornell_box(128, 128), 128, 128, 16, False, False, False),
+            ("cornell_130x97", lambda: scenes.cornell_box(130, 97), 130, 97, 4, True, False, False),   # non-square, not a multiple of 64: w / h swaps in the pixel and sampler index
+            ("glass_direct", lambda: scenes.cornell_box(64, 64, glass_sphere=True), 64, 64, 16, True, False, False),
+            ("glass_nodirect", lambda: scenes.cornell_box(64, 64, glass_sphere=True), 64, 64, 16, False, False, False),
+            ("extra_materials", lambda: scenes.cornell_box(64, 64, extra_materials=True), 64, 64, 8, True, False, False),
+            ("env_extra_lights", lambda: scenes.env_scene(96, 64, extra_lights=True), 96, 64, 8, True, False, False),
+            ("env", lambda: scenes.env_scene(96, 64), 96, 64, 8, True, False, False),
+            ("maps_alpha", lambda: scenes.maps_scene(96, 64, alpha="alpha"), 96, 64, 4, True, False, True),
+            ("regularization_direct", lambda: scenes.cornell_box(64, 64), 64, 64, 4, True, True, False),
+            ("regularization_nodirect", lambda: scenes.cornell_box(64, 64), 64, 64, 4, False, True, False)]
+
+
+def pathtrace_tables(n_passes):
+    """the sampler tables of a case: the oracle's SequenceGenerator (the product's), n_passes computes from a fresh generator"""
+    return oracle.Oracle().sequence_tables(n_passes)
+
+
+def pathtrace_input_digest(d, tables):
+    """sha256 over what a render reads: the compiled scene (traversal arrays, TriangleData, materials, lights, anim blob, images, camera, light CDF, ray epsilon) and the sampler tables"""
+    import hashlib
+    h = hashlib.sha256()
+    h.update(traceray_input_digest(d).encode()); h.update(scene_light_digest(d).encode())
+    h.update(C.string_at(d.materials, d.n_materials * C.sizeof(type(d.materials.contents))))
+    h.update(C.string_at(d.node_transforms, d.n_nodes * 64)); h.update(C.string_at(C.addressof(d.camera), C.sizeof(d.camera)))
+    h.update(np.array([d.num_lights, d.env_map_index], np.uint32).tobytes()); h.update(np.array(list(d.light_indices), np.uint32).tobytes())
+    h.update(np.array(list(d.light_cdf) + [d.ray_trace_eps] + list(d.box_min) + list(d.box_max), np.float32).tobytes())
+    for t1, t2 in tables:
+        h.update(np.ascontiguousarray(t1, np.float32).tobytes()); h.update(np.ascontiguousarray(t2, np.float32).tobytes())
+    return h.hexdigest()
+
+
+def gen_pathtrace(r):
+    """PathTrace<DIRECT> / PathTraceRegularization<DIRECT> with the per-pixel body of pathKernel2 (Integrators/PathTracer.cu:10-170, 186-193) run by the reference's own
+    code (oracle/ref_pathtrace_driver.cpp) over the product's compiled scenes and sampler tables: the accumulated frame (rgb sums, weightSum; the splat channels stay
+    zero) and the rays each pixel traced (g_RayTracedCounter)"""
+    r.ref_pathtrace_render.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    r.ref_pathtrace_render.restype = C.c_int
+    out = {}
+    for key, make, w, h, spp, direct, regu, alpha in pathtrace_cases():
+        sc = make(); tables = pathtrace_tables(spp)
+        t1 = np.ascontiguousarray(np.concatenate([t[0] for t in tables])); t2 = np.ascontiguousarray(np.concatenate([t[1] for t in tables]))
+        px = np.zeros((h, w, 7), np.float32); rays = np.zeros((h, w), np.uint32)
+        assert r.ref_pathtrace_render(C.addressof(sc.desc), w, h, spp, t1.ctypes.data, t2.ctypes.data, int(direct), int(regu), 8, 5, int(alpha), px.ctypes.data, rays.ctypes.data) == 0, key
+        assert (px[..., 3:6] == 0).all() and rays.max() < 65536 and px[..., 6].sum() > 0.9 * w * h * spp, key
+        out[key + "_rgb"] = np.ascontiguousarray(px[..., :3]); out[key + "_weight"] = np.ascontiguousarray(px[..., 6])
+        out[key + "_rays"] = rays.astype(np.uint16); out[key + "_digest"] = np.array(pathtrace_input_digest(sc.desc, tables))
+    np.savez_compressed(os.path.join(HERE, "pathtrace.npz"), **out)
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["image"]:
+    if sys.argv[1:] == ["pathtrace"]:     # only this fixture (the others stay byte-identical)
+        gen_pathtrace(oracle.load_ref())
+    elif sys.argv[1:] == ["image"]:
         gen_image(oracle.load_ref())
     elif sys.argv[1:] == ["emitters"]:
         gen_emitters(oracle.load_ref())
@@ -878,4 +936,5 @@ if __name__ == "__main__":
         gen_bsdf_rough(oracle.load_ref())
         gen_scene_lights(oracle.load_ref())
         gen_material_maps(oracle.load_ref())
+        gen_pathtrace(oracle.load_ref())
         gen_image(oracle.load_ref())
