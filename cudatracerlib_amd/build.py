@@ -38,7 +38,7 @@ def stale(target=None, defines=()):
     if not os.path.exists(key) or open(key).read().strip() != _flag_key(defines):
         return True   # built with another -D / flag set (or by an older build.py): an A/B run must never compare a binary with itself
     t = os.path.getmtime(target)
-    deps = glob.glob(os.path.join(CSRC, "*")) + glob.glob(os.path.join(CSRC, "experiments", "*")) + [os.path.join(HERE, "..", "include", "ctl_amd.h"), __file__]
+    deps = glob.glob(os.path.join(CSRC, "*")) + [os.path.join(HERE, "..", "include", "ctl_amd.h"), __file__]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -4,20 +4,11 @@
 // (Integrators/PathTracer.cu:10-113) re-cut at its two trace points; see DESIGN.md "Kernels".
 #include "kernels.h"
 #include "traverse.h"
-#ifdef CTL_FLAT_EXPERIMENTS
-#include "experiments/traverse_flat_variants.h"   // round 2 / 3's variant arms (F4 / F2 node formats, quad fetch, top cache, stack distances, ...) instead of the product header; no 8-wide format in such a build
-#else
 #include "traverse_flat.h"
 #include "traverse_flat8.h"
-#endif
-#ifndef CTL_LEAF_QUEUE
-#define CTL_LEAF_QUEUE 0   // 1: the 4-wide flattened traversal runs its entry tests from a wave-wide queue (experiments/traverse_flat_wq.h: measured, 38-47 % slower)
-#endif
-#if CTL_LEAF_QUEUE
-#include "experiments/traverse_flat_wq.h"
-#endif
 #include "knobs.h"
 #include <stdexcept>
+#include <type_traits>
 #include "shading.h"
 #include "compaction.h"
 #include <cstdlib>
@@ -67,31 +58,12 @@ __global__ __launch_bounds__(kWideBlock) void k_raygen(dev_scene S, wave_queues 
 #define CTL_INTERSECT_MIN_WAVES 7   // waves per SIMD the register allocation of the FLATTENED traversal kernels leaves room for (72 VGPRs, no spills; the two-level kernels stay at 6: 24 KiB of LDS stack).  Measured with the slab build (profiles/r03_occupancy.log): 6 (80 VGPRs) 18.71 ms per fused launch, 7: 18.25, 8 (64 VGPRs, 11 spilled) 20.98; fewer resident workgroups (LDS padding): 5: 20.1, 4: 22.7, 3: 27.4
 #endif
 // ints of LDS a traversal workgroup keeps for its lanes' stacks, and the body for a flattened layout (LAYOUT = 1 + flat_format)
-#ifdef CTL_FLAT_EXPERIMENTS
-constexpr int lds_stack_ints(int layout) { return (layout ? (kFlatLdsRows + 1) * kFlatStackInts : kLdsStack) * kBlock; }
-template <bool ANY_HIT, bool COUNT, int LAYOUT, bool ALPHA>
-__device__ __forceinline__ void intersect_flat_layout(const dev_scene& S, const float4* __restrict__ ro, const float4* __restrict__ rd, uint32_t n, uint32_t* __restrict__ work, float4* __restrict__ hit, int* __restrict__ hit_node, uint32_t* __restrict__ occ, int* lds_stack, trav_counts& tc) {
-    __shared__ uint16_t lds_dist[CTL_STACK_DIST >= 2 ? (kFlatLdsRows + 1) * kBlock : 1];
-    __shared__ __attribute__((aligned(16))) float lds_top[kTopCacheFloats];
-    fill_top_cache(S, lds_top);
-    intersect_flat<ANY_HIT, COUNT, ALPHA, LAYOUT - 1>(S, ro, rd, n, work, hit, hit_node, occ, lds_stack, lds_top, tc, lds_dist);
-}
-#else
-#if CTL_LEAF_QUEUE
-constexpr int lds_stack_ints(int layout) { return layout == 1 + kFmtQ8 ? (kQ8LdsRows + 1) * 2 * kBlock : layout == 1 + kFmtQ4 ? kWqLdsInts : kLdsStack * kBlock; }
-#else
 constexpr int lds_stack_ints(int layout) { return layout == 1 + kFmtQ8 ? (kQ8LdsRows + 1) * 2 * kBlock : (layout ? kFlatLdsRows + 1 : kLdsStack) * kBlock; }
-#endif
 template <bool ANY_HIT, bool COUNT, int LAYOUT, bool ALPHA>
 __device__ __forceinline__ void intersect_flat_layout(const dev_scene& S, const float4* __restrict__ ro, const float4* __restrict__ rd, uint32_t n, uint32_t* __restrict__ work, float4* __restrict__ hit, int* __restrict__ hit_node, uint32_t* __restrict__ occ, int* lds_stack, trav_counts& tc) {
     if (LAYOUT == 1 + kFmtQ8) intersect_flat8<ANY_HIT, COUNT, ALPHA>(S, ro, rd, n, work, hit, hit_node, occ, (unsigned long long*)lds_stack, tc);
-#if CTL_LEAF_QUEUE
-    else intersect_flat_wq<ANY_HIT, COUNT, ALPHA>(S, ro, rd, n, work, hit, hit_node, occ, lds_stack, tc);
-#else
     else intersect_flat<ANY_HIT, COUNT, ALPHA>(S, ro, rd, n, work, hit, hit_node, occ, lds_stack, tc);
-#endif
 }
-#endif
 template <bool ANY_HIT, bool COUNT, int LAYOUT, bool ALPHA>   // LAYOUT: 0 two-level, 1 + flat_format for the flattened structure; ALPHA: alpha-test candidate hits
 #ifdef CTL_INTERSECT_EXACT_WAVES   // measurement builds: hold the traversal kernels to exactly this many waves per SIMD
 #define CTL_INTERSECT_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(CTL_INTERSECT_EXACT_WAVES, CTL_INTERSECT_EXACT_WAVES)))
@@ -258,7 +230,8 @@ void read_stack_histogram(unsigned long long* h, bool reset) {
 static unsigned g_lds_pad = 0;   // extra dynamic LDS per traversal workgroup: holds the kernels to fewer resident workgroups per CU (occupancy experiment)
 // Grid of a traversal launch: exactly the workgroups that are resident together — per CU the waves per SIMD of the kernel's __launch_bounds__ (a 256-lane workgroup is one wave
 // on each of the four SIMDs), or what the CU's 160 KB of LDS hold if that is fewer.  The waves' first ray claims are static (traverse.h ray_claims): a workgroup that had to
-// wait for a place would keep its share of the rays waiting with it.  (lc.grid_blocks = 8 workgroups per CU.)
+// wait for a place would keep its share of the rays waiting with it.  That is six workgroups per CU (6144 waves on 256 CUs) for every kernel but the 8-wide one without
+// alpha test, which gets seven (its stack takes 22 KiB of LDS).  (lc.grid_blocks = 8 workgroups per CU.)
 static int traversal_blocks(const launch_ctx& lc, int layout, bool alpha) {
     const int cus = lc.grid_blocks / 8, by_regs = (layout && !alpha) ? CTL_INTERSECT_MIN_WAVES : 6;
     const int by_lds = (int)((160u * 1024u) / ((unsigned)sizeof(int) * (unsigned)lds_stack_ints(layout) + g_lds_pad));
@@ -271,68 +244,48 @@ void apply_tuning_from_env() {
     if (const char* e = knob_env("CTL_LDS_PAD")) { int v = atoi(e); if (v >= 0 && v <= 140000) g_lds_pad = (unsigned)v; }
     if (const char* e = knob_env("CTL_REFILL_IDLE")) { int v = atoi(e); if (v >= 1 && v <= 64) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_refill_idle), &v, sizeof(v)); }
     if (const char* e = knob_env("CTL_CHUNK_GUIDED")) { int v = atoi(e) != 0; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_chunk_guided), &v, sizeof(v)); }
-#if CTL_LEAF_QUEUE
-    if (const char* e = knob_env("CTL_WQ_FLUSH")) { int v = atoi(e); if (v >= 1 && v <= 64) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wq_flush), &v, sizeof(v)); }
-    if (const char* e = knob_env("CTL_WQ_MIN_INNER")) { int v = atoi(e); if (v >= 0 && v <= 64) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wq_min_inner), &v, sizeof(v)); }
-#endif
     if (const char* e = knob_env("CTL_LEAF_BATCH")) { int v = atoi(e); if (v >= 1 && v <= 64) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_leaf_batch), &v, sizeof(v)); }
-#if !CTL_LEAF_QUEUE && !defined(CTL_FLAT_EXPERIMENTS)
     if (const char* e = knob_env("CTL_LEAF_BATCH_ANY")) { int v = atoi(e); if (v >= 1 && v <= 64) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_leaf_batch_any), &v, sizeof(v)); }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------ launch wrappers
 void launch_raygen(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P) {
     hipLaunchKernelGGL(k_raygen, dim3(lc.grid_blocks / 4), dim3(kWideBlock), 0, lc.stream, S, Q, P);
 }
-#define CTL_LAUNCH_INTERSECT_L(ANY, CNT, L, ...)                                                                                     \
-    do {                                                                                                                             \
-        if (lc.alpha_test) hipLaunchKernelGGL((k_intersect<ANY, CNT, L, true>), dim3(traversal_blocks(lc, L, true)), dim3(kBlock), g_lds_pad, lc.stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL((k_intersect<ANY, CNT, L, false>), dim3(traversal_blocks(lc, L, false)), dim3(kBlock), g_lds_pad, lc.stream, __VA_ARGS__);     \
-    } while (0)
-// The product traverses Q4 nodes.  The F4 / F2 node formats are measured experiments (0.69x and 0.66x of Q4's rays/s); their kernels are
-// compiled only with -DCTL_FLAT_EXPERIMENTS, and a scene asking for them is refused otherwise (tracer.hip).
-#ifdef CTL_FLAT_EXPERIMENTS
-#define CTL_LAUNCH_INTERSECT(ANY, CNT, ...)                                                                                          \
-    do {                                                                                                                             \
-        if (!S.flat_nodes) CTL_LAUNCH_INTERSECT_L(ANY, CNT, 0, __VA_ARGS__);                                                         \
-        else if (S.flat_format == kFmtF4) CTL_LAUNCH_INTERSECT_L(ANY, CNT, 2, __VA_ARGS__);                                          \
-        else if (S.flat_format == kFmtQ4) CTL_LAUNCH_INTERSECT_L(ANY, CNT, 1, __VA_ARGS__);                                          \
-        else CTL_LAUNCH_INTERSECT_L(ANY, CNT, 3, __VA_ARGS__);                                                                       \
-    } while (0)
-#else
-#define CTL_LAUNCH_INTERSECT(ANY, CNT, ...)                                                                                          \
-    do {                                                                                                                             \
-        if (!S.flat_nodes) CTL_LAUNCH_INTERSECT_L(ANY, CNT, 0, __VA_ARGS__);                                                         \
-        else if (S.flat_format == kFmtQ8) CTL_LAUNCH_INTERSECT_L(ANY, CNT, 4, __VA_ARGS__);                                          \
-        else CTL_LAUNCH_INTERSECT_L(ANY, CNT, 1, __VA_ARGS__);                                                                       \
-    } while (0)
-#endif
+// The scene's traversal kernel as compile-time arguments: f(LAYOUT, ALPHA), std::integral_constant values.  LAYOUT 0 is the two-level BVH, 1 + flat_format the flattened one:
+// 1 = Q4, 4 = Q8 (a scene asking for F4 / F2 nodes is refused at creation, tracer.hip); ALPHA: the scene alpha-tests candidate hits.
+template <class F>
+static void with_traversal_kernel(const launch_ctx& lc, const dev_scene& S, F&& f) {
+    auto alpha = [&](auto layout) { if (lc.alpha_test) f(layout, std::true_type{}); else f(layout, std::false_type{}); };
+    if (!S.flat_nodes) alpha(std::integral_constant<int, 0>{});
+    else if (S.flat_format == kFmtQ8) alpha(std::integral_constant<int, 1 + kFmtQ8>{});
+    else alpha(std::integral_constant<int, 1 + kFmtQ4>{});
+}
+template <bool ANY, bool CNT>
+static void launch_intersect(const launch_ctx& lc, const dev_scene& S, const float4* ro, const float4* rd, const uint32_t* n_ptr, uint32_t* work, float4* hit, int* hit_node,
+                             uint32_t* occ, unsigned long long* counts3) {
+    with_traversal_kernel(lc, S, [&](auto layout, auto alpha) {
+        constexpr int L = decltype(layout)::value; constexpr bool A = decltype(alpha)::value;
+        hipLaunchKernelGGL((k_intersect<ANY, CNT, L, A>), dim3(traversal_blocks(lc, L, A)), dim3(kBlock), g_lds_pad, lc.stream, S, ro, rd, n_ptr, work, hit, hit_node, occ, counts3);
+    });
+}
 void launch_intersect_closest(const launch_ctx& lc, const dev_scene& S, const float4* ro, const float4* rd, const uint32_t* n_ptr, uint32_t* work, float4* hit, int* hit_node) {
-    CTL_LAUNCH_INTERSECT(false, false, S, ro, rd, n_ptr, work, hit, hit_node, (uint32_t*)nullptr, (unsigned long long*)nullptr);
+    launch_intersect<false, false>(lc, S, ro, rd, n_ptr, work, hit, hit_node, nullptr, nullptr);
 }
 void launch_intersect_any(const launch_ctx& lc, const dev_scene& S, const float4* ro, const float4* rd, const uint32_t* n_ptr, uint32_t* work, uint32_t* occ, float4* hit, int* hit_node) {
-    CTL_LAUNCH_INTERSECT(true, false, S, ro, rd, n_ptr, work, hit, hit_node, occ, (unsigned long long*)nullptr);
+    launch_intersect<true, false>(lc, S, ro, rd, n_ptr, work, hit, hit_node, occ, nullptr);
 }
 void launch_intersect_pair(const launch_ctx& lc, const dev_scene& S, const float4* ro, const float4* rd, const uint32_t* n_ptr, uint32_t* work, float4* hit, int* hit_node,
                            const float4* sro, const float4* srd, const uint32_t* sn_ptr, uint32_t* swork, uint32_t* occ) {
-    if (!S.flat_nodes) {
-        if (lc.alpha_test) hipLaunchKernelGGL((k_intersect_pair<0, true>), dim3(traversal_blocks(lc, 0, true)), dim3(kBlock), g_lds_pad, lc.stream, S, ro, rd, n_ptr, work, hit, hit_node, sro, srd, sn_ptr, swork, occ);
-        else hipLaunchKernelGGL((k_intersect_pair<0, false>), dim3(traversal_blocks(lc, 0, false)), dim3(kBlock), g_lds_pad, lc.stream, S, ro, rd, n_ptr, work, hit, hit_node, sro, srd, sn_ptr, swork, occ);
-#ifndef CTL_FLAT_EXPERIMENTS
-    } else if (S.flat_format == kFmtQ8) {
-        if (lc.alpha_test) hipLaunchKernelGGL((k_intersect_pair<4, true>), dim3(traversal_blocks(lc, 4, true)), dim3(kBlock), g_lds_pad, lc.stream, S, ro, rd, n_ptr, work, hit, hit_node, sro, srd, sn_ptr, swork, occ);
-        else hipLaunchKernelGGL((k_intersect_pair<4, false>), dim3(traversal_blocks(lc, 4, false)), dim3(kBlock), g_lds_pad, lc.stream, S, ro, rd, n_ptr, work, hit, hit_node, sro, srd, sn_ptr, swork, occ);
-#endif
-    } else {
-        if (lc.alpha_test) hipLaunchKernelGGL((k_intersect_pair<1, true>), dim3(traversal_blocks(lc, 1, true)), dim3(kBlock), g_lds_pad, lc.stream, S, ro, rd, n_ptr, work, hit, hit_node, sro, srd, sn_ptr, swork, occ);
-        else hipLaunchKernelGGL((k_intersect_pair<1, false>), dim3(traversal_blocks(lc, 1, false)), dim3(kBlock), g_lds_pad, lc.stream, S, ro, rd, n_ptr, work, hit, hit_node, sro, srd, sn_ptr, swork, occ);
-    }
+    with_traversal_kernel(lc, S, [&](auto layout, auto alpha) {
+        constexpr int L = decltype(layout)::value; constexpr bool A = decltype(alpha)::value;
+        hipLaunchKernelGGL((k_intersect_pair<L, A>), dim3(traversal_blocks(lc, L, A)), dim3(kBlock), g_lds_pad, lc.stream, S, ro, rd, n_ptr, work, hit, hit_node, sro, srd, sn_ptr, swork, occ);
+    });
 }
 void launch_intersect_count(const launch_ctx& lc, const dev_scene& S, const float4* ro, const float4* rd, const uint32_t* n_ptr, uint32_t* work, float4* hit, int* hit_node,
                             uint32_t* occ, int any_hit, unsigned long long* counts3) {
-    if (any_hit) CTL_LAUNCH_INTERSECT(true, true, S, ro, rd, n_ptr, work, hit, hit_node, occ, counts3);
-    else CTL_LAUNCH_INTERSECT(false, true, S, ro, rd, n_ptr, work, hit, hit_node, (uint32_t*)nullptr, counts3);
+    if (any_hit) launch_intersect<true, true>(lc, S, ro, rd, n_ptr, work, hit, hit_node, occ, counts3);
+    else launch_intersect<false, true>(lc, S, ro, rd, n_ptr, work, hit, hit_node, nullptr, counts3);
 }
 // ---- material sort: counting sort of the path slots by the BSDF model they hit (16 buckets), between intersection and shading
 __global__ __launch_bounds__(kBlock) void k_mat_count(dev_scene S, wave_queues Q, int depth) {
@@ -429,21 +382,27 @@ void launch_class_partition(const launch_ctx& lc, const wave_queues& Q, int dept
 // the shade kernel exists in feature-specialised builds (shade_basic.hip / shade_full.hip): a scene that uses only the basic
 // material / light / texture set runs the variant whose code does not carry the registers of the rest (dev_scene::shade_features)
 void launch_shade(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image) {
-    if (S.shade_features == 0) { if (P.wavefront_rules) launch_shade_basic_wf(lc, S, Q, P, depth, image); else launch_shade_basic(lc, S, Q, P, depth, image); return; }
-    if (P.model_classes) {   // one launch per model class the scene has (class a also takes the misses): shade_class_*.hip
+    using shade_launch = void (*)(const launch_ctx&, const dev_scene&, const wave_queues&, const pass_params&, int, ctl_pixel_data*);
+    const bool wf = P.wavefront_rules;   // the build of pathIterateKernel's own path rules (shade_*_wf.hip)
+    if (S.shade_features == 0) { (wf ? launch_shade_basic_wf : launch_shade_basic)(lc, S, Q, P, depth, image); return; }
+    if (P.model_classes) {   // one launch per model class the scene has (class a, keys 0, also takes the misses and always runs): shade_class_*.hip
+        static const struct { uint32_t keys; shade_launch launch, launch_wf; } classes[] = {
+            { 0u, launch_shade_class_a, launch_shade_class_a_wf },
+            { CTL_CLASS_B_KEYS, launch_shade_class_b, launch_shade_class_b_wf },
+            { CTL_CLASS_G_KEYS, launch_shade_class_g, launch_shade_class_g_wf },
+            { CTL_CLASS_P_KEYS, launch_shade_class_p, launch_shade_class_p_wf },
+            { CTL_CLASS_C_KEYS, launch_shade_class_c, launch_shade_class_c_wf },
+        };
         launch_class_partition(lc, Q, depth);
-        (P.wavefront_rules ? launch_shade_class_a_wf : launch_shade_class_a)(lc, S, Q, P, depth, image);
-        if (S.shade_models & CTL_CLASS_B_KEYS) (P.wavefront_rules ? launch_shade_class_b_wf : launch_shade_class_b)(lc, S, Q, P, depth, image);
-        if (S.shade_models & CTL_CLASS_G_KEYS) (P.wavefront_rules ? launch_shade_class_g_wf : launch_shade_class_g)(lc, S, Q, P, depth, image);
-        if (S.shade_models & CTL_CLASS_P_KEYS) (P.wavefront_rules ? launch_shade_class_p_wf : launch_shade_class_p)(lc, S, Q, P, depth, image);
-        if (S.shade_models & CTL_CLASS_C_KEYS) (P.wavefront_rules ? launch_shade_class_c_wf : launch_shade_class_c)(lc, S, Q, P, depth, image);
+        for (const auto& c : classes)
+            if (!c.keys || (S.shade_models & c.keys)) (wf ? c.launch_wf : c.launch)(lc, S, Q, P, depth, image);
         return;
     }
     if (P.sort_materials) {
         hipLaunchKernelGGL(k_mat_count, dim3(lc.grid_blocks), dim3(kBlock), 0, lc.stream, S, Q, depth);
         hipLaunchKernelGGL(k_mat_scatter, dim3(lc.grid_blocks), dim3(kBlock), 0, lc.stream, Q, depth);
     }
-    if (P.wavefront_rules) launch_shade_full_wf(lc, S, Q, P, depth, image); else launch_shade_full(lc, S, Q, P, depth, image);
+    (wf ? launch_shade_full_wf : launch_shade_full)(lc, S, Q, P, depth, image);
 }
 void launch_finalize(const launch_ctx& lc, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image) {
     hipLaunchKernelGGL(k_finalize, dim3(lc.grid_blocks), dim3(kBlock), 0, lc.stream, Q, P, depth, image);

@@ -2,10 +2,30 @@
 // one kernel build each: the default follows PathTrace<DIRECT> (Integrators/PathTracer.cu:10-113) — what the reference's deterministic megakernel renders and the
 // oracle pins; CTL_SHADE_WAVEFRONT_RULES follows pathIterateKernel's own rules (tracer parameter PathSemantics = Wavefront): Russian roulette before sampling at
 // pathDepth >= RRStartDepth, no sampling and no next-event estimation at the last bounce, sampleEmitterDirect with one 2-D sample drawn after the BSDF sample, the
-// 16-bit previous normal, the t >= dDist (1 - eps) shadow rule.  Compiled once per feature set: the including file defines CTL_SHADE_FEATURES (bit mask, shading.h),
-// CTL_SHADE_BLOCK (workgroup size: 1024 caps the kernel at 128 VGPRs, 512 at 256), CTL_SHADE_KERNEL and CTL_SHADE_LAUNCH.
+// 16-bit previous normal, the t >= dDist (1 - eps) shadow rule.  Compiled once per feature set: the including file (shade_*.hip) defines CTL_SHADE_NAME, CTL_SHADE_FEATURES
+// (bit mask, shading.h), CTL_SHADE_BLOCK (workgroup size: 1024 caps the kernel at 128 VGPRs, 512 at 256) and, where it holds the register allocation, CTL_SHADE_WAVES.
 #ifndef CTL_SHADE_WAVEFRONT_RULES
 #define CTL_SHADE_WAVEFRONT_RULES 0
+#endif
+// kernel k_shade_<name> and its launch function launch_shade_<name>, both with a _wf suffix in a build with CTL_SHADE_WAVEFRONT_RULES (kernels.h declares the launch functions)
+#define CTL_SHADE_CAT_(a, b, c) a##b##c
+#define CTL_SHADE_CAT(a, b, c) CTL_SHADE_CAT_(a, b, c)
+#if CTL_SHADE_WAVEFRONT_RULES
+#define CTL_SHADE_KERNEL CTL_SHADE_CAT(k_shade_, CTL_SHADE_NAME, _wf)
+#define CTL_SHADE_LAUNCH CTL_SHADE_CAT(launch_shade_, CTL_SHADE_NAME, _wf)
+#else
+#define CTL_SHADE_KERNEL CTL_SHADE_CAT(k_shade_, CTL_SHADE_NAME, )
+#define CTL_SHADE_LAUNCH CTL_SHADE_CAT(launch_shade_, CTL_SHADE_NAME, )
+#endif
+// CTL_SHADE_WAVES: the waves per SIMD the register allocation is held to (undefined or 0: the compiler's choice under __launch_bounds__)
+#if defined(CTL_SHADE_WAVES) && CTL_SHADE_WAVES > 0
+#define CTL_SHADE_ATTR __attribute__((amdgpu_waves_per_eu(CTL_SHADE_WAVES, CTL_SHADE_WAVES)))
+#else
+#define CTL_SHADE_ATTR
+#endif
+#ifndef CTL_SHADE_LDS_TABLES
+// KB of LDS for the emitter records + anim blob (shading.h scene_lights / scene_anim; + 4 KB for the normal table): synthetic-SM shade 1.447 -> 1.356 ms per pass
+#define CTL_SHADE_LDS_TABLES 12
 #endif
 // A model-class build (shade_class_*.hip) defines CTL_SHADE_KEYS: bit k = this launch shades the vertices whose traversal key (Q.mat_key: the BSDF model of the hit, 0 = miss) is k;
 // CTL_SHADE_MODELS (shading.h), the models its dispatch switches carry, defaults to the same set (the nesting class carries all: a coating's inner model can be any).
@@ -16,6 +36,11 @@
 #endif
 #ifdef CTL_SHADE_CLASS   // index of the slot list this build reads (wave_queues::class_order)
 #define CTL_SHADE_CLASSED 1
+// ctl_math.h: one out-of-line copy of each transcendental function instead of one per call site (class b: 293 -> 159 KB of code against a 64-KB instruction cache)
+#define CTL_FMATH_OUTLINE
+// shading.h: no out-of-line emitter function takes the scene by reference — out of line they cost a private copy of the dev_scene argument (496 B of scratch per lane,
+// read back with vector loads): synthetic-bathroom shade 2.52 -> 2.26 ms per pass
+#define CTL_LIGHT_INLINE
 #else
 #define CTL_SHADE_CLASSED 0
 #endif
@@ -28,9 +53,6 @@ namespace ctl {
 
 // ------------------------------------------------------------------------------------------------ shading
 // One lane = one queued path vertex.  `depth` is the megakernel's 1-based depth of this vertex.
-#ifndef CTL_SHADE_ATTR
-#define CTL_SHADE_ATTR
-#endif
 __global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERNEL(dev_scene S, wave_queues Q, pass_params P, int depth, ctl_pixel_data* __restrict__ image) {
     __shared__ uint32_t s_cnt[17][kWideBlock / 64]; __shared__ uint32_t s_base[3];
 #if CTL_SHADE_LDS_TABLES

@@ -272,22 +272,16 @@ Scene::Scene(const ctl_scene_desc& d, bool flatten, int flat_format, bool reduce
     S.hit_key_out = nullptr; S.flat_leaf_keys = 0;
     S.flat_nodes = nullptr; S.flat_leaves = nullptr; S.flat_root = 0; S.flat_format = 0; S.flat_compact = 0; S.inst_w_one = 0; S.flat_top_cached = 0;
     if (flatten) {
-        // node format: Q4 (64-B 4-wide nodes with 8-bit child boxes) unless the caller or $CTL_FLAT_FORMAT asks for F4 / F2 (DESIGN.md §3 has the measurements)
+        // node format: Q4 (64-B 4-wide nodes with 8-bit child boxes) unless the caller or $CTL_FLAT_FORMAT asks for Q8; F4 / F2 are refused (DESIGN.md §3 has the measurements)
         flat_scene F;
         if (flatten_scene(d, F, (size_t)1 << 30, flat_format < 0 ? default_flat_format() : flat_format)) {   // up to 2^30 instanced triangles (64 GiB of leaf entries)
             if (F.stack_need() + 2 > (F.format == kFlatQ8 ? kFlat8StackGroups : kStackSize)) throw std::runtime_error("ctl_scene_create: flattened BVH too deep for the traversal stack");
-#ifndef CTL_FLAT_EXPERIMENTS
-            if (F.format != kFlatQ4 && F.format != kFlatQ8) throw unsupported_error("ctl_scene_create: the F4 / F2 node formats are measurement builds (-DCTL_FLAT_EXPERIMENTS)");
-#else
-            if (F.format == kFlatQ8) throw unsupported_error("ctl_scene_create: a -DCTL_FLAT_EXPERIMENTS build has no kernel for the 8-wide node format");
-#endif
+            if (F.format != kFlatQ4 && F.format != kFlatQ8)
+                throw unsupported_error("ctl_scene_create: the F4 / F2 node formats are flatten-only (ctl_flat_bvh_build / api.FlatBvh): no traversal kernel reads them");
             if (F.format == kFlatQ4) flat_nodes_.upload((const float4*)F.nodes.data(), F.nodes.size() * 4);
-            else if (F.format == kFlatQ8) flat_nodes_.upload((const float4*)F.nodes_q8.data(), F.nodes_q8.size() * 8);
-            else if (F.format == kFlatF4) flat_nodes_.upload((const float4*)F.nodes_f4.data(), F.nodes_f4.size() * 8);
-            else flat_nodes_.upload((const float4*)F.nodes_f2.data(), F.nodes_f2.size() * 4);
+            else flat_nodes_.upload((const float4*)F.nodes_q8.data(), F.nodes_q8.size() * 8);
             for (const flat_leaf& L : F.leaves) if (L.node >= d.n_nodes) throw std::runtime_error("ctl_scene_create: flattened leaf entry out of range");
             S.flat_leaf_keys = 0;
-#ifndef CTL_FLAT_EXPERIMENTS
             // The DEVICE copy of the entries carries the BSDF model of each entry's material in bits 28..31 of its index word (the host arrays, the cache and the oracle's view stay
             // as flatten.cpp made them): a closest-hit traversal leaves it per ray (dev_scene::hit_key_out) and the shade kernel regroups its lanes by it without the
             // hit -> node -> triangle -> material chain of dependent loads that made the regrouping cost more than it won.
@@ -307,7 +301,6 @@ Scene::Scene(const ctl_scene_desc& d, bool flatten, int flat_format, bool reduce
                     const uint32_t tri = (S.flat_leaf_keys ? (L.index & 0x0fffffffu) : L.index) >> 1, mi = d.nodes[L.node].material_offset + ((d.tri_data[tri].nor_mat_extra[1] >> 16) & 0xffu);
                     if (mi >= d.n_materials || d.materials[mi].alpha_state != CTL_ALPHA_DISABLED) L.node |= 0x80000000u;
                 }
-#endif
             F.leaves.emplace_back(); std::memset(&F.leaves.back(), 0, sizeof(flat_leaf)); F.leaves.back().index = 1;   // one spare (closing) entry behind the last leaf
             flat_leaves_.upload((const float4*)F.leaves.data(), F.leaves.size() * 8);
             // every node transform affine with w == 1 exactly (what add_node produces): the kernels skip the load of w and the division by it

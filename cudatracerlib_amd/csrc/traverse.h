@@ -38,10 +38,10 @@ __device__ __forceinline__ uint32_t guided_chunk(uint32_t n, uint32_t last_base)
 }
 
 // A wave's claims from the launch's ray cursor.  The FIRST claim is static — wave w takes rays [w c0, (w + 1) c0), c0 = the guided claim for the whole queue — and only what
-// lies beyond the waves' static shares goes through the cursor (which counts from 0 there).  Round 6: one address serves ~88 atomics per microsecond, a launch has 8192 (7168)
-// waves, and every wave used to open with one claim and end with one that found the cursor past the end — two bursts of ~90 us per queue whatever its size, four per fused
-// launch: the 0.33 ms a near-empty traversal launch took.  A queue of fewer rays than the static shares cover now needs no atomic at all.  (The grid holds exactly the
-// workgroups that are resident together, kernels.hip traversal_blocks: a workgroup that started late would sit on its static share.)
+// lies beyond the waves' static shares goes through the cursor (which counts from 0 there).  Round 6: one address serves ~88 atomics per microsecond, a launch has 6144
+// waves (six 256-lane workgroups per CU; 7168 with 8-wide nodes), and every wave used to open with one claim and end with one that found the cursor past the end —
+// two bursts of ~90 us per queue whatever its size, four per fused launch: the 0.33 ms a near-empty traversal launch took.  A queue of fewer rays than the static shares
+// cover now needs no atomic at all.  (The grid holds exactly the workgroups that are resident together, kernels.hip traversal_blocks: a workgroup that started late would sit on its static share.)
 #ifndef CTL_STATIC_FIRST_CLAIM
 #define CTL_STATIC_FIRST_CLAIM 1
 #endif

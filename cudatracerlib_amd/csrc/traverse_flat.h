@@ -17,14 +17,15 @@
 //    stores (unused ones land in a spare row), the pop is an LDS read issued before the slab arithmetic.
 // Everything that was measured against this and lost — 128-B fp32 and 2-wide node formats, the quad-cooperative node fetch, the top of the tree in LDS, prefetch touches,
 // stack entries with their entry distance, 8 waves per SIMD, and round 4's two structural variants (the 8-wide node format of traverse_flat8.h: 10 % slower; entry tests
-// from a wave-wide LDS queue, experiments/traverse_flat_wq.h: 38-47 % slower) — lives in csrc/experiments/ and builds only with -DCTL_FLAT_EXPERIMENTS / -DCTL_LEAF_QUEUE.
+// from a wave-wide LDS queue: 38-47 % slower) — is recorded in EXPERIMENTS.md and DESIGN.md §3.  The code of the lost arms was deleted; it is in git:
+// `git show 8bbbae7:cudatracerlib_amd/csrc/experiments/traverse_flat_variants.h` (round 2 / 3 arms) and `.../experiments/traverse_flat_wq.h` (the LDS queue).
 #pragma once
 #include "traverse.h"
 #include "flat_slab.h"
 
 namespace ctl {
 
-enum { kFmtQ4 = 0, kFmtF4 = 1, kFmtF2 = 2, kFmtQ8 = 3 };   // = flat_format (flatten.h); Q8 has its own kernel body (traverse_flat8.h), F4 / F2 are experiment builds
+enum { kFmtQ4 = 0, kFmtF4 = 1, kFmtF2 = 2, kFmtQ8 = 3 };   // = flat_format (flatten.h); Q8 has its own kernel body (traverse_flat8.h), F4 / F2 have no traversal kernel
 
 #ifndef CTL_FLAT_LDS_ROWS
 #define CTL_FLAT_LDS_ROWS 23   // round 6: 23 rows + 1 spare = 24 KiB per 256-lane workgroup, SIX workgroups per CU (rounds 3-5: 19 rows, 20 KiB, seven).  Held to six by LDS padding the round-5 kernel
@@ -32,8 +33,7 @@ enum { kFmtQ4 = 0, kFmtF4 = 1, kFmtF2 = 2, kFmtQ8 = 3 };   // = flat_format (fla
                                // one rank of eight 19.86 -> 19.06 ms per 20 passes; 80 VGPRs (6 waves by registers too) the same (profiles/r06_traversal.log)
 #endif
 constexpr int kFlatLdsRows = CTL_FLAT_LDS_ROWS;          // stack entries per lane in LDS (+ 1 spare row); deeper entries live in scratch (19 rows: 0.015 % of the bench rays, profiles/r03a_stack_histogram.log)
-constexpr int kFlatStackInts = 1;
-constexpr int kTopCache = 0, kTopCacheFloats = 12;   // (experiment builds keep the top of the tree in LDS)
+constexpr int kTopCache = 0;   // nodes of the top of the tree kept in LDS: none (the LDS top cache was measured and lost)
 __device__ unsigned long long g_stack_hist[kStackSize];   // counting kernels only: rays by the deepest traversal-stack entry they used (ctl_traversal_stack_histogram)
 __device__ int g_leaf_batch = 20;         // run the leaf phase once this many lanes hold a pending leaf entry (knob CTL_LEAF_BATCH; round 5, on the re-optimised tree: synthetic-SM 12: 3118, 16: 3137, 20: 3143, 24: 3123, 32: 3072 Mrays/s; synthetic-sm-hard 4232 / 4275 / 4382 / 4384 / 4311 — one value serves both, no per-scene choice needed; earlier trees: 8: 2253, 12: 2299, 16: 2315, 20: 2311, 24: 2288, 32: 2216 Mrays/s (profiles/r03_threshold_ab.log)
 

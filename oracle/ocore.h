@@ -248,7 +248,7 @@ inline bool traceRayFlat(const Scene& S, V3 ori, V3 dir, float tmin_tri, float t
     const float* nodes = (const float*)F.nodes; const uint32_t* leaves = (const uint32_t*)F.leaves;
     std::vector<int> stack(4 * (size_t)F.max_depth + 8); int sp = 0; stack[0] = EntrypointSentinel;
     // ORC_STACK_CULL=1 (what-if): every pushed child carries its entry distance and a pop that lies behind the hit found meanwhile is dropped —
-    // the product's -DCTL_STACK_DIST=1 build (csrc/traverse_flat.h), measured and not shipped
+    // the -DCTL_STACK_DIST=1 build of git show 8bbbae7:cudatracerlib_amd/csrc/experiments/traverse_flat_variants.h, measured and not shipped
     std::vector<float> sdist(stack.size(), -INFINITY); static const bool stack_cull = getenv("ORC_STACK_CULL") != nullptr;
     auto pop = [&]() { for (;;) { const int n = stack[sp]; const float dn = sdist[sp]; sp--; if (!stack_cull || !(dn >= res.dist)) return n; } };
     int node = 0; bool found = false;

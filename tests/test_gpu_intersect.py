@@ -92,7 +92,7 @@ def check_flat(gpu, orc, desc, rays, any_hit, fmt):
     return got
 
 
-@pytest.mark.parametrize("fmt", ["q8", "q4"])   # f4 / f2 are measurement builds (-DCTL_FLAT_EXPERIMENTS)
+@pytest.mark.parametrize("fmt", ["q8", "q4"])   # f4 / f2 are flatten-only: no traversal kernel reads them
 @pytest.mark.parametrize("any_hit", [False, True])
 def test_flattened_world_space_bvh(gpu, orc, any_hit, fmt):
     """CTL_SCENE_FLATTEN: one world-space BVH over all instanced triangles, every node format.  The tree only culls — each leaf entry is

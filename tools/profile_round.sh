@@ -3,16 +3,22 @@
 #   tools/profile_round.sh r02a [bench args, default: the driver's --steps 20 --warmup 5]
 # writes gpurun_out/<tag>/{bench.json, stats/, pmc_*/}; tools/summarize_profile.py then condenses them into profiles/<tag>_*.
 # PMC passes are separate runs with --kernel-trace only (never with sys/hip traces).
+# Every step runs under its own time limit, and the first step that fails ends the script (124 / 137: time limit, 134: abort, 139: segfault): nothing more is started on a
+# device that may have faulted.
 set -u
 TAG=${1:-r02}; shift
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 RUN=${*:---steps 20 --warmup 5}
-timeout 900 python bench.py --full $RUN > "$OUT/bench.json" 2> "$OUT/bench.err"
+fail() { echo "profile_round.sh: step $2 ended with exit status $1 (124 / 137: time limit, 134: abort, 139: segfault); see $OUT/$2.*; stopping" >&2; exit "$1"; }
+timeout -k 10 900 python bench.py --full $RUN > "$OUT/bench.json" 2> "$OUT/bench.err" || fail $? bench
 ARGS="--full $RUN --no-cpu-baseline"
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o p -- python bench.py $ARGS > "$OUT/stats.log" 2>&1
-pmc() { local name=$1; shift; timeout 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d "$OUT/pmc_$name" -o p -- python bench.py $ARGS > "$OUT/pmc_$name.log" 2>&1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o p -- python bench.py $ARGS > "$OUT/stats.log" 2>&1 || fail $? stats
+pmc() {
+    local name=$1; shift
+    timeout -k 10 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d "$OUT/pmc_$name" -o p -- python bench.py $ARGS > "$OUT/pmc_$name.log" 2>&1 || fail $? "pmc_$name"
+}
 pmc FETCH_SIZE FETCH_SIZE
 pmc WRITE_SIZE WRITE_SIZE
 pmc TCC TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_128B_sum
