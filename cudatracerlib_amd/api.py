@@ -930,6 +930,18 @@ class PathTracer(WavefrontPathTracer):
     PLUGIN = b"PathTracer"
 
 
+# PathTrace_DrawMode (Integrators/PrimTracer.h:7), in PTDM order: the values of the PrimTracer's DrawingMode parameter
+PathTrace_DrawMode = ("linear_depth", "D3D_depth", "v_absdot_n_geo", "v_dot_n_geo", "v_dot_n_shade", "n_geo_colored", "n_shade_colored", "uv", "bary_coords",
+                      "first_Le", "first_f", "first_f_direct", "first_non_delta_Le", "first_non_delta_f", "first_non_delta_f_direct")
+
+
+class PrimTracer(WavefrontPathTracer):
+    """Integrators/PrimTracer.h:10-27 — PrimTracer : Tracer<false>, IDepthTracer ("direct" in the reference's example program): one sample per pixel at the
+    pixel's own position, the quantity DrawingMode names (PathTrace_DrawMode; default first_f), MaxPathLength (default 7) for the delta chains of the
+    first_non_delta_* modes.  Non-progressive: every pass clears the image, getNumPassesDone() is 1 after any call.  Needs a flattened scene."""
+    PLUGIN = b"PrimTracer"
+
+
 class SequenceGenerator:
     """SamplingSequenceGeneratorHost<IndependantSamplingSequenceGenerator> (Kernel/Sampler.h:36-85)."""
 

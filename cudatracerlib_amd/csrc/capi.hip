@@ -2,6 +2,7 @@
 // error convention, Defines.cpp:15-29) are mapped to ctl_status codes + ctl_last_error().
 #include "../../include/ctl_amd.h"
 #include "tracer.h"
+#include "prim_tracer.h"
 #include "kernels.h"
 #include "scene_builder.h"
 #include "mitsuba_loader.h"
@@ -280,8 +281,9 @@ int ctl_image_write_file(ctl_image* img, float splat_scale, const char* path) { 
 int ctl_tracer_create(const char* plugin, ctl_tracer** out) {
     CTL_REQUIRE(plugin && out, "null argument");
     const bool wave = !std::strcmp(plugin, "WavefrontPathTracer") || !std::strcmp(plugin, "PT_Wave"), mega = !std::strcmp(plugin, "PathTracer") || !std::strcmp(plugin, "PT");   // main.cpp:91-96
-    if (!wave && !mega) return fail(CTL_ERR_UNSUPPORTED, std::string("unknown tracer plugin: ") + plugin);
-    CTL_TRY ctl_tracer* t = new ctl_tracer(); try { if (wave) t->t.reset(new WavefrontPathTracer()); else t->t.reset(new PathTracer()); } catch (...) { delete t; throw; } *out = t; CTL_CATCH
+    const bool prim = !std::strcmp(plugin, "PrimTracer") || !std::strcmp(plugin, "direct");
+    if (!wave && !mega && !prim) return fail(CTL_ERR_UNSUPPORTED, std::string("unknown tracer plugin: ") + plugin);
+    CTL_TRY ctl_tracer* t = new ctl_tracer(); try { if (wave) t->t.reset(new WavefrontPathTracer()); else if (mega) t->t.reset(new PathTracer()); else t->t.reset(new PrimTracer()); } catch (...) { delete t; throw; } *out = t; CTL_CATCH
 }
 void ctl_tracer_destroy(ctl_tracer* t) { delete t; }
 int ctl_tracer_set_param_bool(ctl_tracer* t, const char* key, int value) { CTL_REQUIRE(t && key, "null argument"); CTL_TRY t->t->getParameters().setValue(key, value ? 1 : 0, TracerParameter::Bool); CTL_CATCH }

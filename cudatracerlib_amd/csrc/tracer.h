@@ -144,7 +144,7 @@ public:
     // TracerBase::Debug(Image*, pixel) (Kernel/Tracer.h:119-123): UpdateKernel draws the NEXT set of sampling tables from the tracer's generator (so the following
     // DoPass uses the set after it), then DebugInternal follows one path for that pixel.  rgb (may be null): the radiance of that path (the reference discards it)
     virtual void Debug(Image* I, unsigned int x, unsigned int y, float rgb[3]) = 0;
-    // IDepthTracer::setDepthBuffer (Kernel/Tracer.h:34-57): a device buffer of w x h floats that receives the normalised depth of every primary hit
+    // IDepthTracer::setDepthBuffer (Kernel/Tracer.h:34-57; the wavefront plugin and the PrimTracer, prim_tracer.h): a device buffer of w x h floats that receives the normalised depth of every primary hit
     virtual void setDepthBuffer(float* device_data, unsigned int dw, unsigned int dh);   // default: refuses (the tracer is not an IDepthTracer)
     virtual void reservePasses(unsigned int n) { (void)n; }   // size the queues now for a DoPasses(n) to come (otherwise they grow inside that call)
     void setTileShard(uint32_t rank, uint32_t world) { if (world == 0 || rank >= world) throw std::runtime_error("bad tile shard"); shard_rank = rank; shard_world = world; if (w != 0xffffffffu) Resize(w, h); }

@@ -483,6 +483,8 @@ template <bool PROGRESSIVE> void Tracer<PROGRESSIVE>::Debug(Image* I, unsigned i
     CTL_HIP(hipStreamSynchronize(stream));
     if (rgb) { rgb[0] = out[0]; rgb[1] = out[1]; rgb[2] = out[2]; }
 }
+// Tracer<false> (the PrimTracer) does not use this body: its pass loop, Debug and table staging are explicit specialisations in prim_tracer.hip, so a fix to the
+// pass loop here may be due there too.  Only Tracer<true> is instantiated from this template.
 template <bool PROGRESSIVE> void Tracer<PROGRESSIVE>::DoPasses(Image* I, bool a_NewTrace, unsigned int n) {
     if (!m_pScene) throw std::runtime_error("DoPass: InitializeScene was not called");
     if (w == 0xffffffffu) throw std::runtime_error("DoPass: Resize was not called");

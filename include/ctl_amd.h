@@ -452,7 +452,8 @@ int ctl_image_unpack_tiles(ctl_image* img, uint32_t world, const void* host_in_a
 
 /* ------------------------------------------------------------------- tracer */
 typedef struct ctl_tracer ctl_tracer;
-/* plugin names: "WavefrontPathTracer" (Integrators/PseudoRealtime/WavefrontPathTracer.h:24). */
+/* plugin names: "WavefrontPathTracer" / "PT_Wave" (Integrators/PseudoRealtime/WavefrontPathTracer.h:24), "PathTracer" / "PT" (Integrators/PathTracer.h:7),
+ * "PrimTracer" / "direct" (Integrators/PrimTracer.h:10: non-progressive, one sample per pixel, parameters DrawingMode (enum, 15 names) and MaxPathLength). */
 int ctl_tracer_create(const char* plugin, ctl_tracer** out);
 void ctl_tracer_destroy(ctl_tracer* t);
 /* TracerParameterCollection (Kernel/TracerSettings.h:221-350): keys Direct(bool), MaxPathLength(int>=1),
@@ -482,7 +483,7 @@ int ctl_tracer_do_passes(ctl_tracer* t, ctl_image* img, int new_trace, uint32_t 
 int ctl_tracer_debug_pixel(ctl_tracer* t, ctl_image* img, uint32_t x, uint32_t y, float* rgb_out);
 /* IDepthTracer::setDepthBuffer(DeviceDepthImage{m_pData, w, h}) (Kernel/Tracer.h:16-57; WavefrontPathTracer : IDepthTracer): device_depth = width*height floats in
  * DEVICE memory (ctl_device_malloc); every pass stores DeviceDepthImage::NormalizeDepthD3D of the primary hit distance of pixel (x, y) — clamped to the camera's
- * [near, far], 1 for a miss — as pathIterateKernel does at pathDepth 0 (WavefrontPathTracer.cu:76-77).  NULL, 0, 0 removes it.  Wavefront plugin only. */
+ * [near, far], 1 for a miss — as pathIterateKernel does at pathDepth 0 (WavefrontPathTracer.cu:76-77).  NULL, 0, 0 removes it.  Wavefront and PrimTracer plugins. */
 int ctl_tracer_set_depth_buffer(ctl_tracer* t, float* device_depth, uint32_t width, uint32_t height);
 /* traversal statistics for the roofline: sums over rays of inner-node visits, triangle tests and instance entries
  * (B_ray = 32 + 16 + 64*N_inner + 52*N_tri + 108*N_inst). */
