@@ -120,5 +120,12 @@ __host__ __device__ inline uint32_t shard_pixel_count(uint32_t W, uint32_t H, ui
     uint32_t mine = nt / world + ((rank < nt % world) ? 1u : 0u);
     return mine * 64u * 64u;   // upper bound incl. clipped pixels; clipped lanes generate no path
 }
+// the film pixel (x, y) of local pixel index li of a tile shard, in tile order: the rank's 64x64 tiles one after the other, 8x8 micro-tiles inside = one wave.
+// tiles_x = (film width + 63) / 64.  Returns the tile.  (k_resolve_stage and comm.cpp walk a tile row-major instead.)
+__device__ __forceinline__ uint32_t tile_order_pixel(uint32_t tiles_x, uint32_t tile_rank, uint32_t tile_world, uint32_t li, uint32_t& x, uint32_t& y) {
+    const uint32_t tile = tile_rank + (li >> 12) * tile_world, p = li & 4095u, micro = p >> 6, ln = p & 63u;
+    x = (tile % tiles_x) * 64 + (micro & 7u) * 8 + (ln & 7u); y = (tile / tiles_x) * 64 + (micro >> 3) * 8 + (ln >> 3);
+    return tile;
+}
 
 } // namespace ctl

@@ -25,8 +25,7 @@ __global__ __launch_bounds__(kWideBlock) void k_raygen(dev_scene S, wave_queues 
     const uint32_t n1 = CTL_SAMPLER_NUM_SEQUENCES * CTL_SAMPLER_SEQUENCE_LENGTH;
     for (uint32_t gi = blockIdx.x * kWideBlock + threadIdx.x; gi < n_total; gi += gridDim.x * kWideBlock) {   // n_total is a multiple of 4096
         const uint32_t pass_b = gi / P.n_local_pixels, li = gi - pass_b * P.n_local_pixels;
-        const uint32_t tile = P.tile_rank + (li >> 12) * P.tile_world, p = li & 4095u, micro = p >> 6, lane = p & 63u;
-        const uint32_t x = (tile % tiles_x) * 64 + (micro & 7u) * 8 + (lane & 7u), y = (tile / tiles_x) * 64 + (micro >> 3) * 8 + (lane >> 3);
+        uint32_t x, y; const uint32_t tile = tile_order_pixel(tiles_x, P.tile_rank, P.tile_world, li, x, y);
         // BlockSamplerBuffer::getNumSamplesPerPixel (WavefrontPathTracer.cu:31-36): 0, 1 or more samples, all drawn from the pixel's one sampler
         const uint32_t n_smp = P.block_counts ? P.block_counts[tile] : 1u, max_smp = P.block_counts ? P.max_block_count : 1u;
         for (uint32_t smp = 0; smp < max_smp; smp++) {

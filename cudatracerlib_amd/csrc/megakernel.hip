@@ -13,7 +13,8 @@
 
 namespace ctl {
 
-// single_stack_column, trace_single, light_sample_position and env_eval_differential: single_ray.h (shared with prim_tracer.hip)
+// single_stack_column, trace_single, light_sample_position and env_eval_differential: single_ray.h (shared with prim_tracer.hip); the tile order of the pixels:
+// kernels.h tile_order_pixel
 
 // pathKernel2<DIRECT> + PathTrace<DIRECT> (Integrators/PathTracer.cu:182-194, 10-113), no participating media
 #ifndef CTL_MEGA_WAVES
@@ -26,8 +27,7 @@ __global__ __launch_bounds__(256, CTL_MEGA_WAVES) void k_path_trace(dev_scene S,
     unsigned long long rays = 0;
     for (uint32_t gi = blockIdx.x * 256u + threadIdx.x; gi < n_total; gi += gridDim.x * 256u) {
         const uint32_t pass_b = gi / P.n_local_pixels, li = gi - pass_b * P.n_local_pixels;
-        const uint32_t tile = P.tile_rank + (li >> 12) * P.tile_world, p = li & 4095u, micro = p >> 6, ln = p & 63u;
-        const uint32_t x_ = (tile % tiles_x) * 64 + (micro & 7u) * 8 + (ln & 7u), y_ = (tile / tiles_x) * 64 + (micro >> 3) * 8 + (ln >> 3);
+        uint32_t x_, y_; tile_order_pixel(tiles_x, P.tile_rank, P.tile_world, li, x_, y_);
         if (P.debug_out && gi != 0) break;
         const uint32_t x = P.debug_out ? P.debug_x : x_, y = P.debug_out ? P.debug_y : y_;
         if (x >= P.width || y >= P.height) continue;
@@ -139,8 +139,7 @@ __global__ __launch_bounds__(256) void k_path_trace_regularization(dev_scene S, 
     unsigned long long rays = 0;
     for (uint32_t gi = blockIdx.x * 256u + threadIdx.x; gi < n_total; gi += gridDim.x * 256u) {
         const uint32_t pass_b = gi / P.n_local_pixels, li = gi - pass_b * P.n_local_pixels;
-        const uint32_t tile = P.tile_rank + (li >> 12) * P.tile_world, p = li & 4095u, micro = p >> 6, ln = p & 63u;
-        const uint32_t x = (tile % tiles_x) * 64 + (micro & 7u) * 8 + (ln & 7u), y = (tile / tiles_x) * 64 + (micro >> 3) * 8 + (ln >> 3);
+        uint32_t x, y; tile_order_pixel(tiles_x, P.tile_rank, P.tile_world, li, x, y);
         if (x >= P.width || y >= P.height) continue;
         sampler rng{ P.t1 + pass_b * n1, P.t2 + pass_b * n1, y * P.width + x, 0, 0 };
         const f2 j = rng.next2();
@@ -221,8 +220,7 @@ PathTracer::PathTracer() {
     m_sParameters.addBool("Regularization", false);               // PathTraceRegularization (k_path_trace_regularization)
     m_sParameters.addInterval("MaxPathLength", 50, 1, INT_MAX);
     m_sParameters.addInterval("RRStartDepth", 5, 1, INT_MAX);
-    int dev = 0; hipDeviceProp_t prop; CTL_HIP(hipGetDevice(&dev)); CTL_HIP(hipGetDeviceProperties(&prop, dev));
-    grid_blocks = prop.multiProcessorCount * 8;
+    grid_blocks = persistent_grid_blocks();
 }
 void PathTracer::InitializeScene(Scene* s) {
     if (!s->S.flat_nodes) throw unsupported_error("PathTracer (megakernel): the scene must be created with CTL_SCENE_FLATTEN");

@@ -1,14 +1,8 @@
-// prim_tracer.h — the PrimTracer plugin's host class (prim_tracer.hip); Tracer<false>'s pass loop, Debug and table staging are defined there too.
+// prim_tracer.h — the PrimTracer plugin's host class (prim_tracer.hip); its pass loop, Debug and table staging are Tracer<false>'s, from the template in tracer.hip.
 #pragma once
 #include "tracer.h"
 
 namespace ctl {
-
-// Tracer<false> (Kernel/Tracer.h:209-248 with PROGRESSIVE = false), defined in prim_tracer.hip: every pass starts from a cleared image, one pass per DoRender,
-// m_uPassesDone is 1 after any call, no block sampler (BlockSamplerType is accepted and changes nothing, as in the reference)
-template <> void Tracer<false>::ensureTableRing(unsigned int B);
-template <> void Tracer<false>::Debug(Image* I, unsigned int x, unsigned int y, float rgb[3]);
-template <> void Tracer<false>::DoPasses(Image* I, bool a_NewTrace, unsigned int n);
 
 // Integrators/PrimTracer.h:10-27 — PrimTracer : Tracer<false>, IDepthTracer (prim_tracer.hip): one non-progressive pass per call, 15 drawing modes
 class PrimTracer : public Tracer<false> {

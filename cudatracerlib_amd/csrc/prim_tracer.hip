@@ -12,7 +12,6 @@
 #include "single_ray.h"
 #include "mitsuba_loader.h"   // unsupported_error
 #include <climits>
-#include <cstring>
 
 namespace ctl {
 
@@ -30,12 +29,10 @@ struct prim_params {
     float* debug_out; uint32_t debug_x, debug_y;      // DebugInternal: one pixel, its L written here instead of the image
 };
 
-// local pixel index -> film pixel, the tile order of k_raygen / k_path_trace (tile shards of 64x64 tiles, 8x8 micro-tiles = one wave)
+// local pixel index -> film pixel, the tile order of k_raygen / k_path_trace (kernels.h); Debug: the one pixel asked for
 __device__ __forceinline__ void prim_pixel(const prim_params& P, uint32_t li, uint32_t& x, uint32_t& y) {
     if (P.debug_out) { x = P.debug_x; y = P.debug_y; return; }
-    const uint32_t tiles_x = (P.width + 63) / 64;
-    const uint32_t tile = P.tile_rank + (li >> 12) * P.tile_world, p = li & 4095u, micro = p >> 6, ln = p & 63u;
-    x = (tile % tiles_x) * 64 + (micro & 7u) * 8 + (ln & 7u); y = (tile / tiles_x) * 64 + (micro >> 3) * 8 + (ln >> 3);
+    tile_order_pixel((P.width + 63) / 64, P.tile_rank, P.tile_world, li, x, y);
 }
 // rng = g_SamplerData(y * w + x); sampleRayDifferential(r, rX, rY, Vec2f(x, y), rng.randomFloat2()) — no sub-pixel jitter, the first draw is the aperture sample
 __device__ __forceinline__ sampler prim_camera_ray(const dev_scene& S, const prim_params& P, uint32_t x, uint32_t y, f3& o, f3& d, f3& ox, f3& dx, f3& oy, f3& dy) {
@@ -206,80 +203,6 @@ __global__ __launch_bounds__(256) void k_prim_shade(dev_scene S, prim_params P, 
     if ((threadIdx.x & 63) == 0 && rays) atomicAdd(ray_count, rays);
 }
 
-// ------------------------------------------------------------------------------------------------ Tracer<false>
-// One table set in HBM and its pinned staging; B is always 1 here
-template <> void Tracer<false>::ensureTableRing(unsigned int B) {
-    (void)B;
-    const size_t n1 = (size_t)CTL_SAMPLER_NUM_SEQUENCES * CTL_SAMPLER_SEQUENCE_LENGTH, n2 = n1 * 2;
-    if (d_t1.n < n1) { d_t1.alloc(n1); d_t2.alloc(n2); }
-    if (h_cap < n1) {
-        CTL_HIP(hipHostMalloc((void**)&h_t1, n1 * sizeof(float))); CTL_HIP(hipHostMalloc((void**)&h_t2, n2 * sizeof(float)));
-        h_cap = n1;
-    }
-    if (starts_cap < 1) {
-        CTL_HIP(hipHostMalloc((void**)&h_starts, sizeof(sequence_generator::pass_start)));
-        d_starts.alloc(sizeof(sequence_generator::pass_start) / sizeof(uint32_t));
-        starts_cap = 1;
-    }
-    if (!d_jumps.p) {
-        const std::vector<uint32_t>& J = sequence_generator::chunk_jump_matrices();
-        d_jumps.alloc(J.size()); CTL_HIP(hipMemcpy(d_jumps.p, J.data(), J.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-}
-// the next table set into d_t1 / d_t2: the caller's (setSamplerTables) or the next of the tracer's XORWOW stream (UpdateKernel, Kernel/TraceHelper.cu:182-185).
-// The stream is idle when this runs (every pass and every Debug ends with a synchronisation), so the pinned staging can be rewritten.
-static void next_tables(hipStream_t stream, std::vector<float>& user_t1, std::vector<float>& user_t2, bool& have_user_tables, float* h_t1, float* h_t2,
-                        sequence_generator& gen, sequence_generator::pass_start* h_starts, uint32_t* d_starts, const uint32_t* d_jumps, float* d_t1, float* d_t2) {
-    const size_t n1 = (size_t)CTL_SAMPLER_NUM_SEQUENCES * CTL_SAMPLER_SEQUENCE_LENGTH, n2 = n1 * 2;
-    if (have_user_tables) {
-        std::memcpy(h_t1, user_t1.data(), n1 * 4); std::memcpy(h_t2, user_t2.data(), n2 * 4); have_user_tables = false;
-        CTL_HIP(hipMemcpyAsync(d_t1, h_t1, n1 * 4, hipMemcpyHostToDevice, stream)); CTL_HIP(hipMemcpyAsync(d_t2, h_t2, n2 * 4, hipMemcpyHostToDevice, stream));
-    } else {
-        gen.take_pass_starts(1, h_starts);
-        CTL_HIP(hipMemcpyAsync(d_starts, h_starts, sizeof(sequence_generator::pass_start), hipMemcpyHostToDevice, stream));
-        launch_sequence_fill(stream, d_jumps, d_starts, 1, d_t1, d_t2);
-        CTL_HIP(hipGetLastError());
-    }
-}
-template <> void Tracer<false>::Debug(Image* I, unsigned int x, unsigned int y, float rgb[3]) {   // TracerBase::Debug (Kernel/Tracer.h:119-123)
-    if (!m_pScene) throw std::runtime_error("Debug: InitializeScene was not called");
-    if (w == 0xffffffffu) throw std::runtime_error("Debug: Resize was not called");
-    if (x >= w || y >= h) throw std::runtime_error("Debug: pixel outside the film");
-    ensureTableRing(1);
-    next_tables(stream, user_t1, user_t2, have_user_tables, h_t1, h_t2, m_SamplingSequenceGenerator, h_starts, d_starts.p, d_jumps.p, d_t1.p, d_t2.p);
-    float out[3] = { 0, 0, 0 };
-    DebugInternal(I, x, y, d_t1.p, d_t2.p, out);
-    CTL_HIP(hipStreamSynchronize(stream));
-    if (rgb) { rgb[0] = out[0]; rgb[1] = out[1]; rgb[2] = out[2]; }
-}
-template <> void Tracer<false>::DoPasses(Image* I, bool a_NewTrace, unsigned int n) {
-    (void)a_NewTrace;   // every pass of a non-progressive tracer is a new trace
-    if (!m_pScene) throw std::runtime_error("DoPass: InitializeScene was not called");
-    if (w == 0xffffffffu) throw std::runtime_error("DoPass: Resize was not called");
-    if (I->getWidth() != w || I->getHeight() != h) throw std::runtime_error("DoPass: image size differs from the tracer size");
-    if (n == 0) return;
-    m_uPassesDone = 0; m_uAccNumRaysTraced = 0; m_fAccRuntime = 0;
-    ensureTableRing(1);
-    for (int i = 0; i < 5; i++) kernel_ms[i] = 0;
-    intersect_rays = intersect_launches = shadow_rays = shadow_launches = fused_launches = fused_shadow_rays = fused_closest_rays = 0;
-    CTL_HIP(hipEventRecord(start, stream));
-    for (unsigned int k = 0; k < n; k++) {
-        I->Clear();   // the stream is idle: the previous pass ended with a synchronisation
-        next_tables(stream, user_t1, user_t2, have_user_tables, h_t1, h_t2, m_SamplingSequenceGenerator, h_starts, d_starts.p, d_jumps.p, d_t1.p, d_t2.p);
-        m_uPassesDone = 1;
-        DoRender(I, d_t1.p, d_t2.p, 1);
-    }
-    CTL_HIP(hipEventRecord(stop, stream));
-    CTL_HIP(hipEventSynchronize(stop));
-    CTL_HIP(hipGetLastError());
-    float ms = 0; CTL_HIP(hipEventElapsedTime(&ms, start, stop));
-    timer.collect(kernel_ms);
-    m_fLastRuntime = ms / 1000.0f;
-    takeRayCounts(intersect_rays, shadow_rays);
-    m_uLastNumRaysTraced = intersect_rays + shadow_rays;
-    m_fAccRuntime += m_fLastRuntime; m_uAccNumRaysTraced += m_uLastNumRaysTraced;
-}
-
 // ------------------------------------------------------------------------------------------------ PrimTracer
 static const std::vector<std::string>& prim_mode_names() {
     static const std::vector<std::string> n = { "linear_depth", "D3D_depth", "v_absdot_n_geo", "v_dot_n_geo", "v_dot_n_shade", "n_geo_colored", "n_shade_colored", "uv", "bary_coords",
@@ -289,8 +212,7 @@ static const std::vector<std::string>& prim_mode_names() {
 PrimTracer::PrimTracer() {
     m_sParameters.addEnum("DrawingMode", kFirstF, prim_mode_names());   // PrimTracer.cu:244-248
     m_sParameters.addInterval("MaxPathLength", 7, 1, INT_MAX);
-    int dev = 0; hipDeviceProp_t prop; CTL_HIP(hipGetDevice(&dev)); CTL_HIP(hipGetDeviceProperties(&prop, dev));
-    grid_blocks = prop.multiProcessorCount * 8;   // the traversal's persistent grid, as the wavefront plugin sizes it
+    grid_blocks = persistent_grid_blocks();   // the traversal's persistent grid, as the wavefront plugin sizes it
 }
 void PrimTracer::InitializeScene(Scene* s) {
     if (!s->S.flat_nodes) throw unsupported_error("PrimTracer: the scene must be created with CTL_SCENE_FLATTEN");

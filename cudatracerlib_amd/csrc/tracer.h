@@ -196,6 +196,8 @@ protected:
     void ensureTableRing(unsigned int B);   // device + pinned host staging for `kTableRing` batches of B passes
 public:
     ~Tracer() override { if (h_t1) (void)hipHostFree(h_t1); if (h_t2) (void)hipHostFree(h_t2); if (h_starts) (void)hipHostFree(h_starts); for (auto e : slot_done) (void)hipEventDestroy(e); }
+private:
+    void stageTables(unsigned int slot, unsigned int B, unsigned int nb);   // the tables of nb passes into ring slot `slot`: the caller's first, then the tracer's stream
 };
 
 // Integrators/PseudoRealtime/WavefrontPathTracer.h:24-67
@@ -238,6 +240,7 @@ private:
 
 int device_count();
 void require_device();
+int persistent_grid_blocks();   // grid of the persistent kernels: 8 x 256-thread workgroups per CU of the current device = 32 waves per CU
 
 // comm.cpp: the framebuffer reduce of a multi-GPU render over RCCL (ctl_comm_* in include/ctl_amd.h)
 struct Comm;

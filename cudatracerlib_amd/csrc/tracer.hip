@@ -1,4 +1,4 @@
-// tracer.hip — host side of the plugin: scene upload / re-layout, Image, the Tracer<true> pass loop and the
+// tracer.hip — host side of the plugin: scene upload / re-layout, Image, the Tracer<PROGRESSIVE> pass loop and the
 // WavefrontPathTracer bounce loop (Integrators/PseudoRealtime/WavefrontPathTracer.cu:166-191 re-designed:
 // no host synchronisation inside a pass — queue lengths stay on the device).
 #include "tracer.h"
@@ -24,6 +24,7 @@ void throw_hip(hipError_t e, const char* file, int line) {   // ThrowCudaErrors 
 }
 int device_count() { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) return 0; return n; }
 void require_device() { if (device_count() <= 0) throw hip_error("no HIP device: the MI355X path tracer has no CPU fallback"); apply_tuning_from_env(); }
+int persistent_grid_blocks() { int dev = 0; hipDeviceProp_t prop; CTL_HIP(hipGetDevice(&dev)); CTL_HIP(hipGetDeviceProperties(&prop, dev)); return prop.multiProcessorCount * 8; }
 
 // ------------------------------------------------------------------------------------------------ Scene
 Scene::Scene(const ctl_scene_desc& d, bool flatten, int flat_format, bool reduced_rough_transmittance) {
@@ -403,7 +404,7 @@ void event_timer::collect(double ms_out[5]) {
     used_.clear();
 }
 
-// ------------------------------------------------------------------------------------------------ TracerBase / Tracer<true>
+// ------------------------------------------------------------------------------------------------ TracerBase / Tracer<PROGRESSIVE>
 TracerBase::TracerBase() {
     require_device();
     m_sParameters.addEnum("BlockSamplerType", 0, { "Uniform", "Variance", "Difference", "Select" });   // Tracer.cpp:19 (BlockSamplerTypes::Uniform), an enum parameter as there
@@ -462,40 +463,54 @@ template <bool PROGRESSIVE> void Tracer<PROGRESSIVE>::ensureTableRing(unsigned i
     }
 }
 void TracerBase::setDepthBuffer(float*, unsigned int, unsigned int) { throw unsupported_error("setDepthBuffer: this tracer is not an IDepthTracer (only the WavefrontPathTracer is, WavefrontPathTracer.h:24)"); }
+// The sampler tables of the nb passes of ring slot `slot` (batches of B passes): the caller's tables (setSamplerTables) serve the first of them, the tracer's XORWOW
+// stream the rest (UpdateKernel -> GenerateNewRandomSequences, Kernel/TraceHelper.cu:182-185).  One stream as in the reference (Kernel/Sampler.h:57-85): the host only
+// advances it (one GF(2) jump per pass); the tables are written in HBM by k_sequence_fill — 256 lanes per pass, each two jumps and 1440 draws from the pass's start
+// state — in the time the host threads needed for one pass, and without the 1.5 MB-per-pass upload (measured: 1.9 ms at the head of every 20-pass call -> 0.1 ms).
+// The slot's staging must be idle: the batch that last used it has finished.
+template <bool PROGRESSIVE> void Tracer<PROGRESSIVE>::stageTables(unsigned int slot, unsigned int B, unsigned int nb) {
+    const size_t n1 = (size_t)CTL_SAMPLER_NUM_SEQUENCES * CTL_SAMPLER_SEQUENCE_LENGTH, n2 = n1 * 2;
+    float* dst1 = d_t1.p + (size_t)slot * B * n1; float* dst2 = d_t2.p + (size_t)slot * B * n2;
+    unsigned int j0 = 0;
+    if (have_user_tables) {
+        float* a = h_t1 + (size_t)slot * n1; float* b = h_t2 + (size_t)slot * n2;
+        std::memcpy(a, user_t1.data(), n1 * 4); std::memcpy(b, user_t2.data(), n2 * 4); have_user_tables = false; j0 = 1;
+        CTL_HIP(hipMemcpyAsync(dst1, a, n1 * 4, hipMemcpyHostToDevice, stream));
+        CTL_HIP(hipMemcpyAsync(dst2, b, n2 * 4, hipMemcpyHostToDevice, stream));
+    }
+    if (nb > j0) {
+        sequence_generator::pass_start* hs = h_starts + (size_t)slot * B;
+        uint32_t* ds = d_starts.p + (size_t)slot * B * (sizeof(sequence_generator::pass_start) / sizeof(uint32_t));
+        m_SamplingSequenceGenerator.take_pass_starts(nb - j0, hs);
+        CTL_HIP(hipMemcpyAsync(ds, hs, (size_t)(nb - j0) * sizeof(sequence_generator::pass_start), hipMemcpyHostToDevice, stream));
+        launch_sequence_fill(stream, d_jumps.p, ds, nb - j0, dst1 + (size_t)j0 * n1, dst2 + (size_t)j0 * n2);
+    }
+}
 template <bool PROGRESSIVE> void Tracer<PROGRESSIVE>::Debug(Image* I, unsigned int x, unsigned int y, float rgb[3]) {
     if (!m_pScene) throw std::runtime_error("Debug: InitializeScene was not called");
     if (w == 0xffffffffu) throw std::runtime_error("Debug: Resize was not called");
     if (x >= w || y >= h) throw std::runtime_error("Debug: pixel outside the film");
-    // UpdateKernel(scene, generator) -> GenerateNewRandomSequences (Kernel/TraceHelper.cu:182-185): one more set of tables is drawn from the tracer's stream
-    const size_t n1 = (size_t)CTL_SAMPLER_NUM_SEQUENCES * CTL_SAMPLER_SEQUENCE_LENGTH, n2 = n1 * 2;
+    // UpdateKernel(scene, generator): one more set of tables is drawn, into slot 0 of the ring
     ensureTableRing(std::max(1u, passBatch()));
     for (auto e : slot_done) CTL_HIP(hipEventSynchronize(e));
-    if (have_user_tables) {
-        std::memcpy(h_t1, user_t1.data(), n1 * 4); std::memcpy(h_t2, user_t2.data(), n2 * 4); have_user_tables = false;
-        CTL_HIP(hipMemcpyAsync(d_t1.p, h_t1, n1 * 4, hipMemcpyHostToDevice, stream)); CTL_HIP(hipMemcpyAsync(d_t2.p, h_t2, n2 * 4, hipMemcpyHostToDevice, stream));
-    } else {
-        m_SamplingSequenceGenerator.take_pass_starts(1, h_starts);
-        CTL_HIP(hipMemcpyAsync(d_starts.p, h_starts, sizeof(sequence_generator::pass_start), hipMemcpyHostToDevice, stream));
-        launch_sequence_fill(stream, d_jumps.p, d_starts.p, 1, d_t1.p, d_t2.p);
-    }
+    stageTables(0, 1, 1);
     float out[3] = { 0, 0, 0 };
     DebugInternal(I, x, y, d_t1.p, d_t2.p, out);
     CTL_HIP(hipStreamSynchronize(stream));
     if (rgb) { rgb[0] = out[0]; rgb[1] = out[1]; rgb[2] = out[2]; }
 }
-// Tracer<false> (the PrimTracer) does not use this body: its pass loop, Debug and table staging are explicit specialisations in prim_tracer.hip, so a fix to the
-// pass loop here may be due there too.  Only Tracer<true> is instantiated from this template.
 template <bool PROGRESSIVE> void Tracer<PROGRESSIVE>::DoPasses(Image* I, bool a_NewTrace, unsigned int n) {
     if (!m_pScene) throw std::runtime_error("DoPass: InitializeScene was not called");
     if (w == 0xffffffffu) throw std::runtime_error("DoPass: Resize was not called");
     if (I->getWidth() != w || I->getHeight() != h) throw std::runtime_error("DoPass: image size differs from the tracer size");
     if (n == 0) return;
-    if (a_NewTrace || !PROGRESSIVE) { m_uPassesDone = 0; m_uAccNumRaysTraced = 0; m_fAccRuntime = 0; I->Clear(); }
-    // a block sampler that does not simply take every block once decides pass by pass, from the frame so far (Tracer.h:209-248)
-    BlockSampler* bs = (m_sParameters.getValue("BlockSamplerType") != 0 || block_sampler_) ? getBlockSampler() : nullptr;
+    if (a_NewTrace || !PROGRESSIVE) { m_uPassesDone = 0; m_uAccNumRaysTraced = 0; m_fAccRuntime = 0; if (PROGRESSIVE) I->Clear(); }   // Tracer<false> clears before every pass
+    // a block sampler that does not simply take every block once decides pass by pass, from the frame so far (Tracer.h:209-248).  Tracer<false> has none:
+    // BlockSamplerType is accepted there and changes nothing, as in the reference
+    BlockSampler* bs = PROGRESSIVE && (m_sParameters.getValue("BlockSamplerType") != 0 || block_sampler_) ? getBlockSampler() : nullptr;
     const bool adaptive = bs && !bs->every_block_once();
     if (adaptive && shard_world > 1) throw std::runtime_error("block samplers other than Uniform need the whole frame on one rank");
-    if (bs && (a_NewTrace || !PROGRESSIVE)) bs->start_new_rendering(stream);
+    if (bs && a_NewTrace) bs->start_new_rendering(stream);
     const size_t n1 = (size_t)CTL_SAMPLER_NUM_SEQUENCES * CTL_SAMPLER_SEQUENCE_LENGTH, n2 = n1 * 2;
     // passes are rendered in batches of `B` (one wavefront carries the paths of B passes; each path uses its own pass's
     // tables), B chosen so that a launch holds enough paths to fill 256 CUs even when a rank owns 1/8 of the tiles
@@ -509,24 +524,8 @@ template <bool PROGRESSIVE> void Tracer<PROGRESSIVE>::DoPasses(Image* I, bool a_
     for (unsigned int k = 0; k < n; batch_idx++) {
         const unsigned int nb = std::min(B, n - k), slot = batch_idx % ring;
         if (batch_idx >= ring) CTL_HIP(hipEventSynchronize(slot_done[slot]));   // the batch that last used this slot has finished
-        // One XORWOW stream as in the reference (Kernel/Sampler.h:57-85).  The host only advances it (one GF(2) jump per pass); the tables of the batch are
-        // written in HBM by k_sequence_fill — 256 lanes per pass, each two jumps and 1440 draws from the pass's start state — in the time the host threads
-        // needed for one pass, and without the 1.5 MB-per-pass upload (measured: 1.9 ms at the head of every 20-pass call -> 0.1 ms).
-        float* dst1 = d_t1.p + (size_t)slot * B * n1; float* dst2 = d_t2.p + (size_t)slot * B * n2;
-        unsigned int j0 = 0;
-        if (have_user_tables) {   // setSamplerTables: the caller's tables serve the first pass of the call
-            float* a = h_t1 + (size_t)slot * n1; float* b = h_t2 + (size_t)slot * n2;
-            std::memcpy(a, user_t1.data(), n1 * 4); std::memcpy(b, user_t2.data(), n2 * 4); have_user_tables = false; j0 = 1;
-            CTL_HIP(hipMemcpyAsync(dst1, a, n1 * 4, hipMemcpyHostToDevice, stream));
-            CTL_HIP(hipMemcpyAsync(dst2, b, n2 * 4, hipMemcpyHostToDevice, stream));
-        }
-        if (nb > j0) {
-            sequence_generator::pass_start* hs = h_starts + (size_t)slot * B;
-            uint32_t* ds = d_starts.p + (size_t)slot * B * (sizeof(sequence_generator::pass_start) / sizeof(uint32_t));
-            m_SamplingSequenceGenerator.take_pass_starts(nb - j0, hs);
-            CTL_HIP(hipMemcpyAsync(ds, hs, (size_t)(nb - j0) * sizeof(sequence_generator::pass_start), hipMemcpyHostToDevice, stream));
-            launch_sequence_fill(stream, d_jumps.p, ds, nb - j0, dst1 + (size_t)j0 * n1, dst2 + (size_t)j0 * n2);
-        }
+        if (!PROGRESSIVE) { m_uPassesDone = 0; I->Clear(); }   // every pass of a non-progressive tracer is a new trace (B = 1); the previous pass ended with a synchronisation
+        stageTables(slot, B, nb);
         m_uPassesDone += nb;
         std::vector<unsigned char> block_counts;
         pass_block_counts_ = nullptr; pass_max_block_count_ = 1;
@@ -552,6 +551,7 @@ template <bool PROGRESSIVE> void Tracer<PROGRESSIVE>::DoPasses(Image* I, bool a_
     m_fAccRuntime += m_fLastRuntime; m_uAccNumRaysTraced += m_uLastNumRaysTraced;
 }
 template class Tracer<true>;
+template class Tracer<false>;
 
 // ------------------------------------------------------------------------------------------------ WavefrontPathTracer
 WavefrontPathTracer::WavefrontPathTracer() {
@@ -590,8 +590,7 @@ WavefrontPathTracer::WavefrontPathTracer() {
     m_sParameters.addBool("U16Barycentrics", false);
     m_sParameters.addInterval("OrderedAccumulationMaxMB", 4096, 0, 1 << 20);   // build-specific: largest stage of the ordered accumulation (MB of HBM); a batch that needs more accumulates with atomics
     m_sParameters.addBool("OrderedAccumulation", true);   // build-specific: finished paths are staged per (pass, pixel) and added to the frame in pass order (kernels.h pass_params::stage); false = four float atomics per path as Image::AddSample does
-    int dev = 0; hipDeviceProp_t prop; CTL_HIP(hipGetDevice(&dev)); CTL_HIP(hipGetDeviceProperties(&prop, dev));
-    grid_blocks = prop.multiProcessorCount * 8;   // 8 x 256-thread workgroups per CU = 32 waves/CU
+    grid_blocks = persistent_grid_blocks();
 }
 float4* WavefrontPathTracer::new_f4(size_t n) { f4_.emplace_back(new dbuf<float4>()); f4_.back()->alloc(n); return f4_.back()->p; }
 

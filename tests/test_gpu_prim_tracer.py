@@ -153,6 +153,32 @@ def test_do_passes_is_non_progressive(gpu, orc):
     assert tr.getNumPassesDone() == 1 and (img.getPixelData()[..., 6] == 1).all()
 
 
+def test_debug_and_passes_draw_from_the_tracers_stream(gpu, orc):
+    """Without setSamplerTables, a fresh tracer's Debug spends the stream's first table set and the DoPass after it renders the second (the PrimTracer
+    counterpart of test_gpu_render.py's Debug check); setSamplerTables(T) then DoPasses(img, 2): T serves pass 1, the stream pass 2."""
+    sc = _scene("cornell_glass")
+    tables = orc.sequence_tables(3)
+    mode = "first_f_direct"
+    frames = [_render(gpu, sc, W, H, mode, t)[0] for t in tables]
+    differ = (frames[0][..., :3] != frames[1][..., :3]).any(axis=2)
+    assert differ.any()
+    y, x = (int(v) for v in np.argwhere(differ)[0])
+    tr = _tracer(gpu, sc, W, H, mode)
+    img = gpu.Image(W, H)
+    rgb = tr.Debug(img, x, y)                                                  # set 1
+    assert np.array_equal(rgb, frames[0][y, x, :3]), (x, y, rgb, frames[0][y, x, :3])
+    tr.DoPass(img)                                                             # set 2
+    assert np.array_equal(img.getPixelData(), frames[1])
+    tr = _tracer(gpu, sc, W, H, mode)
+    img = gpu.Image(W, H)
+    tr.setSamplerTables(*tables[2])
+    tr.DoPasses(img, 2)                                                        # pass 1: tables[2], pass 2: the stream's set 1
+    assert tr.getNumPassesDone() == 1
+    assert np.array_equal(img.getPixelData(), frames[0])
+    tr.DoPass(img)                                                             # set 2
+    assert np.array_equal(img.getPixelData(), frames[1])
+
+
 @pytest.mark.parametrize("mode", ["n_geo_colored", "first_non_delta_f_direct"])
 def test_tile_shards_sum_to_the_frame(gpu, orc, mode):
     w, h = 130, 97
