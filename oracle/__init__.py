@@ -137,14 +137,15 @@ class Oracle:
         self.shared_math = shared_math
         self.lib = load(shared_math)
 
-    def intersect(self, desc, rays, any_hit=False, count=False, threads=8, alpha_test=False, flat=None):
-        """flat: a ctl_flat_bvh_desc (cudatracerlib_amd.FlatBvh(...).desc) -> traverse the product's flattened BVH instead of the two-level structure"""
+    def intersect(self, desc, rays, any_hit=False, count=False, threads=8, alpha_test=False, flat=None, half_host_quirk=False):
+        """flat: a ctl_flat_bvh_desc (cudatracerlib_amd.FlatBvh(...).desc) -> traverse the product's flattened BVH instead of the two-level structure.
+        half_host_quirk: the alpha test decodes the triangles' uv with half::ToFloat's host branch (as the reference compiled for the host does)"""
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
         hits = np.zeros(len(r), dtype=[("dist", "f4"), ("node_idx", "i4"), ("tri_idx", "i4"), ("u", "f4"), ("v", "f4")])
         cnt = (u64 * 5)()
         self.lib.orc_set_flat_bvh(C.addressof(flat) if flat is not None else None)
         try:
-            self.lib.orc_intersect(C.addressof(desc), r.ctypes.data, len(r), hits.ctypes.data, (1 if any_hit else 0) | (2 if alpha_test else 0), C.addressof(cnt) if count else None, threads)
+            self.lib.orc_intersect(C.addressof(desc), r.ctypes.data, len(r), hits.ctypes.data, (1 if any_hit else 0) | (2 if alpha_test else 0) | (4 if half_host_quirk else 0), C.addressof(cnt) if count else None, threads)
         finally:
             self.lib.orc_set_flat_bvh(None)
         if count:

@@ -120,7 +120,7 @@ void orc_sensor_sample_rays(const ctl_sensor* s, float px, float py, float ax, f
 static const ctl_flat_bvh_desc* g_flat = nullptr;
 void orc_set_flat_bvh(const ctl_flat_bvh_desc* f) { g_flat = f; }
 void orc_intersect(const ctl_scene_desc* desc, const ctl_ray* rays, uint32_t n, ctl_hit* hits, int any_hit, ctl_traversal_counts* counts, int n_threads) {
-    Scene S; S.d = *desc; S.alpha_test = (any_hit & 2) != 0; any_hit &= 1; S.flat = g_flat;
+    Scene S; S.d = *desc; S.alpha_test = (any_hit & 2) != 0; S.half_host_quirk = (any_hit & 4) != 0; any_hit &= 1; S.flat = g_flat;   // bit 2: half::ToFloat's host branch in the alpha test's uv
     if (n_threads < 1) n_threads = 1;
     std::vector<TravCounts> tc(n_threads);
     auto work = [&](int tid) {
@@ -482,6 +482,20 @@ void orc_debug_pixel(const ctl_scene_desc* desc, uint32_t W, uint32_t H, const f
     uint64_t rays = 0;
     if (rgb) { const Spec c = pathTrace(S, true, o, d, rng, maxPathLength, rrStart, &rays, &diff); rgb[0] = c.x; rgb[1] = c.y; rgb[2] = c.z; }
     if (primary_dist) { Hit h = traceRayClosest(S, o, d); *primary_dist = h.hasHit() ? h.dist : FLT_MAX; }
+}
+
+// InfiniteLight::evalEnvironment(r, rX, rY) (SceneTypes/Light.cu:496-518), what KernelDynamicScene::EvalEnvironment(r, rX, rY) returns, for n rays: dir / dirX / dirY are
+// the main ray's and the two offset rays' directions (3 floats each); the image pyramids are built once.  Spectrum(0) without an environment map.
+void orc_env_eval_differential_n(const ctl_scene_desc* desc, uint32_t n, const float* dir, const float* dirX, const float* dirY, float* out) {
+    Scene S; S.d = *desc;
+    std::vector<MipPyramid> pyramids(desc->n_images); for (uint32_t i = 0; i < desc->n_images; i++) pyramids[i].build(desc->images[i]); S.pyramids = pyramids.data();
+    for (uint32_t i = 0; i < n; i++) {
+        Spec v(0.0f);
+        if (desc->env_map_index != 0xffffffffu)
+            v = envEvalDifferential(S, desc->lights[desc->env_map_index], V3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]), V3(dirX[3 * i], dirX[3 * i + 1], dirX[3 * i + 2]),
+                                    V3(dirY[3 * i], dirY[3 * i + 1], dirY[3 * i + 2]));
+        out[3 * i] = v.x; out[3 * i + 1] = v.y; out[3 * i + 2] = v.z;
+    }
 }
 
 } // extern "C"

@@ -14,7 +14,8 @@
 //                          Kernel/Sampler_device.h:15-18 / Base/SynchronizedBuffer.h (checked against sizeof and the class's own accessors)
 //   g_RayTracedCounterHost zeroed, then read around every pixel: the rays that pixel's path traced (traceRay's Platform::Increment, TraceHelper.cu:176)
 // and renders every pixel of every pass, one thread, into the reference's Image (raw storage, ref_image_view).  The pixel's sampler index is y * w + x, what
-// TracerBase::getPixelIndex returns (Kernel/Tracer.h:89-97).  This file contains no reference source.
+// TracerBase::getPixelIndex returns (Kernel/Tracer.h:89-97).  ref_primtracer_render does the same for one pass of the PrimTracer's computePixel
+// (Integrators/PrimTracer.cu:19-106), with g_DepthImage2 pointed at the caller's depth buffer.  This file contains no reference source.
 #include <Kernel/TraceHelper.h>
 #include <Engine/Material.h>
 #include <Engine/Mesh.h>
@@ -35,6 +36,8 @@ namespace CudaTracerLib {
 extern const BVHNodeData* t_nodesA;       // the generated unit's two node pointers
 extern const BVHNodeData* t_SceneNodes;
 template<bool DIRECT, bool REGU> void ref_path_pixel(unsigned int w, unsigned int h, Vec2i pixel, Sampler rng, Image& img, float m, int maxPathLength, int rrStart);
+void ref_prim_pixel(int x, int y, Sampler& rng, Image& img, bool depth, int mode, int maxPathLength);   // the PrimTracer's computePixel (PrimTracer.cu:19-106)
+void ref_prim_depth_image(float* data, int w, int h);                                                  // g_DepthImage2 (PrimTracer.cu:16)
 }
 using namespace CudaTracerLib;
 
@@ -147,6 +150,32 @@ int ref_pathtrace_render(const ctl_scene_desc* d, uint32_t W, uint32_t H, uint32
         }
         return 0;
     } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return -1; }
+}
+
+// One pass of the PrimTracer (Integrators/PrimTracer.cu:19-106): computePixel for every pixel, one sample each, drawing mode `mode` (PathTrace_DrawMode's order,
+// Integrators/PrimTracer.h:7), the sampler index y * W + x.  t1 / t2: one pass's sampler tables.  alpha: doAlphaMapping.  img: W x H ctl_pixel_data, added to;
+// depth: W x H floats that g_DepthImage2 stores into (NULL: computePixel's depthImage = false); rays: W x H counters, added to (may be NULL).
+// Returns 0, or -1 with the reason on stderr.
+int ref_primtracer_render(const ctl_scene_desc* d, uint32_t W, uint32_t H, const float* t1, const float* t2, int mode, int maxPathLength, int alpha,
+                          ctl_pixel_data* img, float* depth, uint32_t* rays) {
+    try {
+        if (mode < 0 || mode > 14) throw std::runtime_error("ref_primtracer_render: drawing mode out of range");
+        bind_path_scene(d, alpha != 0);
+        bind_sampler(t1, t2);
+        alignas(16) unsigned char raw[sizeof(Image)];
+        Image* I = ref_image_view(raw, sizeof raw, img, (int)W, (int)H);
+        if (!I) throw std::runtime_error("ref_primtracer_render: image layout");
+        ref_prim_depth_image(depth, (int)W, (int)H);
+        for (uint32_t y = 0; y < H; y++)
+            for (uint32_t x = 0; x < W; x++) {
+                g_RayTracedCounterHost = 0;
+                Sampler rng = (*g_SamplerDataHost)(y * W + x);   // TracerBase::getPixelIndex (Kernel/Tracer.h:89-97)
+                ref_prim_pixel((int)x, (int)y, rng, *I, depth != nullptr, mode, maxPathLength);
+                if (rays) rays[(size_t)y * W + x] += g_RayTracedCounterHost;
+            }
+        ref_prim_depth_image(nullptr, 0, 0);
+        return 0;
+    } catch (const std::exception& e) { ref_prim_depth_image(nullptr, 0, 0); std::fprintf(stderr, "%s\n", e.what()); return -1; }
 }
 
 }  // extern "C"

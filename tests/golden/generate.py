@@ -889,9 +889,61 @@ def gen_pathtrace(r):
     np.savez_compressed(os.path.join(HERE, "pathtrace.npz"), **out)
 
 
+PRIM_MODES = ("linear_depth", "D3D_depth", "v_absdot_n_geo", "v_dot_n_geo", "v_dot_n_shade", "n_geo_colored", "n_shade_colored", "uv", "bary_coords",
+              "first_Le", "first_f", "first_f_direct", "first_non_delta_Le", "first_non_delta_f", "first_non_delta_f_direct")   # PathTrace_DrawMode (Integrators/PrimTracer.h:7)
+PRIM_SHADED = PRIM_MODES[9:]
+PRIM_DEPTH_MODES = ("D3D_depth", "first_non_delta_f_direct")   # the depth buffer is recorded for these two (a geometry mode, a chain mode) where a case renders them
+
+
+def primtracer_cases():
+    """the PrimTracer fixture's cases: (key, scene builder, width, height, drawing modes, MaxPathLength).  One pass, alpha test on (traceRay always alpha-tests where
+    the scene has alpha maps).  Image-textured area lights are left out: their value is undefined in the reference itself."""
+    from cudatracerlib_amd import scenes
+    return [("cornell", lambda: scenes.cornell_box(48, 32), 48, 32, PRIM_MODES, 7),
+            ("glass", lambda: scenes.cornell_box(64, 48, glass_sphere=True), 64, 48, PRIM_MODES, 7),
+            ("glass_l1", lambda: scenes.cornell_box(64, 48, glass_sphere=True), 64, 48, PRIM_SHADED, 1),   # chains inside the sphere end before they exit
+            ("extra_materials", lambda: scenes.cornell_box(48, 32, extra_materials=True), 48, 32, PRIM_SHADED, 7),
+            ("env", lambda: scenes.env_scene(48, 32), 48, 32, PRIM_MODES, 7),   # misses: EvalEnvironment(r, rX, rY); image-textured ground
+            ("env_extra_lights", lambda: scenes.env_scene(48, 32, extra_lights=True), 48, 32, ("first_f_direct", "first_non_delta_f_direct"), 7),
+            ("maps", lambda: scenes.maps_scene(48, 32), 48, 32, PRIM_MODES, 7),   # normal map + luminance alpha
+            ("maps_height", lambda: scenes.maps_scene(48, 32, surface_map="height", alpha="alpha"), 48, 32, PRIM_MODES, 7),
+            ("area_checker", lambda: scenes.area_lights_scene(48, 32, "checker"), 48, 32, PRIM_SHADED, 7),
+            ("cornell_130x97", lambda: scenes.cornell_box(130, 97), 130, 97, ("n_geo_colored", "first_non_delta_f_direct"), 7)]   # not a multiple of the tile size
+
+
+def primtracer_tables():
+    """the one pass's sampler tables: the oracle's SequenceGenerator (the product's), the first compute of a fresh generator"""
+    return pathtrace_tables(1)[0]
+
+
+def gen_primtracer(r):
+    """One pass of the PrimTracer's computePixel (Integrators/PrimTracer.cu:19-106) run by the reference's own code (oracle/ref_pathtrace_driver.cpp,
+    ref_primtracer_render) over the product's compiled scenes and sampler tables: per case and drawing mode the frame (rgb, weightSum), the rays each pixel traced
+    (g_RayTracedCounter) and, for PRIM_DEPTH_MODES, the depth buffer (g_DepthImage2)"""
+    r.ref_primtracer_render.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    r.ref_primtracer_render.restype = C.c_int
+    out = {}
+    for key, make, w, h, modes, max_path_length in primtracer_cases():
+        sc = make(); t1, t2 = (np.ascontiguousarray(a, np.float32) for a in primtracer_tables())
+        for mode in modes:
+            px = np.zeros((h, w, 7), np.float32); rays = np.zeros((h, w), np.uint32)
+            depth = np.zeros((h, w), np.float32) if mode in PRIM_DEPTH_MODES else None
+            assert r.ref_primtracer_render(C.addressof(sc.desc), w, h, t1.ctypes.data, t2.ctypes.data, PRIM_MODES.index(mode), max_path_length, 1, px.ctypes.data,
+                                           None if depth is None else depth.ctypes.data, rays.ctypes.data) == 0, (key, mode)
+            assert (px[..., 3:6] == 0).all() and rays.max() < 65536 and px[..., 6].sum() > 0.9 * w * h, (key, mode)
+            k = "%s_%s" % (key, mode)
+            out[k + "_rgb"] = np.ascontiguousarray(px[..., :3]); out[k + "_weight"] = np.ascontiguousarray(px[..., 6]); out[k + "_rays"] = rays.astype(np.uint16)
+            if depth is not None:
+                out[k + "_depth"] = depth
+        out[key + "_digest"] = np.array(pathtrace_input_digest(sc.desc, [(t1, t2)]))
+    np.savez_compressed(os.path.join(HERE, "primtracer.npz"), **out)
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["pathtrace"]:     # only this fixture (the others stay byte-identical)
         gen_pathtrace(oracle.load_ref())
+    elif sys.argv[1:] == ["primtracer"]:  # only this fixture
+        gen_primtracer(oracle.load_ref())
     elif sys.argv[1:] == ["image"]:
         gen_image(oracle.load_ref())
     elif sys.argv[1:] == ["emitters"]:
@@ -937,4 +989,5 @@ if __name__ == "__main__":
         gen_scene_lights(oracle.load_ref())
         gen_material_maps(oracle.load_ref())
         gen_pathtrace(oracle.load_ref())
+        gen_primtracer(oracle.load_ref())
         gen_image(oracle.load_ref())

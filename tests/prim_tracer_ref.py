@@ -4,9 +4,11 @@ primary(orc, desc, w, h, tables, flat) follows every pixel to its first hit as t
 2-D draw, sampleRayDifferential's own ray from the pixel's position (no jitter), traceRay with the alpha test — and returns, per pixel, the quantities the drawing
 modes read after TraceResult::getBsdfSample: the flipped geometric / shading normals, uv, the barycentrics, the local wi, the material, the emission.
 flat: the product's flattened BVH (cudatracerlib_amd.api.FlatBvh(...).desc), so that a ray grazing the edge two triangles share resolves to the triangle the
-device's traversal picks; None traverses the reference's two-level structure.
-geometry_frame(...) turns that into the frame of a geometry mode; shaded_modes(...) runs computePixel in full for the six shaded modes (next-event estimation with
-MIS and its shadow ray, the BSDF-sampled delta chain with its quirks) and counts its traceRay / Occluded calls; shaded_first(...) gives the material's delta flag.
+device's traversal picks; None traverses the reference's two-level structure.  half_host_quirk: the triangles' halves (normals, uv) are decoded with
+half::ToFloat's host branch, as the reference compiled for the host decodes them (tests/test_oracle_prim_tracer.py pins this file on it).
+geometry_frame(...) turns that into the frame of a geometry mode; environment(...) gives the misses' EvalEnvironment(r, rX, rY); shaded_modes(...) runs
+computePixel in full for the six shaded modes (next-event estimation with MIS and its shadow ray, the BSDF-sampled delta chain with its quirks) and counts its
+traceRay / Occluded calls; shaded_first(...) gives the material's delta flag.
 """
 import ctypes as C
 
@@ -34,8 +36,8 @@ def _bind(lib):
 class _Ctx:
     """the scene's arrays and the oracle calls computePixel is made of"""
 
-    def __init__(self, orc, desc):
-        self.orc, self.lib, self.desc = orc, orc.lib, desc
+    def __init__(self, orc, desc, half_host_quirk=False):
+        self.orc, self.lib, self.desc, self.quirk = orc, orc.lib, desc, half_host_quirk
         _bind(self.lib)
         self.tri_data = np.frombuffer(C.string_at(desc.tri_data, desc.n_tri_data * 32), np.uint32).reshape(-1, 8)
         self.xforms = np.frombuffer(C.string_at(desc.node_transforms, desc.n_nodes * 64), np.float32).reshape(-1, 16)
@@ -49,7 +51,7 @@ class _Ctx:
         tri, node = int(hd["tri_idx"]), int(hd["node_idx"])
         t, u, v = f32(hd["dist"]), f32(hd["u"]), f32(hd["v"])
         T = np.ascontiguousarray(self.tri_data[tri]); M = np.ascontiguousarray(self.xforms[node])
-        lib.orc_triangle_fill_dg(T.ctypes.data, M.ctypes.data, float(u), float(v), 0, dg.ctypes.data)
+        lib.orc_triangle_fill_dg(T.ctypes.data, M.ctypes.data, float(u), float(v), 1 if self.quirk else 0, dg.ctypes.data)
         P = np.array([f32(o[k] + f32(t * d[k])) for k in range(3)], np.float32)
         s_, t_, sn, gn = dg[0:3].copy(), dg[3:6].copy(), dg[6:9].copy(), dg[9:12].copy()
         md = -np.asarray(d, np.float32)
@@ -78,7 +80,7 @@ def d3d_depth(near, far, t):
     return f32(f32(f32(far / f32(far - near)) * z - f32(far * near) / f32(far - near)) / z)
 
 
-def primary(orc, desc, w, h, tables, flat=None):
+def primary(orc, desc, w, h, tables, flat=None, half_host_quirk=False):
     lib = orc.lib
     _bind(lib)
     t1, t2 = (np.ascontiguousarray(a, np.float32) for a in tables)
@@ -94,11 +96,11 @@ def primary(orc, desc, w, h, tables, flat=None):
             lib.orc_sensor_sample_rays(C.addressof(desc.camera), float(x), float(y), float(ap[0]), float(ap[1]), o18.ctypes.data, o6.ctypes.data)
             rays[i, :3] = o6[:3]; rays[i, 3] = eps; rays[i, 4:7] = o6[3:]; rays[i, 7] = FLT_MAX
             dX[i] = o18[9:12]; dY[i] = o18[15:18]
-    hits = orc.intersect(desc, rays, alpha_test=True, flat=flat)
-    out = dict(hit=np.zeros(n, bool), t=np.full(n, FLT_MAX, np.float32), n=np.zeros((n, 3), np.float32), sn=np.zeros((n, 3), np.float32),
+    hits = orc.intersect(desc, rays, alpha_test=True, flat=flat, half_host_quirk=half_host_quirk)
+    out = dict(quirk=half_host_quirk, hit=np.zeros(n, bool), t=np.full(n, FLT_MAX, np.float32), n=np.zeros((n, 3), np.float32), sn=np.zeros((n, 3), np.float32),
                uv=np.zeros((n, 2), np.float32), bary=np.zeros((n, 2), np.float32), wi=np.zeros((n, 3), np.float32), P=np.zeros((n, 3), np.float32),
                frame=np.zeros((n, 9), np.float32), mat=np.full(n, -1, np.int64), node=np.full(n, -1, np.int64), rays=rays, dX=dX, dY=dY, flat=flat, tri=hits["tri_idx"].copy())
-    ctx = _Ctx(orc, desc)
+    ctx = _Ctx(orc, desc, half_host_quirk)
     for i in range(n):
         hd = hits[i]
         if hd["tri_idx"] < 0:
@@ -134,6 +136,21 @@ def geometry_frame(pr, desc, w, h, mode):
             L[i] = (pr["bary"][i, 0], pr["bary"][i, 1], 0)
         else:
             raise ValueError(mode)
+    return add_sample_clamp(L).reshape(h, w, 3)
+
+
+def environment(orc, pr, desc, w, h):
+    """EvalEnvironment(r, rX, rY) (KernelDynamicScene.cu:62-68 -> InfiniteLight::evalEnvironment(r, rX, rY)) at every pixel whose primary ray misses (h, w, 3), with
+    the ray differentials of sampleRayDifferential; 0 at hits, and everywhere without an environment map"""
+    lib = orc.lib
+    lib.orc_env_eval_differential_n.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    miss = np.nonzero(~pr["hit"])[0]
+    d = np.ascontiguousarray(pr["rays"][miss, 4:7]); dx = np.ascontiguousarray(pr["dX"][miss]); dy = np.ascontiguousarray(pr["dY"][miss])
+    out = np.zeros((len(miss), 3), np.float32)
+    if len(miss):
+        lib.orc_env_eval_differential_n(C.addressof(desc), len(miss), d.ctypes.data, dx.ctypes.data, dy.ctypes.data, out.ctypes.data)
+    L = np.zeros((w * h, 3), np.float32)
+    L[miss] = out
     return add_sample_clamp(L).reshape(h, w, 3)
 
 
@@ -175,12 +192,13 @@ class _NotRestated(Exception):
 
 
 def shaded_modes(orc, pr, desc, w, h, tables, max_path_length):
-    """computePixel (PrimTracer.cu:19-106) for the six shaded modes, every pixel that hits: {mode: (frame (h, w, 3), rays of the pass)} and the mask of the pixels
-    restated (hits whose path meets no image texture).  The rays are one per traceRay / Occluded, the misses' primary rays included.
+    """computePixel (PrimTracer.cu:19-106) for the six shaded modes, every pixel that hits: {mode: (frame (h, w, 3), rays of the pass, rays of each pixel (h, w),
+    the distance of each pixel's last traceRay (h, w): what g_DepthImage2.Store receives)} and the mask of the pixels restated (hits whose path meets no image
+    texture).  The rays are one per traceRay / Occluded, the misses' primary rays included.
     Built from the oracle's probes: orc_sampler_float2 (the draws, in the device's order), orc_emitter_select + orc_light_sample_direct (UniformSampleOneLight's
     sampleEmitter and sampleDirect), orc_bsdf_eval_uv / orc_bsdf_sample_uv, Oracle.intersect (closest and any hit, alpha-tested) and orc_light_eval."""
     lib = orc.lib
-    ctx = _Ctx(orc, desc)
+    ctx = _Ctx(orc, desc, pr.get("quirk", False))
     lib.orc_bsdf_sample_uv.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]
     lib.orc_light_sample_direct.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
     lib.orc_emitter_select.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -222,7 +240,7 @@ def shaded_modes(orc, pr, desc, w, h, tables, max_path_length):
 
     def trace(o, d, tmax=FLT_MAX, any_hit=False):
         r = np.zeros((1, 8), np.float32); r[0, :3] = o; r[0, 3] = eps; r[0, 4:7] = d; r[0, 7] = tmax
-        return orc.intersect(desc, r, any_hit=any_hit, alpha_test=True, threads=1, flat=pr["flat"])[0]
+        return orc.intersect(desc, r, any_hit=any_hit, alpha_test=True, threads=1, flat=pr["flat"], half_host_quirk=ctx.quirk)[0]
 
     def one_light(mat, rec, draw, cnt):
         """UniformSampleOneLight + EstimateDirect (Kernel/TraceAlgorithms.cu:44-101), mask EAll & ~EDelta, MIS"""
@@ -252,7 +270,8 @@ def shaded_modes(orc, pr, desc, w, h, tables, max_path_length):
         return (r * f32(f32(1) / lpdf[0])).astype(np.float32)   # / pdf (Spectrum::operator/ multiplies by the reciprocal)
 
     res = {m: np.zeros((n, 3), np.float32) for m in SHADED_MODES}
-    rays = {m: n for m in SHADED_MODES}   # the primary traceRay of every pixel
+    rays = {m: np.ones(n, np.int64) for m in SHADED_MODES}   # the primary traceRay of every pixel
+    last_t = {m: pr["t"].copy() for m in SHADED_MODES}
     ok = np.zeros(n, bool)
     for i in np.nonzero(pr["hit"])[0]:
         rec0 = dict(t=pr["t"][i], n=pr["n"][i], uv=pr["uv"][i], wi=pr["wi"][i], P=pr["P"][i], frame=pr["frame"][i], mat=int(pr["mat"][i]), node=int(pr["node"][i]))
@@ -284,6 +303,7 @@ def shaded_modes(orc, pr, desc, w, h, tables, max_path_length):
                         o = rec["P"]; d = to_world(rec["frame"], wo)
                         hd = trace(o, d); cnt[0] += 1
                         hit = hd["tri_idx"] >= 0
+                        last_t[mode][i] = hd["dist"] if hit else FLT_MAX
                         if hit:
                             rec = ctx.surface(o, d, hd); mat = mats[rec["mat"]]
                             f, wo = bsdf_sample(mat, rec, draw())
@@ -303,8 +323,8 @@ def shaded_modes(orc, pr, desc, w, h, tables, max_path_length):
                         else:
                             L = Le2 + through * (one_light(mat, rec, draw, cnt) + f * f32(0.5))
                 res[mode][i] = L
-                rays[mode] += cnt[0]
+                rays[mode][i] += cnt[0]
             ok[i] = True
         except _NotRestated:
             pass
-    return {m: (add_sample_clamp(res[m]).reshape(h, w, 3), rays[m]) for m in SHADED_MODES}, ok.reshape(h, w)
+    return {m: (add_sample_clamp(res[m]).reshape(h, w, 3), int(rays[m].sum()), rays[m].reshape(h, w), last_t[m].reshape(h, w)) for m in SHADED_MODES}, ok.reshape(h, w)
