@@ -124,6 +124,11 @@ lib.ctl_memcpy_d2h.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
 lib.ctl_memcpy_d2d.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
 lib.ctl_intersect_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(f32)]
 lib.ctl_image_resolve_rgb.argtypes = [C.c_void_p, f32, C.c_void_p]
+lib.ctl_image_apply_pipeline_nlm.argtypes = [C.c_void_p, f32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.ctl_image_read_filtered.argtypes = [C.c_void_p, C.c_void_p]
+lib.ctl_image_last_filter_ms.argtypes = [C.c_void_p, C.POINTER(f32)]
+lib.ctl_tracer_set_pixel_variance.argtypes = [C.c_void_p, C.c_int]
+lib.ctl_tracer_read_pixel_variance.argtypes = [C.c_void_p, C.c_void_p]
 lib.ctl_tracer_set_param_float.argtypes = [C.c_void_p, C.c_char_p, f32]
 lib.ctl_builder_add_spot_light.argtypes = [C.c_void_p, C.POINTER(f32), C.POINTER(f32), C.POINTER(f32), f32, f32]
 lib.ctl_builder_add_distant_light.argtypes = [C.c_void_p, C.POINTER(f32), C.POINTER(f32), f32]
@@ -172,6 +177,16 @@ def lanczos_filter(xw=6.0, yw=6.0, tau=3.0):
 def triangle_filter(xw=2.0, yw=2.0):
     """TriangleFilter (SceneTypes/Filter.h:133-150)"""
     return ctl_reconstruction_filter(5, xw, yw, 0.0, 0.0)
+
+
+class ctl_nlm_filter(C.Structure):
+    _fields_ = [("k", f32), ("sigma2_scale", f32)]
+
+
+def nlm_filter(k=0.45, sigma2_scale=0.005):
+    """NonLocalMeansFilter (Kernel/ImagePipeline/Filter/NonLocalMeansFilter.h:103-113): the reference's defaults.  Needs the per-pixel variance: pass
+    tracer= (after tracer.setPixelVariance(True)) or variance= to Image.applyImagePipeline"""
+    return ctl_nlm_filter(k, sigma2_scale)
 
 
 def tonemap(key=0.18, burn=0.0):
@@ -770,16 +785,39 @@ class Image:
     def device_ptr(self):
         return lib.ctl_image_device_ptr(self._h)
 
-    def applyImagePipeline(self, splat_scale=0.0, filter=None, process=None):
+    def applyImagePipeline(self, splat_scale=0.0, filter=None, process=None, tracer=None, variance=None):
         """applyImagePipeline(tracer, img, filter, process) (Kernel/ImagePipeline/ImagePipeline.cu:54-84): (h, w, 4) uint8 display image.
-        filter = ctl_reconstruction_filter (see box_filter ... triangle_filter) or None; process = ctl_tonemap (see tonemap) or None."""
+        filter = ctl_reconstruction_filter (see box_filter ... triangle_filter), ctl_nlm_filter (see nlm_filter) or None; process = ctl_tonemap (see tonemap) or None.
+        The NonLocalMeans filter takes the per-pixel variance from exactly one of tracer= (its PixelVarianceBuffer) and variance= ((h, w) float32)."""
         a = np.zeros((self.height, self.width), np.uint32)
-        if filter is None and process is None:
+        if isinstance(filter, ctl_nlm_filter):
+            v = None
+            if variance is not None:
+                v = np.ascontiguousarray(variance, dtype=np.float32)
+                if v.size != self.width * self.height:
+                    raise ValueError("applyImagePipeline: variance has %d values, the image %d pixels" % (v.size, self.width * self.height))
+            _check(lib.ctl_image_apply_pipeline_nlm(self._h, f32(splat_scale), C.byref(filter), None if tracer is None else tracer._h, None if v is None else v.ctypes.data_as(C.c_void_p),
+                                                    None if process is None else C.byref(process), a.ctypes.data_as(C.c_void_p)))
+        elif tracer is not None or variance is not None:
+            raise ValueError("applyImagePipeline: tracer= / variance= belong to the NonLocalMeans filter")
+        elif filter is None and process is None:
             _check(lib.ctl_image_apply_pipeline(self._h, f32(splat_scale), a.ctypes.data_as(C.c_void_p)))
         else:
             _check(lib.ctl_image_apply_pipeline_ex(self._h, f32(splat_scale), None if filter is None else C.byref(filter),
                                                    None if process is None else C.byref(process), a.ctypes.data_as(C.c_void_p)))
         return a.view(np.uint8).reshape(self.height, self.width, 4)
+
+    def getFilteredData(self):
+        """Image::getFilteredData: (h, w) uint32 RGBE (r | g << 8 | b << 16 | e << 24), the plane the last pipeline call with a filter or a post-process left"""
+        a = np.zeros((self.height, self.width), np.uint32)
+        _check(lib.ctl_image_read_filtered(self._h, a.ctypes.data_as(C.c_void_p)))
+        return a
+
+    def lastFilterMs(self):
+        """HIP-event time (ms) of the NonLocalMeans kernel of the last applyImagePipeline with nlm_filter (measurement)"""
+        v = f32()
+        _check(lib.ctl_image_last_filter_ms(self._h, C.byref(v)))
+        return v.value
 
     def WriteDisplayImage(self, path, splat_scale=0.0):
         """Image::WriteDisplayImage: .png (display image), .hdr / .pfm (linear)."""
@@ -843,6 +881,7 @@ class WavefrontPathTracer:
 
     def Resize(self, w, h):
         _check(lib.ctl_tracer_resize(self._h, u32(w), u32(h)))
+        self._size = (w, h)
 
     def InitializeScene(self, scene):
         self._scene = scene
@@ -904,6 +943,18 @@ class WavefrontPathTracer:
         _check(lib.ctl_device_synchronize())
         _check(lib.ctl_memcpy_d2h(out.ctypes.data_as(C.c_void_p), p, C.c_size_t(out.nbytes)))
         return out
+
+    def setPixelVariance(self, on):
+        """keep the reference's PixelVarianceBuffer up to date after every pass (what nlm_filter is guided by).  Off by default; the frame does not change"""
+        _check(lib.ctl_tracer_set_pixel_variance(self._h, 1 if on else 0))
+
+    def getPixelVariance(self):
+        """PixelVarianceInfo::computeVariance() per pixel: (height, width) float32, NaN before the first pass"""
+        if getattr(self, "_size", None) is None:
+            raise CtlError(-1, "getPixelVariance: Resize was not called")
+        a = np.zeros((self._size[1], self._size[0]), np.float32)
+        _check(lib.ctl_tracer_read_pixel_variance(self._h, a.ctypes.data_as(C.c_void_p)))
+        return a
 
     def setCounting(self, on):
         """count N_inner / N_tri / N_inst in the intersect kernels (measurement mode)"""

@@ -9,8 +9,6 @@ namespace ctl {
 
 namespace {
 
-__device__ __forceinline__ float lum3(float r, float g, float b) { return r * 0.212671f + g * 0.715160f + b * 0.072169f; }
-
 // updateVarianceBuffer + PixelVarianceInfo::updateMoments (PixelVarianceBuffer.cu:10-19, PixelVarianceBuffer.h:22-45): only the pixels of
 // blocks that were sampled in this pass, with the number of samples the block got
 __global__ __launch_bounds__(256) void k_update_variance(pixel_variance* __restrict__ var, const ctl_pixel_data* __restrict__ image, uint32_t w, uint32_t h, uint32_t bx,
@@ -18,18 +16,21 @@ __global__ __launch_bounds__(256) void k_update_variance(pixel_variance* __restr
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= w * h) return;
     const uint32_t x = i % w, y = i / w;
-    const unsigned char c = counts[(y / kSamplerBlock) * bx + x / kSamplerBlock];
+    const unsigned char c = counts ? counts[(y / kSamplerBlock) * bx + x / kSamplerBlock] : (unsigned char)1;   // no counts: every block once
     if (!c) return;
     const ctl_pixel_data p = image[i]; pixel_variance v = var[i];
-    const float performed = (float)c;
-    const float n0 = p.rgb[0] + p.rgb_splat[0] * splat_scale, n1 = p.rgb[1] + p.rgb_splat[1] * splat_scale, n2 = p.rgb[2] + p.rgb_splat[2] * splat_scale;   // value of the pixel sum after the pass
-    const float e0 = (n0 - v.prev_I[0]) / performed, e1 = (n1 - v.prev_I[1]) / performed, e2 = (n2 - v.prev_I[2]) / performed;
-    v.prev_I[0] = n0; v.prev_I[1] = n1; v.prev_I[2] = n2;
-    v.weight = p.weight_sum;
-    if (v.iterations_done++ % 2 == 1) { v.half_buffer[0] += e0; v.half_buffer[1] += e1; v.half_buffer[2] += e2; }
-    const float l = lum3(e0, e1, e2);
-    v.sum_x += l; v.sum_x2 += l * l; v.num_samples_var++;
+    // value of the pixel sum after the pass
+    update_moments(v, p.rgb[0] + p.rgb_splat[0] * splat_scale, p.rgb[1] + p.rgb_splat[1] * splat_scale, p.rgb[2] + p.rgb_splat[2] * splat_scale, p.weight_sum, (float)c);
     var[i] = v;
+}
+
+// PixelVarianceInfo::computeVariance = VarAccumulator::Var(num_samples_var) (PixelVarianceBuffer.h:43-46, Math/VarAccumulator.h:7-11): NaN while num_samples_var is 0
+__global__ __launch_bounds__(256) void k_compute_variance(const pixel_variance* __restrict__ var, uint32_t n, float* __restrict__ out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const pixel_variance v = var[i];
+    const float invN = 1.0f / (float)v.num_samples_var;
+    out[i] = (v.sum_x2 - (v.sum_x * v.sum_x) * invN) * invN;
 }
 
 // VarianceBlockSampler's and DifferenceBlockSampler's updateInfo (VarianceBlockSampler.cu:7-32, DifferenceBlockSampler.cu:7-24) for one
@@ -70,15 +71,28 @@ __global__ __launch_bounds__(256) void k_block_stats(const pixel_variance* __res
 
 }  // namespace
 
+PixelVarianceBuffer::PixelVarianceBuffer(uint32_t w, uint32_t h) : w_(w), h_(h) {
+    CTL_HIP(hipMalloc((void**)&d_var_, (size_t)w * h * sizeof(pixel_variance)));
+    CTL_HIP(hipMemset(d_var_, 0, (size_t)w * h * sizeof(pixel_variance)));
+}
+PixelVarianceBuffer::~PixelVarianceBuffer() { (void)hipFree(d_var_); }
+void PixelVarianceBuffer::clear(hipStream_t s) { CTL_HIP(hipMemsetAsync(d_var_, 0, (size_t)w_ * h_ * sizeof(pixel_variance), s)); }
+void PixelVarianceBuffer::add_pass(const ctl_pixel_data* image, float splat_scale, const unsigned char* d_counts, hipStream_t s) {
+    const uint32_t n = w_ * h_;
+    hipLaunchKernelGGL(k_update_variance, dim3((n + 255) / 256), dim3(256), 0, s, d_var_, image, w_, h_, (w_ + kSamplerBlock - 1) / kSamplerBlock, d_counts, splat_scale);
+}
+void PixelVarianceBuffer::compute_variance(float* d_out, hipStream_t s) const {
+    const uint32_t n = w_ * h_;
+    hipLaunchKernelGGL(k_compute_variance, dim3((n + 255) / 256), dim3(256), 0, s, (const pixel_variance*)d_var_, n, d_out);
+}
+
 BlockSampler::BlockSampler(Type t, uint32_t w, uint32_t h) : type_(t), w_(w), h_(h), bx_((w + kSamplerBlock - 1) / kSamplerBlock), by_((h + kSamplerBlock - 1) / kSamplerBlock) {
     user_w_.assign(n_blocks(), t == Select ? 0.0f : 1.0f);
     indices_.resize(n_blocks()); for (uint32_t i = 0; i < n_blocks(); i++) indices_[i] = (int)i;
-    CTL_HIP(hipMalloc((void**)&d_var_, (size_t)w * h * sizeof(pixel_variance)));
     CTL_HIP(hipMalloc((void**)&d_stats_, (size_t)n_blocks() * sizeof(block_stats)));
     CTL_HIP(hipMalloc((void**)&d_counts_, n_blocks()));
-    CTL_HIP(hipMemset(d_var_, 0, (size_t)w * h * sizeof(pixel_variance)));
 }
-BlockSampler::~BlockSampler() { (void)hipFree(d_var_); (void)hipFree(d_stats_); (void)hipFree(d_counts_); }
+BlockSampler::~BlockSampler() { (void)hipFree(d_stats_); (void)hipFree(d_counts_); }
 
 void BlockSampler::set_weight(uint32_t x, uint32_t y, float w) { if (x >= bx_ || y >= by_) throw std::runtime_error("block sampler: block index out of range"); user_w_[y * bx_ + x] = w; }
 float BlockSampler::get_weight(uint32_t x, uint32_t y) const { if (x >= bx_ || y >= by_) throw std::runtime_error("block sampler: block index out of range"); return user_w_[y * bx_ + x]; }
@@ -86,11 +100,6 @@ bool BlockSampler::every_block_once() const {
     if (type_ != Uniform) return false;
     for (float w : user_w_) if (w != 1.0f) return false;
     return !non_zero_;
-}
-
-void BlockSampler::start_new_rendering(hipStream_t s) {
-    passes_done_ = 0;
-    CTL_HIP(hipMemsetAsync(d_var_, 0, (size_t)w_ * h_ * sizeof(pixel_variance), s));   // PixelVarianceBuffer::Clear
 }
 
 void BlockSampler::mixed(std::vector<unsigned char>& c) const {   // IBlockSampler::MixedBlockIterate (IBlockSampler.h:131-153)
@@ -122,12 +131,10 @@ const unsigned char* BlockSampler::upload_counts(const std::vector<unsigned char
     return d_counts_;
 }
 
-void BlockSampler::add_pass(const ctl_pixel_data* image, float splat_scale, const std::vector<unsigned char>& c, hipStream_t s) {
+void BlockSampler::add_pass(const PixelVarianceBuffer& var, const std::vector<unsigned char>& c, hipStream_t s) {
     last_counts_ = c;
-    const uint32_t n = w_ * h_;
-    hipLaunchKernelGGL(k_update_variance, dim3((n + 255) / 256), dim3(256), 0, s, d_var_, image, w_, h_, bx_, (const unsigned char*)d_counts_, splat_scale);
     auto fetch_stats = [&]() {
-        hipLaunchKernelGGL(k_block_stats, dim3(n_blocks()), dim3(256), 0, s, (const pixel_variance*)d_var_, d_stats_, w_, h_, bx_);
+        hipLaunchKernelGGL(k_block_stats, dim3(n_blocks()), dim3(256), 0, s, var.device(), d_stats_, w_, h_, bx_);
         stats_host_.resize(n_blocks());
         CTL_HIP(hipMemcpyAsync(stats_host_.data(), d_stats_, n_blocks() * sizeof(block_stats), hipMemcpyDeviceToHost, s));
         CTL_HIP(hipStreamSynchronize(s));

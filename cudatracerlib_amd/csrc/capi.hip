@@ -274,6 +274,26 @@ int ctl_image_resolve_rgb(ctl_image* img, float splat_scale, float* host_rgb_out
 int ctl_image_apply_pipeline_ex(ctl_image* img, float splat_scale, const ctl_reconstruction_filter* filter, const ctl_tonemap* process, uint32_t* host_rgbcol_out) {
     CTL_REQUIRE(img && host_rgbcol_out, "null argument"); CTL_TRY img->img.apply_pipeline_ex(splat_scale, filter, process, host_rgbcol_out); CTL_CATCH
 }
+int ctl_image_apply_pipeline_nlm(ctl_image* img, float splat_scale, const ctl_nlm_filter* nlm, ctl_tracer* tracer, const float* host_variance, const ctl_tonemap* process,
+                                 uint32_t* host_rgbcol_out) {
+    // what can be judged from the arguments alone comes first (also without a device), then the device, then the state of the handles
+    CTL_REQUIRE(img && nlm && host_rgbcol_out, "null argument");
+    CTL_REQUIRE((tracer != nullptr) != (host_variance != nullptr), "applyImagePipeline: the NonLocalMeans filter takes its variance from exactly one of a tracer and a host array");
+    CTL_REQUIRE(nlm->k >= 0.0f && nlm->sigma2_scale >= 0.0f, "applyImagePipeline: the NonLocalMeans settings k and sigma2_scale must not be negative or NaN");
+    CTL_TRY
+        require_device();
+        const PixelVarianceBuffer* vb = nullptr;
+        if (tracer) {
+            TracerBase& T = *tracer->t;
+            if (T.getWidth() != img->img.getWidth() || T.getHeight() != img->img.getHeight()) throw std::runtime_error("applyImagePipeline: the tracer's size differs from the image's");
+            if (!T.pixelVarianceOn()) throw std::runtime_error("applyImagePipeline: the tracer keeps no pixel variance (ctl_tracer_set_pixel_variance)");
+            vb = T.getPixelVarianceBuffer();
+        }
+        img->img.apply_pipeline_nlm(splat_scale, *nlm, vb, tracer ? tracer->t->getStream() : nullptr, host_variance, process, host_rgbcol_out);
+    CTL_CATCH
+}
+int ctl_image_read_filtered(ctl_image* img, uint32_t* host_rgbe_out) { CTL_REQUIRE(img && host_rgbe_out, "null argument"); CTL_TRY img->img.read_filtered(host_rgbe_out); CTL_CATCH }
+int ctl_image_last_filter_ms(ctl_image* img, float* ms_out) { CTL_REQUIRE(img && ms_out, "null argument"); *ms_out = img->img.last_filter_ms(); return CTL_OK; }
 int ctl_image_apply_pipeline(ctl_image* img, float splat_scale, uint32_t* host_rgbcol_out) { CTL_REQUIRE(img && host_rgbcol_out, "null argument"); CTL_TRY img->img.apply_pipeline(splat_scale, host_rgbcol_out); CTL_CATCH }
 int ctl_image_write_file(ctl_image* img, float splat_scale, const char* path) { CTL_REQUIRE(img && path, "null argument"); CTL_TRY img->img.write_file(splat_scale, path); CTL_CATCH }
 
@@ -315,6 +335,8 @@ int ctl_tracer_get_block_counts(ctl_tracer* t, uint8_t* out, uint32_t n) {
 int ctl_tracer_get_stats(ctl_tracer* t, ctl_tracer_stats* out) { CTL_REQUIRE(t && out, "null argument"); CTL_TRY t->t->getKernelStats(*out); CTL_CATCH }
 int ctl_tracer_debug_pixel(ctl_tracer* t, ctl_image* img, uint32_t x, uint32_t y, float* rgb_out) { CTL_REQUIRE(t && img, "null argument"); CTL_TRY t->t->Debug(&img->img, x, y, rgb_out); CTL_CATCH }
 int ctl_tracer_set_depth_buffer(ctl_tracer* t, float* device_depth, uint32_t width, uint32_t height) { CTL_REQUIRE(t, "null tracer"); CTL_REQUIRE(device_depth || (width == 0 && height == 0), "null buffer"); CTL_TRY t->t->setDepthBuffer(device_depth, width, height); CTL_CATCH }
+int ctl_tracer_set_pixel_variance(ctl_tracer* t, int on) { CTL_REQUIRE(t, "null tracer"); CTL_TRY t->t->setPixelVariance(on != 0); CTL_CATCH }
+int ctl_tracer_read_pixel_variance(ctl_tracer* t, float* host_out) { CTL_REQUIRE(t && host_out, "null argument"); CTL_TRY t->t->readPixelVariance(host_out); CTL_CATCH }
 int ctl_tracer_set_counting(ctl_tracer* t, int on) { CTL_REQUIRE(t, "null tracer"); CTL_TRY t->t->setCounting(on != 0); CTL_CATCH }
 
 // ---- intersect (row a7 on its own)

@@ -105,7 +105,9 @@ __device__ __forceinline__ void add_sample_ordered(const PARAMS& P, ctl_pixel_da
     const uint32_t idx = (uint32_t)y * P.width + (uint32_t)x;
     // the stage holds THIS RANK'S pixels only (stage_stride = its 64 x 64 tiles x 4096): slot = local tile * 4096 + row-major position in the tile (k_resolve_stage, kernels.hip, inverts it)
     const uint32_t tile = ((uint32_t)y >> 6) * ((P.width + 63u) >> 6) + ((uint32_t)x >> 6);
-    if (idx == pixel) P.stage[(size_t)pass_b * P.stage_stride + (size_t)(tile / P.tile_world) * 4096u + (((uint32_t)y & 63u) << 6) + ((uint32_t)x & 63u)] = make_float4(L.x, L.y, L.z, 1.0f);
+    const size_t slot = (size_t)pass_b * P.stage_stride + (size_t)(tile / P.tile_world) * 4096u + (((uint32_t)y & 63u) << 6) + ((uint32_t)x & 63u);
+    if (idx == pixel) P.stage[slot] = make_float4(L.x, L.y, L.z, 1.0f);
+    else if (P.stray_stage) { float4* r = P.stray_stage + slot; atomicAdd(&r->x, L.x); atomicAdd(&r->y, L.y); atomicAdd(&r->z, L.z); atomicAdd(&r->w, 1.0f); }   // (whole frame: the landing pixel is this rank's)
     else { ctl_pixel_data* r = img + idx; atomicAdd(&r->rgb[0], L.x); atomicAdd(&r->rgb[1], L.y); atomicAdd(&r->rgb[2], L.z); atomicAdd(&r->weight_sum, 1.0f); }
 }
 

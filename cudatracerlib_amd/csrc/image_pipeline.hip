@@ -3,6 +3,7 @@
 // Engine/Image.cu:88-168).  Pure bandwidth kernels over the PixelData frame; one pixel per lane, rows contiguous.
 #include "kernels.h"
 #include "tracer.h"
+#include "pipeline_pixel.h"
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -11,25 +12,6 @@ namespace ctl {
 
 namespace {
 
-__device__ __forceinline__ f3 to_spectrum(const ctl_pixel_data& p, float splat_scale) {   // PixelData::toSpectrum (Engine/Image.h:21-28)
-    const float w = p.weight_sum != 0 ? p.weight_sum : 1;
-    return f3(p.rgb[0] / w + p.rgb_splat[0] * splat_scale, p.rgb[1] / w + p.rgb_splat[1] * splat_scale, p.rgb[2] / w + p.rgb_splat[2] * splat_scale);
-}
-// SpectrumConverter::Float3ToRGBE / RGBEToFloat3 (Math/Spectrum.h:534-565)
-__device__ __forceinline__ uint32_t to_rgbe(f3 c) {
-    float m = max2(max2(c.x, c.y), c.z);
-    if (m < 1e-32f) return 0u;
-    int e; m = (float)frexp((double)m, &e) * 256.0f / m;
-    // float -> unsigned char saturates on the reference's device (negative lobes of the Mitchell / Lanczos filters reach here): say so explicitly
-    auto u8 = [](float v) { return (uint32_t)min2(max2(v, 0.0f), 255.0f); };
-    return u8(c.x * m) | (u8(c.y * m) << 8) | (u8(c.z * m) << 16) | ((uint32_t)(unsigned char)(e + 128) << 24);
-}
-__device__ __forceinline__ f3 from_rgbe(uint32_t v) {
-    const uint32_t w = v >> 24;
-    if (!w) return f3(0.0f);
-    const float e = ldexpf(1.0f, (int)w - (128 + 8));
-    return f3((v & 0xff) * e, ((v >> 8) & 0xff) * e, ((v >> 16) & 0xff) * e);
-}
 // Float3ToCOLORREF / COLORREFToFloat3 (Math/Spectrum.h:521-532)
 __device__ __forceinline__ uint32_t to_rgbcol(f3 c) {
     return (uint32_t)(unsigned char)(clampf(c.x, 0.0f, 1.0f) * 255.0f) | ((uint32_t)(unsigned char)(clampf(c.y, 0.0f, 1.0f) * 255.0f) << 8) |
@@ -140,6 +122,35 @@ void Image::apply_pipeline_ex(float splat_scale, const ctl_reconstruction_filter
     } else {
         hipLaunchKernelGGL(k_to_filtered, dim3(grid), dim3(256), 0, nullptr, px_.p, n, splat_scale, filtered_.p);
     }
+    pipeline_tail(process, host_rgbcol);
+}
+
+void Image::apply_pipeline_nlm(float splat_scale, const ctl_nlm_filter& nlm, const PixelVarianceBuffer* tracer_variance, hipStream_t tracer_stream, const float* host_variance,
+                               const ctl_tonemap* process, uint32_t* host_rgbcol) {
+    const uint32_t n = (uint32_t)px_.n;
+    if (!out_.p) out_.alloc(n);
+    if (!filtered_.p) filtered_.alloc(n);
+    if (!variance_.p) variance_.alloc(n);
+    if (tracer_variance) { tracer_variance->compute_variance(variance_.p, tracer_stream); CTL_HIP(hipStreamSynchronize(tracer_stream)); }
+    else CTL_HIP(hipMemcpy(variance_.p, host_variance, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    CTL_HIP(hipDeviceSynchronize());   // the frame is complete (a tracer renders on its own stream)
+    if (!ev_[0]) { CTL_HIP(hipEventCreate(&ev_[0])); CTL_HIP(hipEventCreate(&ev_[1])); }
+    CTL_HIP(hipEventRecord(ev_[0], nullptr));
+    launch_nlm_filter(nullptr, px_.p, variance_.p, w_, h_, splat_scale, nlm.k, nlm.sigma2_scale, filtered_.p);
+    CTL_HIP(hipEventRecord(ev_[1], nullptr));
+    pipeline_tail(process, host_rgbcol);   // synchronises
+    CTL_HIP(hipEventElapsedTime(&filter_ms_, ev_[0], ev_[1]));
+}
+
+void Image::read_filtered(uint32_t* host_rgbe) {
+    if (!filtered_.p) throw std::runtime_error("getFilteredData: no pipeline call with a filter or a post-process has filled the filtered plane yet");
+    CTL_HIP(hipDeviceSynchronize());
+    CTL_HIP(hipMemcpy(host_rgbe, filtered_.p, px_.n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+}
+
+void Image::pipeline_tail(const ctl_tonemap* process, uint32_t* host_rgbcol) {
+    const uint32_t n = (uint32_t)px_.n;
+    const int grid = (int)std::min<uint32_t>(4096, (n + 255) / 256);
     if (process) {
         if (!lum_.p) lum_.alloc(4);
         const lum_info init{ INT_MAX, 0, 0.0f, 0.0f };   // g_minLum = INT_MAX, the other symbols zeroed (Image.cu:157-158)

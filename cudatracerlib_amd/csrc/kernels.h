@@ -1,6 +1,7 @@
 // kernels.h — per-bounce HIP kernels of the wavefront path tracer and their launch wrappers (kernels.hip).
 #pragma once
 #include "device_scene.h"
+#include "block_sampler.h"
 #include <hip/hip_runtime.h>
 
 namespace ctl {
@@ -71,6 +72,10 @@ struct pass_params {
     // stage[pass-in-batch][pixel] with one plain store (one path per pixel and pass: no two writers), and k_resolve_stage adds the batch to the frame pass by pass, in pass order — the order in which
     // the reference's one-pass-at-a-time loop adds them.  nullptr: atomics (block samplers hand out 0 / 1 / 2 samples per pixel; the megakernel plugin).
     float4* stage; size_t stage_stride;
+    // With the per-pixel variance updated inside the batch (k_resolve_stage): a sample whose film position rounds into the NEXT pixel is not the only one its landing pixel gets in
+    // that pass, so it cannot take the landing pixel's stage slot, and added to the frame at once it would count for the batch's first pass.  It is added (atomics) to
+    // stray_stage[pass-in-batch][landing pixel] instead (same layout as `stage`), and the resolve adds it when it reaches its pass.  nullptr: such a sample goes to the frame at once.
+    float4* stray_stage;
 };
 
 struct launch_ctx { hipStream_t stream; int grid_blocks; bool alpha_test = false; };   // alpha_test: intersect kernels run Material::AlphaTest on candidate hits
@@ -107,7 +112,11 @@ void launch_shade_class_c_wf(const launch_ctx& lc, const dev_scene& S, const wav
 void launch_shade_basic_wf(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
 void launch_shade_full_wf(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
 void launch_finalize(const launch_ctx& lc, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
-void launch_resolve_stage(const launch_ctx& lc, float4* stage, size_t stride, uint32_t n_passes, ctl_pixel_data* image, uint32_t W, uint32_t H, uint32_t tile_rank, uint32_t tile_world);   // frame += the staged samples of a batch, pass by pass; clears the stage
+// frame += the staged samples of a batch, pass by pass; clears the stage.  variance + stray_stage (both or neither; whole frames only): per pass the samples that strayed into the pixel
+// (pass_params::stray_stage) are added before the pixel's own — the order of a pass rendered on its own — and PixelVarianceInfo::updateMoments follows with the frame as it then stands,
+// the first pass of the batch being pass number passes_before + 1 of the rendering (its splat scale)
+void launch_resolve_stage(const launch_ctx& lc, float4* stage, size_t stride, uint32_t n_passes, ctl_pixel_data* image, uint32_t W, uint32_t H, uint32_t tile_rank, uint32_t tile_world,
+                          pixel_variance* variance = nullptr, float4* stray_stage = nullptr, uint32_t passes_before = 0);
 int flat_top_cache_nodes();   // nodes at the head of the flattened node array that the traversal workgroups keep in LDS (traverse_flat.h kTopCache)
 void launch_accumulate_stats(const launch_ctx& lc, const wave_queues& Q, int max_depth);
 void launch_apply_pipeline(const launch_ctx& lc, const ctl_pixel_data* image, uint32_t n, float splat_scale, uint32_t* rgbcol_out);

@@ -119,7 +119,8 @@ __global__ __launch_bounds__(kBlock) void k_finalize(wave_queues Q, pass_params 
 
 // frame += the staged samples of a batch (pass_params::stage), pass by pass in pass order; the stage is left cleared for the next batch.  One lane = one slot of the rank's
 // own tiles (compaction.h add_sample_ordered: local tile * 4096 + row-major position in the tile); the n_passes reads of a lane are n_passes coalesced streams.
-__global__ __launch_bounds__(256) void k_resolve_stage(float4* __restrict__ stage, size_t stride, uint32_t n_passes, ctl_pixel_data* __restrict__ image, uint32_t W, uint32_t H, uint32_t tile_rank, uint32_t tile_world) {
+__global__ __launch_bounds__(256) void k_resolve_stage(float4* __restrict__ stage, size_t stride, uint32_t n_passes, ctl_pixel_data* __restrict__ image, uint32_t W, uint32_t H, uint32_t tile_rank, uint32_t tile_world,
+                                                       pixel_variance* __restrict__ variance, float4* __restrict__ stray_stage, uint32_t passes_before) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= stride) return;
     const uint32_t tiles_x = (W + 63u) >> 6, tile = (uint32_t)(i >> 12) * tile_world + tile_rank, p = (uint32_t)i & 4095u;
@@ -127,14 +128,26 @@ __global__ __launch_bounds__(256) void k_resolve_stage(float4* __restrict__ stag
     if (x >= W || y >= H) return;     // the clipped part of a border tile: nothing was staged there
     ctl_pixel_data* r = image + ((size_t)y * W + x);
     float a = r->rgb[0], b = r->rgb[1], c = r->rgb[2], w = r->weight_sum; bool any = false;
+    pixel_variance pv; float s0 = 0, s1 = 0, s2 = 0;
+    if (variance) { pv = variance[(size_t)y * W + x]; s0 = r->rgb_splat[0]; s1 = r->rgb_splat[1]; s2 = r->rgb_splat[2]; }
     for (uint32_t q = 0; q < n_passes; q++) {
+        if (stray_stage) {   // what strayed into this pixel in pass q: before the pixel's own sample, as where a pass is rendered on its own (atomics while it is traced, then its resolve)
+            const float4 s = stray_stage[(size_t)q * stride + i];
+            if (s.w != 0.0f) { a += s.x; b += s.y; c += s.z; w += s.w; any = true; stray_stage[(size_t)q * stride + i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+        }
         const float4 v = stage[(size_t)q * stride + i];
         if (v.w != 0.0f) { a += v.x; b += v.y; c += v.z; w += v.w; any = true; stage[(size_t)q * stride + i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+        if (variance) {   // the frame as it stands after this pass of the batch (PixelVarianceBuffer::AddPass after every pass, Tracer.h:233-237)
+            const float splat_scale = 1.0f / float(passes_before + q + 1);
+            update_moments(pv, a + s0 * splat_scale, b + s1 * splat_scale, c + s2 * splat_scale, w, 1.0f);
+        }
     }
     if (any) { r->rgb[0] = a; r->rgb[1] = b; r->rgb[2] = c; r->weight_sum = w; }
+    if (variance) variance[(size_t)y * W + x] = pv;
 }
-void launch_resolve_stage(const launch_ctx& lc, float4* stage, size_t stride, uint32_t n_passes, ctl_pixel_data* image, uint32_t W, uint32_t H, uint32_t tile_rank, uint32_t tile_world) {
-    hipLaunchKernelGGL(k_resolve_stage, dim3((unsigned)((stride + 255) / 256)), dim3(256), 0, lc.stream, stage, stride, n_passes, image, W, H, tile_rank, tile_world);
+void launch_resolve_stage(const launch_ctx& lc, float4* stage, size_t stride, uint32_t n_passes, ctl_pixel_data* image, uint32_t W, uint32_t H, uint32_t tile_rank, uint32_t tile_world,
+                          pixel_variance* variance, float4* stray_stage, uint32_t passes_before) {
+    hipLaunchKernelGGL(k_resolve_stage, dim3((unsigned)((stride + 255) / 256)), dim3(256), 0, lc.stream, stage, stride, n_passes, image, W, H, tile_rank, tile_world, variance, stray_stage, passes_before);
 }
 
 // rays of a pass = sum over bounces of (path rays + shadow rays)  (Kernel/TraceHelper.cu:176,745)

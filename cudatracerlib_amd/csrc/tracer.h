@@ -52,6 +52,8 @@ private:
 class Image {
 public:
     Image(uint32_t w, uint32_t h);
+    ~Image() { for (auto e : ev_) if (e) (void)hipEventDestroy(e); }
+    Image(const Image&) = delete; Image& operator=(const Image&) = delete;
     void Clear();
     uint32_t getWidth() const { return w_; }
     uint32_t getHeight() const { return h_; }
@@ -64,11 +66,20 @@ public:
     void resolve_rgb(float splat_scale, float* host_rgb);
     void apply_pipeline(float splat_scale, uint32_t* host_rgbcol);                 // applyImagePipeline without filter / post-process
     void apply_pipeline_ex(float splat_scale, const ctl_reconstruction_filter* filter, const ctl_tonemap* process, uint32_t* host_rgbcol);   // image_pipeline.hip
+    // applyImagePipeline with the NonLocalMeansFilter (nlm_filter.hip).  The per-pixel variance (computeVariance(), w x h floats) comes from the tracer's
+    // PixelVarianceBuffer (device to device) or from host memory: exactly one of the two is given
+    void apply_pipeline_nlm(float splat_scale, const ctl_nlm_filter& nlm, const PixelVarianceBuffer* tracer_variance, hipStream_t tracer_stream, const float* host_variance,
+                            const ctl_tonemap* process, uint32_t* host_rgbcol);
+    void read_filtered(uint32_t* host_rgbe);                                       // Image::getFilteredData: the RGBE plane the last filter / post-process call left
+    float last_filter_ms() const { return filter_ms_; }                            // HIP-event time of the NonLocalMeans kernels of the last apply_pipeline_nlm
     void write_file(float splat_scale, const char* path);                          // Image::WriteDisplayImage (Engine/Image.cpp:67-75)
 private:
-    bool reduced_ = false;
-    uint32_t w_, h_; dbuf<ctl_pixel_data> px_; dbuf<float> rgb_; dbuf<uint32_t> out_, filtered_; dbuf<int> lum_;   // filtered_: m_filteredColorsDevice (RGBE)
+    void pipeline_tail(const ctl_tonemap* process, uint32_t* host_rgbcol);         // the post-process or the plain conversion of the filtered plane, then the D2H
+    bool reduced_ = false; float filter_ms_ = 0; hipEvent_t ev_[2] = { nullptr, nullptr };   // ev_: around the NonLocalMeans kernel, created on first use
+    uint32_t w_, h_; dbuf<ctl_pixel_data> px_; dbuf<float> rgb_, variance_; dbuf<uint32_t> out_, filtered_; dbuf<int> lum_;   // filtered_: m_filteredColorsDevice (RGBE)
 };
+// nlm_filter.hip: one fused launch on `s`; variance = computeVariance() per pixel (device), filtered_rgbe = the RGBE plane written
+void launch_nlm_filter(hipStream_t s, const ctl_pixel_data* px, const float* variance, uint32_t w, uint32_t h, float splat_scale, float k, float sigma2_scale, uint32_t* filtered_rgbe);
 
 // Kernel/TracerSettings.h:14-350 — typed parameters with interval / set constraints: bool, int and float intervals (IntervalParameterConstraint), and
 // enumerations (SetParameterConstraint over the enum's values, addressed by value or by name as TracerParameter<enum> does through its string table)
@@ -153,8 +164,21 @@ public:
     // 2 Difference, 3 Select), re-created by Resize; user weights as IUserPreferenceSampler::setWeight
     BlockSampler* getBlockSampler();
     void setBlockWeight(uint32_t block_x, uint32_t block_y, float w) { getBlockSampler()->set_weight(block_x, block_y, w); }
+    // The PixelVarianceBuffer of Tracer<true> (Kernel/Tracer.h:151,233-237).  The reference updates it after every pass; here that is an opt-in (off by default): the
+    // adaptive block samplers keep it up to date on their own, the switch adds the update where they do not run — inside the batch where the tracer can
+    // (updatesVarianceInBatch), else by rendering one pass per launch.
+    // Refused on a Tracer<false> (one sample per pixel: no variance) and on a tile shard (the NonLocalMeans filter, its consumer, needs the whole frame)
+    void setPixelVariance(bool on);
+    bool pixelVarianceOn() const { return pixel_variance_on_; }
+    const PixelVarianceBuffer* getPixelVarianceBuffer();   // nullptr before Resize
+    void readPixelVariance(float* host_out);                // computeVariance() of every pixel, w x h floats
+    hipStream_t getStream() const { return stream; }
+    unsigned int getWidth() const { return w; }
+    unsigned int getHeight() const { return h; }
     void getKernelStats(ctl_tracer_stats& s) const;
 protected:
+    PixelVarianceBuffer* ensureVarianceBuffer();
+    std::unique_ptr<PixelVarianceBuffer> var_buffer_; bool pixel_variance_on_ = false;
     Scene* m_pScene = nullptr;
     TracerParameterCollection m_sParameters;
     unsigned int w = 0xffffffffu, h = 0xffffffffu;
@@ -192,6 +216,9 @@ protected:
     dbuf<uint32_t> d_jumps, d_starts; sequence_generator::pass_start* h_starts = nullptr; size_t starts_cap = 0;
     std::vector<hipEvent_t> slot_done;
     virtual unsigned int passBatch() const { return 1; }
+    // can DoRender update the PixelVarianceBuffer itself, after each pass of a batch of b (batch_variance_)?  Otherwise the passes are rendered one per launch
+    virtual bool updatesVarianceInBatch(unsigned int b) { (void)b; return false; }
+    pixel_variance* batch_variance_ = nullptr; unsigned int batch_first_pass_ = 0;   // set for a DoRender that has to: the buffer, and the passes rendered before this batch
     static constexpr unsigned int kTableRing = 2;
     void ensureTableRing(unsigned int B);   // device + pinned host staging for `kTableRing` batches of B passes
 public:
@@ -211,13 +238,14 @@ protected:
     void DoRender(Image* I, const float* d_t1, const float* d_t2, unsigned int n_batch) override;
     void takeRayCounts(uint64_t& path_rays, uint64_t& shadow_rays_) override;
     unsigned int passBatch() const override;
+    bool updatesVarianceInBatch(unsigned int b) override;   // where the ordered accumulation's stage holds the batch: its resolve walks the passes in order
 private:
     void growBatch(unsigned int b, const char* who);
     float4* ensureStage(unsigned int b);   // queues for b passes per wavefront; validated before anything changes
     wave_queues Q{};
     uint32_t capacity = 0, n_local_pixels = 0, alloc_batch_ = 1;
     float* depth_buffer_ = nullptr; unsigned int depth_w_ = 0, depth_h_ = 0;
-    std::vector<std::unique_ptr<dbuf<float4>>> f4_; dbuf<float2> px_[2]; dbuf<float4> stage_; dbuf<int> hit_node_; dbuf<uint32_t> occ_[2], counts_, work_, order_, class_order_, mat_counts_; dbuf<unsigned char> mat_key_; dbuf<unsigned long long> stats_;
+    std::vector<std::unique_ptr<dbuf<float4>>> f4_; dbuf<float2> px_[2]; dbuf<float4> stage_, stray_stage_; dbuf<int> hit_node_; dbuf<uint32_t> occ_[2], counts_, work_, order_, class_order_, mat_counts_; dbuf<unsigned char> mat_key_; dbuf<unsigned long long> stats_;
     int grid_blocks = 0;
     float4* new_f4(size_t n);
 };

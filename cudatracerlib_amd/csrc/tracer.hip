@@ -421,10 +421,34 @@ TracerBase::~TracerBase() {
 BlockSampler* TracerBase::getBlockSampler() {   // setCorrectBlockSampler (Tracer.cpp:89-101)
     if (w == 0xffffffffu) throw std::runtime_error("the block sampler exists once Resize was called");
     const auto type = (BlockSampler::Type)m_sParameters.getValue("BlockSamplerType");
-    if (!block_sampler_ || block_sampler_->type() != type || block_sampler_->width() != w || block_sampler_->height() != h) block_sampler_.reset(new BlockSampler(type, w, h));
+    if (!block_sampler_ || block_sampler_->type() != type || block_sampler_->width() != w || block_sampler_->height() != h) {
+        block_sampler_.reset(new BlockSampler(type, w, h));
+        // an adaptive sampler starts from empty statistics, as when it owned them; a Uniform one (also created by the readers and setters outside a render) reads none
+        if (var_buffer_ && type != BlockSampler::Uniform) var_buffer_->clear(stream);
+    }
     block_sampler_->fraction_deterministic = m_sParameters.getValue("FractionDeterministic");
     block_sampler_->fraction_weighted = m_sParameters.getValue("FractionWeighted");
     return block_sampler_.get();
+}
+PixelVarianceBuffer* TracerBase::ensureVarianceBuffer() {
+    if (w == 0xffffffffu) return nullptr;
+    if (!var_buffer_ || var_buffer_->width() != w || var_buffer_->height() != h) var_buffer_.reset(new PixelVarianceBuffer(w, h));
+    return var_buffer_.get();
+}
+void TracerBase::setPixelVariance(bool on) {
+    if (!isMultiPass()) throw unsupported_error("setPixelVariance: a Tracer<false> takes one sample per pixel and keeps no PixelVarianceBuffer");
+    if (on && shard_world > 1) throw std::runtime_error("setPixelVariance: the pixel variance needs the whole frame on one rank");
+    pixel_variance_on_ = on;
+    if (!on && !block_sampler_) var_buffer_.reset();
+}
+const PixelVarianceBuffer* TracerBase::getPixelVarianceBuffer() { return (pixel_variance_on_ || block_sampler_ || var_buffer_) ? ensureVarianceBuffer() : nullptr; }
+void TracerBase::readPixelVariance(float* host_out) {
+    const PixelVarianceBuffer* vb = getPixelVarianceBuffer();
+    if (!vb) throw std::runtime_error("readPixelVariance: the tracer keeps no pixel variance (setPixelVariance is off, or Resize was not called)");
+    dbuf<float> tmp; tmp.alloc((size_t)w * h);
+    vb->compute_variance(tmp.p, stream);
+    CTL_HIP(hipMemcpyAsync(host_out, tmp.p, (size_t)w * h * sizeof(float), hipMemcpyDeviceToHost, stream));
+    CTL_HIP(hipStreamSynchronize(stream));
 }
 void TracerBase::setSamplerTables(const float* t1, const float* t2) {
     const size_t n1 = (size_t)CTL_SAMPLER_NUM_SEQUENCES * CTL_SAMPLER_SEQUENCE_LENGTH;
@@ -510,11 +534,17 @@ template <bool PROGRESSIVE> void Tracer<PROGRESSIVE>::DoPasses(Image* I, bool a_
     BlockSampler* bs = PROGRESSIVE && (m_sParameters.getValue("BlockSamplerType") != 0 || block_sampler_) ? getBlockSampler() : nullptr;
     const bool adaptive = bs && !bs->every_block_once();
     if (adaptive && shard_world > 1) throw std::runtime_error("block samplers other than Uniform need the whole frame on one rank");
-    if (bs && a_NewTrace) bs->start_new_rendering(stream);
+    // the PixelVarianceBuffer is updated after every pass (Tracer.h:233-237) where an adaptive sampler reads it or setPixelVariance asked for it
+    const bool per_pass = adaptive || (PROGRESSIVE && pixel_variance_on_);
+    if (per_pass && shard_world > 1) throw std::runtime_error("the pixel variance needs the whole frame on one rank");
+    PixelVarianceBuffer* vb = (bs || per_pass) ? ensureVarianceBuffer() : nullptr;
+    if (a_NewTrace) { if (bs) bs->start_new_rendering(); if (vb) vb->clear(stream); }
     const size_t n1 = (size_t)CTL_SAMPLER_NUM_SEQUENCES * CTL_SAMPLER_SEQUENCE_LENGTH, n2 = n1 * 2;
     // passes are rendered in batches of `B` (one wavefront carries the paths of B passes; each path uses its own pass's
     // tables), B chosen so that a launch holds enough paths to fill 256 CUs even when a rank owns 1/8 of the tiles
-    const unsigned int B = adaptive ? 1u : std::min(passBatch(), n);
+    // a tracer that can update the variance between the passes of a batch keeps its batches (the adaptive samplers decide pass by pass in any case)
+    const bool var_in_batch = per_pass && !adaptive && updatesVarianceInBatch(std::min(passBatch(), n));
+    const unsigned int B = (per_pass && !var_in_batch) ? 1u : std::min(passBatch(), n);
     const unsigned int ring = kTableRing;   // batches in flight; slot reuse is guarded by an event per slot
     ensureTableRing(B);
     for (int i = 0; i < 5; i++) kernel_ms[i] = 0;
@@ -535,8 +565,10 @@ template <bool PROGRESSIVE> void Tracer<PROGRESSIVE>::DoPasses(Image* I, bool a_
             pass_max_block_count_ = 0; pass_paths_ = 0;
             for (unsigned char c : block_counts) { pass_max_block_count_ = std::max<uint32_t>(pass_max_block_count_, c); pass_paths_ += (uint64_t)c * 4096u; }
         }
+        batch_variance_ = var_in_batch ? vb->device() : nullptr; batch_first_pass_ = m_uPassesDone - nb;
         DoRender(I, d_t1.p + (size_t)slot * B * n1, d_t2.p + (size_t)slot * B * n2, nb);
-        if (adaptive) bs->add_pass(I->device(), getSplatScale(), block_counts, stream);   // PixelVarianceBuffer::AddPass + IBlockSampler::AddPass; synchronises
+        if (per_pass && !var_in_batch) vb->add_pass(I->device(), getSplatScale(), pass_block_counts_, stream);   // PixelVarianceBuffer::AddPass: the sampled blocks (no counts: every block once)
+        if (adaptive) bs->add_pass(*vb, block_counts, stream);                                  // IBlockSampler::AddPass; synchronises
         CTL_HIP(hipEventRecord(slot_done[slot], stream));
         k += nb;
     }
@@ -612,6 +644,19 @@ float4* WavefrontPathTracer::ensureStage(unsigned int b) {
     }
     return stage_.n >= need ? stage_.p : nullptr;
 }
+bool WavefrontPathTracer::updatesVarianceInBatch(unsigned int b) {
+    if (w == 0xffffffffu) return false;
+    growBatch(b, "DoPasses");
+    if (!ensureStage(b)) return false;
+    // the second stage of such a batch (kernels.h pass_params::stray_stage); both within OrderedAccumulationMaxMB, or the passes are rendered one per launch
+    const size_t need = (size_t)n_local_pixels * b;
+    if (2 * need * sizeof(float4) > (size_t)m_sParameters.getValue("OrderedAccumulationMaxMB") << 20) return false;
+    if (stray_stage_.n < need) {
+        try { stray_stage_.alloc(need); CTL_HIP(hipMemsetAsync(stray_stage_.p, 0, need * sizeof(float4), stream)); }
+        catch (const std::exception&) { stray_stage_.free(); (void)hipGetLastError(); return false; }
+    }
+    return true;
+}
 void WavefrontPathTracer::growBatch(unsigned int b, const char* who) {
     if (w == 0xffffffffu || (uint64_t)n_local_pixels * b <= capacity) return;
     check_batch(n_local_pixels, b, who);
@@ -638,7 +683,7 @@ void WavefrontPathTracer::Resize(unsigned int _w, unsigned int _h) {
     Q.capacity = capacity;
     order_.alloc(capacity); Q.order = order_.p; class_order_.free(); for (int c = 0; c < 5; c++) Q.class_order[c] = nullptr;   // the model-class lists (20 B per slot) are allocated by the first render that shades by class
     mat_key_.alloc(capacity); Q.mat_key = mat_key_.p;
-    counts_.free(); work_.free(); mat_counts_.free(); stage_.free();
+    counts_.free(); work_.free(); mat_counts_.free(); stage_.free(); stray_stage_.free();
 }
 
 // stats: [0] path rays, [1] shadow rays, [2..6] closest-hit traversal counts, [7..11] any-hit traversal counts
@@ -695,6 +740,7 @@ void WavefrontPathTracer::DoRender(Image* I, const float* d_t1p, const float* d_
     // four float atomics — same sums, hardware order.
     P.stage = nullptr; P.stage_stride = (size_t)n_local_pixels;
     if (!pass_block_counts_) P.stage = ensureStage(n_batch);
+    P.stray_stage = (batch_variance_ && P.stage) ? stray_stage_.p : nullptr;
     if (pass_block_counts_ && pass_paths_ > capacity) throw std::runtime_error("ray queue overflow: the block sampler asks for more samples in one pass than the queues hold (DoubleRayBuffer.h:86-89)");
     CTL_HIP(hipMemsetAsync(mat_counts_.p, 0, n_mat * sizeof(uint32_t), stream));
     CTL_HIP(hipMemsetAsync(counts_.p, 0, n_counts * sizeof(uint32_t), stream));
@@ -745,7 +791,8 @@ void WavefrontPathTracer::DoRender(Image* I, const float* d_t1p, const float* d_
         shadow_pass(maxPathLength);
         timer.begin(stream, 2); launch_finalize(lc, Q, P, maxPathLength, I->device()); timer.end(stream);
     }
-    if (P.stage) { timer.begin(stream, 2); launch_resolve_stage(lc, P.stage, P.stage_stride, n_batch, I->device(), w, h, shard_rank, shard_world); timer.end(stream); }
+    if (batch_variance_ && !P.stage) throw std::runtime_error("WavefrontPathTracer::DoRender: the batch's variance update needs the stage of the ordered accumulation");
+    if (P.stage) { timer.begin(stream, 2); launch_resolve_stage(lc, P.stage, P.stage_stride, n_batch, I->device(), w, h, shard_rank, shard_world, batch_variance_, P.stray_stage, batch_first_pass_); timer.end(stream); }
     launch_accumulate_stats(lc, Q, maxPathLength);
 }
 

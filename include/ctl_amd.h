@@ -402,7 +402,7 @@ int ctl_image_apply_pipeline(ctl_image* img, float splat_scale, uint32_t* host_r
  *           ids = TYPE_FUNC ids; p0 / p1 = Gaussian alpha | Mitchell B, C | Lanczos tau); the filtered image is kept as RGBE.
  * process = ToneMapPostProcess, Reinhard et al. (PostProcess/ToneMapPostProcess.cu:6-42) driven by Image::ComputeLuminanceInfo
  *           (Engine/Image.cu:88-168) of the RGBE image; the result is quantised to RGBCOL and then gamma-corrected, as there.
- * Either may be NULL (both NULL = ctl_image_apply_pipeline).  The NonLocalMeans filter is not part of this build. */
+ * Either may be NULL (both NULL = ctl_image_apply_pipeline). */
 enum { CTL_RFILTER_BOX = 1, CTL_RFILTER_GAUSSIAN = 2, CTL_RFILTER_MITCHELL = 3, CTL_RFILTER_LANCZOS = 4, CTL_RFILTER_TRIANGLE = 5 };
 typedef struct { uint32_t type; float x_width, y_width, p0, p1; } ctl_reconstruction_filter;
 typedef struct { float key, burn; } ctl_tonemap;           /* defaults of the reference: key 0.18, burn 0 */
@@ -524,6 +524,30 @@ int ctl_tracer_get_stats(ctl_tracer* t, ctl_tracer_stats* out);
 int ctl_tracer_reserve_passes(ctl_tracer* t, uint32_t n_passes);
 int ctl_tracer_set_block_weight(ctl_tracer* t, uint32_t block_x, uint32_t block_y, float weight);
 int ctl_tracer_get_block_counts(ctl_tracer* t, uint8_t* counts_out, uint32_t n_blocks);
+/* The PixelVarianceBuffer of Tracer<true> (Kernel/Tracer.h:233-237, Kernel/PixelVarianceBuffer.h): per-pixel moments of the pass estimates' luminance, what the
+ * NonLocalMeans filter is guided by.  Off by default: with it on, a progressive tracer updates the buffer after every pass (the adaptive block samplers do that on
+ * their own) — the wavefront tracer inside its batches, a tracer without the ordered accumulation's stage by rendering one pass per launch; a new trace clears it.
+ * Frame and variance are those of the passes rendered one at a time, bit for bit.  Against the frame with the switch off: bit-equal, except that a pixel into which a
+ * sample of the neighbouring pixel strayed (its position rounded up: ~1 in 10^4 samples at 1080p) may differ by a rounding — there a batch with the switch off adds the strays
+ * of all its passes first.  CTL_ERR_UNSUPPORTED on a Tracer<false> (PrimTracer),
+ * CTL_ERR_INVALID on a tile shard (world > 1).  ctl_tracer_read_pixel_variance: computeVariance() per pixel, width * height floats, NaN before the first pass. */
+int ctl_tracer_set_pixel_variance(ctl_tracer* t, int on);
+int ctl_tracer_read_pixel_variance(ctl_tracer* t, float* host_out);
+/* applyImagePipeline with the other ImageSamplesFilter, NonLocalMeansFilter (Kernel/ImagePipeline/Filter/NonLocalMeansFilter.{h,cu}): variance-guided non-local means,
+ * search window 13 x 13 (R = 6), patches 7 x 7 (F = 3), from the RGBE frame into the filtered RGBE plane; then `process` (may be NULL) as above.
+ * nlm      = the reference's settings k (default 0.45) and sigma2Scale (default 0.005); both >= 0.  The weights are computed on every call (the reference reuses them
+ *            for UpdateWeightPeriodicity passes; that setting is not offered) and there is no feature buffer (the reference fills one and never reads it).
+ * variance = PixelVarianceInfo::computeVariance() per pixel, from exactly ONE of: `tracer` (its PixelVarianceBuffer, device to device; needs
+ *            ctl_tracer_set_pixel_variance(tracer, 1) and the image's size) or `host_variance` (width * height floats).
+ * Argument values are checked before the device (both or neither variance source, a negative or NaN setting, a null pointer -> CTL_ERR_INVALID), then
+ * CTL_ERR_NO_DEVICE, then what needs the handles (size mismatch, variance switch off -> CTL_ERR_INVALID). */
+typedef struct { float k, sigma2_scale; } ctl_nlm_filter;
+int ctl_image_apply_pipeline_nlm(ctl_image* img, float splat_scale, const ctl_nlm_filter* nlm, ctl_tracer* tracer, const float* host_variance, const ctl_tonemap* process,
+                                 uint32_t* host_rgbcol_out);
+/* Image::getFilteredData: the RGBE plane (r | g << 8 | b << 16 | e << 24 per pixel) that the last pipeline call with a filter or a post-process left. */
+int ctl_image_read_filtered(ctl_image* img, uint32_t* host_rgbe_out);
+/* Measurement: HIP-event time in ms of the NonLocalMeans kernel of the last ctl_image_apply_pipeline_nlm on this image (0 before the first). */
+int ctl_image_last_filter_ms(ctl_image* img, float* ms_out);
 /* run the intersect kernels in counting mode (N_inner / N_tri / N_inst of SURVEY §8d); slower, for measurement only */
 int ctl_tracer_set_counting(ctl_tracer* t, int on);
 
