@@ -10,4 +10,5 @@ from .api import (  # noqa: F401
     ctl_material, ctl_texture, ctl_light, ctl_sensor, ctl_scene_desc, ctl_ray, ctl_hit, ctl_pixel_data,
     ctl_tracer_stats, ctl_traversal_counts, ctl_float4x4,
     diffuse, dielectric, conductor, roughconductor, device_count, intersect, intersect_count,
+    FlatBvh, scene_desc_diff, DIFF_CAMERA, DIFF_MATERIALS, DIFF_LIGHTS, DIFF_TRANSFORMS, DIFF_TOPOLOGY,
 )

@@ -213,7 +213,8 @@ def flatten_probe(desc, format=FLAT_Q4):
 
 class FlatBvhDesc(C.Structure):
     _fields_ = [("format", u32), ("max_depth", u32), ("nodes", C.c_void_p), ("n_nodes", u64), ("node_bytes", u32),
-                ("leaves", C.c_void_p), ("n_leaves", u64), ("child_links", C.c_void_p), ("compact", u32), ("root_slab", u32), ("n_slab_nodes", u64)]
+                ("leaves", C.c_void_p), ("n_leaves", u64), ("child_links", C.c_void_p), ("compact", u32), ("root_slab", u32), ("n_slab_nodes", u64),
+                ("part_index", C.c_void_p), ("part_boxes", C.c_void_p), ("n_part_boxes", u64)]
 
 
 class FlatBvh:
@@ -226,6 +227,21 @@ class FlatBvh:
         self.desc = FlatBvhDesc()
         _check(lib.ctl_flat_bvh_arrays(self._h, C.byref(self.desc)))
 
+    @classmethod
+    def _from_handle(cls, handle, keepalive=None):
+        self = cls.__new__(cls)
+        self._h, self._keepalive = handle, keepalive
+        self.desc = FlatBvhDesc()
+        _check(lib.ctl_flat_bvh_arrays(self._h, C.byref(self.desc)))
+        return self
+
+    def refit(self, desc):
+        """ctl_flat_bvh_refit: the tree refitted in place to the node transforms of `desc` (the description it was built from, moved) with the arithmetic
+        of Scene.update (csrc/flat_refit.h), on the host.  Q4 only.  Returns self."""
+        _check(lib.ctl_flat_bvh_refit(self._h, C.byref(desc)))
+        _check(lib.ctl_flat_bvh_arrays(self._h, C.byref(self.desc)))
+        return self
+
     def nodes(self):
         n = self.desc.n_nodes * self.desc.node_bytes // 4
         return np.ctypeslib.as_array(C.cast(self.desc.nodes, C.POINTER(C.c_uint32)), shape=(n,)).reshape(self.desc.n_nodes, -1)
@@ -234,6 +250,15 @@ class FlatBvh:
         """the explicit links: Q4 (n_nodes, 4) int32, Q8 (n_nodes, 8) in slot order"""
         w = 8 if self.desc.format == FLAT_Q8 else 4
         return np.ctypeslib.as_array(C.cast(self.desc.child_links, C.POINTER(C.c_int32)), shape=(self.desc.n_nodes * w,)).reshape(-1, w)
+
+    def parts(self):
+        """the refit side data of a built Q4 tree: (part_index (n_leaves,) uint32 — 0xffffffff or the entry's clip box, part_boxes (n, 6) float32 {lo, hi} at creation)"""
+        if not self.desc.part_index:
+            return None, None
+        idx = np.ctypeslib.as_array(C.cast(self.desc.part_index, C.POINTER(C.c_uint32)), shape=(self.desc.n_leaves,))
+        n = self.desc.n_part_boxes
+        boxes = np.ctypeslib.as_array(C.cast(self.desc.part_boxes, C.POINTER(C.c_float)), shape=(n * 6,)).reshape(-1, 6) if n else np.zeros((0, 6), np.float32)
+        return idx, boxes
 
     def leaves(self):
         return np.ctypeslib.as_array(C.cast(self.desc.leaves, C.POINTER(C.c_uint32)), shape=(self.desc.n_leaves * 32,)).reshape(-1, 32)
@@ -562,6 +587,12 @@ class DynamicScene:
         _check(lib.ctl_builder_add_node(self._h, u32(mesh_index), None if m is None else C.byref(m), C.byref(out)))
         return out.value
 
+    def SetNodeTransform(self, node, to_world):
+        """DynamicScene::SetNodeTransform (DynamicScene.cpp:338-346): the node's area lights follow; UpdateScene() then gives the moved description."""
+        m = ctl_float4x4()
+        m.m[:] = [float(x) for x in np.asarray(to_world, dtype=np.float32).reshape(16)]
+        _check(lib.ctl_builder_set_node_transform(self._h, u32(node), C.byref(m)))
+
     def CreateLight(self, node, local_material, radiance, rad_texture=None, orthogonal=False):
         """DynamicScene::CreateLight(node, materialName, L) (DynamicScene.cpp:689-711); materials are addressed by local index.
         rad_texture / orthogonal: DiffuseLight::m_rad_texture (a checker or image ctl_texture) and m_bOrthogonal (Light.h:100-101)."""
@@ -656,10 +687,48 @@ class Scene:
             flags |= (FLAT_FORMATS.get(flat_format, flat_format) + 1) << 8
         _check(lib.ctl_scene_create_ex(C.byref(desc), u32(flags), C.byref(self._h)))
 
+    def update(self, desc):
+        """ctl_scene_update: applies what differs between the description the scene holds and `desc` — camera, materials, lights, node transforms (the
+        flattened Q4 tree is refitted on the device) — in place and returns the DIFF_* mask.  Raises CtlError(ERR_INVALID) when the topology differs (the
+        scene is untouched; .last_mask says what was found) and CtlError(ERR_UNSUPPORTED) for a transform change on a Q8 scene.  Start the next pass with new_trace."""
+        mask = u32()
+        code = lib.ctl_scene_update(self._h, C.byref(desc), C.byref(mask))
+        self.last_mask = mask.value
+        _check(code)
+        self._keepalive = desc
+        return mask.value
+
+    def update_stats(self):
+        """ctl_scene_get_update_stats of the last update: dict(node_area_before, node_area_after, refit_ms, refit_levels, mask, restamped)"""
+        st = ctl_scene_update_stats()
+        _check(lib.ctl_scene_get_update_stats(self._h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def flat_bvh(self):
+        """ctl_scene_read_flat_bvh: the device tree copied back as a FlatBvh, without the model / alpha bits stamped into the device copy"""
+        h = C.c_void_p()
+        _check(lib.ctl_scene_read_flat_bvh(self._h, C.byref(h)))
+        return FlatBvh._from_handle(h)
+
     def __del__(self):
         if getattr(self, "_h", None):
             lib.ctl_scene_destroy(self._h)
             self._h = None
+
+
+DIFF_CAMERA, DIFF_MATERIALS, DIFF_LIGHTS, DIFF_TRANSFORMS, DIFF_TOPOLOGY = 1, 2, 4, 8, 16   # CTL_DIFF_*
+ERR_INVALID, ERR_NO_DEVICE, ERR_UNSUPPORTED = -1, -2, -5
+
+
+class ctl_scene_update_stats(C.Structure):
+    _fields_ = [("node_area_before", C.c_double), ("node_area_after", C.c_double), ("refit_ms", f32), ("refit_levels", u32), ("mask", u32), ("restamped", u32)]
+
+
+def scene_desc_diff(a, b):
+    """ctl_scene_desc_diff: the DIFF_* bits of what differs between two descriptions (host only)"""
+    mask = u32()
+    _check(lib.ctl_scene_desc_diff(C.byref(a), C.byref(b), C.byref(mask)))
+    return mask.value
 
 
 def _rays_struct(rays):

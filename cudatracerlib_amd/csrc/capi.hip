@@ -103,6 +103,7 @@ int ctl_builder_set_camera_lookat(ctl_builder* b, const float pos[3], const floa
     CTL_TRY b->b.set_camera_lookat(pos, target, up, fov_degrees, width, height); CTL_CATCH
 }
 int ctl_builder_set_camera(ctl_builder* b, const ctl_sensor* sensor) { CTL_REQUIRE(b && sensor, "null argument"); CTL_TRY b->b.set_camera(*sensor); CTL_CATCH }
+int ctl_builder_set_node_transform(ctl_builder* b, uint32_t node_index, const ctl_float4x4* to_world) { CTL_REQUIRE(b && to_world, "null argument"); CTL_TRY b->b.set_node_transform(node_index, *to_world, true); CTL_CATCH }
 int ctl_builder_finalize(ctl_builder* b, ctl_scene_desc* out) { CTL_REQUIRE(b && out, "null argument"); CTL_TRY b->b.finalize(*out); CTL_CATCH }
 
 int ctl_material_update(ctl_material* m) {   // (a weight from an IMAGE texture's average is final after ctl_builder_finalize, material_textures.h)
@@ -155,6 +156,21 @@ int ctl_scene_create_ex(const ctl_scene_desc* desc, uint32_t flags, ctl_scene** 
     *out = new ctl_scene(*desc, (flags & CTL_SCENE_FLATTEN) != 0, (int)fmt - 1, (flags & CTL_SCENE_REDUCED_ROUGH_TRANSMITTANCE) != 0);
 CTL_CATCH }
 void ctl_scene_destroy(ctl_scene* s) { delete s; }
+// ---- in-place updates (scene_update.hip)
+int ctl_scene_desc_diff(const ctl_scene_desc* a, const ctl_scene_desc* b, uint32_t* mask_out) { CTL_REQUIRE(a && b && mask_out, "null argument"); CTL_TRY *mask_out = scene_desc_diff(*a, *b); CTL_CATCH }
+int ctl_scene_update(ctl_scene* scene, const ctl_scene_desc* new_desc, uint32_t* mask_out) {
+    if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, "no HIP device: the MI355X path tracer has no CPU fallback");
+    CTL_REQUIRE(scene && new_desc, "null argument");
+    const int rc = [&]() -> int { CTL_TRY scene->s.update(*new_desc, nullptr); CTL_CATCH }();
+    if (mask_out) *mask_out = scene->s.last_mask();   // also when the update is refused: the caller sees why
+    return rc;
+}
+int ctl_scene_get_update_stats(ctl_scene* scene, ctl_scene_update_stats* out) { CTL_REQUIRE(scene && out, "null argument"); *out = scene->s.last_update(); return CTL_OK; }
+int ctl_flat_bvh_refit(ctl_flat_bvh* h, const ctl_scene_desc* new_desc) { CTL_REQUIRE(h && new_desc, "null argument"); CTL_TRY refit_flat_scene(h->f, *new_desc, nullptr); CTL_CATCH }
+int ctl_scene_read_flat_bvh(ctl_scene* scene, ctl_flat_bvh** out) {
+    CTL_REQUIRE(scene && out, "null argument");
+    CTL_TRY std::unique_ptr<ctl_flat_bvh> h(new ctl_flat_bvh()); scene->s.read_flat_bvh(h->f); *out = h.release(); CTL_CATCH
+}
 int ctl_set_cache_dir(const char* dir) { CTL_TRY set_cache_dir(dir); CTL_CATCH }
 int ctl_flatten_probe(const ctl_scene_desc* desc, uint32_t format, uint64_t* out4) {
     CTL_REQUIRE(desc && out4 && format <= CTL_FLAT_Q8, "null argument or bad format");
@@ -185,6 +201,9 @@ int ctl_flat_bvh_arrays(const ctl_flat_bvh* h, ctl_flat_bvh_desc* out) {
     out->leaves = F.leaves.data(); out->n_leaves = F.leaves.size();
     out->child_links = (F.format == kFlatQ4 || F.format == kFlatQ8) ? F.child_links.data() : nullptr; out->compact = ((F.format == kFlatQ4 && F.compact_links) || F.format == kFlatQ8) ? 1u : 0u;
     out->root_slab = F.root_slab ? 1u : 0u; out->n_slab_nodes = F.slab_nodes;
+    const bool side = F.format == kFlatQ4 && F.refit.part_index.size() == F.leaves.size();
+    out->part_index = side ? F.refit.part_index.data() : nullptr; out->n_part_boxes = side ? F.refit.part_boxes.size() : 0;
+    out->part_boxes = (side && !F.refit.part_boxes.empty()) ? F.refit.part_boxes[0].lo : nullptr;
     return CTL_OK;
 }
 void ctl_flat_bvh_destroy(ctl_flat_bvh* h) { delete h; }

@@ -9,6 +9,7 @@
 #include "flat_slab.h"
 #include "bvh_builder.h"
 #include "scene_cache.h"
+#include "mitsuba_loader.h"   // unsupported_error
 #include <cmath>
 #include <cstring>
 #include <algorithm>
@@ -147,6 +148,23 @@ bool flat_links_valid(const flat_scene& F) {
 struct slab_ctri { double w[3][3]; double slack; int c; };   // a triangle under child c of the node whose slab is being chosen
 float round_down(double x) { float f = (float)x; return ((double)f > x) ? std::nextafterf(f, -INFINITY) : f; }
 float round_up(double x) { float f = (float)x; return ((double)f < x) ? std::nextafterf(f, INFINITY) : f; }
+// the part of the refit side data (flat_refit.h) that the tree and the description give: the nodes by depth and the transforms the tree was built for
+void finish_refit_side(flat_scene& F, const ctl_scene_desc& d) {
+    F.refit.level_start.clear(); F.refit.level_nodes.clear(); F.refit.xf0.clear();
+    if (F.format != kFlatQ4 || F.nodes.empty()) return;
+    F.refit.xf0.assign(d.node_transforms, d.node_transforms + d.n_nodes);
+    std::vector<uint32_t> depth(F.nodes.size(), 0u), count;
+    for (size_t i = 0; i < F.nodes.size(); i++) {   // children come later in memory than their parent
+        if (depth[i] >= count.size()) count.resize(depth[i] + 1, 0u);
+        count[depth[i]]++;
+        for (int c = 0; c < 4; c++) { const int32_t k = F.child_links[i * 4 + c]; if (((F.nodes[i].mask >> c) & 1) && k >= 0 && k != 0x76543210) depth[(size_t)k / 4] = depth[i] + 1; }
+    }
+    F.refit.level_start.assign(count.size() + 1, 0u);
+    for (size_t l = 0; l < count.size(); l++) F.refit.level_start[l + 1] = F.refit.level_start[l] + count[l];
+    F.refit.level_nodes.resize(F.nodes.size());
+    std::vector<uint32_t> fill(F.refit.level_start.begin(), F.refit.level_start.end() - 1);
+    for (size_t i = 0; i < F.nodes.size(); i++) F.refit.level_nodes[fill[depth[i]]++] = (uint32_t)i;
+}
 
 }  // namespace
 
@@ -163,6 +181,7 @@ int default_flat_format() {
 
 bool flatten_scene(const ctl_scene_desc& d, flat_scene& out, size_t max_triangles, int format) {
     out.nodes.clear(); out.nodes_q8.clear(); out.nodes_f4.clear(); out.nodes_f2.clear(); out.leaves.clear(); out.compact_links = true; out.split_refs = 0;
+    out.refit = flat_scene::refit_side();
     out.format = (format == kFlatF4 || format == kFlatF2 || format == kFlatQ8) ? format : kFlatQ4;
     phase_timer pt;
     // leaf-entry range of every mesh (the woop stream is shared; a mesh ends where the next one starts)
@@ -196,13 +215,26 @@ bool flatten_scene(const ctl_scene_desc& d, flat_scene& out, size_t max_triangle
         key = H.hex();
         cache_reader rd("flat", key);
         int c_format = -1, c_depth = 0, c_compact = 0, c_root_slab = 0; uint64_t c_slab_nodes = 0, c_split_refs = 0;
-        if (rd.found() && rd.value(c_format) && rd.value(c_depth) && rd.value(c_compact) && rd.vector(out.nodes) && rd.vector(out.nodes_q8) && rd.vector(out.nodes_f4) && rd.vector(out.nodes_f2) && rd.vector(out.leaves) && rd.vector(out.child_links) && rd.value(c_root_slab) && rd.value(c_slab_nodes) && rd.value(c_split_refs) && rd.verify() &&
-            c_format == out.format && ((out.compact_links = c_compact != 0), flat_links_valid(out))) {
+        // The refit side data (flat_refit.h) follows the tree in files written since it exists.  A file without it still loads when its tree holds no split
+        // reference (every entry then stands for its whole triangle); one with split references is rebuilt and rewritten.  rd.verify() runs first and wants every
+        // section read, so the two optional sections are read inside the chain, right before it
+        auto side_ok = [](cache_reader&, flat_scene& F, size_t split_refs) {
+            if (F.format != kFlatQ4) { F.refit.part_index.clear(); F.refit.part_boxes.clear(); return true; }
+            if (F.refit.part_index.size() == F.leaves.size()) { for (uint32_t p : F.refit.part_index) if (p != kRefitNoPart && p >= F.refit.part_boxes.size()) return false; return true; }
+            if (!F.refit.part_index.empty() || split_refs != 0) return false;
+            F.refit.part_index.assign(F.leaves.size(), kRefitNoPart); F.refit.part_boxes.clear();
+            return true;
+        };
+        out.refit = flat_scene::refit_side();
+        if (rd.found() && rd.value(c_format) && rd.value(c_depth) && rd.value(c_compact) && rd.vector(out.nodes) && rd.vector(out.nodes_q8) && rd.vector(out.nodes_f4) && rd.vector(out.nodes_f2) && rd.vector(out.leaves) && rd.vector(out.child_links) && rd.value(c_root_slab) && rd.value(c_slab_nodes) && rd.value(c_split_refs) && (rd.remaining() == 0 || (rd.vector(out.refit.part_index) && rd.vector(out.refit.part_boxes))) && rd.verify() &&
+            c_format == out.format && ((out.compact_links = c_compact != 0), flat_links_valid(out)) && side_ok(rd, out, (size_t)c_split_refs)) {
+            finish_refit_side(out, d);
             out.max_depth = c_depth; out.root_slab = c_root_slab != 0; out.slab_nodes = (size_t)c_slab_nodes; out.split_refs = (size_t)c_split_refs; pt.lap("cache hit");
             return true;
         }
         out.nodes.clear(); out.nodes_q8.clear(); out.nodes_f4.clear(); out.nodes_f2.clear(); out.leaves.clear(); out.child_links.clear(); out.compact_links = true;
     }
+    out.refit = flat_scene::refit_side();
     struct wtri { uint32_t tri, node, woop, local; };   // local: index into mesh_local[mesh of node] (a triangle split below is referenced by several entries)
     // object-space vertices of every mesh's triangles once (degenerate ones can never be hit and are dropped), then per node in parallel
     struct ltri { double v[3][3]; uint32_t tri, woop; };
@@ -250,6 +282,7 @@ bool flatten_scene(const ctl_scene_desc& d, flat_scene& out, size_t max_triangle
     // flat_split_ratio() x the MEDIAN length of the scene's triangle boxes: the scene's own scale, so a beam through fine geometry ends up in finer pieces than a floor under coarse
     // one.  The total is held to + 30 % references by doubling that length.  The traversal tests the whole triangle wherever a reference leads it (same hit, same bits; a second
     // encounter of the closest hit does not pass t < t_hit).  Measured with the oracle's counting traversal (tools/bvh_quality_probe.py): DESIGN.md §3.
+    std::vector<uint8_t> is_part;
     if (flat_split_ratio() > 0.0f) {
         const size_t n0 = boxes.size(), budget = n0 * 3 / 10 + 64;
         auto longest = [](const aabb& b) { return std::max(std::max(b.hi[0] - b.lo[0], b.hi[1] - b.lo[1]), b.hi[2] - b.lo[2]); };
@@ -324,6 +357,9 @@ bool flatten_scene(const ctl_scene_desc& d, flat_scene& out, size_t max_triangle
         for (size_t i = 0; i < big.size(); i++) boxes[big[i]] = first[i];
         tris.reserve(n0 + extra.size()); boxes.reserve(n0 + extra.size());
         for (const piece& e : extra) { tris.push_back(tris[e.src]); boxes.push_back(e.box); }
+        is_part.assign(boxes.size(), 0);   // references whose box is the clip box of a part (the refit side data keeps it)
+        for (uint32_t g : big) is_part[g] = 1;
+        for (size_t g = n0; g < boxes.size(); g++) is_part[g] = 1;
         out.split_refs = extra.size();
         pt.lap("split large triangles");
     }
@@ -572,6 +608,16 @@ bool flatten_scene(const ctl_scene_desc& d, flat_scene& out, size_t max_triangle
             L.index = (t.tri << 1) | (R.leaf_last[src] ? 1u : 0u); L.node = t.node;
         }
     });
+    if (out.format == kFlatQ4) {
+        out.refit.part_index.assign(entry_src.size(), kRefitNoPart);
+        for (size_t i = 0; i < entry_src.size(); i++) {
+            const size_t g = R.leaf_prims[entry_src[i]];
+            if (g >= is_part.size() || !is_part[g]) continue;
+            out.refit.part_index[i] = (uint32_t)out.refit.part_boxes.size();
+            refit_box pb; for (int r = 0; r < 3; r++) { pb.lo[r] = boxes[g].lo[r]; pb.hi[r] = boxes[g].hi[r]; }
+            out.refit.part_boxes.push_back(pb);
+        }
+    }
     pt.lap("leaf entries");
     out.max_depth = wdepth;
     if (out.format != kFlatQ8) out.child_links.clear();
@@ -783,9 +829,63 @@ bool flatten_scene(const ctl_scene_desc& d, flat_scene& out, size_t max_triangle
     }
     if (!key.empty()) {
         cache_writer wr("flat", key);
-        if (wr.active()) { wr.value(out.format); wr.value(out.max_depth); { const int cl = out.compact_links ? 1 : 0; wr.value(cl); } wr.vector(out.nodes); wr.vector(out.nodes_q8); wr.vector(out.nodes_f4); wr.vector(out.nodes_f2); wr.vector(out.leaves); wr.vector(out.child_links); { const int rs = out.root_slab ? 1 : 0; wr.value(rs); const uint64_t sn = out.slab_nodes; wr.value(sn); const uint64_t sr = out.split_refs; wr.value(sr); } wr.commit(); pt.lap("cache write"); }
+        if (wr.active()) { wr.value(out.format); wr.value(out.max_depth); { const int cl = out.compact_links ? 1 : 0; wr.value(cl); } wr.vector(out.nodes); wr.vector(out.nodes_q8); wr.vector(out.nodes_f4); wr.vector(out.nodes_f2); wr.vector(out.leaves); wr.vector(out.child_links); { const int rs = out.root_slab ? 1 : 0; wr.value(rs); const uint64_t sn = out.slab_nodes; wr.value(sn); const uint64_t sr = out.split_refs; wr.value(sr); } if (out.format == kFlatQ4) { wr.vector(out.refit.part_index); wr.vector(out.refit.part_boxes); } wr.commit(); pt.lap("cache write"); }
     }
+    finish_refit_side(out, d);
     return true;
+}
+
+double flat_scene_node_area(const flat_scene& F) {
+    double a = 0.0;
+    for (const flat4_node& n : F.nodes) { uint32_t w[10]; std::memcpy(w, &n, 40); a += refit_node_area(w); }
+    return a;
+}
+
+// The host refit: the yardstick of the kernels in flat_refit.hip, which run the same functions of flat_refit.h in the same order.
+void refit_flat_scene(flat_scene& F, const ctl_scene_desc& d, double* area_before_after) {
+    if (F.format != kFlatQ4) throw unsupported_error("refit: only the Q4 node format can be refitted");
+    if (!F.refit.ready() || F.refit.part_index.size() != F.leaves.size()) throw std::runtime_error("refit: the tree carries no refit data");
+    if (d.n_nodes != F.refit.xf0.size()) throw std::runtime_error("refit: the description has another number of nodes than the tree was built from");
+    if (area_before_after) area_before_after[0] = flat_scene_node_area(F);
+    std::vector<double> P((size_t)d.n_nodes * 12);
+    for (uint32_t k = 0; k < d.n_nodes; k++)
+        if (!refit_carry_matrix(d.node_transforms[k].m, F.refit.xf0[k].m, &P[(size_t)k * 12])) throw std::runtime_error("refit: singular node transform");
+    for (const flat_leaf& L : F.leaves) if (L.node >= d.n_nodes) throw std::runtime_error("refit: leaf entry out of range");
+    std::vector<refit_box> ebox(F.leaves.size()), nbox(F.nodes.size());
+    parallel_for(F.leaves.size(), [&](size_t i0, size_t i1) {
+        for (size_t i = i0; i < i1; i++) {
+            flat_leaf& L = F.leaves[i];
+            std::memcpy(L.inv, d.node_inv_transforms[L.node].m, 48); L.w33 = d.node_inv_transforms[L.node].m[15];
+            const uint32_t pi = F.refit.part_index[i];
+            refit_entry_box(L.a, L.b, L.c, d.node_transforms[L.node].m, pi == kRefitNoPart ? nullptr : &F.refit.part_boxes[pi], &P[(size_t)L.node * 12], ebox[i]);
+        }
+    });
+    const auto& R = F.refit;
+    for (size_t l = R.level_start.size() - 1; l-- > 0;) {
+        parallel_for(R.level_start[l + 1] - R.level_start[l], [&](size_t j0, size_t j1) {
+            for (size_t j = j0; j < j1; j++) {
+                const uint32_t i = R.level_nodes[R.level_start[l] + j];
+                flat4_node& n = F.nodes[i];
+                const uint32_t exist = n.mask & 15u;
+                refit_box cb[4];
+                for (int c = 0; c < 4; c++) {
+                    if (!((exist >> c) & 1u)) continue;
+                    const int32_t k = F.child_links[(size_t)i * 4 + c];
+                    if (k >= 0) { cb[c] = nbox[(size_t)k / 4]; continue; }
+                    for (int r = 0; r < 3; r++) { cb[c].lo[r] = kRefitBig; cb[c].hi[r] = -kRefitBig; }
+                    for (uint32_t e = (uint32_t)~k;; e++) {
+                        for (int r = 0; r < 3; r++) { cb[c].lo[r] = std::min(cb[c].lo[r], ebox[e].lo[r]); cb[c].hi[r] = std::max(cb[c].hi[r], ebox[e].hi[r]); }
+                        if (F.leaves[e].index & 1u) break;
+                    }
+                }
+                uint32_t w[10]; std::memcpy(w, &n, 40);
+                refit_node_boxes(w, exist, cb, nbox[i]);
+                std::memcpy(&n, w, 40);
+                if (F.compact_links && n.slab_n != 0u) { n.slab_n = kRefitNeutralSlabN; std::memcpy(&n.slab_base, &kRefitNeutralSlabBase, 4); uint32_t lo = 0, hi = 0; for (int c = 0; c < 4; c++) { if ((exist >> c) & 1u) hi |= 255u << (8 * c); else lo |= 255u << (8 * c); } n.slab_lo = lo; n.slab_hi = hi; }
+            }
+        }, 1024);
+    }
+    if (area_before_after) area_before_after[1] = flat_scene_node_area(F);
 }
 
 }  // namespace ctl

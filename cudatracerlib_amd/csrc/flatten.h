@@ -8,6 +8,7 @@
 #pragma once
 #include "../../include/ctl_amd.h"
 #include "flat8.h"
+#include "flat_refit.h"
 #include <vector>
 #include <cstddef>
 
@@ -110,12 +111,25 @@ struct flat_scene {
     bool root_slab = false;               // Q4: the root node itself carries a slab (single-node trees)
     size_t slab_nodes = 0;                // Q4: nodes that carry a slab
     size_t split_refs = 0;                // references added by early split clipping (flatten.cpp; a triangle with k references has k leaf entries)
+    // what a refit needs besides the tree (flat_refit.h; Q4 only, empty otherwise).  Not part of the tree arrays: ctl_flatten_probe's hash does not cover it
+    struct refit_side {
+        std::vector<uint32_t> part_index;       // per leaf entry: kRefitNoPart, or its clip box in part_boxes (a split reference)
+        std::vector<refit_box> part_boxes;      // world space, at creation
+        std::vector<ctl_float4x4> xf0;          // node transforms at creation
+        std::vector<uint32_t> level_start, level_nodes;   // node ids grouped by depth: level l = level_nodes[level_start[l] .. level_start[l + 1])
+        bool ready() const { return !level_nodes.empty(); }
+        size_t bytes() const { return part_index.size() * 4 + part_boxes.size() * sizeof(refit_box) + xf0.size() * sizeof(ctl_float4x4) + (level_start.size() + level_nodes.size()) * 4; }
+    } refit;
     size_t node_bytes() const { return nodes.size() * sizeof(flat4_node) + nodes_f4.size() * sizeof(flat4f_node) + nodes_f2.size() * sizeof(ctl_bvh_node) + nodes_q8.size() * sizeof(flat8_node); }
     int stack_need() const { return (format == kFlatF2 || format == kFlatQ8) ? max_depth + 2 : 3 * max_depth + 2; }   // traversal-stack entries a ray can need (Q8: one sibling group per level)
 };
 
 // false when the scene has no triangles or more than `max_triangles` instanced triangles
 bool flatten_scene(const ctl_scene_desc& d, flat_scene& out, size_t max_triangles, int format = kFlatQ4);
+// Refit of a Q4 tree to the node transforms of `d` (flat_refit.h): same nodes / meshes as the description the tree was built from, links, masks and memory order
+// unchanged.  area_before_after (may be null): summed surface area of the nodes' boxes before and after, a SAH proxy.  Throws when the tree cannot be refitted.
+void refit_flat_scene(flat_scene& F, const ctl_scene_desc& d, double* area_before_after);
+double flat_scene_node_area(const flat_scene& F);   // Q4: sum over the nodes of the surface area of the box around their decoded child boxes
 int default_flat_format();   // kFlatQ4 unless $CTL_FLAT_FORMAT says q4 / f4 / f2 (measurement knob)
 
 }  // namespace ctl

@@ -242,14 +242,21 @@ uint32_t scene_builder::add_node(uint32_t mesh_index, const ctl_float4x4* to_wor
     return (uint32_t)nodes.size() - 1;
 }
 
-// DynamicScene::SetNodeTransform (Engine/DynamicScene.cpp:338-346).  Area lights created from the node BEFORE the call keep the
-// triangles of the old transform (the reference recalculates them; the loader always sets the transform first).
-void scene_builder::set_node_transform(uint32_t node_index, const ctl_float4x4& m) {
+// DynamicScene::SetNodeTransform (Engine/DynamicScene.cpp:338-346).  recalculate_lights: the area lights of the node have their shape sets recalculated for the
+// new transform, as the reference does (ctl_builder_set_node_transform).  The Mitsuba loader sets a transform before it creates the node's lights — except for the
+// first instance of a shapegroup, whose lights keep the triangles of the group's own transform as they always did here — and passes false.
+void scene_builder::set_node_transform(uint32_t node_index, const ctl_float4x4& m, bool recalculate_lights) {
     if (node_index >= nodes.size()) throw std::runtime_error("set_node_transform: bad node index");
     if (m.m[12] != 0.0f || m.m[13] != 0.0f || m.m[14] != 0.0f || m.m[15] != 1.0f) throw std::runtime_error("set_node_transform: node transform must be affine (last row 0 0 0 1)");
     ctl_float4x4 inv; mat_inverse(m.m, inv.m);
     if (inv.m[12] != 0.0f || inv.m[13] != 0.0f || inv.m[14] != 0.0f || !(inv.m[15] > 0.0f)) throw std::runtime_error("set_node_transform: node transform is singular");
     xf[node_index] = m; ixf[node_index] = inv;
+    const ctl_node& N = nodes[node_index];
+    for (uint32_t k = 0; recalculate_lights && k < N.n_lights && k < 2; k++) {
+        if (N.lights[k] >= lights.size()) continue;
+        ctl_light& L = lights[N.lights[k]];
+        if (L.type == CTL_LIGHT_DIFFUSE && L.node_idx == node_index && L.count) L.sum_area = recalculate_shape_set(node_index, L.area_dist_index, L.triangles_index, L.count);
+    }
 }
 // `mat->bsdf = ...; mat->bsdf.As()->m_enableTwoSided = ...` of BsdfParser::apply_bsdf (ObjectParser.h:996-1010): replaces the BSDF
 // of one of the node's materials and keeps its NodeLightIndex
@@ -278,6 +285,29 @@ aabb scene_builder::scene_box() const {
     return scene;
 }
 
+// ShapeSet::Recalculate (Engine/ShapeSet.cpp:17-59 / triData::Recalculate, ShapeSet.cu:11-23) of one area light: world-space corners, normal and area of its
+// triangles (named by i_dat / t_dat of the records in the anim blob) from the node's CURRENT transform, and the normalised area CDF.  Returns the summed area.
+float scene_builder::recalculate_shape_set(uint32_t node_index, uint32_t cdf_off, uint32_t tri_off, uint32_t count) {
+    m34 l2w = as_m34(xf[node_index].m);
+    std::vector<float> cdf(count + 1); std::vector<ctl_shape_tri> st(count);
+    std::memcpy(st.data(), anim.data() + tri_off, st.size() * sizeof(ctl_shape_tri));
+    float sumArea = 0; cdf[0] = 0.0f;
+    for (uint32_t i = 0; i < count; i++) {
+        ctl_shape_tri& s = st[i];
+        f3 p[3]; woop_get_data(woop[s.i_dat], p[0], p[1], p[2]);
+        f3 n = tri_data_center_normal(tri[s.t_dat], l2w);
+        for (int k = 0; k < 3; k++) p[k] = xform_point(l2w, p[k]);
+        float area = 0.5f * length(cross(p[2] - p[0], p[1] - p[0]));
+        for (int k = 0; k < 3; k++) { s.p[k][0] = p[k].x; s.p[k][1] = p[k].y; s.p[k][2] = p[k].z; }
+        s.n[0] = n.x; s.n[1] = n.y; s.n[2] = n.z; s.area = area;
+        sumArea += area; cdf[i + 1] = cdf[i] + area;
+    }
+    for (uint32_t i = 0; i <= count; i++) cdf[i] = cdf[i] / sumArea;
+    std::memcpy(anim.data() + cdf_off, cdf.data(), cdf.size() * sizeof(float));
+    std::memcpy(anim.data() + tri_off, st.data(), st.size() * sizeof(ctl_shape_tri));
+    return sumArea;
+}
+
 // DynamicScene::CreateLight(node, matName, L) + CreateShape (Engine/DynamicScene.cpp:689-767) + ShapeSet (Engine/ShapeSet.cpp:17-59)
 uint32_t scene_builder::add_area_light(uint32_t node_index, uint32_t local_material, const float radiance[3], const ctl_texture* rad_texture, bool orthogonal) {
     if (node_index >= nodes.size()) throw std::runtime_error("ctl_builder_add_area_light: bad node index");
@@ -299,22 +329,10 @@ uint32_t scene_builder::add_area_light(uint32_t node_index, uint32_t local_mater
     auto align_to = [&](size_t a) { while (anim.size() % a) anim.push_back(0); };
     align_to(4); uint32_t cdf_off = (uint32_t)anim.size(); anim.resize(anim.size() + (count + 1) * sizeof(float));
     align_to(16); uint32_t tri_off = (uint32_t)anim.size(); anim.resize(anim.size() + (size_t)count * sizeof(ctl_shape_tri));
-    m34 l2w = as_m34(xf[node_index].m);
-    std::vector<float> cdf(count + 1); std::vector<ctl_shape_tri> st(count);
-    float sumArea = 0; cdf[0] = 0.0f;
-    for (uint32_t i = 0; i < count; i++) {   // ShapeSet::triData::Recalculate (Engine/ShapeSet.cu:11-23)
-        f3 p[3]; woop_get_data(woop[sel_woop[i]], p[0], p[1], p[2]);
-        f3 n = tri_data_center_normal(tri[sel_tri[i]], l2w);
-        for (int k = 0; k < 3; k++) p[k] = xform_point(l2w, p[k]);
-        float area = 0.5f * length(cross(p[2] - p[0], p[1] - p[0]));
-        ctl_shape_tri& s = st[i];
-        for (int k = 0; k < 3; k++) { s.p[k][0] = p[k].x; s.p[k][1] = p[k].y; s.p[k][2] = p[k].z; }
-        s.n[0] = n.x; s.n[1] = n.y; s.n[2] = n.z; s.area = area; s.i_dat = sel_woop[i]; s.t_dat = sel_tri[i];
-        sumArea += area; cdf[i + 1] = cdf[i] + area;
-    }
-    for (uint32_t i = 0; i <= count; i++) cdf[i] = cdf[i] / sumArea;
-    std::memcpy(anim.data() + cdf_off, cdf.data(), cdf.size() * sizeof(float));
+    std::vector<ctl_shape_tri> st(count);
+    for (uint32_t i = 0; i < count; i++) { st[i] = ctl_shape_tri{}; st[i].i_dat = sel_woop[i]; st[i].t_dat = sel_tri[i]; }
     std::memcpy(anim.data() + tri_off, st.data(), st.size() * sizeof(ctl_shape_tri));
+    const float sumArea = recalculate_shape_set(node_index, cdf_off, tri_off, count);
     ctl_light L{};
     L.type = CTL_LIGHT_DIFFUSE; L.radiance[0] = radiance[0]; L.radiance[1] = radiance[1]; L.radiance[2] = radiance[2];
     L.area_dist_index = cdf_off; L.triangles_index = tri_off; L.sum_area = sumArea; L.count = count; L.orthogonal = orthogonal ? 1u : 0u; L.node_idx = node_index;

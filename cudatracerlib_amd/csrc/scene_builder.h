@@ -47,7 +47,8 @@ struct scene_builder {
                       const uint8_t* tri_material, const ctl_material* materials, uint32_t n_mat,
                       bool flip_normals = false, bool face_normals = false, float max_smooth_angle = 0.0f);   // Mesh::CompileMesh options (Mesh.cpp:199)
     uint32_t add_node(uint32_t mesh_index, const ctl_float4x4* to_world);
-    void set_node_transform(uint32_t node_index, const ctl_float4x4& to_world);
+    void set_node_transform(uint32_t node_index, const ctl_float4x4& to_world, bool recalculate_lights = false);
+    float recalculate_shape_set(uint32_t node_index, uint32_t cdf_off, uint32_t tri_off, uint32_t count);   // ShapeSet::Recalculate of one area light in the anim blob
     void set_node_bsdf(uint32_t node_index, uint32_t local_material, const ctl_material& m);
     uint32_t add_aux_material(const ctl_material& m);   // a material no triangle refers to: the nested BSDF of a coating / roughcoating / blend; returns its absolute index
     const ctl_material& node_material(uint32_t node_index, uint32_t local_material) const;

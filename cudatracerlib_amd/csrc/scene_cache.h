@@ -61,6 +61,7 @@ public:
         return bytes == 0 || body(v.data(), bytes);
     }
     template <typename T> bool value(T& v) { uint64_t bytes; return next(bytes) && bytes == sizeof(T) && body(&v, sizeof(T)); }
+    uint32_t remaining() const { return f_ ? left_ : 0; }   // sections not read yet (a file may end with sections a later version added)
     bool verify();   // every section was read and the trailing checksum matches what was read
 private:
     FILE* f_ = nullptr; uint32_t left_ = 0; content_hash sum_; bool ok_ = true;

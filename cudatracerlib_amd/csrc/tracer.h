@@ -7,6 +7,7 @@
 #include "kernels.h"
 #include "sequence_generator.h"
 #include "block_sampler.h"
+#include "flatten.h"
 #include <hip/hip_runtime.h>
 #include <map>
 #include <string>
@@ -31,18 +32,54 @@ template <typename T> struct dbuf {   // tracked device allocation (Base/CudaMem
     void upload(const T* h, size_t count, hipStream_t s = 0) { if (count > n) alloc(count); if (count) CTL_HIP(hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, s)); }
 };
 
+// ctl_scene_desc_diff: the CTL_DIFF_* bits of what differs between two descriptions.  a_geometry_hash: when given, `a` is a snapshot without its geometry arrays
+// (triangles, Woop rows, mesh BVHs, texels, transmittance tables) and they are compared through scene_geometry_hash(b) instead
+uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const uint64_t* a_geometry_hash = nullptr);
+void scene_geometry_hash(const ctl_scene_desc& d, uint64_t out[2]);
+// the host copy of a description that a scene keeps to diff an update against (scene_update.hip)
+struct desc_snapshot {
+    ctl_scene_desc d{};   // pointers into the vectors below; the geometry arrays are null
+    std::vector<ctl_kernel_mesh> meshes; std::vector<ctl_node> nodes; std::vector<ctl_material> materials; std::vector<ctl_light> lights; std::vector<uint8_t> anim;
+    std::vector<ctl_bvh_node> top; std::vector<ctl_float4x4> xf, ixf; std::vector<ctl_mipmap> images;
+    uint64_t geometry_hash[2] = { 0, 0 };
+};
+
 // KernelDynamicScene in HBM (UpdateKernel, Kernel/TraceHelper.cu:182-217)
 class Scene {
 public:
     // flatten: also build the single-level world-space BVH (flatten.cpp) and make the intersect kernels use it
     // flat_format: flat_format of flatten.h, or -1 for the default (Q4 / $CTL_FLAT_FORMAT)
     explicit Scene(const ctl_scene_desc& d, bool flatten = false, int flat_format = -1, bool reduced_rough_transmittance = false);
+    ~Scene();
     bool flattened() const { return S.flat_nodes != nullptr; }
+    // ctl_scene_update (scene_update.hip): applies what differs between the description the scene holds and `d` in place — everything but topology — and returns the CTL_DIFF_* mask.
+    // Throws std::runtime_error (topology differs; nothing was changed) or unsupported_error (a transform change on a tree that cannot be refitted).  Synchronous.
+    uint32_t update(const ctl_scene_desc& d, ctl_scene_update_stats* stats);
+    uint32_t last_mask() const { return last_mask_; }   // the CTL_DIFF_* bits the last update() found, also when it refused
+    const ctl_scene_update_stats& last_update() const { return last_update_; }
+    void read_flat_bvh(flat_scene& out);   // the device tree copied back, un-stamped: what flatten_scene handed to the upload, after any refit
     dev_scene S{};
     uint32_t n_nodes = 0;
     float box_min[3] = { 0, 0, 0 }, box_max[3] = { 0, 0, 0 };   // KernelDynamicScene::m_sBox
     float near_depth = 0, far_depth = 0;                        // SensorBase::m_fNearFarDepths of the scene's camera (DeviceDepthImage::NormalizeDepthD3D)
 private:
+    // the upload, block by block: the constructor runs all of them, update() those whose part of the description changed
+    void upload_top_level(const ctl_scene_desc& d);
+    void upload_instances(const ctl_scene_desc& d);
+    void upload_lights(const ctl_scene_desc& d);
+    void upload_materials(const ctl_scene_desc& d);
+    void derive_shading_state(const ctl_scene_desc& d);   // shade_features / shade_models / alpha_maps + the checks of materials and lights
+    void bind(const ctl_scene_desc& d);                   // device pointers and the scalars of the description into S
+    void set_camera(const ctl_scene_desc& d);
+    void snapshot(const ctl_scene_desc& d);               // host copy of the description an update diffs against (the geometry arrays as a hash)
+    void refit_flat(const ctl_scene_desc& d, bool boxes, bool restamp, ctl_scene_update_stats* stats);
+    bool reduced_rough_transmittance_ = false;
+    ctl_scene_update_stats last_update_{}; uint32_t last_mask_ = 0;
+    std::unique_ptr<desc_snapshot> snap_;
+    flat_scene::refit_side refit_;   // host part: xf0, level_start
+    std::vector<int32_t> flat_child_links_;
+    size_t flat_n_nodes_ = 0, flat_n_entries_ = 0, flat_slab_nodes_ = 0; int flat_max_depth_ = 0; bool flat_root_slab_ = false;
+    dbuf<uint32_t> refit_part_index_, refit_level_nodes_; dbuf<refit_box> refit_part_boxes_, refit_ebox_, refit_nbox_; dbuf<double> refit_carry_, refit_area_;
     dbuf<float4> top_nodes_, bot_nodes_, leaf_tris_, inst_, inst_fwd_, flat_nodes_, flat_leaves_; dbuf<float2> normal_lut_;
     dbuf<uint4> tri_data_, node_info_;
     dbuf<ctl_material> mats_; dbuf<ctl_light> lights_; dbuf<unsigned char> anim_; dbuf<uint32_t> texels_; dbuf<ctl_mipmap> images_; dbuf<dev_mip_levels> mip_levels_; dbuf<float> mip_lut_; dbuf<float> rt_data_, rt_reduced_; dbuf<ctl_rough_transmittance> rt_;
@@ -79,6 +116,19 @@ private:
     uint32_t w_, h_; dbuf<ctl_pixel_data> px_; dbuf<float> rgb_, variance_; dbuf<uint32_t> out_, filtered_; dbuf<int> lum_;   // filtered_: m_filteredColorsDevice (RGBE)
 };
 // nlm_filter.hip: one fused launch on `s`; variance = computeVariance() per pixel (device), filtered_rgbe = the RGBE plane written
+// flat_refit.hip: the refit of the Q4 tree on the device, the arithmetic of flat_refit.h.  Plain launches on `s`, deepest level first; no kernel waits for another workgroup.
+struct refit_device {
+    float4* nodes; float4* leaves; uint32_t n_nodes, n_entries; int compact;
+    const uint32_t* part_index; const refit_box* part_boxes; const double* carry;   // side data; carry = P per scene node (12 doubles)
+    const float4* inst; const float4* inst_fwd;                                       // the scene's node transforms, as the two-level traversal keeps them
+    refit_box* ebox; refit_box* nbox;                                                 // scratch: the new box of every entry / node
+    // re-stamp of the model nibble (index bits 28..31) and the alpha bit (node bit 31) of every entry from node_info + tri_data + the materials;
+    // restamp: 0 = leave the bits alone, else the NUMBER of materials (a material index beyond it is never read)
+    int restamp, leaf_keys, alpha_maps; const uint4* tri_data; const uint4* node_info; const ctl_material* mats;
+};
+void launch_refit_entries(hipStream_t s, const refit_device& R, bool boxes);
+void launch_refit_level(hipStream_t s, const refit_device& R, const uint32_t* level_nodes, uint32_t count);
+void launch_refit_area(hipStream_t s, const float4* nodes, uint32_t n_nodes, double* sum_out);   // adds the nodes' box areas to *sum_out
 void launch_nlm_filter(hipStream_t s, const ctl_pixel_data* px, const float* variance, uint32_t w, uint32_t h, float splat_scale, float k, float sigma2_scale, uint32_t* filtered_rgbe);
 
 // Kernel/TracerSettings.h:14-350 — typed parameters with interval / set constraints: bool, int and float intervals (IntervalParameterConstraint), and

@@ -27,41 +27,14 @@ void require_device() { if (device_count() <= 0) throw hip_error("no HIP device:
 int persistent_grid_blocks() { int dev = 0; hipDeviceProp_t prop; CTL_HIP(hipGetDevice(&dev)); CTL_HIP(hipGetDeviceProperties(&prop, dev)); return prop.multiProcessorCount * 8; }
 
 // ------------------------------------------------------------------------------------------------ Scene
-Scene::Scene(const ctl_scene_desc& d, bool flatten, int flat_format, bool reduced_rough_transmittance) {
-    for (int k = 0; k < 3; k++) { box_min[k] = d.box_min[k]; box_max[k] = d.box_max[k]; }
-    near_depth = d.camera.near_depth; far_depth = d.camera.far_depth;
-    require_device();
-    if (!d.n_nodes) throw std::runtime_error("ctl_scene_create: scene has no nodes");
-    if (d.env_map_index != 0xffffffffu && (d.env_map_index >= d.n_lights_buf || d.lights[d.env_map_index].type != CTL_LIGHT_INFINITE))
-        throw std::runtime_error("ctl_scene_create: env_map_index does not name an InfiniteLight");
-    n_nodes = d.n_nodes;
-    std::vector<float4> tmp;
-    // scene BVH and mesh BVHs keep the reference's 64-B node (one aligned 64-B fetch group per visit)
-    tmp.assign(std::max<size_t>(4, (size_t)d.n_scene_bvh_nodes * 4), make_float4(0, 0, 0, 0));
+// The blocks of the upload that Scene::update repeats for the part of a description that changed (scene_update.hip); the constructor runs them all, in the order it always did.
+void Scene::upload_top_level(const ctl_scene_desc& d) {
+    // the scene BVH keeps the reference's 64-B node (one aligned 64-B fetch group per visit)
+    std::vector<float4> tmp(std::max<size_t>(4, (size_t)d.n_scene_bvh_nodes * 4), make_float4(0, 0, 0, 0));
     if (d.n_scene_bvh_nodes) std::memcpy(tmp.data(), d.scene_bvh_nodes, (size_t)d.n_scene_bvh_nodes * 64);
     top_nodes_.upload(tmp.data(), tmp.size());
-    tmp.assign(std::max<size_t>(4, (size_t)d.n_bvh_nodes * 4), make_float4(0, 0, 0, 0));
-    if (d.n_bvh_nodes) std::memcpy(tmp.data(), d.bvh_nodes, (size_t)d.n_bvh_nodes * 64);
-    bot_nodes_.upload(tmp.data(), tmp.size());
-    // leaf entries: Woop rows + index word interleaved to a 64-B stride so a leaf streams as whole 64-B groups
-    // (the reference reads 3 float4 from t_tris and 1 uint from t_triIndices, Kernel/TraceHelper.cu:641-644)
-    std::vector<std::pair<uint32_t, uint32_t>> ranges;   // (first woop entry, mesh)
-    for (uint32_t m = 0; m < d.n_meshes; m++) ranges.emplace_back(d.meshes[m].bvh_tri_offset / 3, m);
-    std::sort(ranges.begin(), ranges.end());
-    tmp.assign(std::max<size_t>(4, (size_t)d.n_woop * 4), make_float4(0, 0, 0, 0));
-    for (size_t r = 0; r < ranges.size(); r++) {
-        const uint32_t first = ranges[r].first, last = (r + 1 < ranges.size()) ? ranges[r + 1].first : d.n_woop;
-        const ctl_kernel_mesh& km = d.meshes[ranges[r].second];
-        for (uint32_t w = first; w < last; w++) {
-            const ctl_woop_tri& t = d.woop[w];
-            tmp[w * 4 + 0] = make_float4(t.a[0], t.a[1], t.a[2], t.a[3]);
-            tmp[w * 4 + 1] = make_float4(t.b[0], t.b[1], t.b[2], t.b[3]);
-            tmp[w * 4 + 2] = make_float4(t.c[0], t.c[1], t.c[2], t.c[3]);
-            const uint32_t idx = d.woop_index[km.bvh_index_offset + (w - first)].index;
-            tmp[w * 4 + 3] = make_float4(__builtin_bit_cast(float, idx), 0, 0, 0);
-        }
-    }
-    leaf_tris_.upload(tmp.data(), tmp.size());
+}
+void Scene::upload_instances(const ctl_scene_desc& d) {
     // instances: inverse transform rows + the mesh offsets the reference fetches from Node / KernelMesh (TraceHelper.cu:530,557-560)
     std::vector<float4> inst((size_t)d.n_nodes * 4), fwd((size_t)d.n_nodes * 3);
     std::vector<uint4> ninfo(d.n_nodes);
@@ -77,56 +50,15 @@ Scene::Scene(const ctl_scene_desc& d, bool flatten, int flat_format, bool reduce
         ninfo[k] = make_uint4(N.material_offset, N.lights[0], N.lights[1], N.n_lights);
     }
     inst_.upload(inst.data(), inst.size()); inst_fwd_.upload(fwd.data(), fwd.size()); node_info_.upload(ninfo.data(), ninfo.size());
-    { std::vector<float> lut(1024); normal_codec_lut(lut.data()); normal_lut_.upload((const float2*)lut.data(), 512); }
-    static_assert(sizeof(ctl_triangle_data) == 32, "TriangleData is 32 B");
-    static_assert(sizeof(ctl_material) == 384 && sizeof(ctl_texture) == 48, "material descriptor layout (include/ctl_amd.h)");
-    tri_data_.upload((const uint4*)d.tri_data, (size_t)d.n_tri_data * 2);
+}
+void Scene::upload_lights(const ctl_scene_desc& d) {
+    if (d.n_lights_buf) lights_.upload(d.lights, d.n_lights_buf); else if (!lights_.p) lights_.alloc(1);
+    if (d.n_anim_bytes) anim_.upload(d.anim, d.n_anim_bytes); else if (!anim_.p) anim_.alloc(16);
+}
+
+void Scene::upload_materials(const ctl_scene_desc& d) {
     std::vector<ctl_material> dmats(d.materials, d.materials + d.n_materials);   // uploaded below, once the reduced transmittance tables are attached
     for (auto& m : dmats) m.reserved_[0] = m.reserved_[1] = 0;
-    if (d.n_lights_buf) lights_.upload(d.lights, d.n_lights_buf); else lights_.alloc(1);
-    if (d.n_anim_bytes) anim_.upload(d.anim, d.n_anim_bytes); else anim_.alloc(16);
-    // KernelMIPMap of every image: one texel pool (level 0, then the pyramid MIPMap::CompileToBinary builds, Engine/MIPMap.cpp:41-95: nLevels = 1 + log2(min(w, h)),
-    // level i = the 2x2 box average of level i-1, decoded, averaged and re-encoded) + a table of level-0 descriptors with device pointers + the level offsets
-    {
-        std::vector<uint32_t> pool;
-        std::vector<size_t> off(d.n_images);
-        std::vector<dev_mip_levels> lv(std::max<uint32_t>(1, d.n_images));
-        static_assert(sizeof(mip_level_table) == sizeof(dev_mip_levels), "one layout");
-        for (uint32_t i = 0; i < d.n_images; i++) {
-            const ctl_mipmap& m = d.images[i];
-            if (!m.texels || !m.width || !m.height) throw std::runtime_error("ctl_scene_create: empty image");
-            mip_level_table L; off[i] = mip_pyramid_append(m, pool, L);   // mip_pyramid.h
-            std::memcpy(&lv[i], &L, sizeof(L));
-        }
-        if (!pool.empty()) texels_.upload(pool.data(), pool.size()); else texels_.alloc(4);
-        std::vector<ctl_mipmap> tab(d.n_images);
-        for (uint32_t i = 0; i < d.n_images; i++) { tab[i] = d.images[i]; tab[i].texels = texels_.p + off[i]; }
-        if (d.n_images) images_.upload(tab.data(), tab.size()); else images_.alloc(1);
-        mip_levels_.upload(lv.data(), lv.size());
-        float lut[64];   // MIPMap.cpp:87-92
-        for (int i = 0; i < 64; i++) { const float r2 = (float)i / (float)(64 - 1); lut[i] = std::exp(-2.0f * r2) - std::exp(-2.0f); }
-        mip_lut_.upload(lut, 64);
-        S.images = images_.p; S.mip_levels = mip_levels_.p; S.mip_weight_lut = mip_lut_.p;
-    }
-    // RoughTransmittanceManager's tables (roughplastic): one float pool + 3 descriptors with device pointers
-    S.rough_transmittance = nullptr;
-    if (d.rough_transmittance) {
-        std::vector<float> pool; size_t off_t[3] = {}, off_d[3] = {};
-        for (int i = 0; i < 3; i++) {
-            const ctl_rough_transmittance& t = d.rough_transmittance[i];
-            if (!t.trans || !t.diff_trans) continue;
-            const size_t nt = (size_t)2 * t.eta_samples * t.alpha_samples * t.theta_samples, nd = (size_t)2 * t.eta_samples * t.alpha_samples;
-            off_t[i] = pool.size(); pool.insert(pool.end(), t.trans, t.trans + nt);
-            off_d[i] = pool.size(); pool.insert(pool.end(), t.diff_trans, t.diff_trans + nd);
-        }
-        if (!pool.empty()) {
-            rt_data_.upload(pool.data(), pool.size());
-            ctl_rough_transmittance tab[3];
-            for (int i = 0; i < 3; i++) { tab[i] = d.rough_transmittance[i]; const bool ok = tab[i].trans && tab[i].diff_trans; tab[i].trans = ok ? rt_data_.p + off_t[i] : nullptr; tab[i].diff_trans = ok ? rt_data_.p + off_d[i] : nullptr; }
-            rt_.upload(tab, 3);
-            S.rough_transmittance = rt_.p;
-        }
-    }
     // Rough plastics with a CONSTANT roughness texture look RoughTransmittanceManager's table up at a fixed (alpha, eta) (RoughTransmittance.cu:55-88 -> Math/Spline.cu:376-453).
     // What depends on those two alone is made here, once per material (bsdf_rough.h roughplastic_T):
     //  * default — the sixteen rows the 3-D interpolation reads for this (alpha, eta) and the sixteen products wy * wz of its weights; the device runs the reference's own sum
@@ -135,6 +67,7 @@ Scene::Scene(const ctl_scene_desc& d, bool flatten, int flat_format, bool reduce
     //    equal: the last bits move the rescaled lobe sample, and a texture boundary under the next hit turns that into another colour (profiles/r05_fuzz.log: up to 0.13 % of a
     //    textured scene's pixels beyond the tolerance, 5 % of the bathroom miniature's pixels equal to the bit against 100 %).
     // The arithmetic is the device's: ctl_fmath.h's pow (the kernels' m_pow), fp32, no contraction.
+    const bool reduced_rough_transmittance = reduced_rough_transmittance_;
     S.rt_reduced = nullptr;
     if (d.rough_transmittance) {
         std::vector<float> pool;
@@ -182,6 +115,8 @@ Scene::Scene(const ctl_scene_desc& d, bool flatten, int flat_format, bool reduce
         else for (auto& m : dmats) m.reserved_[0] = 0;
     }
     mats_.upload(dmats.data(), dmats.size());
+}
+void Scene::derive_shading_state(const ctl_scene_desc& d) {
     // which shade-kernel build this scene needs (kernels.hip launch_shade)
     S.shade_features = 0; S.alpha_maps = 0; S.shade_models = 0;
     for (uint32_t i = 0; i < d.n_lights_buf; i++) if (d.lights[i].type != CTL_LIGHT_POINT && d.lights[i].type != CTL_LIGHT_DIFFUSE) S.shade_features |= kShadeMoreLights;
@@ -248,6 +183,128 @@ Scene::Scene(const ctl_scene_desc& d, bool flatten, int flat_format, bool reduce
         if (!ok)
             throw std::runtime_error("ctl_scene_create: BSDF type " + std::to_string(t) + " has no HIP implementation yet");
     }
+}
+void Scene::bind(const ctl_scene_desc& d) {
+    for (int k = 0; k < 3; k++) { box_min[k] = d.box_min[k]; box_max[k] = d.box_max[k]; }
+    S.top_nodes = top_nodes_.p; S.bot_nodes = bot_nodes_.p; S.leaf_tris = leaf_tris_.p; S.inst = inst_.p; S.inst_fwd = inst_fwd_.p; S.normal_lut = normal_lut_.p;
+    S.tri_data = tri_data_.p; S.node_info = node_info_.p; S.mats = mats_.p; S.lights = lights_.p; S.anim = anim_.p; S.n_lights_buf = d.n_lights_buf; S.n_anim_bytes = (uint32_t)d.n_anim_bytes; S.n_materials_probe = std::max(1u, d.n_materials);
+    S.start_node = d.scene_start_node; S.n_nodes = d.n_nodes; S.num_lights = d.num_lights; S.env_map_index = d.env_map_index; S.eps = d.ray_trace_eps;
+    for (int i = 0; i < CTL_MAX_NUM_LIGHTS; i++) { S.light_indices[i] = d.light_indices[i]; S.light_cdf[i] = d.light_cdf[i]; }
+}
+void Scene::set_camera(const ctl_scene_desc& d) {
+    near_depth = d.camera.near_depth; far_depth = d.camera.far_depth;
+    // PerspectiveSensor / ThinLensSensor / OrthographicSensor / TelecentricSensor ::Update (SceneTypes/Sensor.cu:76-96, :226-246, :408-427, :515-535)
+    const ctl_sensor& c = d.camera;
+    if (c.type < CTL_SENSOR_SPHERICAL || c.type > CTL_SENSOR_TELECENTRIC) throw std::runtime_error("ctl_scene_create: unknown sensor type " + std::to_string(c.type));
+    const bool ortho = c.type == CTL_SENSOR_ORTHOGRAPHIC || c.type == CTL_SENSOR_TELECENTRIC;
+    const float aspect = c.resolution[0] / c.resolution[1];
+    const float recip = 1.0f / (c.far_depth - c.near_depth), cot = 1.0f / tanf(c.fov / 2.0f);
+    float persp[16] = { cot, 0, 0, 0, 0, cot, 0, 0, 0, 0, c.far_depth * recip, -c.near_depth * c.far_depth * recip, 0, 0, 1, 0 };
+    if (ortho) {   // float4x4::orthographic (float4x4.h:625-628) = Scale(1, 1, 1 / (far - near)) % Translate(0, 0, -near)
+        const float so[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1.0f / (c.far_depth - c.near_depth), 0, 0, 0, 0, 1 };
+        const float to[16] = { 1, 0, 0, 0.0f, 0, 1, 0, 0.0f, 0, 0, 1, -c.near_depth, 0, 0, 0, 1 };
+        mat_mul(so, to, persp);
+    }
+    S.cam.type = c.type; S.cam.aperture_radius = c.aperture_radius; S.cam.focus_distance = c.focus_distance; S.cam.screen_scale_x = c.screen_scale[0] != 0.0f ? c.screen_scale[0] : 1.0f;
+    const float sc[16] = { -0.5f, 0, 0, 0, 0, -0.5f * aspect, 0, 0, 0, 0, 1.0f, 0, 0, 0, 0, 1 };
+    const float tr[16] = { 1, 0, 0, -1.0f, 0, 1, 0, -1.0f / aspect, 0, 0, 1, 0.0f, 0, 0, 0, 1 };
+    float a[16], c2s[16];
+    mat_mul(sc, tr, a); mat_mul(a, persp, c2s);
+    mat_inverse(c2s, S.cam.s2c);
+    std::memcpy(S.cam.to_world, c.to_world, 48);
+    S.cam.inv_res[0] = 1.0f / c.resolution[0]; S.cam.inv_res[1] = 1.0f / c.resolution[1];
+    {   // m_dx, m_dy (Sensor.cu:86-89): sampleToCamera(1/w, 0, 0) - sampleToCamera(0), projective TransformPoint
+        auto tp = [&](float x, float y, float out[3]) {
+            float r[4];
+            for (int i = 0; i < 4; i++) { float s2 = 0.0f; s2 += S.cam.s2c[i * 4] * x; s2 += S.cam.s2c[i * 4 + 1] * y; s2 += S.cam.s2c[i * 4 + 2] * 0.0f; s2 += S.cam.s2c[i * 4 + 3] * 1.0f; r[i] = s2; }
+            out[0] = r[0] / r[3]; out[1] = r[1] / r[3]; out[2] = r[2] / r[3];
+        };
+        float p0[3], px[3], py[3]; tp(0, 0, p0); tp(S.cam.inv_res[0], 0, px); tp(0, S.cam.inv_res[1], py);
+        for (int k = 0; k < 3; k++) { S.cam.dx[k] = px[k] - p0[k]; S.cam.dy[k] = py[k] - p0[k]; }
+    }
+}
+
+Scene::Scene(const ctl_scene_desc& d, bool flatten, int flat_format, bool reduced_rough_transmittance) : reduced_rough_transmittance_(reduced_rough_transmittance) {
+    require_device();
+    if (!d.n_nodes) throw std::runtime_error("ctl_scene_create: scene has no nodes");
+    if (d.env_map_index != 0xffffffffu && (d.env_map_index >= d.n_lights_buf || d.lights[d.env_map_index].type != CTL_LIGHT_INFINITE))
+        throw std::runtime_error("ctl_scene_create: env_map_index does not name an InfiniteLight");
+    n_nodes = d.n_nodes;
+    std::vector<float4> tmp;
+    upload_top_level(d);
+    // the mesh BVHs keep the reference's 64-B node too
+    tmp.assign(std::max<size_t>(4, (size_t)d.n_bvh_nodes * 4), make_float4(0, 0, 0, 0));
+    if (d.n_bvh_nodes) std::memcpy(tmp.data(), d.bvh_nodes, (size_t)d.n_bvh_nodes * 64);
+    bot_nodes_.upload(tmp.data(), tmp.size());
+    // leaf entries: Woop rows + index word interleaved to a 64-B stride so a leaf streams as whole 64-B groups
+    // (the reference reads 3 float4 from t_tris and 1 uint from t_triIndices, Kernel/TraceHelper.cu:641-644)
+    std::vector<std::pair<uint32_t, uint32_t>> ranges;   // (first woop entry, mesh)
+    for (uint32_t m = 0; m < d.n_meshes; m++) ranges.emplace_back(d.meshes[m].bvh_tri_offset / 3, m);
+    std::sort(ranges.begin(), ranges.end());
+    tmp.assign(std::max<size_t>(4, (size_t)d.n_woop * 4), make_float4(0, 0, 0, 0));
+    for (size_t r = 0; r < ranges.size(); r++) {
+        const uint32_t first = ranges[r].first, last = (r + 1 < ranges.size()) ? ranges[r + 1].first : d.n_woop;
+        const ctl_kernel_mesh& km = d.meshes[ranges[r].second];
+        for (uint32_t w = first; w < last; w++) {
+            const ctl_woop_tri& t = d.woop[w];
+            tmp[w * 4 + 0] = make_float4(t.a[0], t.a[1], t.a[2], t.a[3]);
+            tmp[w * 4 + 1] = make_float4(t.b[0], t.b[1], t.b[2], t.b[3]);
+            tmp[w * 4 + 2] = make_float4(t.c[0], t.c[1], t.c[2], t.c[3]);
+            const uint32_t idx = d.woop_index[km.bvh_index_offset + (w - first)].index;
+            tmp[w * 4 + 3] = make_float4(__builtin_bit_cast(float, idx), 0, 0, 0);
+        }
+    }
+    leaf_tris_.upload(tmp.data(), tmp.size());
+    upload_instances(d);
+    { std::vector<float> lut(1024); normal_codec_lut(lut.data()); normal_lut_.upload((const float2*)lut.data(), 512); }
+    static_assert(sizeof(ctl_triangle_data) == 32, "TriangleData is 32 B");
+    static_assert(sizeof(ctl_material) == 384 && sizeof(ctl_texture) == 48, "material descriptor layout (include/ctl_amd.h)");
+    tri_data_.upload((const uint4*)d.tri_data, (size_t)d.n_tri_data * 2);
+    upload_lights(d);
+    // KernelMIPMap of every image: one texel pool (level 0, then the pyramid MIPMap::CompileToBinary builds, Engine/MIPMap.cpp:41-95: nLevels = 1 + log2(min(w, h)),
+    // level i = the 2x2 box average of level i-1, decoded, averaged and re-encoded) + a table of level-0 descriptors with device pointers + the level offsets
+    {
+        std::vector<uint32_t> pool;
+        std::vector<size_t> off(d.n_images);
+        std::vector<dev_mip_levels> lv(std::max<uint32_t>(1, d.n_images));
+        static_assert(sizeof(mip_level_table) == sizeof(dev_mip_levels), "one layout");
+        for (uint32_t i = 0; i < d.n_images; i++) {
+            const ctl_mipmap& m = d.images[i];
+            if (!m.texels || !m.width || !m.height) throw std::runtime_error("ctl_scene_create: empty image");
+            mip_level_table L; off[i] = mip_pyramid_append(m, pool, L);   // mip_pyramid.h
+            std::memcpy(&lv[i], &L, sizeof(L));
+        }
+        if (!pool.empty()) texels_.upload(pool.data(), pool.size()); else texels_.alloc(4);
+        std::vector<ctl_mipmap> tab(d.n_images);
+        for (uint32_t i = 0; i < d.n_images; i++) { tab[i] = d.images[i]; tab[i].texels = texels_.p + off[i]; }
+        if (d.n_images) images_.upload(tab.data(), tab.size()); else images_.alloc(1);
+        mip_levels_.upload(lv.data(), lv.size());
+        float lut[64];   // MIPMap.cpp:87-92
+        for (int i = 0; i < 64; i++) { const float r2 = (float)i / (float)(64 - 1); lut[i] = std::exp(-2.0f * r2) - std::exp(-2.0f); }
+        mip_lut_.upload(lut, 64);
+        S.images = images_.p; S.mip_levels = mip_levels_.p; S.mip_weight_lut = mip_lut_.p;
+    }
+    // RoughTransmittanceManager's tables (roughplastic): one float pool + 3 descriptors with device pointers
+    S.rough_transmittance = nullptr;
+    if (d.rough_transmittance) {
+        std::vector<float> pool; size_t off_t[3] = {}, off_d[3] = {};
+        for (int i = 0; i < 3; i++) {
+            const ctl_rough_transmittance& t = d.rough_transmittance[i];
+            if (!t.trans || !t.diff_trans) continue;
+            const size_t nt = (size_t)2 * t.eta_samples * t.alpha_samples * t.theta_samples, nd = (size_t)2 * t.eta_samples * t.alpha_samples;
+            off_t[i] = pool.size(); pool.insert(pool.end(), t.trans, t.trans + nt);
+            off_d[i] = pool.size(); pool.insert(pool.end(), t.diff_trans, t.diff_trans + nd);
+        }
+        if (!pool.empty()) {
+            rt_data_.upload(pool.data(), pool.size());
+            ctl_rough_transmittance tab[3];
+            for (int i = 0; i < 3; i++) { tab[i] = d.rough_transmittance[i]; const bool ok = tab[i].trans && tab[i].diff_trans; tab[i].trans = ok ? rt_data_.p + off_t[i] : nullptr; tab[i].diff_trans = ok ? rt_data_.p + off_d[i] : nullptr; }
+            rt_.upload(tab, 3);
+            S.rough_transmittance = rt_.p;
+        }
+    }
+    upload_materials(d);
+    derive_shading_state(d);
     {   // the two-level traversal keeps (scene-BVH depth + exit marker + mesh-BVH depth) entries on its per-lane stack: check it fits
         auto depth_of = [](const ctl_bvh_node* nodes, size_t n_nodes, int root) {   // child >= 0: float4 index of an inner node
             int best = 0; std::vector<std::pair<int, int>> st;
@@ -310,42 +367,22 @@ Scene::Scene(const ctl_scene_desc& d, bool flatten, int flat_format, bool reduce
             S.flat_nodes = flat_nodes_.p; S.flat_leaves = flat_leaves_.p; S.flat_format = F.format; S.flat_compact = (F.format == kFlatQ4 && F.compact_links) ? 1 : 0;
             S.flat_root = ((S.flat_compact || F.format == kFlatQ8) && F.root_slab) ? 1 : 0;   // bit 0 of an inner link: the node carries an oriented slab (flat_slab.h); Q8 links are node index << 1 | that bit
             S.flat_top_cached = S.flat_compact ? (int)std::min<size_t>(F.nodes.size(), (size_t)flat_top_cache_nodes()) : 0;
+            // what ctl_scene_update needs to refit this tree in place (flat_refit.h; Q4 only): the side arrays go to HBM now, the scratch boxes with the first transform update
+            flat_n_nodes_ = F.format == kFlatQ4 ? F.nodes.size() : F.nodes_q8.size(); flat_n_entries_ = F.leaves.size() - 1; flat_max_depth_ = F.max_depth; flat_root_slab_ = F.root_slab; flat_slab_nodes_ = F.slab_nodes;
+            if (F.format == kFlatQ4 && F.refit.ready()) {
+                refit_part_index_.upload(F.refit.part_index.data(), F.refit.part_index.size());
+                if (!F.refit.part_boxes.empty()) refit_part_boxes_.upload(F.refit.part_boxes.data(), F.refit.part_boxes.size());
+                refit_level_nodes_.upload(F.refit.level_nodes.data(), F.refit.level_nodes.size());
+                if (!S.flat_compact) flat_child_links_ = F.child_links;   // host view of a tree with explicit links (read_flat_bvh); a compact tree's links are derived
+                refit_ = std::move(F.refit); refit_.part_index.clear(); refit_.part_index.shrink_to_fit(); refit_.level_nodes.clear(); refit_.level_nodes.shrink_to_fit();
+                CTL_HIP(hipDeviceSynchronize());
+            }
         }
     }
     CTL_HIP(hipDeviceSynchronize());
-    S.top_nodes = top_nodes_.p; S.bot_nodes = bot_nodes_.p; S.leaf_tris = leaf_tris_.p; S.inst = inst_.p; S.inst_fwd = inst_fwd_.p; S.normal_lut = normal_lut_.p;
-    S.tri_data = tri_data_.p; S.node_info = node_info_.p; S.mats = mats_.p; S.lights = lights_.p; S.anim = anim_.p; S.n_lights_buf = d.n_lights_buf; S.n_anim_bytes = (uint32_t)d.n_anim_bytes; S.n_materials_probe = std::max(1u, d.n_materials);
-    S.start_node = d.scene_start_node; S.n_nodes = d.n_nodes; S.num_lights = d.num_lights; S.env_map_index = d.env_map_index; S.eps = d.ray_trace_eps;
-    for (int i = 0; i < CTL_MAX_NUM_LIGHTS; i++) { S.light_indices[i] = d.light_indices[i]; S.light_cdf[i] = d.light_cdf[i]; }
-    // PerspectiveSensor / ThinLensSensor / OrthographicSensor / TelecentricSensor ::Update (SceneTypes/Sensor.cu:76-96, :226-246, :408-427, :515-535)
-    const ctl_sensor& c = d.camera;
-    if (c.type < CTL_SENSOR_SPHERICAL || c.type > CTL_SENSOR_TELECENTRIC) throw std::runtime_error("ctl_scene_create: unknown sensor type " + std::to_string(c.type));
-    const bool ortho = c.type == CTL_SENSOR_ORTHOGRAPHIC || c.type == CTL_SENSOR_TELECENTRIC;
-    const float aspect = c.resolution[0] / c.resolution[1];
-    const float recip = 1.0f / (c.far_depth - c.near_depth), cot = 1.0f / tanf(c.fov / 2.0f);
-    float persp[16] = { cot, 0, 0, 0, 0, cot, 0, 0, 0, 0, c.far_depth * recip, -c.near_depth * c.far_depth * recip, 0, 0, 1, 0 };
-    if (ortho) {   // float4x4::orthographic (float4x4.h:625-628) = Scale(1, 1, 1 / (far - near)) % Translate(0, 0, -near)
-        const float so[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1.0f / (c.far_depth - c.near_depth), 0, 0, 0, 0, 1 };
-        const float to[16] = { 1, 0, 0, 0.0f, 0, 1, 0, 0.0f, 0, 0, 1, -c.near_depth, 0, 0, 0, 1 };
-        mat_mul(so, to, persp);
-    }
-    S.cam.type = c.type; S.cam.aperture_radius = c.aperture_radius; S.cam.focus_distance = c.focus_distance; S.cam.screen_scale_x = c.screen_scale[0] != 0.0f ? c.screen_scale[0] : 1.0f;
-    const float sc[16] = { -0.5f, 0, 0, 0, 0, -0.5f * aspect, 0, 0, 0, 0, 1.0f, 0, 0, 0, 0, 1 };
-    const float tr[16] = { 1, 0, 0, -1.0f, 0, 1, 0, -1.0f / aspect, 0, 0, 1, 0.0f, 0, 0, 0, 1 };
-    float a[16], c2s[16];
-    mat_mul(sc, tr, a); mat_mul(a, persp, c2s);
-    mat_inverse(c2s, S.cam.s2c);
-    std::memcpy(S.cam.to_world, c.to_world, 48);
-    S.cam.inv_res[0] = 1.0f / c.resolution[0]; S.cam.inv_res[1] = 1.0f / c.resolution[1];
-    {   // m_dx, m_dy (Sensor.cu:86-89): sampleToCamera(1/w, 0, 0) - sampleToCamera(0), projective TransformPoint
-        auto tp = [&](float x, float y, float out[3]) {
-            float r[4];
-            for (int i = 0; i < 4; i++) { float s2 = 0.0f; s2 += S.cam.s2c[i * 4] * x; s2 += S.cam.s2c[i * 4 + 1] * y; s2 += S.cam.s2c[i * 4 + 2] * 0.0f; s2 += S.cam.s2c[i * 4 + 3] * 1.0f; r[i] = s2; }
-            out[0] = r[0] / r[3]; out[1] = r[1] / r[3]; out[2] = r[2] / r[3];
-        };
-        float p0[3], px[3], py[3]; tp(0, 0, p0); tp(S.cam.inv_res[0], 0, px); tp(0, S.cam.inv_res[1], py);
-        for (int k = 0; k < 3; k++) { S.cam.dx[k] = px[k] - p0[k]; S.cam.dy[k] = py[k] - p0[k]; }
-    }
+    bind(d);
+    set_camera(d);
+    snapshot(d);
 }
 
 // ------------------------------------------------------------------------------------------------ Image

@@ -309,6 +309,10 @@ int ctl_builder_set_camera(ctl_builder* b, const ctl_sensor* sensor);
 /* DynamicScene::UpdateScene + getKernelSceneData (DynamicScene.cpp:480-589): builds the scene BVH and fills
  * `out` with pointers that stay valid until the builder is destroyed or finalized again. */
 int ctl_builder_finalize(ctl_builder* b, ctl_scene_desc* out);
+/* DynamicScene::SetNodeTransform (Engine/DynamicScene.cpp:338-346): a new to_world (affine, invertible) for a node.  The area lights of the node get their shape
+ * sets recalculated (ShapeSet::triData::Recalculate, Engine/ShapeSet.cu:11-23); the next ctl_builder_finalize rebuilds the scene BVH, the scene box, ray_trace_eps
+ * and the box-dependent lights from the new transforms. */
+int ctl_builder_set_node_transform(ctl_builder* b, uint32_t node_index, const ctl_float4x4* to_world);
 
 /* ------------------------------------------------------------------- scenes */
 typedef struct ctl_scene ctl_scene;
@@ -332,6 +336,30 @@ enum { CTL_FLAT_Q4 = 0,    /* 4-wide, 64-B nodes, 8-bit child boxes (default) */
 #define CTL_SCENE_FLAT_FORMAT(f) ((((uint32_t)(f)) + 1u) << 8)
 int ctl_scene_create_ex(const ctl_scene_desc* desc, uint32_t flags, ctl_scene** out);
 void ctl_scene_destroy(ctl_scene* s);
+/* ---- in-place updates: what UpdateKernel(m_pScene) does for a host that moves the camera, edits a material or calls SetNodeTransform between passes
+ * (Kernel/Tracer.h:121,229; INTEGRATION.md "Updating a scene").
+ * ctl_scene_desc_diff classifies what differs between two descriptions of the same scene (host only): */
+enum { CTL_DIFF_CAMERA = 1,       /* ctl_scene_desc::camera                                                                                        */
+       CTL_DIFF_MATERIALS = 2,    /* the contents of `materials`                                                                                   */
+       CTL_DIFF_LIGHTS = 4,       /* lights, anim blob, num_lights, light_indices, light_cdf, env_map_index, the nodes' light slots                 */
+       CTL_DIFF_TRANSFORMS = 8,   /* node_transforms, node_inv_transforms, the scene BVH and its start node, box_min / box_max, ray_trace_eps       */
+       CTL_DIFF_TOPOLOGY = 16 };  /* anything else: triangle / Woop / mesh-BVH arrays, any count but the lights', meshes, node -> mesh / material
+                                     assignment, images, rough-transmittance tables                                                               */
+int ctl_scene_desc_diff(const ctl_scene_desc* a, const ctl_scene_desc* b, uint32_t* mask_out);
+/* Applies everything that differs between the description `scene` holds and `new_desc`, except topology, in place; *mask_out (may be NULL) = the CTL_DIFF_* bits found.
+ * Camera, materials, lights: host -> HBM copies (a material whose bsdf_type or alpha_state changed has the leaf entries of a flattened scene re-stamped by a kernel).
+ * Transforms: the two-level arrays are re-uploaded and the flattened Q4 tree is REFITTED on the device (csrc/flat_refit.h: links, masks and memory order stay, every
+ * box is recomputed, oriented slabs are neutralised) — the traversal still returns the reference's (t, u, v, triangle, node) bit for bit, a refitted tree only culls
+ * less well than a rebuilt one the further the nodes moved.  Synchronous; call between passes and start the next one with new_trace.
+ *   CTL_ERR_NO_DEVICE    no device (checked first)
+ *   CTL_ERR_INVALID      CTL_DIFF_TOPOLOGY is set: the scene is untouched, re-create it
+ *   CTL_ERR_UNSUPPORTED  CTL_DIFF_TRANSFORMS on a CTL_FLAT_Q8 scene (the measurement format is not refitted); camera / material / light updates work there
+ * The scene keeps its own host copy of the description (the geometry arrays as a hash): new_desc's pointers are not kept. */
+int ctl_scene_update(ctl_scene* scene, const ctl_scene_desc* new_desc, uint32_t* mask_out);
+/* Report of the last ctl_scene_update: summed surface area of the flattened tree's node boxes before and after a refit (a SAH proxy: a host re-creates the scene when
+ * the ratio says the tree has degraded — the library has no policy), both 0 when the update did not refit; HIP-event time of the refit kernels. */
+typedef struct { double node_area_before, node_area_after; float refit_ms; uint32_t refit_levels; uint32_t mask; uint32_t restamped; } ctl_scene_update_stats;
+int ctl_scene_get_update_stats(ctl_scene* scene, ctl_scene_update_stats* out);
 /* On-disk cache of compiled geometry — the role of the reference's .xmsh files (Engine/Mesh.cpp:46-98,199-290; DynamicScene::CreateNode
  * compiles a mesh only when its .xmsh is missing).  With a directory set, ctl_builder_add_mesh stores / reloads a compiled mesh
  * (TriangleData, BVH nodes, Woop rows) and CTL_SCENE_FLATTEN stores / reloads the flattened BVH, both keyed by a hash of their
@@ -351,10 +379,19 @@ typedef struct {
     uint32_t compact;                /* CTL_FLAT_Q4: 1 = the kernels derive the links from the layout (flat4_node::links) and the nodes' last 16 B hold oriented slabs; CTL_FLAT_Q8: always 1 */
     uint32_t root_slab;              /* the root node carries a slab (Q4: bit 0 of the link a traversal starts with; Q8: the root's q5 is loaded)            */
     uint64_t n_slab_nodes;           /* nodes that carry an oriented slab (flat_slab.h)                                                  */
+    /* the refit side data of a built CTL_FLAT_Q4 tree (csrc/flat_refit.h; NULL / 0 otherwise, and for a tree read back from a scene): per leaf entry UINT32_MAX or the
+     * index of its clip box — the entry is a split reference —, and the clip boxes {lo xyz, hi xyz} in world space as they were when the tree was built */
+    const uint32_t* part_index; const float* part_boxes; uint64_t n_part_boxes;
 } ctl_flat_bvh_desc;
 int ctl_flat_bvh_build(const ctl_scene_desc* desc, uint32_t format, ctl_flat_bvh** out);
 int ctl_flat_bvh_arrays(const ctl_flat_bvh* h, ctl_flat_bvh_desc* out);
 void ctl_flat_bvh_destroy(ctl_flat_bvh* h);
+/* The refit of ctl_scene_update on the arrays of a CTL_FLAT_Q4 handle, host only, with the same arithmetic (csrc/flat_refit.h): the yardstick of the device kernels.
+ * new_desc = the description the handle was built from with other node transforms.  Other formats: CTL_ERR_UNSUPPORTED. */
+int ctl_flat_bvh_refit(ctl_flat_bvh* h, const ctl_scene_desc* new_desc);
+/* The flattened tree of a CTL_SCENE_FLATTEN scene copied back from HBM into a handle for ctl_flat_bvh_arrays, with the BSDF-model bits (28..31 of the index word)
+ * and the alpha bit (31 of the node word) that ctl_scene_create_ex stamps into the device copy removed: the arrays the test oracle traverses. */
+int ctl_scene_read_flat_bvh(ctl_scene* scene, ctl_flat_bvh** out);
 /* ParseMitsubaScene (Engine/SceneLoader/Mitsuba/MitsubaLoader.h:13): fills a builder from a Mitsuba-0.5 XML file. */
 int ctl_parse_mitsuba_scene(ctl_builder* b, const char* xml_path, int32_t* width_inout, int32_t* height_inout);
 /* The bitmap reader behind the loader's textures and environment maps (the reference goes through FreeImage, Engine/MIPMap.cu:542-592): PNG, JPEG

@@ -1,0 +1,176 @@
+#!/usr/bin/env python3
+"""Cost of ctl_scene_update against re-creating the scene, and the traversal rate of a refitted tree against a freshly built one.
+
+    python tools/scene_update_bench.py [--workloads synthetic-sm,synthetic-sm-hard] [--hard-scale full|small] [--passes 4] [--out profiles/scene_update.jsonl] [--results RESULTS.md]
+
+Per workload, on one GPU, in one process:
+  1. ctl_scene_update for a camera change, a material change (a reflectance; and one that changes a bsdf_type, which re-stamps the leaf entries) and a one-node
+     transform change: wall time around the (synchronous) call, median of 10, and the HIP-event time of the refit kernels alone;
+  2. what a host without ctl_scene_update pays for the same transform change: ctl_builder_finalize + ctl_scene_create_ex, once with the geometry cache disabled and
+     once with the cache warm for the NEW transforms (its best case);
+  3. Mrays/s of the WavefrontPathTracer (depth 8) on the refitted tree against a freshly built tree of the same description, for three motions of one node
+     (M1 small move, M2 rotation + non-uniform scale, M3 a move across a third of the scene), next to the surface-area ratio ctl_scene_get_update_stats reports.
+One JSON line per workload is appended to --out; --results appends a section to that Markdown file.  bench.py is not involved.
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from cudatracerlib_amd import api, scenes   # noqa: E402
+import cudatracerlib_amd as ctl              # noqa: E402
+
+
+def build(workload, args):
+    if workload == "synthetic-sm":
+        return scenes.synthetic_sm(args.width, args.height)
+    if workload == "synthetic-sm-hard":
+        nx, nz = (4096, 1024) if args.hard_scale == "full" else (1024, 256)
+        d = os.path.join(os.environ.get("TMPDIR", "/tmp"), "ctl_scene_sm_hard_%dx%d_%dx%d" % (nx, nz, args.width, args.height))
+        if not os.path.exists(os.path.join(d, "scene.xml")):
+            scenes.write_sm_hard_mitsuba(d, args.width, args.height, nx=nx, nz=nz, cards=4000 if args.hard_scale == "full" else 1000, beams=3000 if args.hard_scale == "full" else 600)
+        return scenes.load_mitsuba(os.path.join(d, "scene.xml"), args.width, args.height)
+    raise SystemExit("unknown workload " + workload)
+
+
+def transforms(desc):
+    return desc.view("node_transforms", np.float32, desc.n_nodes, 16).reshape(-1, 4, 4).astype(np.float64)
+
+
+def rot(axis, angle):
+    a = np.asarray(axis, np.float64); a /= np.linalg.norm(a)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    return np.eye(3) + np.sin(angle) * K + (1 - np.cos(angle)) * (K @ K)
+
+
+def motion(X0, size, which, step=0):
+    Y = X0.copy()
+    if which == "M1":
+        Y[:3, 3] += 0.01 * size * np.array([1.0, 0.3, -0.6]) * (1 + step)
+    elif which == "M2":
+        Y[:3, :3] = rot((0.3, 1.0, 0.2), 0.7312) @ np.diag([1.3, 0.8, 1.1]) @ X0[:3, :3]
+    else:
+        Y[:3, 3] += size * np.array([0.33, 0.0, 0.2])
+    return Y.astype(np.float32)
+
+
+def mrays(scene, args):
+    tr = ctl.WavefrontPathTracer()
+    tr.getParameters().setValue("MaxPathLength", args.depth)
+    tr.Resize(args.width, args.height); tr.InitializeScene(scene)
+    img = ctl.Image(args.width, args.height)
+    tr.DoPasses(img, 1, new_trace=True)                  # warm-up
+    t0 = tr.stats()
+    tr.DoPasses(img, args.passes, new_trace=False)
+    t1 = tr.stats()
+    return (t1.rays_total - t0.rays_total) / max(1e-9, t1.seconds_total - t0.seconds_total) / 1e6
+
+
+def timed(f, n=10):
+    ts = []
+    for k in range(n):
+        t = time.perf_counter(); f(k); ts.append((time.perf_counter() - t) * 1e3)
+    return float(np.median(ts))
+
+
+def run(workload, args):
+    api.set_cache_dir(None)
+    sc = build(workload, args)
+    d = sc.desc
+    size = np.array(d.box_max[:]) - np.array(d.box_min[:])
+    node = d.n_nodes // 2
+    X0 = transforms(d)[node].copy()
+    t = time.perf_counter(); scene = ctl.Scene(d, flatten=True); create_ms = (time.perf_counter() - t) * 1e3
+    fb = scene.flat_bvh()
+    rec = dict(workload=workload, width=args.width, height=args.height, nodes=int(d.n_nodes), flat_nodes=int(fb.desc.n_nodes), flat_entries=int(fb.desc.n_leaves), create_ms=create_ms, moved_node=int(node))
+    del fb
+    cam0 = api.ctl_sensor.from_buffer_copy(d.camera)
+
+    def camera(k):
+        s = api.ctl_sensor.from_buffer_copy(cam0); s.to_world[3] += 0.001 * size[0] * (k + 1); sc.setSensor(s); assert scene.update(sc.UpdateScene()) == api.DIFF_CAMERA
+    rec["update_camera_ms"] = timed(camera)
+
+    def material(k):
+        sc.desc.materials[0].tex[0].value[0] = 0.3 + 0.01 * k; assert scene.update(sc.desc) == api.DIFF_MATERIALS
+    rec["update_material_ms"] = timed(material)
+
+    def material_type(k):
+        m = sc.desc.materials[0]; m.bsdf_type, m.combined_type = (2, m.combined_type) if m.bsdf_type == 1 else (1, m.combined_type); assert scene.update(sc.desc) == api.DIFF_MATERIALS
+    if sc.desc.materials[0].bsdf_type in (1, 2):          # diffuse <-> rough diffuse: same parameter slots, another model nibble
+        rec["update_material_restamp_ms"] = timed(material_type, 10)
+    refit = []
+
+    def transform(k):
+        sc.SetNodeTransform(node, motion(X0, size, "M1", k)); assert scene.update(sc.UpdateScene()) & api.DIFF_TRANSFORMS; refit.append(scene.update_stats()["refit_ms"])
+    rec["update_transform_ms"] = timed(transform)
+    rec["refit_kernels_ms"] = float(np.median(refit))
+    # the same change without ctl_scene_update: finalize + create, cache off / cache warm for the new transforms
+    sc.SetNodeTransform(node, motion(X0, size, "M1", 20))
+    t = time.perf_counter(); s2 = ctl.Scene(sc.UpdateScene(), flatten=True); rec["recreate_nocache_ms"] = (time.perf_counter() - t) * 1e3; del s2
+    with tempfile.TemporaryDirectory() as cache:
+        api.set_cache_dir(cache)
+        s2 = ctl.Scene(sc.desc, flatten=True); del s2     # warms the cache for exactly these transforms
+        t = time.perf_counter(); s2 = ctl.Scene(sc.UpdateScene(), flatten=True); rec["recreate_warmcache_ms"] = (time.perf_counter() - t) * 1e3; del s2
+        api.set_cache_dir(None)
+    # traversal rate: refitted against fresh, per motion (the scene is refitted from the tree it was created with; a refit never reads an earlier one's result)
+    rec["traversal"] = {}
+    for which in ("M1", "M2", "M3"):
+        sc.SetNodeTransform(node, motion(X0, size, which))
+        scene.update(sc.UpdateScene())
+        st = scene.update_stats()
+        r = mrays(scene, args)
+        fresh = ctl.Scene(sc.desc, flatten=True)
+        f = mrays(fresh, args)
+        del fresh
+        rec["traversal"][which] = dict(refit_mrays=r, fresh_mrays=f, ratio=r / f, node_area_before=st["node_area_before"], node_area_after=st["node_area_after"],
+                                       area_ratio=st["node_area_after"] / st["node_area_before"], refit_ms=st["refit_ms"])
+    rec["faster_than_warm_recreate"] = bool(rec["update_transform_ms"] < rec["recreate_warmcache_ms"])
+    return rec
+
+
+def markdown(recs):
+    out = ["", "## In-place scene updates (tools/scene_update_bench.py)", "",
+           "| workload | entries | update: camera | material | material + re-stamp | one-node transform (refit kernels) | re-create, no cache | re-create, warm cache |", "|---|---|---|---|---|---|---|---|"]
+    for r in recs:
+        out.append("| %s | %d | %.2f ms | %.2f ms | %s | %.2f ms (%.2f ms) | %.0f ms | %.0f ms |" % (r["workload"], r["flat_entries"], r["update_camera_ms"], r["update_material_ms"],
+                   ("%.2f ms" % r["update_material_restamp_ms"]) if "update_material_restamp_ms" in r else "-", r["update_transform_ms"], r["refit_kernels_ms"], r["recreate_nocache_ms"], r["recreate_warmcache_ms"]))
+    out += ["", "| workload | motion | refitted tree | fresh tree | ratio | node-area ratio (SAH proxy) |", "|---|---|---|---|---|---|"]
+    for r in recs:
+        for m, t in r["traversal"].items():
+            out.append("| %s | %s | %.0f Mrays/s | %.0f Mrays/s | %.3f | %.3f |" % (r["workload"], m, t["refit_mrays"], t["fresh_mrays"], t["ratio"], t["area_ratio"]))
+    return "\n".join(out) + "\n"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workloads", default="synthetic-sm,synthetic-sm-hard")
+    ap.add_argument("--hard-scale", default="full", choices=["full", "small"])
+    ap.add_argument("--width", type=int, default=1920); ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--depth", type=int, default=8); ap.add_argument("--passes", type=int, default=4)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scene_update.jsonl"))
+    ap.add_argument("--results", default=None)
+    args = ap.parse_args()
+    if ctl.device_count() < 1:
+        raise SystemExit("scene_update_bench needs a HIP device")
+    recs = []
+    for w in args.workloads.split(","):
+        rec = run(w, args)
+        recs.append(rec)
+        print(json.dumps(rec), flush=True)
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(json.dumps(rec) + "\n")
+    if args.results:
+        with open(args.results, "a") as f:
+            f.write(markdown(recs))
+
+
+if __name__ == "__main__":
+    main()
