@@ -127,6 +127,7 @@ lib.ctl_image_resolve_rgb.argtypes = [C.c_void_p, f32, C.c_void_p]
 lib.ctl_image_apply_pipeline_nlm.argtypes = [C.c_void_p, f32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 lib.ctl_image_read_filtered.argtypes = [C.c_void_p, C.c_void_p]
 lib.ctl_image_last_filter_ms.argtypes = [C.c_void_p, C.POINTER(f32)]
+lib.ctl_image_luminance_info.argtypes = [C.c_void_p, C.c_void_p]
 lib.ctl_tracer_set_pixel_variance.argtypes = [C.c_void_p, C.c_int]
 lib.ctl_tracer_read_pixel_variance.argtypes = [C.c_void_p, C.c_void_p]
 lib.ctl_tracer_set_param_float.argtypes = [C.c_void_p, C.c_char_p, f32]
@@ -880,6 +881,13 @@ class Image:
         """Image::getFilteredData: (h, w) uint32 RGBE (r | g << 8 | b << 16 | e << 24), the plane the last pipeline call with a filter or a post-process left"""
         a = np.zeros((self.height, self.width), np.uint32)
         _check(lib.ctl_image_read_filtered(self._h, a.ctypes.data_as(C.c_void_p)))
+        return a
+
+    def getLuminanceInfo(self):
+        """Image::ComputeLuminanceInfo, read-only: (min, max, avg, logAvg) float32 of the filtered plane's luminance as the last pipeline call with a post-process
+        computed and used them (stored by that call, not recomputed here)"""
+        a = np.zeros(4, np.float32)
+        _check(lib.ctl_image_luminance_info(self._h, a.ctypes.data_as(C.c_void_p)))
         return a
 
     def lastFilterMs(self):

@@ -312,6 +312,11 @@ int ctl_image_apply_pipeline_nlm(ctl_image* img, float splat_scale, const ctl_nl
     CTL_CATCH
 }
 int ctl_image_read_filtered(ctl_image* img, uint32_t* host_rgbe_out) { CTL_REQUIRE(img && host_rgbe_out, "null argument"); CTL_TRY img->img.read_filtered(host_rgbe_out); CTL_CATCH }
+int ctl_image_luminance_info(ctl_image* img, float* out4) {
+    CTL_REQUIRE(img && out4, "null argument");
+    CTL_REQUIRE(img->img.luminance_info(out4), "getLuminanceInfo: no pipeline call with a post-process has computed the luminance info yet");
+    return CTL_OK;
+}
 int ctl_image_last_filter_ms(ctl_image* img, float* ms_out) { CTL_REQUIRE(img && ms_out, "null argument"); *ms_out = img->img.last_filter_ms(); return CTL_OK; }
 int ctl_image_apply_pipeline(ctl_image* img, float splat_scale, uint32_t* host_rgbcol_out) { CTL_REQUIRE(img && host_rgbcol_out, "null argument"); CTL_TRY img->img.apply_pipeline(splat_scale, host_rgbcol_out); CTL_CATCH }
 int ctl_image_write_file(ctl_image* img, float splat_scale, const char* path) { CTL_REQUIRE(img && path, "null argument"); CTL_TRY img->img.write_file(splat_scale, path); CTL_CATCH }

@@ -50,6 +50,8 @@ __device__ __forceinline__ float filter_eval(const dev_filter& F, float x, float
 __global__ __launch_bounds__(256) void k_filter(const ctl_pixel_data* __restrict__ px, int w, int h, float splat_scale, dev_filter F, uint32_t* __restrict__ filtered) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= w || y >= h) return;
+    // GaussianFilter::Update: evaluated here, by the expf that evaluates the taps, so that a tap exactly on the filter's edge weighs exactly 0 whatever the host's expf rounds to
+    if (F.type == CTL_RFILTER_GAUSSIAN) { F.ex = expf(-F.p0 * F.xw * F.xw); F.ey = expf(-F.p0 * F.yw * F.yw); }
     const int x0 = max(0, (int)ceilf(x - F.xw)), x1 = min(w - 1, (int)floorf(x + F.xw)), y0 = max(0, (int)ceilf(y - F.yw)), y1 = min(h - 1, (int)floorf(y + F.yw));
     f3 acc(0.0f); float accw = 0;
     if (x1 - x0 >= 0 && y1 - y0 >= 0) {
@@ -59,7 +61,7 @@ __global__ __launch_bounds__(256) void k_filter(const ctl_pixel_data* __restrict
                 acc = acc + to_spectrum(px[(size_t)yy * w + xx], splat_scale) * wt;
                 accw += wt;
             }
-        acc = acc / accw;
+        acc = acc * (1.0f / accw);   // Spectrum / scalar: times the reciprocal (Math/Spectrum.h:122-128)
     }
     filtered[(size_t)y * w + x] = to_rgbe(acc);
 }
@@ -116,8 +118,7 @@ void Image::apply_pipeline_ex(float splat_scale, const ctl_reconstruction_filter
     CTL_HIP(hipDeviceSynchronize());
     const int grid = (int)std::min<uint32_t>(4096, (n + 255) / 256);
     if (filter) {
-        dev_filter F{ filter->type, filter->x_width, filter->y_width, 1.0f / filter->x_width, 1.0f / filter->y_width, filter->p0, filter->p1, 0, 0 };
-        if (F.type == CTL_RFILTER_GAUSSIAN) { F.ex = expf(-F.p0 * F.xw * F.xw); F.ey = expf(-F.p0 * F.yw * F.yw); }   // GaussianFilter::Update
+        const dev_filter F{ filter->type, filter->x_width, filter->y_width, 1.0f / filter->x_width, 1.0f / filter->y_width, filter->p0, filter->p1, 0, 0 };
         hipLaunchKernelGGL(k_filter, dim3((w_ + 63) / 64, (h_ + 3) / 4), dim3(256), 0, nullptr, px_.p, (int)w_, (int)h_, splat_scale, F, filtered_.p);
     } else {
         hipLaunchKernelGGL(k_to_filtered, dim3(grid), dim3(256), 0, nullptr, px_.p, n, splat_scale, filtered_.p);
@@ -159,6 +160,7 @@ void Image::pipeline_tail(const ctl_tonemap* process, uint32_t* host_rgbcol) {
         lum_info li; CTL_HIP(hipMemcpy(&li, lum_.p, sizeof(li), hipMemcpyDeviceToHost));
         auto unordered = [](int i) { const int v = i >= 0 ? i : i ^ 0x7FFFFFFF; float f; std::memcpy(&f, &v, 4); return f; };
         const float maxLum = unordered(li.max_i), logAvg = expf(li.sum_log / float(w_ * h_));
+        lum_info_[0] = unordered(li.min_i); lum_info_[1] = maxLum; lum_info_[2] = li.sum / float(w_ * h_); lum_info_[3] = logAvg; have_lum_ = true;
         const float scale = process->key / logAvg, Lwhite = maxLum * scale;
         const float burn = std::min(1.0f, std::max(1e-8f, 1.0f - process->burn));
         const float invWp2 = 1 / (Lwhite * Lwhite * std::pow(burn, 4.0f));

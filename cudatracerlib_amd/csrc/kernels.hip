@@ -203,10 +203,10 @@ void launch_sequence_fill(hipStream_t stream, const uint32_t* jumps, const void*
 __global__ __launch_bounds__(kBlock) void k_resolve_rgb(const ctl_pixel_data* __restrict__ image, uint32_t n, float splat_scale, float* __restrict__ out) {
     for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
         const ctl_pixel_data p = image[i];
-        const float w = p.weight_sum != 0 ? p.weight_sum : 1;
-        out[i * 3 + 0] = p.rgb[0] / w + p.rgb_splat[0] * splat_scale;
-        out[i * 3 + 1] = p.rgb[1] / w + p.rgb_splat[1] * splat_scale;
-        out[i * 3 + 2] = p.rgb[2] / w + p.rgb_splat[2] * splat_scale;
+        const float r = 1.0f / (p.weight_sum != 0 ? p.weight_sum : 1);   // PixelData::toSpectrum: Spectrum / scalar multiplies by the reciprocal (Math/Spectrum.h:122-128)
+        out[i * 3 + 0] = p.rgb[0] * r + p.rgb_splat[0] * splat_scale;
+        out[i * 3 + 1] = p.rgb[1] * r + p.rgb_splat[1] * splat_scale;
+        out[i * 3 + 2] = p.rgb[2] * r + p.rgb_splat[2] * splat_scale;
     }
 }
 
@@ -215,10 +215,10 @@ __global__ __launch_bounds__(kBlock) void k_resolve_rgb(const ctl_pixel_data* __
 __global__ __launch_bounds__(kBlock) void k_apply_pipeline(const ctl_pixel_data* __restrict__ image, uint32_t n, float splat_scale, uint32_t* __restrict__ out) {
     for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
         const ctl_pixel_data p = image[i];
-        const float w = p.weight_sum != 0 ? p.weight_sum : 1;
+        const float r = 1.0f / (p.weight_sum != 0 ? p.weight_sum : 1);   // (times the reciprocal, as above)
         uint32_t packed = 255u << 24;
         for (int c = 0; c < 3; c++) {
-            float v = p.rgb[c] / w + p.rgb_splat[c] * splat_scale;
+            float v = p.rgb[c] * r + p.rgb_splat[c] * splat_scale;
             v = v <= 0.0031308f ? 12.92f * v : 1.055f * powf(v, (float)(1.0 / 2.4)) - 0.055f;
             packed |= (uint32_t)(unsigned char)(clampf(v, 0.0f, 1.0f) * 255.0f) << (8 * c);
         }

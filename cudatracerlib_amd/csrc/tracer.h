@@ -109,9 +109,11 @@ public:
                             const ctl_tonemap* process, uint32_t* host_rgbcol);
     void read_filtered(uint32_t* host_rgbe);                                       // Image::getFilteredData: the RGBE plane the last filter / post-process call left
     float last_filter_ms() const { return filter_ms_; }                            // HIP-event time of the NonLocalMeans kernels of the last apply_pipeline_nlm
+    bool luminance_info(float out[4]) const { if (!have_lum_) return false; for (int i = 0; i < 4; i++) out[i] = lum_info_[i]; return true; }   // Image::ComputeLuminanceInfo as the last tone-mapped call used it
     void write_file(float splat_scale, const char* path);                          // Image::WriteDisplayImage (Engine/Image.cpp:67-75)
 private:
     void pipeline_tail(const ctl_tonemap* process, uint32_t* host_rgbcol);         // the post-process or the plain conversion of the filtered plane, then the D2H
+    bool have_lum_ = false; float lum_info_[4] = { 0, 0, 0, 0 };                    // (min, max, avg, logAvg) of the last pipeline_tail with a post-process
     bool reduced_ = false; float filter_ms_ = 0; hipEvent_t ev_[2] = { nullptr, nullptr };   // ev_: around the NonLocalMeans kernel, created on first use
     uint32_t w_, h_; dbuf<ctl_pixel_data> px_; dbuf<float> rgb_, variance_; dbuf<uint32_t> out_, filtered_; dbuf<int> lum_;   // filtered_: m_filteredColorsDevice (RGBE)
 };

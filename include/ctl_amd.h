@@ -583,6 +583,9 @@ int ctl_image_apply_pipeline_nlm(ctl_image* img, float splat_scale, const ctl_nl
                                  uint32_t* host_rgbcol_out);
 /* Image::getFilteredData: the RGBE plane (r | g << 8 | b << 16 | e << 24 per pixel) that the last pipeline call with a filter or a post-process left. */
 int ctl_image_read_filtered(ctl_image* img, uint32_t* host_rgbe_out);
+/* Image::ComputeLuminanceInfo, read-only: out4 = (min, max, avg, logAvg) of the filtered plane's luminance as the last pipeline call with a post-process computed
+ * and used them (stored then, not recomputed here).  CTL_ERR_INVALID before the first such call. */
+int ctl_image_luminance_info(ctl_image* img, float* out4);
 /* Measurement: HIP-event time in ms of the NonLocalMeans kernel of the last ctl_image_apply_pipeline_nlm on this image (0 before the first). */
 int ctl_image_last_filter_ms(ctl_image* img, float* ms_out);
 /* run the intersect kernels in counting mode (N_inner / N_tri / N_inst of SURVEY §8d); slower, for measurement only */

@@ -119,6 +119,10 @@ def load_ref():
         r.ref_float3_to_rgbe.restype = u32; r.ref_float3_to_rgbe.argtypes = [f32, f32, f32]
         r.ref_float3_to_rgbcol.restype = u32; r.ref_float3_to_rgbcol.argtypes = [f32, f32, f32]
         r.ref_rgbe_to_float3.argtypes = [u32, C.c_void_p]; r.ref_rgbcol_to_float3.argtypes = [u32, C.c_void_p]
+    if hasattr(r, "ref_pipeline_filter"):
+        r.ref_pipeline_filter.restype = C.c_int; r.ref_pipeline_filter.argtypes = [C.c_void_p, C.c_int, C.c_int, f32, C.c_int, f32, f32, f32, f32, C.c_void_p, C.c_void_p]
+        r.ref_pipeline_reinhard.restype = u32; r.ref_pipeline_reinhard.argtypes = [u32, f32, f32]
+        r.ref_pipeline_gamma.restype = u32; r.ref_pipeline_gamma.argtypes = [f32, f32, f32]
     if hasattr(r, "ref_filter_evaluate"):
         r.ref_filter_evaluate.restype = f32; r.ref_filter_evaluate.argtypes = [C.c_int, f32, f32, f32, f32, f32, f32]
     if hasattr(r, "ref_sensor_rays"):

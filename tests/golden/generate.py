@@ -939,8 +939,43 @@ def gen_primtracer(r):
     np.savez_compressed(os.path.join(HERE, "primtracer.npz"), **out)
 
 
+def gen_pipeline(r):
+    """The canonical image pipeline run by the reference's own code (oracle/ref_pipeline_driver.cpp) over the cases of tests/pipeline_cases.py: evalFilter + toRGBE per
+    pixel (the filtered RGBE plane), the Reinhard05Kernel body per RGBE word, gammaCorrecture per Spectrum.  Where the reference's C++ defines no value the fixture says so
+    in `undef`, one byte per pixel: bit 3 = the maximum is NaN or infinite (Float3ToRGBE's frexp_self leaves the exponent unwritten; the word is stored as 0),
+    bits 0..2 = that channel's scaled value is NaN, <= -1 or >= 256 under a finite maximum (a float -> unsigned char conversion out of range; the byte is stored as 0)."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import pipeline_cases as K
+    from oracle import pipeline as P
+    out = {}; planes = []; undefs = []
+    for key, px, f in K.golden_filter_cases():
+        h, w = px.shape[:2]
+        frame = np.ascontiguousarray(px, np.float32)
+        plane = np.zeros((h, w), np.uint32); spec = np.zeros((h, w, 3), np.float32)
+        assert r.ref_pipeline_filter(frame.ctypes.data, w, h, f32(K.SPLAT_SCALE), f["type"], f32(f["xw"]), f32(f["yw"]), f32(f["p0"]), f32(f["p1"]), plane.ctypes.data, spec.ctypes.data) == 0, key
+        with np.errstate(invalid="ignore"):
+            m = np.where(spec[..., 0] > spec[..., 1], spec[..., 0], spec[..., 1]); m = np.where(m > spec[..., 2], m, spec[..., 2])
+            unwritten = np.isnan(m) | np.isinf(m) & (m > 0)
+            ok, v, _ = P.rgbe_scaled(spec)
+            out_of_range = (np.isnan(v) | (v <= -1) | (v >= 256)) & (ok & ~unwritten)[..., None]
+        undef = (unwritten.astype(np.uint8) << 3) | out_of_range[..., 0].astype(np.uint8) | (out_of_range[..., 1].astype(np.uint8) << 1) | (out_of_range[..., 2].astype(np.uint8) << 2)
+        keep = np.uint32(0xffffffff) ^ (out_of_range[..., 0] * np.uint32(0xff)) ^ (out_of_range[..., 1] * np.uint32(0xff00)) ^ (out_of_range[..., 2] * np.uint32(0xff0000))
+        planes.append(np.where(unwritten, np.uint32(0), plane & keep).astype(np.uint32).ravel()); undefs.append(undef.ravel())
+        if f["type"] in (2, 4) and f["p0"] > 0 and key.startswith("plain"):     # the fixture's frames keep the ambiguity rule's cap by themselves (float64 only)
+            assert K.ambiguous_channels(px, K.SPLAT_SCALE, f)[0].mean() <= K.AMBIGUOUS_SHARE_CAP, key
+    out["planes"] = np.concatenate(planes); out["undef"] = np.concatenate(undefs)   # in the order and with the shapes of golden_filter_cases()
+    words, scale, inv = K.golden_reinhard_inputs()
+    out["reinhard_rgbcol"] = np.array([r.ref_pipeline_reinhard(int(a), f32(b), f32(c)) for a, b, c in zip(words, scale, inv)], np.uint32)
+    assert (out["reinhard_rgbcol"] >> 24 == 255).all()
+    c = K.golden_gamma_inputs()
+    out["gamma_rgbcol"] = np.array([r.ref_pipeline_gamma(f32(a), f32(b), f32(d)) for a, b, d in c], np.uint32)
+    np.savez_compressed(os.path.join(HERE, "pipeline.npz"), **out)
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["pathtrace"]:     # only this fixture (the others stay byte-identical)
+    if sys.argv[1:] == ["pipeline"]:      # only this fixture
+        gen_pipeline(oracle.load_ref())
+    elif sys.argv[1:] == ["pathtrace"]:     # only this fixture (the others stay byte-identical)
         gen_pathtrace(oracle.load_ref())
     elif sys.argv[1:] == ["primtracer"]:  # only this fixture
         gen_primtracer(oracle.load_ref())
@@ -991,3 +1026,4 @@ if __name__ == "__main__":
         gen_pathtrace(oracle.load_ref())
         gen_primtracer(oracle.load_ref())
         gen_image(oracle.load_ref())
+        gen_pipeline(oracle.load_ref())
