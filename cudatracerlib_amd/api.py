@@ -732,6 +732,30 @@ def scene_desc_diff(a, b):
     return mask.value
 
 
+# ---- ctl_shading_eval (TEST INFRASTRUCTURE): the device BSDF / emitter / texture functions one call per query (include/ctl_amd.h CTL_EVAL_*)
+EVAL_BUILD_BASIC, EVAL_BUILD_FULL, EVAL_BUILD_PARTIALS = 0, 1, 2
+(EVAL_BSDF_SAMPLE, EVAL_BSDF_EVAL, EVAL_BSDF_SAMPLE_EVAL, EVAL_LIGHT_SAMPLE, EVAL_EMITTER_SAMPLE, EVAL_LIGHT_PDF, EVAL_LIGHT_EVAL, EVAL_ENV_EVAL, EVAL_TEXTURE, EVAL_MIP,
+ EVAL_NORMAL_MAP, EVAL_ALPHA_TEST) = range(12)
+EVAL_QUERY_FLOATS = (8, 10, 11, 9, 8, 14, 10, 3, 4, 7, 21, 3)
+EVAL_RESULT_FLOATS = (9, 4, 13, 15, 19, 1, 3, 3, 3, 3, 9, 1)
+lib.ctl_shading_eval.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, u32, u32, C.c_void_p, u32, C.c_void_p, u32]
+
+
+def shading_eval(scene, build, what, queries, materials=None):
+    """ctl_shading_eval: `queries` is an (n, EVAL_QUERY_FLOATS[what]) float32 array whose index columns hold the BITS of a uint32 (np.uint32(i).view(np.float32));
+    materials: None or a ctypes array of ctl_material that replaces the scene's for this call.  Returns the (n, EVAL_RESULT_FLOATS[what]) float32 result rows.
+    Raises CtlError with the library's code when the call is refused (nothing is launched then)."""
+    import numpy as np
+    q = np.ascontiguousarray(queries, np.float32)
+    if q.ndim != 2:
+        q = q.reshape(-1, EVAL_QUERY_FLOATS[what] if 0 <= what < len(EVAL_QUERY_FLOATS) else 1)
+    ow = EVAL_RESULT_FLOATS[what] if 0 <= what < len(EVAL_RESULT_FLOATS) else 1
+    out = np.zeros((len(q), ow), np.float32)
+    n_m = len(materials) if materials is not None else 0
+    _check(lib.ctl_shading_eval(scene._h, build, what, C.addressof(materials) if materials is not None else None, n_m, len(q), q.ctypes.data, q.shape[1], out.ctypes.data, ow))
+    return out
+
+
 def _rays_struct(rays):
     r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
     return r, r.ctypes.data_as(C.c_void_p)

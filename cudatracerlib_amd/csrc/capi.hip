@@ -12,6 +12,7 @@
 #include "image_io.h"
 #include <memory>
 #include "scene_cache.h"
+#include "shading_eval.h"
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -20,7 +21,10 @@
 using namespace ctl;
 
 struct ctl_builder { scene_builder b; };
-struct ctl_scene { Scene s; ctl_scene(const ctl_scene_desc& d, bool flatten, int fmt = -1, bool reduced_rt = false) : s(d, flatten, fmt, reduced_rt) {} };
+struct ctl_scene {
+    Scene s; uint32_t n_materials, n_images;   // the sizes of the description's material and image arrays (ctl_shading_eval checks a query's indices against them)
+    ctl_scene(const ctl_scene_desc& d, bool flatten, int fmt = -1, bool reduced_rt = false) : s(d, flatten, fmt, reduced_rt), n_materials(d.n_materials), n_images(d.n_images) {}
+};
 struct ctl_flat_bvh { flat_scene f; };
 struct ctl_image { Image img; ctl_image(uint32_t w, uint32_t h) : img(w, h) {} };
 struct ctl_tracer { std::unique_ptr<TracerBase> t; };
@@ -139,6 +143,155 @@ int ctl_shared_math_eval(int32_t which, uint32_t n, const float* x, const float*
         }
     CTL_CATCH
 }
+// ---- ctl_shading_eval (TEST INFRASTRUCTURE): the device shading functions one call per query (shading_eval.h).  Everything a query can name is checked here, on the
+// host, against host copies of the scene's materials and emitters: a kernel is launched only for queries it can answer.
+namespace {
+struct eval_check {
+    int build; bool override_mats; std::vector<ctl_material> mats; std::vector<ctl_light> lights; uint32_t n_images; bool tables[3]; bool have_reduced;
+    int code = CTL_OK; std::string why;
+    bool refuse(int c, const std::string& w) { code = c; why = "ctl_shading_eval: " + w; return false; }
+    bool texture(const ctl_texture& t, bool any_build = false) {   // any_build: the caller's function reads image textures in every build (the alpha test, mipmap.h)
+        if (t.type != 0 && t.type != CTL_TEX_CONSTANT && t.type != CTL_TEX_CHECKER && t.type != CTL_TEX_IMAGE) return refuse(CTL_ERR_INVALID, "unknown texture type " + std::to_string(t.type));
+        if (t.type == CTL_TEX_IMAGE) {
+            if (t.image != 0xffffffffu && t.image >= n_images) return refuse(CTL_ERR_INVALID, "image index " + std::to_string(t.image) + " of " + std::to_string(n_images));
+            if (build == 0 && !any_build) return refuse(CTL_ERR_UNSUPPORTED, "the basic build carries no image textures");
+        }
+        return true;
+    }
+    bool material(uint32_t mi, bool nested) {
+        if (mi >= mats.size()) return refuse(CTL_ERR_INVALID, std::string(nested ? "nested " : "") + "material index " + std::to_string(mi) + " of " + std::to_string(mats.size()));
+        const ctl_material& M = mats[mi]; const uint32_t t = M.bsdf_type;
+        const bool nesting = t == CTL_BSDF_COATING || t == CTL_BSDF_ROUGHCOATING || t == CTL_BSDF_BLEND;
+        const bool simple = t == CTL_BSDF_DIFFUSE || t == CTL_BSDF_DIELECTRIC || t == CTL_BSDF_THINDIELECTRIC || t == CTL_BSDF_ROUGHDIELECTRIC || t == CTL_BSDF_CONDUCTOR || t == CTL_BSDF_ROUGHCONDUCTOR ||
+                            t == CTL_BSDF_PLASTIC || t == CTL_BSDF_PHONG || t == CTL_BSDF_ROUGHDIFFUSE || t == CTL_BSDF_WARD || t == CTL_BSDF_ROUGHPLASTIC;
+        if (!simple && !nesting) return refuse(CTL_ERR_INVALID, "unknown bsdf_type " + std::to_string(t));
+        if (nested && nesting) return refuse(CTL_ERR_INVALID, "a nested material is itself a nesting model");
+        if (build == 0) {
+            if (t != CTL_BSDF_DIFFUSE && t != CTL_BSDF_DIELECTRIC && t != CTL_BSDF_CONDUCTOR && t != CTL_BSDF_ROUGHCONDUCTOR) return refuse(CTL_ERR_UNSUPPORTED, "the basic build does not carry bsdf_type " + std::to_string(t));
+            if (t == CTL_BSDF_ROUGHCONDUCTOR && (M.u[0] == CTL_MF_PHONG || (M.u[0] == CTL_MF_BECKMANN && M.u[1]))) return refuse(CTL_ERR_UNSUPPORTED, "the basic build carries neither the Phong distribution nor Beckmann visible-normal sampling");
+        }
+        if (t == CTL_BSDF_ROUGHCONDUCTOR || t == CTL_BSDF_ROUGHDIELECTRIC || t == CTL_BSDF_ROUGHCOATING) { if (M.u[0] > CTL_MF_PHONG) return refuse(CTL_ERR_INVALID, "unknown microfacet distribution"); }
+        if (t == CTL_BSDF_ROUGHPLASTIC || t == CTL_BSDF_ROUGHCOATING) {
+            const uint32_t slot = t == CTL_BSDF_ROUGHPLASTIC ? M.u[2] : M.u[0];
+            if (slot > 2 || !tables[slot]) return refuse(CTL_ERR_INVALID, "a rough BSDF without its transmittance table (slot " + std::to_string(slot) + ")");
+            if (M.reserved_[0] && (override_mats || !have_reduced)) return refuse(CTL_ERR_INVALID, "a material that names a reduced transmittance table the call does not have");
+        }
+        for (int k = 0; k < 4; k++) if (!texture(M.tex[k])) return false;
+        if (t == CTL_BSDF_COATING || t == CTL_BSDF_ROUGHCOATING) return material(M.u[2], true);
+        if (t == CTL_BSDF_BLEND) return material(M.u[2], true) && material(M.u[3], true);
+        return true;
+    }
+    bool light(uint32_t li) {
+        if (li >= lights.size()) return refuse(CTL_ERR_INVALID, "light index " + std::to_string(li) + " of " + std::to_string(lights.size()));
+        const ctl_light& L = lights[li];
+        if (L.type < CTL_LIGHT_POINT || L.type > CTL_LIGHT_INFINITE) return refuse(CTL_ERR_INVALID, "unknown light type");
+        const bool more = (L.type != CTL_LIGHT_POINT && L.type != CTL_LIGHT_DIFFUSE) || (L.type == CTL_LIGHT_DIFFUSE && (L.orthogonal || L.rad_texture.type == CTL_TEX_CHECKER || L.rad_texture.type == CTL_TEX_IMAGE));
+        if (more && build == 0) return refuse(CTL_ERR_UNSUPPORTED, "the basic build carries point lights and plain area lights only");
+        if (L.type == CTL_LIGHT_INFINITE && L.env_image >= n_images) return refuse(CTL_ERR_INVALID, "environment image index out of range");
+        if (L.type == CTL_LIGHT_DIFFUSE && L.rad_texture.type == CTL_TEX_IMAGE && L.rad_texture.image != 0xffffffffu && L.rad_texture.image >= n_images) return refuse(CTL_ERR_INVALID, "image index of a light texture out of range");
+        return true;
+    }
+};
+uint32_t eval_word(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
+}
+int ctl_shading_eval(const ctl_scene* scene, int32_t build, int32_t what, const ctl_material* materials, uint32_t n_materials, uint32_t n, const float* queries, uint32_t query_stride,
+                     float* out, uint32_t out_stride) {
+    if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, "no HIP device: the MI355X path tracer has no CPU fallback");
+    CTL_REQUIRE(scene && (n == 0 || (queries && out)), "null argument");
+    CTL_REQUIRE(build >= 0 && build <= 2, "ctl_shading_eval: unknown build");
+    CTL_REQUIRE(what >= 0 && what < kEvalCount, "ctl_shading_eval: unknown function");
+    CTL_REQUIRE(query_stride >= kEvalQueryFloats[what] && out_stride >= kEvalResultFloats[what], "ctl_shading_eval: a row is shorter than the function's query / result");
+    CTL_REQUIRE(!materials || n_materials, "ctl_shading_eval: an empty material array");
+    if (what == kEvalMip && build != 2) return fail(CTL_ERR_UNSUPPORTED, "ctl_shading_eval: filtered texture lookups live in the partials build");
+    if (what == kEvalNormalMap && build == 0) return fail(CTL_ERR_UNSUPPORTED, "ctl_shading_eval: the basic build carries no surface maps");
+    CTL_TRY
+        require_device();
+        dev_scene S = scene->s.S;   // this call's copy: a material override replaces its mats pointer only
+        eval_check K; K.build = build; K.override_mats = materials != nullptr; K.n_images = scene->n_images; K.have_reduced = S.rt_reduced != nullptr;
+        if (materials) K.mats.assign(materials, materials + n_materials);
+        else { K.mats.resize(scene->n_materials); if (scene->n_materials) CTL_HIP(hipMemcpy(K.mats.data(), S.mats, sizeof(ctl_material) * scene->n_materials, hipMemcpyDeviceToHost)); }
+        K.lights.resize(S.n_lights_buf); if (S.n_lights_buf) CTL_HIP(hipMemcpy(K.lights.data(), S.lights, sizeof(ctl_light) * S.n_lights_buf, hipMemcpyDeviceToHost));
+        K.tables[0] = K.tables[1] = K.tables[2] = false;
+        if (S.rough_transmittance) { ctl_rough_transmittance t3[3]; CTL_HIP(hipMemcpy(t3, S.rough_transmittance, sizeof(t3), hipMemcpyDeviceToHost)); for (int k = 0; k < 3; k++) K.tables[k] = t3[k].trans && t3[k].diff_trans; }
+        bool ok = true;
+        if (what == kEvalEnvEval && n) {
+            if (S.env_map_index == 0xffffffffu) ok = K.refuse(CTL_ERR_INVALID, "the scene has no environment emitter"); else ok = K.light(S.env_map_index);
+        }
+        if (what == kEvalEmitterSample && n) {
+            if (S.num_lights > CTL_MAX_NUM_LIGHTS) ok = K.refuse(CTL_ERR_INVALID, "more lights than CTL_MAX_NUM_LIGHTS");
+            for (uint32_t k = 0; ok && k < S.num_lights; k++) ok = K.light(S.light_indices[k]);
+        }
+        // the distinct (index, ...) keys of a batch are few: remember what passed
+        std::vector<uint8_t> mat_ok(K.mats.size(), 0), light_ok(K.lights.size(), 0);
+        for (uint32_t i = 0; ok && i < n; i++) {
+            const float* a = queries + (size_t)i * query_stride;
+            switch (what) {
+            case kEvalBsdfSample: case kEvalBsdfEval: case kEvalBsdfSampleEval: case kEvalNormalMap: {
+                const uint32_t mi = eval_word(a[0]);
+                if (mi < mat_ok.size() && mat_ok[mi]) break;
+                ok = K.material(mi, false);
+                if (ok && what == kEvalNormalMap) {
+                    const ctl_material& M = K.mats[mi];
+                    if (M.map_kind > CTL_MAP_HEIGHT) ok = K.refuse(CTL_ERR_INVALID, "unknown surface map kind");
+                    else if (M.map_kind != CTL_MAP_NONE) ok = K.texture(M.map_tex);
+                }
+                if (ok) mat_ok[mi] = 1;
+                break; }
+            case kEvalLightSample: case kEvalLightPdf: case kEvalLightEval: {
+                const uint32_t li = eval_word(a[0]);
+                if (li < light_ok.size() && light_ok[li]) break;
+                ok = K.light(li); if (ok) light_ok[li] = 1;
+                break; }
+            case kEvalTexture: {
+                const uint32_t kind = eval_word(a[0]), idx = eval_word(a[1]);
+                if (kind > 6) { ok = K.refuse(CTL_ERR_INVALID, "unknown texture slot"); break; }
+                if (kind == 6) { if (idx >= K.lights.size()) ok = K.refuse(CTL_ERR_INVALID, "light index out of range"); else ok = K.texture(K.lights[idx].rad_texture); break; }
+                if (idx >= K.mats.size()) { ok = K.refuse(CTL_ERR_INVALID, "material index out of range"); break; }
+                ok = K.texture(kind == 5 ? K.mats[idx].alpha_tex : (kind == 4 ? K.mats[idx].map_tex : K.mats[idx].tex[kind]));
+                break; }
+            case kEvalAlphaTest: {
+                const uint32_t mi = eval_word(a[0]);
+                if (mi >= K.mats.size()) { ok = K.refuse(CTL_ERR_INVALID, "material index " + std::to_string(mi) + " of " + std::to_string(K.mats.size())); break; }
+                const ctl_material& M = K.mats[mi];
+                if (M.alpha_state > CTL_ALPHA_REFLECTANCE_COLOR || M.alpha_state == 4) { ok = K.refuse(CTL_ERR_INVALID, "unknown alpha blend state"); break; }
+                if (M.alpha_state != CTL_ALPHA_DISABLED) ok = K.texture((M.alpha_state & 4) ? M.tex[0] : M.alpha_tex, true);
+                // the device function takes its uv from a triangle's half-precision vertex coordinates: only such a uv can be asked
+                if (ok && !(half_to_float(float_to_half(a[1])) == a[1] && half_to_float(float_to_half(a[2])) == a[2])) ok = K.refuse(CTL_ERR_INVALID, "the uv of an alpha-test query must be representable in half precision");
+                break; }
+            case kEvalMip: {
+                const uint32_t im = eval_word(a[0]);
+                if (im >= K.n_images) ok = K.refuse(CTL_ERR_INVALID, "image index " + std::to_string(im) + " of " + std::to_string(K.n_images));
+                break; }
+            default: break;
+            }
+        }
+        if (!ok) return fail(K.code, K.why);
+        dbuf<ctl_material> dmats; dbuf<float> dq, dout; dbuf<uint4> dtri, dnode;
+        if (what == kEvalAlphaTest && n) {   // one synthetic triangle and node per query: node_info[i].x = the material, the three vertices at the query's uv (u in the HIGH half of a word, as getUVSetData reads it)
+            std::vector<uint4> tri((size_t)n * 2), node(n);
+            for (uint32_t i = 0; i < n; i++) {
+                const float* a = queries + (size_t)i * query_stride;
+                const uint32_t w = ((uint32_t)float_to_half(a[1]) << 16) | float_to_half(a[2]);
+                tri[2 * (size_t)i] = make_uint4(0, 0, 0, 0); tri[2 * (size_t)i + 1] = make_uint4(0, w, w, w); node[i] = make_uint4(eval_word(a[0]), 0, 0, 0);
+            }
+            dtri.alloc(tri.size()); dnode.alloc(node.size());
+            CTL_HIP(hipMemcpy(dtri.p, tri.data(), tri.size() * sizeof(uint4), hipMemcpyHostToDevice)); CTL_HIP(hipMemcpy(dnode.p, node.data(), node.size() * sizeof(uint4), hipMemcpyHostToDevice));
+            S.tri_data = dtri.p; S.node_info = dnode.p;
+        }
+        if (materials) { dmats.alloc(n_materials); CTL_HIP(hipMemcpy(dmats.p, materials, sizeof(ctl_material) * n_materials, hipMemcpyHostToDevice)); S.mats = dmats.p; S.rt_reduced = nullptr; }
+        if (n) {
+            dq.alloc((size_t)n * query_stride); dout.alloc((size_t)n * out_stride);
+            CTL_HIP(hipMemcpy(dq.p, queries, (size_t)n * query_stride * 4, hipMemcpyHostToDevice));
+            CTL_HIP(hipMemset(dout.p, 0, (size_t)n * out_stride * 4));
+            const bool launched = build == 0 ? launch_shading_eval_basic(S, what, n, dq.p, query_stride, dout.p, out_stride)
+                                : build == 1 ? launch_shading_eval_full(S, what, n, dq.p, query_stride, dout.p, out_stride)
+                                             : launch_shading_eval_partials(S, what, n, dq.p, query_stride, dout.p, out_stride);
+            if (!launched) throw unsupported_error("ctl_shading_eval: this build does not carry the function");
+            CTL_HIP(hipGetLastError());
+            CTL_HIP(hipMemcpy(out, dout.p, (size_t)n * out_stride * 4, hipMemcpyDeviceToHost));
+        }
+    CTL_CATCH
+}
 int ctl_traversal_stack_histogram(uint64_t* out, uint32_t n_bins, int reset) {
     CTL_REQUIRE(out && n_bins >= 1, "null argument");
     CTL_TRY
@@ -163,6 +316,7 @@ int ctl_scene_update(ctl_scene* scene, const ctl_scene_desc* new_desc, uint32_t*
     CTL_REQUIRE(scene && new_desc, "null argument");
     const int rc = [&]() -> int { CTL_TRY scene->s.update(*new_desc, nullptr); CTL_CATCH }();
     if (mask_out) *mask_out = scene->s.last_mask();   // also when the update is refused: the caller sees why
+    if (rc == CTL_OK) { scene->n_materials = new_desc->n_materials; scene->n_images = new_desc->n_images; }
     return rc;
 }
 int ctl_scene_get_update_stats(ctl_scene* scene, ctl_scene_update_stats* out) { CTL_REQUIRE(scene && out, "null argument"); *out = scene->s.last_update(); return CTL_OK; }

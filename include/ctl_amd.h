@@ -615,6 +615,34 @@ int ctl_traversal_stack_histogram(uint64_t* out, uint32_t n_bins, int reset);
  * bit-identical (tests/test_fmath.py).  No reference counterpart: the reference calls the CUDA / C library's functions. */
 int ctl_shared_math_eval(int32_t which, uint32_t n, const float* x, const float* y, float* out, int32_t on_device);
 
+/* TEST INFRASTRUCTURE: the device BSDF, emitter and texture functions (csrc/shading.h) evaluated one call per query, so that the tests hold them to the oracle call by
+ * call (tests/test_gpu_shading_eval.py).  One lane per query fills the record as the oracle's call of the same name does — an identity frame at the origin, uv from
+ * the query — calls the function the shade kernels call and stores the result row.  No reference counterpart.
+ *   scene      supplies images, mip pyramids, the EWA weights, the rough-transmittance tables, emitters, the emitter CDF, shape sets and eps
+ *   build      CTL_EVAL_BUILD_*: the feature set the functions are compiled under, mirroring a product build
+ *   what       CTL_EVAL_*: the function; a query row / result row holds the floats listed below, an [index] travels as the BITS of its float
+ *   materials  NULL, or an array that replaces the scene's materials for this call (nested indices of coating / blend refer to it)
+ * Everything a query names is checked on the host before anything is launched: a material, nested material, image or light index out of range, a rough BSDF whose
+ * transmittance table the scene does not carry, an unknown `what` / `build` -> CTL_ERR_INVALID; a model, texture or emitter kind the chosen build does not carry ->
+ * CTL_ERR_UNSUPPORTED.  CTL_ERR_NO_DEVICE without a device (checked first). */
+enum { CTL_EVAL_BUILD_BASIC = 0,      /* shade_basic.hip: the basic feature set (diffuse, dielectric, conductor, rough conductor; constant / checker textures; point and plain area lights) */
+       CTL_EVAL_BUILD_FULL = 1,       /* shade_full / shade_class_*: every model, texture and emitter kind, transcendental functions out of line, scene tables in LDS */
+       CTL_EVAL_BUILD_PARTIALS = 2 }; /* megakernel.hip / prim_tracer.hip: the full set with uv partials (CTL_TEX_PARTIALS), scene tables in global memory */
+enum { CTL_EVAL_BSDF_SAMPLE = 0,      /* [material] wi(3) sample(2) uv(2)          -> f(3) pdf wo(3) sampledType eta                       (bsdf_sample_top)                    */
+       CTL_EVAL_BSDF_EVAL = 1,        /* [material] wi(3) wo(3) [typeMask] uv(2)   -> f(3) pdf, solid-angle measure                        (bsdf_f_top, bsdf_pdf_top)           */
+       CTL_EVAL_BSDF_SAMPLE_EVAL = 2, /* [material] wi(3) sample(2) uv(2) wo2(3)   -> the sample's row, then f(3) pdf for wo2 under EAll & ~EDelta ON THE SAME RECORD (next-event estimation as the shade kernels do it) */
+       CTL_EVAL_LIGHT_SAMPLE = 3,     /* [light] ref(3) refN(3) sample(2)          -> value(3) pdf d(3) dist p(3) n(3) measure             (light_sample_direct)                */
+       CTL_EVAL_EMITTER_SAMPLE = 4,   /* ref(3) refN(3) sample(2)                  -> sampleEmitterDirect: value(3) pdf d(3) dist p(3) n(3) slot, emitter pdf, re-scaled sample.x; sample_emitter's slot, pdf */
+       CTL_EVAL_LIGHT_PDF = 5,        /* [light] ref(3) refN(3) d(3) dist n(3)     -> pdfDirect, solid-angle measure                       (light_pdf_direct / env_pdf_direct)  */
+       CTL_EVAL_LIGHT_EVAL = 6,       /* [light] p(3) n(3) d(3)                    -> radiance(3)                                          (light_eval)                         */
+       CTL_EVAL_ENV_EVAL = 7,         /* dir(3)                                    -> radiance(3) of the scene's environment emitter       (env_eval)                           */
+       CTL_EVAL_TEXTURE = 8,          /* [slot] [index] uv(2)                      -> rgb(3), unfiltered; slot 0..3 = tex[slot] of material `index`, 4 its map_tex, 5 its alpha_tex, 6 = rad_texture of light `index` (tex_eval) */
+       CTL_EVAL_MIP = 9,              /* [image] uv(2) d0(2) d1(2)                 -> rgb(3), KernelMIPMap::eval; CTL_EVAL_BUILD_PARTIALS only (mip_eval)                       */
+       CTL_EVAL_NORMAL_MAP = 10,     /* [material] uv(2) frame s,t,n(9) n_geo,dpdu,dpdv(9) -> the perturbed frame s,t,n(9)                (sample_normal_map)                  */
+       CTL_EVAL_ALPHA_TEST = 11 };    /* [material] uv(2), each representable in half precision -> 1 / 0: Material::AlphaTest as the traversal asks it (alpha_survives), through one synthetic triangle per query whose vertices carry the uv; every build */
+int ctl_shading_eval(const ctl_scene* scene, int32_t build, int32_t what, const ctl_material* materials, uint32_t n_materials,
+                     uint32_t n, const float* queries, uint32_t query_stride, float* out, uint32_t out_stride);
+
 /* device memory helpers so that Python callers need no HIP binding */
 int ctl_device_malloc(size_t bytes, void** out);
 int ctl_device_free(void* p);

@@ -84,6 +84,19 @@ def load(shared_math=False):
     o.orc_triangle_data_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_int, C.c_void_p]
     o.orc_triangle_fill_dg.argtypes = [C.c_void_p, C.c_void_p, f32, f32, C.c_int, C.c_void_p]
     o.orc_woop_intersect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, f32, f32, C.c_void_p]
+    o.orc_bsdf_sample_uv.argtypes = [C.c_void_p, C.c_void_p, f32, f32, f32, f32, C.c_void_p]
+    o.orc_bsdf_eval_uv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_int, f32, f32, C.c_void_p]
+    o.orc_light_eval.argtypes = [C.c_void_p, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    o.orc_emitter_select.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    o.orc_sample_emitter_direct.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, f32, f32, C.c_void_p]
+    # the batched probes (rows of ctl_shading_eval): (first arguments..., n, queries, query stride, out, out stride)
+    rows = [u32, C.c_void_p, u32, C.c_void_p, u32]
+    for name, head in (("orc_bsdf_sample_uv_n", [C.c_void_p]), ("orc_bsdf_eval_uv_n", [C.c_void_p, C.c_int]), ("orc_bsdf_sample_then_eval_n", [C.c_void_p]),
+                       ("orc_light_sample_direct_n", [C.c_void_p]), ("orc_sample_emitter_direct_n", [C.c_void_p]), ("orc_light_pdf_direct_n", [C.c_void_p]),
+                       ("orc_light_eval_n", [C.c_void_p]), ("orc_env_eval_n", [C.c_void_p]), ("orc_texture_eval_n", [C.c_void_p, C.c_void_p]), ("orc_mip_eval_n", [C.c_void_p]),
+                       ("orc_sample_normal_map_n", [C.c_void_p, C.c_void_p])):
+        getattr(o, name).argtypes = head + rows; getattr(o, name).restype = None
+    o.orc_alpha_test_n.argtypes = [C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p]; o.orc_alpha_test_n.restype = None
     return o
 
 

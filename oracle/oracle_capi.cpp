@@ -301,6 +301,136 @@ int orc_sample_normal_map(const ctl_scene_desc* desc, const ctl_material* mat, f
 }
 int orc_alpha_test(const ctl_scene_desc* desc, const ctl_material* mat, float u, float v) { return materialAlphaTest(*mat, V2{ u, v }, desc ? desc->images : nullptr) ? 1 : 0; }
 
+// ---- batched forms of the probes above (tests/shading_cases.py): n query rows in, n result rows out, strides in floats.  The rows are those of the product's
+// ctl_shading_eval (include/ctl_amd.h CTL_EVAL_*: an [index] travels as the bits of its float), so one query array serves the kernels and the oracle.  Each equals its
+// one-call form bit for bit (tests/test_oracle_shading_cases.py); where the one-call form leaves fields of a DirectSamplingRecord as its constructor found them
+// (d, dist, pdf of a rejected sample), these start from zero.  mats: the material array the [material] indices and the nested indices refer to.
+static inline uint32_t rowWord(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
+static inline void probeRec(BRec& b, const ctl_material* mats, V3 wi, V3 wo, unsigned mask, float u, float v) {
+    b.dg.P = V3(0.0f); b.dg.sys = Frame(V3(1, 0, 0), V3(0, 1, 0), V3(0, 0, 1)); b.dg.n = V3(0, 0, 1); b.dg.uv = V2{ u, v };
+    b.wi = wi; b.wo = wo; b.eta = 1.0f; b.typeMask = mask; b.sampledType = 0; b.dg.rough_transmittance = g_probe_rt; b.dg.materials = mats;
+}
+static inline void put3(float* o, V3 v) { o[0] = v.x; o[1] = v.y; o[2] = v.z; }
+// [material] wi(3) sample(2) uv(2) -> f(3) pdf wo(3) sampledType eta
+void orc_bsdf_sample_uv_n(const ctl_material* mats, uint32_t n, const float* q, uint32_t qs, float* out, uint32_t os) {
+    for (uint32_t i = 0; i < n; i++) {
+        const float* a = q + (size_t)i * qs; float* o = out + (size_t)i * os;
+        BRec b; probeRec(b, mats, V3(a[1], a[2], a[3]), V3(0.0f), EAll, a[6], a[7]);
+        float pdf = 0; Spec f = bsdfSample(mats[rowWord(a[0])], b, pdf, V2{ a[4], a[5] });
+        put3(o, f); o[3] = pdf; put3(o + 4, b.wo); o[7] = (float)b.sampledType; o[8] = b.eta;
+    }
+}
+// [material] wi(3) wo(3) [typeMask] uv(2) -> f(3) pdf; mode 1 solid angle, 2 discrete
+void orc_bsdf_eval_uv_n(const ctl_material* mats, int mode, uint32_t n, const float* q, uint32_t qs, float* out, uint32_t os) {
+    const int measure = mode == 2 ? EDiscrete : ESolidAngle;
+    for (uint32_t i = 0; i < n; i++) {
+        const float* a = q + (size_t)i * qs; float* o = out + (size_t)i * os;
+        BRec b; probeRec(b, mats, V3(a[1], a[2], a[3]), V3(a[4], a[5], a[6]), rowWord(a[7]), a[8], a[9]);
+        const ctl_material& M = mats[rowWord(a[0])];
+        put3(o, bsdfF(M, b, measure)); o[3] = bsdfPdf(M, b, measure);
+    }
+}
+// [material] wi(3) sample(2) uv(2) wo2(3) -> the sample's row, then f(3) pdf of a FRESH record (wi, wo2, EAll & ~EDelta): EstimateDirect's own bRec (TraceAlgorithms.cu:62-64)
+void orc_bsdf_sample_then_eval_n(const ctl_material* mats, uint32_t n, const float* q, uint32_t qs, float* out, uint32_t os) {
+    for (uint32_t i = 0; i < n; i++) {
+        const float* a = q + (size_t)i * qs; float* o = out + (size_t)i * os;
+        const ctl_material& M = mats[rowWord(a[0])];
+        BRec b; probeRec(b, mats, V3(a[1], a[2], a[3]), V3(0.0f), EAll, a[6], a[7]);
+        float pdf = 0; Spec f = bsdfSample(M, b, pdf, V2{ a[4], a[5] });
+        put3(o, f); o[3] = pdf; put3(o + 4, b.wo); o[7] = (float)b.sampledType; o[8] = b.eta;
+        BRec e; probeRec(e, mats, V3(a[1], a[2], a[3]), V3(a[8], a[9], a[10]), EAll & ~EDelta, a[6], a[7]);
+        put3(o + 9, bsdfF(M, e, ESolidAngle)); o[12] = bsdfPdf(M, e, ESolidAngle);
+    }
+}
+static inline DirectRec probeDirect(V3 ref, V3 refN) { DirectRec d(ref, refN); d.pdf = 0.0f; d.d = V3(0.0f); d.dist = 0.0f; d.uv = V2{ 0.0f, 0.0f }; return d; }
+static inline void putDirect(float* o, Spec v, const DirectRec& d) { put3(o, v); o[3] = d.pdf; put3(o + 4, d.d); o[7] = d.dist; put3(o + 8, d.p); put3(o + 11, d.n); }
+// [light] ref(3) refN(3) sample(2) -> value(3) pdf d(3) dist p(3) n(3) measure
+void orc_light_sample_direct_n(const ctl_scene_desc* desc, uint32_t n, const float* q, uint32_t qs, float* out, uint32_t os) {
+    Scene S; S.d = *desc;
+    for (uint32_t i = 0; i < n; i++) {
+        const float* a = q + (size_t)i * qs; float* o = out + (size_t)i * os;
+        DirectRec d = probeDirect(V3(a[1], a[2], a[3]), V3(a[4], a[5], a[6]));
+        Spec v = lightSampleDirect(S, desc->lights[rowWord(a[0])], d, V2{ a[7], a[8] });
+        putDirect(o, v, d); o[14] = (float)d.measure;
+    }
+}
+// ref(3) refN(3) sample(2) -> sampleEmitterDirect: value(3) pdf d(3) dist p(3) n(3) slot; then sampleEmitter alone: emitter pdf, re-scaled sample.x, slot, pdf
+void orc_sample_emitter_direct_n(const ctl_scene_desc* desc, uint32_t n, const float* q, uint32_t qs, float* out, uint32_t os) {
+    Scene S; S.d = *desc;
+    for (uint32_t i = 0; i < n; i++) {
+        const float* a = q + (size_t)i * qs; float* o = out + (size_t)i * os;
+        DirectRec d = probeDirect(V3(a[0], a[1], a[2]), V3(a[3], a[4], a[5]));
+        const ctl_light* obj = nullptr;
+        Spec v = sampleEmitterDirect(S, d, V2{ a[6], a[7] }, &obj);
+        putDirect(o, v, d); o[14] = obj ? (float)(obj - desc->lights) : -1.0f;
+        V2 s{ a[6], a[7] }; float emPdf = 0.0f;
+        const ctl_light* L = sampleEmitter(S, emPdf, s);
+        o[15] = emPdf; o[16] = s.x; o[17] = L ? (float)(L - desc->lights) : -1.0f; o[18] = emPdf;
+    }
+}
+// [light] ref(3) refN(3) d(3) dist n(3) -> pdfDirect, solid-angle measure
+void orc_light_pdf_direct_n(const ctl_scene_desc* desc, uint32_t n, const float* q, uint32_t qs, float* out, uint32_t os) {
+    Scene S; S.d = *desc;
+    for (uint32_t i = 0; i < n; i++) {
+        const float* a = q + (size_t)i * qs;
+        DirectRec r(V3(a[1], a[2], a[3]), V3(a[4], a[5], a[6]));
+        r.d = V3(a[7], a[8], a[9]); r.dist = a[10]; r.n = V3(a[11], a[12], a[13]); r.measure = ESolidAngle;
+        out[(size_t)i * os] = lightPdfDirect(S, desc->lights[rowWord(a[0])], r);
+    }
+}
+// [light] p(3) n(3) d(3) -> DiffuseLight::eval
+void orc_light_eval_n(const ctl_scene_desc* desc, uint32_t n, const float* q, uint32_t qs, float* out, uint32_t os) {
+    Scene S; S.d = *desc;
+    for (uint32_t i = 0; i < n; i++) {
+        const float* a = q + (size_t)i * qs;
+        put3(out + (size_t)i * os, lightEval(S, desc->lights[rowWord(a[0])], V3(a[1], a[2], a[3]), Frame(V3(a[4], a[5], a[6])), V3(a[7], a[8], a[9])));
+    }
+}
+// dir(3) -> InfiniteLight::evalEnvironment
+void orc_env_eval_n(const ctl_scene_desc* desc, uint32_t n, const float* q, uint32_t qs, float* out, uint32_t os) {
+    Scene S; S.d = *desc;
+    for (uint32_t i = 0; i < n; i++) {
+        const float* a = q + (size_t)i * qs;
+        Spec v(0.0f);
+        if (desc->env_map_index != 0xffffffffu) v = envEval(S, desc->lights[desc->env_map_index], V3(a[0], a[1], a[2]));
+        put3(out + (size_t)i * os, v);
+    }
+}
+// [slot] [index] uv(2) -> Texture::Evaluate(dg) without partials; slot 0..3 = tex[slot] of mats[index], 4 its map_tex, 5 its alpha_tex, 6 = rad_texture of light `index`
+void orc_texture_eval_n(const ctl_scene_desc* desc, const ctl_material* mats, uint32_t n, const float* q, uint32_t qs, float* out, uint32_t os) {
+    for (uint32_t i = 0; i < n; i++) {
+        const float* a = q + (size_t)i * qs;
+        const uint32_t kind = rowWord(a[0]), idx = rowWord(a[1]);
+        const ctl_texture& t = kind == 6 ? desc->lights[idx].rad_texture : (kind == 5 ? mats[idx].alpha_tex : (kind == 4 ? mats[idx].map_tex : mats[idx].tex[kind]));
+        DG dg; dg.uv = V2{ a[2], a[3] }; dg.images = desc->images;
+        put3(out + (size_t)i * os, texEval(t, dg));
+    }
+}
+// [image] uv(2) d0(2) d1(2) -> KernelMIPMap::eval; the pyramids are built once
+void orc_mip_eval_n(const ctl_scene_desc* desc, uint32_t n, const float* q, uint32_t qs, float* out, uint32_t os) {
+    std::vector<MipPyramid> pyramids(desc->n_images); std::vector<char> built(desc->n_images, 0);
+    for (uint32_t i = 0; i < n; i++) {
+        const float* a = q + (size_t)i * qs; const uint32_t im = rowWord(a[0]);
+        if (!built[im]) { pyramids[im].build(desc->images[im]); built[im] = 1; }
+        put3(out + (size_t)i * os, mipEval(desc->images[im], pyramids[im], V2{ a[1], a[2] }, V2{ a[3], a[4] }, V2{ a[5], a[6] }));
+    }
+}
+// [material] uv(2) frame s,t,n(9) n_geo,dpdu,dpdv(9) -> applied, the perturbed frame(9)
+void orc_sample_normal_map_n(const ctl_scene_desc* desc, const ctl_material* mats, uint32_t n, const float* q, uint32_t qs, float* out, uint32_t os) {
+    for (uint32_t i = 0; i < n; i++) {
+        const float* a = q + (size_t)i * qs; float* o = out + (size_t)i * os;
+        DG dg; dg.uv = V2{ a[1], a[2] }; dg.images = desc ? desc->images : nullptr;
+        dg.sys = Frame(V3(a[3], a[4], a[5]), V3(a[6], a[7], a[8]), V3(a[9], a[10], a[11]));
+        dg.n = V3(a[12], a[13], a[14]); dg.dpdu = V3(a[15], a[16], a[17]); dg.dpdv = V3(a[18], a[19], a[20]);
+        o[0] = sampleNormalMap(mats[rowWord(a[0])], dg) ? 1.0f : 0.0f;
+        put3(o + 1, dg.sys.s); put3(o + 4, dg.sys.t); put3(o + 7, dg.sys.n);
+    }
+}
+// uv(2) per query -> Material::AlphaTest
+void orc_alpha_test_n(const ctl_scene_desc* desc, const ctl_material* mat, uint32_t n, const float* uv, int32_t* out) {
+    for (uint32_t i = 0; i < n; i++) out[i] = materialAlphaTest(*mat, V2{ uv[2 * i], uv[2 * i + 1] }, desc ? desc->images : nullptr) ? 1 : 0;
+}
+
 // ---- full render: pathKernel2<DIRECT,false> looped over all pixels (Integrators/PathTracer.cu:182-194) ---------
 // samples per 64x64 block for the following orc_render calls (a block sampler's decision for one pass); NULL = one sample everywhere
 static const uint8_t* g_block_counts = nullptr; static uint32_t g_blocks_x = 0;
