@@ -732,6 +732,14 @@ def scene_desc_diff(a, b):
     return mask.value
 
 
+def scene_desc_check(desc, parts=0):
+    """ctl_scene_desc_check (host only): raises CtlError(ERR_INVALID) with the message ctl_scene_create (parts == 0) or ctl_scene_update (parts = the DIFF_* bits it would
+    find) refuses `desc` with; returns dict(features, models, alpha_maps), the shade-kernel selection of the description"""
+    state = (u32 * 3)()
+    _check(lib.ctl_scene_desc_check(C.byref(desc), u32(parts), state))
+    return {"features": state[0], "models": state[1], "alpha_maps": state[2]}
+
+
 # ---- ctl_shading_eval (TEST INFRASTRUCTURE): the device BSDF / emitter / texture functions one call per query (include/ctl_amd.h CTL_EVAL_*)
 EVAL_BUILD_BASIC, EVAL_BUILD_FULL, EVAL_BUILD_PARTIALS = 0, 1, 2
 (EVAL_BSDF_SAMPLE, EVAL_BSDF_EVAL, EVAL_BSDF_SAMPLE_EVAL, EVAL_LIGHT_SAMPLE, EVAL_EMITTER_SAMPLE, EVAL_LIGHT_PDF, EVAL_LIGHT_EVAL, EVAL_ENV_EVAL, EVAL_TEXTURE, EVAL_MIP,

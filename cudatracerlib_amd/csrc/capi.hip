@@ -5,6 +5,7 @@
 #include "prim_tracer.h"
 #include "kernels.h"
 #include "scene_builder.h"
+#include "scene_checks.h"
 #include "mitsuba_loader.h"
 #include "flatten.h"
 #include "material_factory.h"
@@ -161,32 +162,29 @@ struct eval_check {
     bool material(uint32_t mi, bool nested) {
         if (mi >= mats.size()) return refuse(CTL_ERR_INVALID, std::string(nested ? "nested " : "") + "material index " + std::to_string(mi) + " of " + std::to_string(mats.size()));
         const ctl_material& M = mats[mi]; const uint32_t t = M.bsdf_type;
-        const bool nesting = t == CTL_BSDF_COATING || t == CTL_BSDF_ROUGHCOATING || t == CTL_BSDF_BLEND;
-        const bool simple = t == CTL_BSDF_DIFFUSE || t == CTL_BSDF_DIELECTRIC || t == CTL_BSDF_THINDIELECTRIC || t == CTL_BSDF_ROUGHDIELECTRIC || t == CTL_BSDF_CONDUCTOR || t == CTL_BSDF_ROUGHCONDUCTOR ||
-                            t == CTL_BSDF_PLASTIC || t == CTL_BSDF_PHONG || t == CTL_BSDF_ROUGHDIFFUSE || t == CTL_BSDF_WARD || t == CTL_BSDF_ROUGHPLASTIC;
-        if (!simple && !nesting) return refuse(CTL_ERR_INVALID, "unknown bsdf_type " + std::to_string(t));
-        if (nested && nesting) return refuse(CTL_ERR_INVALID, "a nested material is itself a nesting model");
-        if (build == 0) {
-            if (t != CTL_BSDF_DIFFUSE && t != CTL_BSDF_DIELECTRIC && t != CTL_BSDF_CONDUCTOR && t != CTL_BSDF_ROUGHCONDUCTOR) return refuse(CTL_ERR_UNSUPPORTED, "the basic build does not carry bsdf_type " + std::to_string(t));
-            if (t == CTL_BSDF_ROUGHCONDUCTOR && (M.u[0] == CTL_MF_PHONG || (M.u[0] == CTL_MF_BECKMANN && M.u[1]))) return refuse(CTL_ERR_UNSUPPORTED, "the basic build carries neither the Phong distribution nor Beckmann visible-normal sampling");
+        if (!is_simple_bsdf(t) && !is_nesting_bsdf(t)) return refuse(CTL_ERR_INVALID, "unknown bsdf_type " + std::to_string(t));
+        if (nested && is_nesting_bsdf(t)) return refuse(CTL_ERR_INVALID, "a nested material is itself a nesting model");
+        if (build == 0) {   // what the scene's shade kernel would need the full build for (device_scene.h).  A BSDF query does not read the surface map: kEvalNormalMap judges it
+            const uint32_t f = bsdf_shade_features(M);
+            if (f & (kShadeMoreBsdfs | kShadeRoughBsdfs | kShadeNestingBsdfs)) return refuse(CTL_ERR_UNSUPPORTED, "the basic build does not carry bsdf_type " + std::to_string(t));
+            if (f & kShadeMoreMicrofacet) return refuse(CTL_ERR_UNSUPPORTED, "the basic build carries neither the Phong distribution nor Beckmann visible-normal sampling");
         }
-        if (t == CTL_BSDF_ROUGHCONDUCTOR || t == CTL_BSDF_ROUGHDIELECTRIC || t == CTL_BSDF_ROUGHCOATING) { if (M.u[0] > CTL_MF_PHONG) return refuse(CTL_ERR_INVALID, "unknown microfacet distribution"); }
-        if (t == CTL_BSDF_ROUGHPLASTIC || t == CTL_BSDF_ROUGHCOATING) {
-            const uint32_t slot = t == CTL_BSDF_ROUGHPLASTIC ? M.u[2] : M.u[0];
-            if (slot > 2 || !tables[slot]) return refuse(CTL_ERR_INVALID, "a rough BSDF without its transmittance table (slot " + std::to_string(slot) + ")");
-            if (M.reserved_[0] && (override_mats || !have_reduced)) return refuse(CTL_ERR_INVALID, "a material that names a reduced transmittance table the call does not have");
+        if (const uint32_t* dist = bsdf_distribution(M)) {
+            if (*dist > CTL_MF_PHONG) return refuse(CTL_ERR_INVALID, "unknown microfacet distribution");
+            if (bsdf_reads_rough_transmittance(t)) {
+                if (!tables[*dist]) return refuse(CTL_ERR_INVALID, "a rough BSDF without its transmittance table (slot " + std::to_string(*dist) + ")");
+                if (M.reserved_[0] && (override_mats || !have_reduced)) return refuse(CTL_ERR_INVALID, "a material that names a reduced transmittance table the call does not have");
+            }
         }
         for (int k = 0; k < 4; k++) if (!texture(M.tex[k])) return false;
-        if (t == CTL_BSDF_COATING || t == CTL_BSDF_ROUGHCOATING) return material(M.u[2], true);
-        if (t == CTL_BSDF_BLEND) return material(M.u[2], true) && material(M.u[3], true);
+        for (int k = 0; k < nested_bsdf_count(t); k++) if (!material(M.u[2 + k], true)) return false;
         return true;
     }
     bool light(uint32_t li) {
         if (li >= lights.size()) return refuse(CTL_ERR_INVALID, "light index " + std::to_string(li) + " of " + std::to_string(lights.size()));
         const ctl_light& L = lights[li];
         if (L.type < CTL_LIGHT_POINT || L.type > CTL_LIGHT_INFINITE) return refuse(CTL_ERR_INVALID, "unknown light type");
-        const bool more = (L.type != CTL_LIGHT_POINT && L.type != CTL_LIGHT_DIFFUSE) || (L.type == CTL_LIGHT_DIFFUSE && (L.orthogonal || L.rad_texture.type == CTL_TEX_CHECKER || L.rad_texture.type == CTL_TEX_IMAGE));
-        if (more && build == 0) return refuse(CTL_ERR_UNSUPPORTED, "the basic build carries point lights and plain area lights only");
+        if (build == 0 && (light_shade_features(L) & kShadeMoreLights)) return refuse(CTL_ERR_UNSUPPORTED, "the basic build carries point lights and plain area lights only");
         if (L.type == CTL_LIGHT_INFINITE && L.env_image >= n_images) return refuse(CTL_ERR_INVALID, "environment image index out of range");
         if (L.type == CTL_LIGHT_DIFFUSE && L.rad_texture.type == CTL_TEX_IMAGE && L.rad_texture.image != 0xffffffffu && L.rad_texture.image >= n_images) return refuse(CTL_ERR_INVALID, "image index of a light texture out of range");
         return true;
@@ -311,6 +309,15 @@ CTL_CATCH }
 void ctl_scene_destroy(ctl_scene* s) { delete s; }
 // ---- in-place updates (scene_update.hip)
 int ctl_scene_desc_diff(const ctl_scene_desc* a, const ctl_scene_desc* b, uint32_t* mask_out) { CTL_REQUIRE(a && b && mask_out, "null argument"); CTL_TRY *mask_out = scene_desc_diff(*a, *b); CTL_CATCH }
+int ctl_scene_desc_check(const ctl_scene_desc* desc, uint32_t parts, uint32_t state_out[3]) {
+    CTL_REQUIRE(desc, "null argument");
+    CTL_REQUIRE(!(parts & ~kCheckAllParts), "ctl_scene_desc_check: unknown CTL_DIFF_* bits");
+    CTL_TRY
+        if (!parts) parts = kCheckAllParts;
+        check_scene_desc(*desc, parts, (parts & CTL_DIFF_TOPOLOGY) ? "ctl_scene_create" : "ctl_scene_update");
+        if (state_out) { const shading_state s = derive_shading_state(*desc); state_out[0] = s.features; state_out[1] = s.models; state_out[2] = s.alpha_maps; }
+    CTL_CATCH
+}
 int ctl_scene_update(ctl_scene* scene, const ctl_scene_desc* new_desc, uint32_t* mask_out) {
     if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, "no HIP device: the MI355X path tracer has no CPU fallback");
     CTL_REQUIRE(scene && new_desc, "null argument");

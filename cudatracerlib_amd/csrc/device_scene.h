@@ -11,6 +11,53 @@ constexpr int kExitMarker = 0x76543211;   // traversal-stack marker: leave the c
 enum { kShadeMoreBsdfs = 1, kShadeRoughBsdfs = 2, kShadeImageTextures = 4, kShadeMoreLights = 8, kShadeNestingBsdfs = 16, kShadeSurfaceMaps = 32, kShadeMoreMicrofacet = 64 };
 constexpr int kStackSize = 96;            // two-level: top depth + bottom depth + markers; 4-wide flat tree: 3 * depth + 1 — both checked at upload
 
+// ---- which kShade* bits a description needs (host).  The BSDF models are listed here and nowhere else: creation, ctl_scene_update and ctl_shading_eval all ask these.
+inline bool is_simple_bsdf(uint32_t t) {
+    return t == CTL_BSDF_DIFFUSE || t == CTL_BSDF_DIELECTRIC || t == CTL_BSDF_THINDIELECTRIC || t == CTL_BSDF_ROUGHDIELECTRIC || t == CTL_BSDF_CONDUCTOR || t == CTL_BSDF_ROUGHCONDUCTOR ||
+           t == CTL_BSDF_PLASTIC || t == CTL_BSDF_PHONG || t == CTL_BSDF_ROUGHDIFFUSE || t == CTL_BSDF_WARD || t == CTL_BSDF_ROUGHPLASTIC;
+}
+inline int nested_bsdf_count(uint32_t t) { return t == CTL_BSDF_BLEND ? 2 : (t == CTL_BSDF_COATING || t == CTL_BSDF_ROUGHCOATING) ? 1 : 0; }   // nested material indices: u[2], u[3]
+inline bool is_nesting_bsdf(uint32_t t) { return nested_bsdf_count(t) != 0; }
+// the CTL_MF_* word of a microfacet model (roughplastic keeps it in u[2], where it is also the slot of its transmittance table), nullptr for every other model
+inline const uint32_t* bsdf_distribution(const ctl_material& m) {
+    const uint32_t t = m.bsdf_type;
+    if (t == CTL_BSDF_ROUGHPLASTIC) return &m.u[2];
+    return (t == CTL_BSDF_ROUGHCONDUCTOR || t == CTL_BSDF_ROUGHDIELECTRIC || t == CTL_BSDF_ROUGHCOATING) ? &m.u[0] : nullptr;
+}
+inline bool bsdf_reads_rough_transmittance(uint32_t t) { return t == CTL_BSDF_ROUGHPLASTIC || t == CTL_BSDF_ROUGHCOATING; }   // RoughTransmittanceManager's table of slot *bsdf_distribution()
+// the model, its microfacet settings and tex[0..3]: what a BSDF query of ctl_shading_eval evaluates
+inline uint32_t bsdf_shade_features(const ctl_material& m) {
+    const uint32_t t = m.bsdf_type;
+    uint32_t f = 0;
+    if (t == CTL_BSDF_THINDIELECTRIC || t == CTL_BSDF_ROUGHDIELECTRIC || t == CTL_BSDF_PLASTIC || t == CTL_BSDF_PHONG) f |= kShadeMoreBsdfs;
+    if (t == CTL_BSDF_ROUGHDIFFUSE || t == CTL_BSDF_WARD || t == CTL_BSDF_ROUGHPLASTIC) f |= kShadeRoughBsdfs;
+    if (is_nesting_bsdf(t)) f |= kShadeNestingBsdfs | kShadeMoreBsdfs | kShadeRoughBsdfs;
+    for (int k = 0; k < 4; k++) if (m.tex[k].type == CTL_TEX_IMAGE) f |= kShadeImageTextures;
+    // visible-normal sampling of the Beckmann distribution (erf / erfinv iteration) and the Phong distribution live in the full build only
+    if (const uint32_t* dist = bsdf_distribution(m)) if (*dist == CTL_MF_PHONG || (*dist == CTL_MF_BECKMANN && m.u[1])) f |= kShadeMoreMicrofacet;
+    return f;
+}
+inline uint32_t material_shade_features(const ctl_material& m) { return bsdf_shade_features(m) | (m.map_kind != CTL_MAP_NONE ? kShadeSurfaceMaps | kShadeImageTextures : 0u); }
+inline uint32_t light_shade_features(const ctl_light& L) {
+    if (L.type != CTL_LIGHT_POINT && L.type != CTL_LIGHT_DIFFUSE) return kShadeMoreLights;
+    if (L.type == CTL_LIGHT_DIFFUSE && (L.orthogonal || L.rad_texture.type == CTL_TEX_CHECKER || L.rad_texture.type == CTL_TEX_IMAGE))   // orthogonal / textured area lights live in the full build
+        return kShadeMoreLights | (L.rad_texture.type == CTL_TEX_IMAGE ? kShadeImageTextures : 0u);
+    return 0;
+}
+// which shade-kernel build a scene needs (kernels.hip launch_shade): the OR over its records.  Judges nothing: check_scene_desc (scene_checks.h) does, first.
+struct shading_state { uint32_t features, models, alpha_maps; };   // dev_scene::shade_features, shade_models, alpha_maps
+inline shading_state derive_shading_state(const ctl_scene_desc& d) noexcept {
+    shading_state s{ 0, 0, 0 };
+    for (uint32_t i = 0; i < d.n_lights_buf; i++) s.features |= light_shade_features(d.lights[i]);
+    for (uint32_t i = 0; i < d.n_materials; i++) {
+        const ctl_material& m = d.materials[i];
+        s.features |= material_shade_features(m);
+        s.models |= 1u << (m.bsdf_type & 15u);
+        if (m.alpha_state != CTL_ALPHA_DISABLED) s.alpha_maps = 1;
+    }
+    return s;
+}
+
 // precomputed PerspectiveSensor state (SceneTypes/Sensor.cu:76-96)
 struct dev_sensor {
     float s2c[16];        // m_sampleToCamera, row-major 4x4 (projective: TransformPoint divides by w)

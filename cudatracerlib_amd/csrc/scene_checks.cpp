@@ -1,0 +1,115 @@
+// scene_checks.cpp — check_scene_desc / check_traversal_stack (scene_checks.h): host arithmetic over a description, nothing else.
+#include "scene_checks.h"
+#include "device_scene.h"   // kStackSize and the BSDF model classifiers
+#include <algorithm>
+#include <stdexcept>
+#include <string>
+#include <utility>
+#include <vector>
+
+namespace ctl {
+namespace {
+
+[[noreturn]] void refuse(const char* who, const std::string& what) { throw std::runtime_error(std::string(who) + ": " + what); }
+
+// depth of a BVH in the reference's node layout (child >= 0: float4 index of an inner node)
+int depth_of(const ctl_bvh_node* nodes, size_t n_nodes, int root, bool strict, const char* who) {
+    int best = 0; std::vector<std::pair<int, int>> st;
+    auto inside = [&](int link) { return (size_t)(link / 4) < n_nodes && !(strict && (link & 3)); };
+    if (root >= 0) { if (inside(root)) st.emplace_back(root / 4, 1); else if (strict) refuse(who, "scene BVH start node outside the array"); }
+    while (!st.empty()) {
+        const auto [i, dpt] = st.back(); st.pop_back();
+        best = std::max(best, dpt);
+        if (dpt > 4 * kStackSize) refuse(who, "BVH child links form a cycle");
+        for (int c : { nodes[i].child0, nodes[i].child1 }) {
+            if (c < 0 || c == 0x76543210) continue;
+            if (inside(c)) st.emplace_back(c / 4, dpt + 1);
+            else if (strict) refuse(who, "scene BVH child link outside the array");
+        }
+    }
+    return best;
+}
+
+void check_nodes(const ctl_scene_desc& d, uint32_t parts, const char* who) {
+    for (uint32_t k = 0; k < d.n_nodes; k++) {
+        if (parts & CTL_DIFF_TRANSFORMS) {
+            const float* im = d.node_inv_transforms[k].m; const float* fm = d.node_transforms[k].m;
+            if (im[12] != 0.0f || im[13] != 0.0f || im[14] != 0.0f || fm[12] != 0.0f || fm[13] != 0.0f || fm[14] != 0.0f) refuse(who, "node transforms must be affine");
+        }
+        if ((parts & CTL_DIFF_TOPOLOGY) && d.nodes[k].mesh_index >= d.n_meshes) refuse(who, "node references a missing mesh");
+    }
+}
+
+void check_lights(const ctl_scene_desc& d, const char* who) {
+    for (uint32_t i = 0; i < d.n_lights_buf; i++) {
+        const ctl_light& L = d.lights[i];
+        if (L.type < CTL_LIGHT_POINT || L.type > CTL_LIGHT_INFINITE) refuse(who, "unknown light type " + std::to_string(L.type));
+        if (L.type == CTL_LIGHT_DIFFUSE && L.rad_texture.type == CTL_TEX_IMAGE && L.rad_texture.image != 0xffffffffu && L.rad_texture.image >= d.n_images) refuse(who, "light texture references a missing image");
+        if (L.type == CTL_LIGHT_INFINITE && L.env_image >= d.n_images) refuse(who, "InfiniteLight references a missing image");
+    }
+}
+
+void check_materials(const ctl_scene_desc& d, const char* who) {
+    auto table = [&](uint32_t slot) -> const ctl_rough_transmittance* { return d.rough_transmittance ? &d.rough_transmittance[slot] : nullptr; };
+    for (uint32_t i = 0; i < d.n_materials; i++) {
+        const ctl_material& mi = d.materials[i];
+        if (mi.map_kind > CTL_MAP_HEIGHT) refuse(who, "unknown surface map kind");
+        if (mi.alpha_state > CTL_ALPHA_REFLECTANCE_COLOR || mi.alpha_state == 4) refuse(who, "unknown alpha blend state");
+        for (int k = 0; k < 6; k++) {   // the map and the alpha texture count only where they are read
+            if (k == 4 && mi.map_kind == CTL_MAP_NONE) continue;
+            if (k == 5 && mi.alpha_state == CTL_ALPHA_DISABLED) continue;
+            const ctl_texture& t = k < 4 ? mi.tex[k] : (k == 4 ? mi.map_tex : mi.alpha_tex);
+            if (t.type == CTL_TEX_IMAGE && t.image != 0xffffffffu && t.image >= d.n_images) refuse(who, "texture references a missing image");
+            if (t.type != CTL_TEX_CONSTANT && t.type != CTL_TEX_CHECKER && t.type != CTL_TEX_IMAGE && t.type != 0) refuse(who, "texture type " + std::to_string(t.type) + " has no HIP implementation yet");
+        }
+        const uint32_t t = mi.bsdf_type;
+        for (int k = 0; k < nested_bsdf_count(t); k++) {
+            const uint32_t ni = mi.u[2 + k];
+            if (ni >= d.n_materials || d.materials[ni].bsdf_type >= CTL_BSDF_HK) refuse(who, "nested BSDF index out of range or not a simple BSDF (BSDFFirst)");
+        }
+        if (const uint32_t* dist = bsdf_distribution(mi)) {
+            const ctl_rough_transmittance* T = *dist <= CTL_MF_PHONG ? table(*dist) : nullptr;
+            if (t == CTL_BSDF_ROUGHCOATING) {
+                if (!T || !T->trans) refuse(who, "roughcoating needs the rough-transmittance table of its distribution");
+            } else {
+                if (*dist > CTL_MF_PHONG) refuse(who, "unknown microfacet distribution");
+                if (t == CTL_BSDF_ROUGHPLASTIC && (!T || !T->trans || !T->diff_trans)) refuse(who, "roughplastic needs the rough-transmittance table of its distribution (ctl_builder_set_rough_transmittance)");
+            }
+        }
+        if (!is_simple_bsdf(t) && !is_nesting_bsdf(t)) refuse(who, "BSDF type " + std::to_string(t) + " has no HIP implementation yet");
+    }
+}
+
+}  // namespace
+
+void check_traversal_stack(const ctl_scene_desc& d, bool strict_top_level, const char* who) {
+    if (strict_top_level) {
+        if (d.scene_start_node < 0 && (uint32_t)~d.scene_start_node >= d.n_nodes) refuse(who, "scene BVH start node names a missing node");
+        for (uint32_t i = 0; i < d.n_scene_bvh_nodes; i++)
+            for (int c : { d.scene_bvh_nodes[i].child0, d.scene_bvh_nodes[i].child1 }) if (c < 0 && (uint32_t)~c >= d.n_nodes) refuse(who, "scene BVH leaf names a missing node");
+    }
+    const int top = d.scene_start_node >= 0 ? depth_of(d.scene_bvh_nodes, d.n_scene_bvh_nodes, d.scene_start_node, strict_top_level, who) : 0;
+    int bottom = 0;
+    for (uint32_t m = 0; m < d.n_meshes; m++) {
+        const uint32_t first = d.meshes[m].bvh_node_offset / 4;
+        if (first < d.n_bvh_nodes) bottom = std::max(bottom, depth_of(d.bvh_nodes + first, d.n_bvh_nodes - first, 0, false, who));
+    }
+    if (top + bottom + 3 > kStackSize)
+        refuse(who, "scene BVH depth " + std::to_string(top) + " + mesh BVH depth " + std::to_string(bottom) + " does not fit the traversal stack of " + std::to_string(kStackSize) + " entries" +
+                    (strict_top_level ? "" : " (rebuild the meshes with CTL_BVH_BINNED, whose depth is bounded)"));   // (a hint for whoever builds the meshes: an update cannot)
+}
+
+void check_scene_desc(const ctl_scene_desc& d, uint32_t parts, const char* who) {
+    const bool creating = (parts & CTL_DIFF_TOPOLOGY) != 0;
+    if (creating && !d.n_nodes) refuse(who, "scene has no nodes");
+    if ((parts & CTL_DIFF_LIGHTS) && d.env_map_index != 0xffffffffu && (d.env_map_index >= d.n_lights_buf || d.lights[d.env_map_index].type != CTL_LIGHT_INFINITE))
+        refuse(who, "env_map_index does not name an InfiniteLight");
+    if (parts & (CTL_DIFF_TRANSFORMS | CTL_DIFF_TOPOLOGY)) check_nodes(d, parts, who);
+    if (parts & CTL_DIFF_LIGHTS) check_lights(d, who);
+    if (parts & CTL_DIFF_MATERIALS) check_materials(d, who);
+    if (parts & (CTL_DIFF_TRANSFORMS | CTL_DIFF_TOPOLOGY)) check_traversal_stack(d, !creating, who);
+    if ((parts & CTL_DIFF_CAMERA) && (d.camera.type < CTL_SENSOR_SPHERICAL || d.camera.type > CTL_SENSOR_TELECENTRIC))
+        refuse(who, creating ? "unknown sensor type " + std::to_string(d.camera.type) : std::string("unknown sensor type"));   // (creation has always named the value, an update never has)
+}
+
+}  // namespace ctl

@@ -5,6 +5,7 @@
 #include "tracer.h"
 #include "flatten.h"
 #include "flat_refit.h"
+#include "scene_checks.h"
 #include "scene_cache.h"
 #include "mitsuba_loader.h"   // unsupported_error
 #include <cstring>
@@ -65,38 +66,6 @@ uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const
 }
 
 Scene::~Scene() {}
-
-// The two-level traversal keeps (scene-BVH depth + exit marker + mesh-BVH depth) entries on its per-lane stack of kStackSize.  A transform change brings a new scene
-// BVH, so an update repeats the check the constructor makes on the description (tracer.hip): child links that stay inside the array and form no cycle, and a depth
-// that fits next to the deepest mesh BVH — before anything is uploaded.  The mesh BVHs are those of creation (the geometry hash matched), read from `d`.
-static void check_traversal_stack(const ctl_scene_desc& d) {
-    auto depth_of = [](const ctl_bvh_node* nodes, size_t n_nodes, int root, bool strict) {
-        int best = 0; std::vector<std::pair<int, int>> st;
-        if (root >= 0) { if ((root & 3) || (size_t)(root / 4) >= n_nodes) throw std::runtime_error("ctl_scene_update: scene BVH start node outside the array"); st.emplace_back(root / 4, 1); }
-        while (!st.empty()) {
-            const std::pair<int, int> top = st.back(); st.pop_back();
-            best = std::max(best, top.second);
-            if (top.second > 4 * kStackSize) throw std::runtime_error("ctl_scene_update: BVH child links form a cycle");
-            for (int c : { nodes[top.first].child0, nodes[top.first].child1 }) {
-                if (c < 0 || c == 0x76543210) continue;
-                if ((size_t)(c / 4) < n_nodes && !(c & 3)) st.emplace_back(c / 4, top.second + 1);
-                else if (strict) throw std::runtime_error("ctl_scene_update: scene BVH child link outside the array");
-            }
-        }
-        return best;
-    };
-    if (d.scene_start_node < 0 && (uint32_t)~d.scene_start_node >= d.n_nodes) throw std::runtime_error("ctl_scene_update: scene BVH start node names a missing node");
-    for (uint32_t i = 0; i < d.n_scene_bvh_nodes; i++)
-        for (int c : { d.scene_bvh_nodes[i].child0, d.scene_bvh_nodes[i].child1 }) if (c < 0 && (uint32_t)~c >= d.n_nodes) throw std::runtime_error("ctl_scene_update: scene BVH leaf names a missing node");
-    const int top = d.scene_start_node >= 0 ? depth_of(d.scene_bvh_nodes, d.n_scene_bvh_nodes, d.scene_start_node, true) : 0;
-    int bottom = 0;
-    for (uint32_t m = 0; m < d.n_meshes; m++) {
-        const uint32_t first = d.meshes[m].bvh_node_offset / 4;
-        if (first < d.n_bvh_nodes) bottom = std::max(bottom, depth_of(d.bvh_nodes + first, d.n_bvh_nodes - first, 0, false));
-    }
-    if (top + bottom + 3 > kStackSize)
-        throw std::runtime_error("ctl_scene_update: scene BVH depth " + std::to_string(top) + " + mesh BVH depth " + std::to_string(bottom) + " does not fit the traversal stack of " + std::to_string(kStackSize) + " entries");
-}
 
 void Scene::snapshot(const ctl_scene_desc& d) {
     std::unique_ptr<desc_snapshot> s(new desc_snapshot());
@@ -160,35 +129,26 @@ uint32_t Scene::update(const ctl_scene_desc& d, ctl_scene_update_stats* stats) {
     const bool refit = (mask & CTL_DIFF_TRANSFORMS) && flattened();
     if (refit && S.flat_format != kFlatQ4) throw unsupported_error("ctl_scene_update: the Q8 node format is not refitted; a transform change needs a scene in the default format (or a new scene)");
     if (refit && refit_.level_start.size() < 2) throw unsupported_error("ctl_scene_update: the flattened tree carries no refit data");
-    if (d.env_map_index != 0xffffffffu && (d.env_map_index >= d.n_lights_buf || d.lights[d.env_map_index].type != CTL_LIGHT_INFINITE))
-        throw std::runtime_error("ctl_scene_update: env_map_index does not name an InfiniteLight");
+    // Everything that can refuse the new description runs before anything is written, and before a tracer is stalled.  A transform change brings a new scene BVH: its
+    // links must stay inside the array (creation is more lenient there, scene_checks.h) and its depth fit next to the mesh BVHs of creation (the geometry hash matched)
+    check_scene_desc(d, mask, "ctl_scene_update");
     ctl_scene_update_stats st{}; st.mask = mask;
-    // Everything that can refuse the new description runs before anything is written: the checks of materials and lights (they work on S's feature words only,
-    // which are restored when they throw), the traversal-stack check of a new scene BVH, affine transforms, the sensor type
-    const dev_scene before = S;
-    if (mask & (CTL_DIFF_MATERIALS | CTL_DIFF_LIGHTS)) { try { derive_shading_state(d); } catch (...) { S = before; throw; } }
-    if (mask & CTL_DIFF_TRANSFORMS) {
-        try { check_traversal_stack(d); } catch (...) { S = before; throw; }
-        for (uint32_t k = 0; k < d.n_nodes; k++) {
-            const float* im = d.node_inv_transforms[k].m; const float* fm = d.node_transforms[k].m;
-            if (im[12] != 0.0f || im[13] != 0.0f || im[14] != 0.0f || fm[12] != 0.0f || fm[13] != 0.0f || fm[14] != 0.0f) { S = before; throw std::runtime_error("ctl_scene_update: node transforms must be affine"); }
-        }
-    }
-    if ((mask & CTL_DIFF_CAMERA) && (d.camera.type < CTL_SENSOR_SPHERICAL || d.camera.type > CTL_SENSOR_TELECENTRIC)) { S = before; throw std::runtime_error("ctl_scene_update: unknown sensor type"); }
     CTL_HIP(hipDeviceSynchronize());   // no trace reads the arrays any more
+    const uint32_t had_alpha_maps = S.alpha_maps;
+    if (mask & (CTL_DIFF_MATERIALS | CTL_DIFF_LIGHTS)) set_shading_state(derive_shading_state(d));
     bool restamp = false;
     if (mask & CTL_DIFF_MATERIALS) {
         upload_materials(d);
         // the entries of a flattened scene carry their material's BSDF model and "has an alpha map": re-stamped on the device where either changed
         if (flattened() && d.n_materials) {
             for (uint32_t i = 0; i < d.n_materials; i++) if (d.materials[i].bsdf_type != snap_->materials[i].bsdf_type || d.materials[i].alpha_state != snap_->materials[i].alpha_state) restamp = true;
-            if (before.alpha_maps != S.alpha_maps) restamp = true;
+            if (had_alpha_maps != S.alpha_maps) restamp = true;
         }
     }
     if (mask & CTL_DIFF_LIGHTS) { upload_lights(d); if (!(mask & CTL_DIFF_TRANSFORMS)) upload_instances(d); }   // node_info carries the nodes' light slots
     if (mask & CTL_DIFF_TRANSFORMS) {
         upload_top_level(d); upload_instances(d);
-        if (flattened()) { S.inst_w_one = 1; for (uint32_t k = 0; k < d.n_nodes; k++) if (d.node_inv_transforms[k].m[15] != 1.0f) S.inst_w_one = 0; }
+        if (flattened()) S.inst_w_one = inverse_transforms_have_w_one(d);
     }
     CTL_HIP(hipDeviceSynchronize());
     bind(d);

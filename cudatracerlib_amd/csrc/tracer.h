@@ -44,6 +44,9 @@ struct desc_snapshot {
     uint64_t geometry_hash[2] = { 0, 0 };
 };
 
+// dev_scene::inst_w_one of a flattened scene: every node transform affine with w == 1 exactly (what add_node produces), so the kernels skip the load of w and the division by it
+inline int inverse_transforms_have_w_one(const ctl_scene_desc& d) { for (uint32_t k = 0; k < d.n_nodes; k++) if (d.node_inv_transforms[k].m[15] != 1.0f) return 0; return 1; }
+
 // KernelDynamicScene in HBM (UpdateKernel, Kernel/TraceHelper.cu:182-217)
 class Scene {
 public:
@@ -63,12 +66,13 @@ public:
     float box_min[3] = { 0, 0, 0 }, box_max[3] = { 0, 0, 0 };   // KernelDynamicScene::m_sBox
     float near_depth = 0, far_depth = 0;                        // SensorBase::m_fNearFarDepths of the scene's camera (DeviceDepthImage::NormalizeDepthD3D)
 private:
-    // the upload, block by block: the constructor runs all of them, update() those whose part of the description changed
+    // the upload, block by block: the constructor runs all of them, update() those whose part of the description changed.  None of them judges the description:
+    // check_scene_desc (scene_checks.h) has, before the first of them runs
     void upload_top_level(const ctl_scene_desc& d);
     void upload_instances(const ctl_scene_desc& d);
     void upload_lights(const ctl_scene_desc& d);
     void upload_materials(const ctl_scene_desc& d);
-    void derive_shading_state(const ctl_scene_desc& d);   // shade_features / shade_models / alpha_maps + the checks of materials and lights
+    void set_shading_state(const shading_state& s) { S.shade_features = s.features; S.shade_models = s.models; S.alpha_maps = s.alpha_maps; }   // derive_shading_state (device_scene.h)
     void bind(const ctl_scene_desc& d);                   // device pointers and the scalars of the description into S
     void set_camera(const ctl_scene_desc& d);
     void snapshot(const ctl_scene_desc& d);               // host copy of the description an update diffs against (the geometry arrays as a hash)

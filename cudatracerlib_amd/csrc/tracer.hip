@@ -3,6 +3,7 @@
 // no host synchronisation inside a pass — queue lengths stay on the device).
 #include "tracer.h"
 #include "scene_builder.h"
+#include "scene_checks.h"
 #include "flatten.h"
 #include "image_io.h"
 #include "mitsuba_loader.h"   // unsupported_error
@@ -40,10 +41,7 @@ void Scene::upload_instances(const ctl_scene_desc& d) {
     std::vector<uint4> ninfo(d.n_nodes);
     for (uint32_t k = 0; k < d.n_nodes; k++) {
         const float* im = d.node_inv_transforms[k].m; const float* fm = d.node_transforms[k].m;
-        if (im[12] != 0.0f || im[13] != 0.0f || im[14] != 0.0f || fm[12] != 0.0f || fm[13] != 0.0f || fm[14] != 0.0f)
-            throw std::runtime_error("ctl_scene_create: node transforms must be affine");
-        const ctl_node& N = d.nodes[k];
-        if (N.mesh_index >= d.n_meshes) throw std::runtime_error("ctl_scene_create: node references a missing mesh");
+        const ctl_node& N = d.nodes[k];   // (affine transforms, an existing mesh: check_scene_desc)
         const ctl_kernel_mesh& km = d.meshes[N.mesh_index];
         for (int r = 0; r < 3; r++) { inst[k * 4 + r] = make_float4(im[r * 4], im[r * 4 + 1], im[r * 4 + 2], im[r * 4 + 3]); fwd[k * 3 + r] = make_float4(fm[r * 4], fm[r * 4 + 1], fm[r * 4 + 2], fm[r * 4 + 3]); }
         inst[k * 4 + 3] = make_float4(im[15], __builtin_bit_cast(float, km.bvh_node_offset), __builtin_bit_cast(float, km.bvh_tri_offset / 3), __builtin_bit_cast(float, km.tri_offset));
@@ -116,74 +114,6 @@ void Scene::upload_materials(const ctl_scene_desc& d) {
     }
     mats_.upload(dmats.data(), dmats.size());
 }
-void Scene::derive_shading_state(const ctl_scene_desc& d) {
-    // which shade-kernel build this scene needs (kernels.hip launch_shade)
-    S.shade_features = 0; S.alpha_maps = 0; S.shade_models = 0;
-    for (uint32_t i = 0; i < d.n_lights_buf; i++) if (d.lights[i].type != CTL_LIGHT_POINT && d.lights[i].type != CTL_LIGHT_DIFFUSE) S.shade_features |= kShadeMoreLights;
-    for (uint32_t i = 0; i < d.n_materials; i++) {
-        const uint32_t t = d.materials[i].bsdf_type;
-        S.shade_models |= 1u << (t & 15u);
-        if (t == CTL_BSDF_THINDIELECTRIC || t == CTL_BSDF_ROUGHDIELECTRIC || t == CTL_BSDF_PLASTIC || t == CTL_BSDF_PHONG) S.shade_features |= kShadeMoreBsdfs;
-        if (t == CTL_BSDF_ROUGHDIFFUSE || t == CTL_BSDF_WARD || t == CTL_BSDF_ROUGHPLASTIC) S.shade_features |= kShadeRoughBsdfs;
-        if (t == CTL_BSDF_COATING || t == CTL_BSDF_ROUGHCOATING || t == CTL_BSDF_BLEND) S.shade_features |= kShadeNestingBsdfs | kShadeMoreBsdfs | kShadeRoughBsdfs;
-        for (int k = 0; k < 4; k++) if (d.materials[i].tex[k].type == CTL_TEX_IMAGE) S.shade_features |= kShadeImageTextures;
-        if (d.materials[i].map_kind != CTL_MAP_NONE) S.shade_features |= kShadeSurfaceMaps | kShadeImageTextures;
-        if (d.materials[i].alpha_state != CTL_ALPHA_DISABLED) S.alpha_maps = 1;
-        // visible-normal sampling of the Beckmann distribution (erf / erfinv iteration) and the Phong distribution live in the full build only
-        if (t == CTL_BSDF_ROUGHCONDUCTOR || t == CTL_BSDF_ROUGHDIELECTRIC || t == CTL_BSDF_ROUGHPLASTIC || t == CTL_BSDF_ROUGHCOATING) {
-            const uint32_t dist = t == CTL_BSDF_ROUGHPLASTIC ? d.materials[i].u[2] : d.materials[i].u[0], vis = d.materials[i].u[1];
-            if (dist == CTL_MF_PHONG || (dist == CTL_MF_BECKMANN && vis)) S.shade_features |= kShadeMoreMicrofacet;
-        }
-    }
-    for (uint32_t i = 0; i < d.n_lights_buf; i++) {
-        const ctl_light& L = d.lights[i];
-        if (L.type < CTL_LIGHT_POINT || L.type > CTL_LIGHT_INFINITE) throw std::runtime_error("ctl_scene_create: unknown light type " + std::to_string(L.type));
-        if (L.type == CTL_LIGHT_DIFFUSE && (L.orthogonal || L.rad_texture.type == CTL_TEX_CHECKER || L.rad_texture.type == CTL_TEX_IMAGE)) {
-            S.shade_features |= kShadeMoreLights;   // orthogonal / textured area lights live in the full build
-            if (L.rad_texture.type == CTL_TEX_IMAGE) {
-                if (L.rad_texture.image != 0xffffffffu && L.rad_texture.image >= d.n_images) throw std::runtime_error("ctl_scene_create: light texture references a missing image");
-                S.shade_features |= kShadeImageTextures;
-            }
-        }
-        if (L.type == CTL_LIGHT_INFINITE && L.env_image >= d.n_images) throw std::runtime_error("ctl_scene_create: InfiniteLight references a missing image");
-    }
-    for (uint32_t i = 0; i < d.n_materials; i++) {
-        const ctl_material& mi = d.materials[i];
-        if (mi.map_kind > CTL_MAP_HEIGHT) throw std::runtime_error("ctl_scene_create: unknown surface map kind");
-        if (mi.alpha_state > CTL_ALPHA_REFLECTANCE_COLOR || mi.alpha_state == 4) throw std::runtime_error("ctl_scene_create: unknown alpha blend state");
-        for (int k = 0; k < 6; k++) {
-            if (k == 4 && mi.map_kind == CTL_MAP_NONE) continue;
-            if (k == 5 && mi.alpha_state == CTL_ALPHA_DISABLED) continue;
-            const ctl_texture& t = k < 4 ? mi.tex[k] : (k == 4 ? mi.map_tex : mi.alpha_tex);
-            if (t.type == CTL_TEX_IMAGE && t.image != 0xffffffffu && t.image >= d.n_images) throw std::runtime_error("ctl_scene_create: texture references a missing image");
-            if (t.type != CTL_TEX_CONSTANT && t.type != CTL_TEX_CHECKER && t.type != CTL_TEX_IMAGE && t.type != 0) throw std::runtime_error("ctl_scene_create: texture type " + std::to_string(t.type) + " has no HIP implementation yet");
-        }
-        const uint32_t t = d.materials[i].bsdf_type;
-        const bool ok = t == CTL_BSDF_DIFFUSE || t == CTL_BSDF_DIELECTRIC || t == CTL_BSDF_THINDIELECTRIC || t == CTL_BSDF_ROUGHDIELECTRIC || t == CTL_BSDF_CONDUCTOR ||
-                        t == CTL_BSDF_ROUGHCONDUCTOR || t == CTL_BSDF_PLASTIC || t == CTL_BSDF_PHONG || t == CTL_BSDF_ROUGHDIFFUSE || t == CTL_BSDF_WARD || t == CTL_BSDF_ROUGHPLASTIC ||
-                        t == CTL_BSDF_COATING || t == CTL_BSDF_ROUGHCOATING || t == CTL_BSDF_BLEND;
-        if (t == CTL_BSDF_COATING || t == CTL_BSDF_ROUGHCOATING || t == CTL_BSDF_BLEND) {
-            for (int k = 0; k < (t == CTL_BSDF_BLEND ? 2 : 1); k++) {
-                const uint32_t ni = d.materials[i].u[2 + k];
-                if (ni >= d.n_materials || d.materials[ni].bsdf_type >= CTL_BSDF_HK) throw std::runtime_error("ctl_scene_create: nested BSDF index out of range or not a simple BSDF (BSDFFirst)");
-            }
-            if (t == CTL_BSDF_ROUGHCOATING) {
-                const uint32_t slot = d.materials[i].u[0];
-                if (slot > CTL_MF_PHONG || !d.rough_transmittance || !d.rough_transmittance[slot].trans) throw std::runtime_error("ctl_scene_create: roughcoating needs the rough-transmittance table of its distribution");
-            }
-        }
-        if (t == CTL_BSDF_ROUGHPLASTIC) {
-            const uint32_t slot = d.materials[i].u[2];
-            if (slot > CTL_MF_PHONG) throw std::runtime_error("ctl_scene_create: unknown microfacet distribution");
-            if (!d.rough_transmittance || !d.rough_transmittance[slot].trans || !d.rough_transmittance[slot].diff_trans)
-                throw std::runtime_error("ctl_scene_create: roughplastic needs the rough-transmittance table of its distribution (ctl_builder_set_rough_transmittance)");
-        }
-        if ((t == CTL_BSDF_ROUGHCONDUCTOR || t == CTL_BSDF_ROUGHDIELECTRIC) && d.materials[i].u[0] > CTL_MF_PHONG)
-            throw std::runtime_error("ctl_scene_create: unknown microfacet distribution");
-        if (!ok)
-            throw std::runtime_error("ctl_scene_create: BSDF type " + std::to_string(t) + " has no HIP implementation yet");
-    }
-}
 void Scene::bind(const ctl_scene_desc& d) {
     for (int k = 0; k < 3; k++) { box_min[k] = d.box_min[k]; box_max[k] = d.box_max[k]; }
     S.top_nodes = top_nodes_.p; S.bot_nodes = bot_nodes_.p; S.leaf_tris = leaf_tris_.p; S.inst = inst_.p; S.inst_fwd = inst_fwd_.p; S.normal_lut = normal_lut_.p;
@@ -195,7 +125,6 @@ void Scene::set_camera(const ctl_scene_desc& d) {
     near_depth = d.camera.near_depth; far_depth = d.camera.far_depth;
     // PerspectiveSensor / ThinLensSensor / OrthographicSensor / TelecentricSensor ::Update (SceneTypes/Sensor.cu:76-96, :226-246, :408-427, :515-535)
     const ctl_sensor& c = d.camera;
-    if (c.type < CTL_SENSOR_SPHERICAL || c.type > CTL_SENSOR_TELECENTRIC) throw std::runtime_error("ctl_scene_create: unknown sensor type " + std::to_string(c.type));
     const bool ortho = c.type == CTL_SENSOR_ORTHOGRAPHIC || c.type == CTL_SENSOR_TELECENTRIC;
     const float aspect = c.resolution[0] / c.resolution[1];
     const float recip = 1.0f / (c.far_depth - c.near_depth), cot = 1.0f / tanf(c.fov / 2.0f);
@@ -226,9 +155,7 @@ void Scene::set_camera(const ctl_scene_desc& d) {
 
 Scene::Scene(const ctl_scene_desc& d, bool flatten, int flat_format, bool reduced_rough_transmittance) : reduced_rough_transmittance_(reduced_rough_transmittance) {
     require_device();
-    if (!d.n_nodes) throw std::runtime_error("ctl_scene_create: scene has no nodes");
-    if (d.env_map_index != 0xffffffffu && (d.env_map_index >= d.n_lights_buf || d.lights[d.env_map_index].type != CTL_LIGHT_INFINITE))
-        throw std::runtime_error("ctl_scene_create: env_map_index does not name an InfiniteLight");
+    check_scene_desc(d, kCheckAllParts, "ctl_scene_create");   // everything that can be judged from the description alone, before the first upload
     n_nodes = d.n_nodes;
     std::vector<float4> tmp;
     upload_top_level(d);
@@ -304,29 +231,7 @@ Scene::Scene(const ctl_scene_desc& d, bool flatten, int flat_format, bool reduce
         }
     }
     upload_materials(d);
-    derive_shading_state(d);
-    {   // the two-level traversal keeps (scene-BVH depth + exit marker + mesh-BVH depth) entries on its per-lane stack: check it fits
-        auto depth_of = [](const ctl_bvh_node* nodes, size_t n_nodes, int root) {   // child >= 0: float4 index of an inner node
-            int best = 0; std::vector<std::pair<int, int>> st;
-            if (root >= 0 && (size_t)(root / 4) < n_nodes) st.emplace_back(root / 4, 1);
-            while (!st.empty()) {
-                const auto [i, dpt] = st.back(); st.pop_back();
-                best = std::max(best, dpt);
-                if (dpt > 4 * kStackSize) throw std::runtime_error("ctl_scene_create: BVH child links form a cycle");
-                for (int c : { nodes[i].child0, nodes[i].child1 }) if (c >= 0 && c != 0x76543210 && (size_t)(c / 4) < n_nodes) st.emplace_back(c / 4, dpt + 1);
-            }
-            return best;
-        };
-        const int top = d.scene_start_node >= 0 ? depth_of(d.scene_bvh_nodes, d.n_scene_bvh_nodes, d.scene_start_node) : 0;
-        int bottom = 0;
-        for (uint32_t m = 0; m < d.n_meshes; m++) {
-            const uint32_t first = d.meshes[m].bvh_node_offset / 4;
-            if (first < d.n_bvh_nodes) bottom = std::max(bottom, depth_of(d.bvh_nodes + first, d.n_bvh_nodes - first, 0));
-        }
-        if (top + bottom + 3 > kStackSize)
-            throw std::runtime_error("ctl_scene_create: scene BVH depth " + std::to_string(top) + " + mesh BVH depth " + std::to_string(bottom) +
-                                     " does not fit the traversal stack of " + std::to_string(kStackSize) + " entries (rebuild the meshes with CTL_BVH_BINNED, whose depth is bounded)");
-    }
+    set_shading_state(derive_shading_state(d));
     S.hit_key_out = nullptr; S.flat_leaf_keys = 0;
     S.flat_nodes = nullptr; S.flat_leaves = nullptr; S.flat_root = 0; S.flat_format = 0; S.flat_compact = 0; S.inst_w_one = 0; S.flat_top_cached = 0;
     if (flatten) {
@@ -361,8 +266,7 @@ Scene::Scene(const ctl_scene_desc& d, bool flatten, int flat_format, bool reduce
                 }
             F.leaves.emplace_back(); std::memset(&F.leaves.back(), 0, sizeof(flat_leaf)); F.leaves.back().index = 1;   // one spare (closing) entry behind the last leaf
             flat_leaves_.upload((const float4*)F.leaves.data(), F.leaves.size() * 8);
-            // every node transform affine with w == 1 exactly (what add_node produces): the kernels skip the load of w and the division by it
-            S.inst_w_one = 1; for (uint32_t k = 0; k < d.n_nodes; k++) if (d.node_inv_transforms[k].m[15] != 1.0f) S.inst_w_one = 0;
+            S.inst_w_one = inverse_transforms_have_w_one(d);
             CTL_HIP(hipDeviceSynchronize());
             S.flat_nodes = flat_nodes_.p; S.flat_leaves = flat_leaves_.p; S.flat_format = F.format; S.flat_compact = (F.format == kFlatQ4 && F.compact_links) ? 1 : 0;
             S.flat_root = ((S.flat_compact || F.format == kFlatQ8) && F.root_slab) ? 1 : 0;   // bit 0 of an inner link: the node carries an oriented slab (flat_slab.h); Q8 links are node index << 1 | that bit

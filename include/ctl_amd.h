@@ -346,6 +346,11 @@ enum { CTL_DIFF_CAMERA = 1,       /* ctl_scene_desc::camera                     
        CTL_DIFF_TOPOLOGY = 16 };  /* anything else: triangle / Woop / mesh-BVH arrays, any count but the lights', meshes, node -> mesh / material
                                      assignment, images, rough-transmittance tables                                                               */
 int ctl_scene_desc_diff(const ctl_scene_desc* a, const ctl_scene_desc* b, uint32_t* mask_out);
+/* Everything ctl_scene_create and ctl_scene_update refuse a description for that can be judged from the description alone (host only, no device call): node transforms,
+ * sensor, lights, textures, materials, the depth of the two-level BVH.  parts == 0: as ctl_scene_create checks; else the CTL_DIFF_* parts to check, as ctl_scene_update
+ * checks the parts it found changed (CTL_DIFF_TOPOLOGY among them: as creation checks them).  CTL_ERR_INVALID and ctl_last_error() name the first rule broken.
+ * state_out (may be NULL): dev_scene's shade_features (the kShade* bits of csrc/device_scene.h), shade_models (bit m: some material has bsdf_type m) and alpha_maps. */
+int ctl_scene_desc_check(const ctl_scene_desc* desc, uint32_t parts, uint32_t state_out[3]);
 /* Applies everything that differs between the description `scene` holds and `new_desc`, except topology, in place; *mask_out (may be NULL) = the CTL_DIFF_* bits found.
  * Camera, materials, lights: host -> HBM copies (a material whose bsdf_type or alpha_state changed has the leaf entries of a flattened scene re-stamped by a kernel).
  * Transforms: the two-level arrays are re-uploaded and the flattened Q4 tree is REFITTED on the device (csrc/flat_refit.h: links, masks and memory order stay, every

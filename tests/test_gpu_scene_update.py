@@ -223,3 +223,39 @@ def test_a_top_level_bvh_that_does_not_fit_the_traversal_stack_is_refused(gpu, o
     # a chain that fits is taken (every ray then also visits node 0 once per level: slower, same hits)
     ok = with_top_level(d, chain(20, ~1), 0)
     assert s.update(ok) == api.DIFF_TRANSFORMS
+
+
+def test_the_validator_and_the_scene_agree(gpu, orc):
+    """ctl_scene_desc_check is what creation and update themselves ask (csrc/scene_checks.cpp): a malformed description (tests/scene_check_cases.py) is refused by
+    gpu.Scene with the status and message the host-only check gives, and as an update it is refused with the update's prefix, before anything is written — the mask
+    is reported as for any refusal and the next frame is the one rendered before."""
+    import scene_check_cases as K
+    for name in ("forward transform not affine", "bad sensor type", "unknown light type", "unknown texture type", "nested index out of range", "scene BVH too deep"):
+        d, _, message = K.make(name)
+        with pytest.raises(api.CtlError) as want:
+            api.scene_desc_check(d, 0)
+        assert want.value.code == api.ERR_INVALID and str(want.value).endswith(message), name
+        for flatten in (False, True):
+            with pytest.raises(api.CtlError) as got:
+                gpu.Scene(d, flatten=flatten)
+            assert (got.value.code, str(got.value)) == (want.value.code, str(want.value)), name
+    base = K.base("cornell").desc
+    tables = orc.sequence_tables(1)
+    s = gpu.Scene(base, flatten=True)
+    tr = gpu.WavefrontPathTracer(); tr.getParameters().setValue("MaxPathLength", 5); tr.Resize(64, 64); tr.InitializeScene(s)
+
+    def frame():
+        img = gpu.Image(64, 64)
+        tr.setSamplerTables(*tables[0]); tr.DoPass(img, new_trace=True)
+        return img.getPixelData()
+    a = frame()
+    for name, mask in (("unknown texture type", api.DIFF_MATERIALS), ("bad sensor type", api.DIFF_CAMERA)):
+        d, _, message = K.make(name)
+        assert api.scene_desc_diff(base, d) == mask
+        with pytest.raises(api.CtlError) as want:
+            api.scene_desc_check(d, mask)
+        assert str(want.value).split(": ", 1)[1].startswith("ctl_scene_update: "), str(want.value)
+        with pytest.raises(api.CtlError) as got:
+            s.update(d)
+        assert (got.value.code, str(got.value)) == (api.ERR_INVALID, str(want.value)) and s.last_mask == mask, name
+        assert_bit_equal(frame(), a, "frame A after the refused update (%s)" % name)
