@@ -35,13 +35,11 @@ struct wave_queues {
     uint32_t* work;            // dynamic-fetch cursors, one per intersect launch of a pass
     unsigned long long* stats; // [0] rays traced (primary + continuation + shadow)
     uint32_t capacity;
-    // material sort of the shading queue (scenes that need the full shade kernel): path slots grouped by BSDF model, so that the 64 lanes of
-    // a wave run one model's code instead of all of them
-    uint32_t* order;           // [capacity] path slots in shading order
-    unsigned char* mat_key;    // [capacity] BSDF model of the hit (0 = miss)
-    uint32_t* mat_counts;      // [depth * 32 + k]: k < 16 paths per model, 16 + k scatter cursors, 24 + c vertices of model class c (k_class_partition)
-    // model-class shading (pass_params::model_classes): k_class_partition splits the slots of a depth into one list per model class, class_order[c][0 .. mat_counts[depth * 32 + 24 + c])
+    unsigned char* mat_key;    // [capacity] BSDF model of the hit (0 = miss), left by the closest-hit traversal (pass_params::key_from_traversal): keys the regrouping of k_shade_basic and the model-class lists
+    // model-class shading (pass_params::model_classes): k_class_partition splits the slots of a depth into one list per model class, class_order[c][0 .. class_counts[depth * 8 + c]),
+    // so that the 64 lanes of a wave run one class's code instead of all fifteen models'
     uint32_t* class_order[5];  // [capacity] each: classes a, b, c, p, g
+    uint32_t* class_counts;    // [depth * 8 + c]: vertices of model class c at this depth (written by k_class_partition, read by the class builds)
 };
 // the model classes of shade_class_a/b/c/p.hip: which traversal keys (Q.mat_key: CTL_BSDF_* of the hit, 0 = miss) each launch shades
 #define CTL_CLASS_A_KEYS 0x004Bu   // miss, diffuse, dielectric, conductor
@@ -57,11 +55,8 @@ struct pass_params {
     uint32_t tile_rank, tile_world;      // image-tile shard: tiles t with t % world == rank
     uint32_t n_local_pixels;             // pixels rendered by this rank
     int direct, max_path_length, rr_start_depth;
-    int sort_materials;                  // shade in wave_queues::order
     int key_from_traversal;              // Q.mat_key[i] = BSDF model (CTL_BSDF_*, all >= 1) of path i's hit (0 = miss), left there by the closest-hit traversal (dev_scene::hit_key_out)
     int model_classes;                   // the full feature set shaded by one launch per model class present in the scene (shade_class_*.hip) instead of the one k_shade_full; needs key_from_traversal
-    int block_sort;                      // full shade kernel: regroup the path slots of a workgroup by BSDF model (shade_kernel.inc)
-    int sort_octants;                    // append the new rays of a workgroup grouped by direction octant (compaction.h)
     const unsigned char* block_counts;   // samples per 64x64 film block in this pass (a block sampler's decision), nullptr = one everywhere
     uint32_t max_block_count;            // largest entry of block_counts
     int wavefront_rules;                 // pathIterateKernel's own path rules (PathSemantics = Wavefront): selects the *_wf shade kernels
@@ -96,21 +91,16 @@ void launch_intersect_count(const launch_ctx& lc, const dev_scene& S, const floa
                             uint32_t* occ, int any_hit, unsigned long long* counts3);
 void launch_shade(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
 void read_stack_histogram(unsigned long long* h, bool reset);   // kernels.hip: rays of the counting traversals by deepest stack entry
-void launch_shade_basic(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
-void launch_shade_full(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
+// The shade builds, X(name, keys): shade_<name>.hip defines launch_shade_<name> and shade_<name>_wf.hip launch_shade_<name>_wf (both from shade_kernel.inc).  keys: a model-class
+// build is launched for a scene that has one of these models (dev_scene::shade_models), 0 = whatever the scene has; the class builds in the order launch_shade runs them.
+#define CTL_SHADE_BUILDS(X) \
+    X(basic, 0u) X(full, 0u) \
+    X(class_a, 0u) X(class_b, CTL_CLASS_B_KEYS) X(class_g, CTL_CLASS_G_KEYS) X(class_p, CTL_CLASS_P_KEYS) X(class_c, CTL_CLASS_C_KEYS)
+using shade_launch = void(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
+#define CTL_SHADE_DECLARE(name, keys) shade_launch launch_shade_##name, launch_shade_##name##_wf;
+CTL_SHADE_BUILDS(CTL_SHADE_DECLARE)
+#undef CTL_SHADE_DECLARE
 void launch_class_partition(const launch_ctx& lc, const wave_queues& Q, int depth);
-void launch_shade_class_a(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
-void launch_shade_class_b(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
-void launch_shade_class_c(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
-void launch_shade_class_g(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
-void launch_shade_class_g_wf(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
-void launch_shade_class_p(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
-void launch_shade_class_p_wf(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
-void launch_shade_class_a_wf(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
-void launch_shade_class_b_wf(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
-void launch_shade_class_c_wf(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
-void launch_shade_basic_wf(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
-void launch_shade_full_wf(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
 void launch_finalize(const launch_ctx& lc, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
 // frame += the staged samples of a batch, pass by pass; clears the stage.  variance + stray_stage (both or neither; whole frames only): per pass the samples that strayed into the pixel
 // (pass_params::stray_stage) are added before the pixel's own — the order of a pass rendered on its own — and PixelVarianceInfo::updateMoments follows with the frame as it then stands,

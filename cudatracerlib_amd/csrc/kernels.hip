@@ -299,45 +299,6 @@ void launch_intersect_count(const launch_ctx& lc, const dev_scene& S, const floa
     if (any_hit) launch_intersect<true, true>(lc, S, ro, rd, n_ptr, work, hit, hit_node, occ, counts3);
     else launch_intersect<false, true>(lc, S, ro, rd, n_ptr, work, hit, hit_node, nullptr, counts3);
 }
-// ---- material sort: counting sort of the path slots by the BSDF model they hit (16 buckets), between intersection and shading
-__global__ __launch_bounds__(kBlock) void k_mat_count(dev_scene S, wave_queues Q, int depth) {
-    __shared__ uint32_t h[16];
-    if (threadIdx.x < 16) h[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t n = Q.counts[(depth - 1) * 4 + 0];
-    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
-        const int tri = __float_as_int(Q.hit[i].w);
-        uint32_t key = 0;
-        if (tri >= 0) key = S.mats[S.node_info[Q.hit_node[i]].x + tri_mat_index(S, tri)].bsdf_type & 15u;
-        Q.mat_key[i] = (unsigned char)key;
-        atomicAdd(&h[key], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x < 16 && h[threadIdx.x]) atomicAdd(&Q.mat_counts[depth * 32 + threadIdx.x], h[threadIdx.x]);
-}
-__global__ __launch_bounds__(kBlock) void k_mat_scatter(wave_queues Q, int depth) {
-    __shared__ uint32_t base[16];
-    if (threadIdx.x == 0) { uint32_t s = 0; for (int k = 0; k < 16; k++) { base[k] = s; s += Q.mat_counts[depth * 32 + k]; } }
-    __syncthreads();
-    const uint32_t n = Q.counts[(depth - 1) * 4 + 0];
-    const uint32_t n_round = (n + 63u) & ~63u;
-    const int lane = threadIdx.x & 63;
-    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n_round; i += gridDim.x * kBlock) {
-        const bool active = i < n;
-        const uint32_t key = active ? Q.mat_key[i] : 0xffu;
-        unsigned long long todo = __ballot(active);
-        while (todo) {   // one atomic per model present in the wave
-            const int leader = (int)__builtin_ctzll(todo);
-            const uint32_t k = (uint32_t)__shfl((int)key, leader, 64);
-            const unsigned long long mine = __ballot(active && key == k);
-            uint32_t first = 0;
-            if (lane == leader) first = atomicAdd(&Q.mat_counts[depth * 32 + 16 + k], (uint32_t)__popcll(mine));
-            first = (uint32_t)__shfl((int)first, leader, 64);
-            if (active && key == k) Q.order[base[k] + first + (uint32_t)__popcll(mine & ((1ull << lane) - 1ull))] = i;
-            todo &= ~mine;
-        }
-    }
-}
 
 // Model-class shading (shade_class_*.hip): split the vertices of a depth into one slot list per model class.  A workgroup takes windows of 16384 consecutive slots; inside a window the
 // slots of a class are ordered by model (Q.mat_key, the byte per ray the closest-hit traversal left) and go to the class's list as ONE contiguous chunk (one atomic per class
@@ -377,7 +338,7 @@ __global__ __launch_bounds__(kPartBlock) void k_class_partition(wave_queues Q, i
         if (threadIdx.x < 5) {   // thread c: the chunk of class c in its list, the models of the class in key order inside it
             uint32_t tot = 0;
             for (uint32_t k = 0; k < 16; k++) if (class_of_key(k) == threadIdx.x) tot += s_hist[k];
-            uint32_t at = tot ? atomicAdd(&Q.mat_counts[depth * 32 + 24 + threadIdx.x], tot) : 0u;
+            uint32_t at = tot ? atomicAdd(&Q.class_counts[depth * 8 + threadIdx.x], tot) : 0u;
             for (uint32_t k = 0; k < 16; k++) if (class_of_key(k) == threadIdx.x) { s_start[k] = at; at += s_hist[k]; }
         }
         __syncthreads();
@@ -391,30 +352,22 @@ void launch_class_partition(const launch_ctx& lc, const wave_queues& Q, int dept
     hipLaunchKernelGGL(k_class_partition, dim3(lc.grid_blocks / 4), dim3(kPartBlock), 0, lc.stream, Q, depth);
 }
 
-// the shade kernel exists in feature-specialised builds (shade_basic.hip / shade_full.hip): a scene that uses only the basic
+// the shade kernel exists in feature-specialised builds (kernels.h CTL_SHADE_BUILDS): a scene that uses only the basic
 // material / light / texture set runs the variant whose code does not carry the registers of the rest (dev_scene::shade_features)
 void launch_shade(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image) {
-    using shade_launch = void (*)(const launch_ctx&, const dev_scene&, const wave_queues&, const pass_params&, int, ctl_pixel_data*);
-    const bool wf = P.wavefront_rules;   // the build of pathIterateKernel's own path rules (shade_*_wf.hip)
-    if (S.shade_features == 0) { (wf ? launch_shade_basic_wf : launch_shade_basic)(lc, S, Q, P, depth, image); return; }
-    if (P.model_classes) {   // one launch per model class the scene has (class a, keys 0, also takes the misses and always runs): shade_class_*.hip
-        static const struct { uint32_t keys; shade_launch launch, launch_wf; } classes[] = {
-            { 0u, launch_shade_class_a, launch_shade_class_a_wf },
-            { CTL_CLASS_B_KEYS, launch_shade_class_b, launch_shade_class_b_wf },
-            { CTL_CLASS_G_KEYS, launch_shade_class_g, launch_shade_class_g_wf },
-            { CTL_CLASS_P_KEYS, launch_shade_class_p, launch_shade_class_p_wf },
-            { CTL_CLASS_C_KEYS, launch_shade_class_c, launch_shade_class_c_wf },
-        };
-        launch_class_partition(lc, Q, depth);
-        for (const auto& c : classes)
-            if (!c.keys || (S.shade_models & c.keys)) (wf ? c.launch_wf : c.launch)(lc, S, Q, P, depth, image);
-        return;
-    }
-    if (P.sort_materials) {
-        hipLaunchKernelGGL(k_mat_count, dim3(lc.grid_blocks), dim3(kBlock), 0, lc.stream, S, Q, depth);
-        hipLaunchKernelGGL(k_mat_scatter, dim3(lc.grid_blocks), dim3(kBlock), 0, lc.stream, Q, depth);
-    }
-    (wf ? launch_shade_full_wf : launch_shade_full)(lc, S, Q, P, depth, image);
+#define CTL_SHADE_INDEX(name, keys) build_##name,
+#define CTL_SHADE_ROW(name, keys) { keys, { launch_shade_##name, launch_shade_##name##_wf } },
+    enum { CTL_SHADE_BUILDS(CTL_SHADE_INDEX) n_builds };
+    static const struct { uint32_t keys; shade_launch* launch[2]; } builds[] = { CTL_SHADE_BUILDS(CTL_SHADE_ROW) };   // [build][wavefront_rules]: shade_<name>.hip, shade_<name>_wf.hip
+#undef CTL_SHADE_INDEX
+#undef CTL_SHADE_ROW
+    const int wf = P.wavefront_rules ? 1 : 0;   // the build of pathIterateKernel's own path rules
+    if (S.shade_features == 0) { builds[build_basic].launch[wf](lc, S, Q, P, depth, image); return; }
+    if (!P.model_classes) { builds[build_full].launch[wf](lc, S, Q, P, depth, image); return; }
+    // one launch per model class the scene has (class a, keys 0, also takes the misses and always runs)
+    launch_class_partition(lc, Q, depth);
+    for (int b = build_class_a; b < n_builds; b++)
+        if (!builds[b].keys || (S.shade_models & builds[b].keys)) builds[b].launch[wf](lc, S, Q, P, depth, image);
 }
 void launch_finalize(const launch_ctx& lc, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image) {
     hipLaunchKernelGGL(k_finalize, dim3(lc.grid_blocks), dim3(kBlock), 0, lc.stream, Q, P, depth, image);

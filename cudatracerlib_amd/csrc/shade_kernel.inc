@@ -54,7 +54,7 @@ namespace ctl {
 // ------------------------------------------------------------------------------------------------ shading
 // One lane = one queued path vertex.  `depth` is the megakernel's 1-based depth of this vertex.
 __global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERNEL(dev_scene S, wave_queues Q, pass_params P, int depth, ctl_pixel_data* __restrict__ image) {
-    __shared__ uint32_t s_cnt[17][kWideBlock / 64]; __shared__ uint32_t s_base[3];
+    __shared__ uint32_t s_cnt[3][kWideBlock / 64]; __shared__ uint32_t s_base[3];
 #if CTL_SHADE_LDS_TABLES
     scene_tables_to_lds<CTL_SHADE_BLOCK>(S);   // emitter records, anim blob, normal table: LDS for the whole launch (shading.h scene_lights / scene_anim / scene_normal_lut)
 #endif
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERN
     const path_soa& A = Q.path[cur];
     const path_soa& B = Q.path[nxt];
 #if CTL_SHADE_CLASSED
-    const uint32_t n = Q.mat_counts[depth * 32 + 24 + CTL_SHADE_CLASS];
+    const uint32_t n = Q.class_counts[depth * 8 + CTL_SHADE_CLASS];
 #else
     const uint32_t n = Q.counts[(depth - 1) * 4 + 0];
 #endif
@@ -75,12 +75,7 @@ __global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERN
     const uint32_t n_round = (n + (CTL_SHADE_BLOCK - 1u)) & ~(CTL_SHADE_BLOCK - 1u);   // whole workgroups iterate together (barriers in block_append3)
     for (uint32_t j = blockIdx.x * CTL_SHADE_BLOCK + threadIdx.x; j < n_round; j += gridDim.x * CTL_SHADE_BLOCK) {
         bool active = j < n;
-#if CTL_SHADE_FEATURES != 0
-        const bool sorted_order = P.sort_materials != 0;   // shading order: slots grouped by BSDF model (k_mat_scatter)
-#else
-        const bool sorted_order = false;
-#endif
-        uint32_t i = (sorted_order && active) ? Q.order[j] : j;
+        uint32_t i = j;
 #ifndef CTL_SHADE_SORT_WINDOW
 #define CTL_SHADE_SORT_WINDOW CTL_SHADE_BLOCK   // lanes that exchange slots: the whole workgroup, or a power-of-two part of it (smaller window = the permuted reads stay closer)
 #endif
@@ -89,7 +84,7 @@ __global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERN
         // queue, by model inside a window: every wave is full, (mostly) of one model, and reads slots of one window; the other launches of the depth take the other lists.
         i = active ? Q.class_order[CTL_SHADE_CLASS][j] : 0u;
 #else
-        if (CTL_SHADE_SORT_WINDOW > 0 && P.block_sort) {
+        if (CTL_SHADE_SORT_WINDOW > 0) {
             // Workgroup-local regrouping: the lanes of a window exchange their path slots so that every wave shades (mostly) one BSDF model.
             // The slots stay inside the window's consecutive slots, so the permuted path-state reads touch the same
             // lines as the straight ones (a device-wide sort turns them into random gathers and loses more than the coherence wins, DESIGN.md §4).
@@ -117,7 +112,7 @@ __global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERN
             const uint32_t src = s_perm[threadIdx.x];
             const uint32_t j2 = j - lane_w + src;
             active = j2 < n;
-            i = (sorted_order && active) ? Q.order[j2] : j2;
+            i = j2;
         }
 #endif
         bool alive = false, want_shadow = false, terminated = false;
@@ -290,8 +285,7 @@ __global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERN
             specular = specularBounce; bsdf_pdf_out = brdf_scattering_pdf; d1 = rng.d1; d2 = rng.d2;
         }
         // ---- stream compaction: survivors, shadow rays and waiting terminations are appended densely, one atomic per wave
-        const block_slots bs = P.sort_octants ? block_append3_keyed(n_shadow, want_shadow, octant_of(sh_dir), n_next, alive, octant_of(new_d), n_final, terminated && want_shadow, s_cnt, s_base)
-                                              : block_append3(n_shadow, want_shadow, n_next, alive, n_final, terminated && want_shadow, s_cnt, s_base);
+        const block_slots bs = block_append3(n_shadow, want_shadow, n_next, alive, n_final, terminated && want_shadow, s_cnt, s_base);
         const uint32_t sslot = bs.s[0], nslot = bs.s[1], fslot = bs.s[2];
         if (!active) continue;
         if (want_shadow) { sh_o[sslot] = make_float4(sh_org.x, sh_org.y, sh_org.z, S.eps); sh_d[sslot] = make_float4(sh_dir.x, sh_dir.y, sh_dir.z, sh_tmax); }

@@ -537,22 +537,15 @@ WavefrontPathTracer::WavefrontPathTracer() {
     // build-specific: run Material::AlphaTest on candidate hits.  Off = the reference's wavefront tracer (its intersectKernel has no
     // alpha test, only the single-ray traceRay of the megakernel integrators does, TraceHelper.cu:135-153)
     m_sParameters.addBool("AlphaTest", false);
-    // build-specific: group the shading queue by BSDF model before the full shade kernel runs (no effect on scenes served by the basic build).
-    // Off by default: measured on the synthetic-bathroom workload it LOSES (shade 9.1 -> 11.5 ms / pass) — the time goes into the spline
-    // lookups of the rough plastics, not into divergence, and the sorted order turns the path-state reads into gathers
-    m_sParameters.addBool("SortMaterials", false);
-    // build-specific: the full shade kernel regroups the paths of each workgroup by BSDF model before shading them (shade_kernel.inc)
-    m_sParameters.addBool("BlockSort", true);
     // build-specific: a scene that needs the full feature set is shaded by one launch per MODEL CLASS present in it (shade_class_a/b/p/c.hip: basic models + misses / the other single-layer
     // models / rough plastic / the nesting models), each register-allocated for its own models, instead of the one kernel that carries all fifteen (k_shade_full: 104 spilled registers).  Needs the
-    // BSDF model per hit from the closest-hit traversal (flattened BVH).  false = k_shade_full
+    // BSDF model per hit from the closest-hit traversal (flattened BVH).  false = k_shade_full.
+    // Not an experiment arm: k_shade_full runs by itself whenever the traversal leaves no key (two-level scene, counting batch, >= 2^27 triangles); the parameter lets a test hold both paths to one frame on one scene
     m_sParameters.addBool("ShadeByModelClass", true);
-    // build-specific: the rays a shade workgroup emits are appended grouped by direction octant (compaction.h block_append3_keyed).
-    // Off by default: measured on synthetic-SM the traversal kernels gain 1 % (6.10 -> 6.05 ms / pass) and the shade kernel pays 0.5 ms for it
-    m_sParameters.addBool("SortOctants", false);
     // build-specific: trace a bounce's path rays and the previous bounce's shadow rays in one persistent launch (k_intersect_pair).  Every traversal launch
     // pays ~0.4 ms of ramp and drain whatever its size (tools/shard_time_probe.py: 4 % of the time at 20 passes per launch on one GPU, a quarter on one rank
-    // of eight); the fused launch fills the drain of the first set with the second: +2 % on the whole frame, +7 % on a rank of eight.  false = two launches
+    // of eight); the fused launch fills the drain of the first set with the second: +2 % on the whole frame, +7 % on a rank of eight.  false = two launches.
+    // Not an experiment arm: the unfused launches run by themselves when counting or with Direct = false; the parameter lets a test hold both paths to one frame on one scene
     m_sParameters.addBool("FuseTraversal", true);
     // build-specific: whose per-path rules the shading stage follows.  PathTrace (default): the reference's deterministic megakernel PathTrace<DIRECT> (PathTracer.cu:10-113),
     // what the oracle pins and the PathTracer plugin renders.  Wavefront: pathIterateKernel's own rules (WavefrontPathTracer.cu:51-164) — Russian roulette before sampling at
@@ -622,9 +615,9 @@ void WavefrontPathTracer::Resize(unsigned int _w, unsigned int _h) {
     Q.fin.rad = new_f4(capacity); Q.fin.dir = new_f4(capacity); Q.fin.px = new_f4(capacity);
     stats_.alloc(14); Q.stats = stats_.p; CTL_HIP(hipMemset(stats_.p, 0, 14 * sizeof(unsigned long long)));
     Q.capacity = capacity;
-    order_.alloc(capacity); Q.order = order_.p; class_order_.free(); for (int c = 0; c < 5; c++) Q.class_order[c] = nullptr;   // the model-class lists (20 B per slot) are allocated by the first render that shades by class
+    class_order_.free(); for (int c = 0; c < 5; c++) Q.class_order[c] = nullptr;   // the model-class lists (20 B per slot) are allocated by the first render that shades by class
     mat_key_.alloc(capacity); Q.mat_key = mat_key_.p;
-    counts_.free(); work_.free(); mat_counts_.free(); stage_.free(); stray_stage_.free();
+    counts_.free(); work_.free(); class_counts_.free(); stage_.free(); stray_stage_.free();
 }
 
 // stats: [0] path rays, [1] shadow rays, [2..6] closest-hit traversal counts, [7..11] any-hit traversal counts
@@ -659,9 +652,9 @@ void WavefrontPathTracer::DoRender(Image* I, const float* d_t1p, const float* d_
     const int maxPathLength = m_sParameters.getValue("MaxPathLength"), rrStart = m_sParameters.getValue("RRStartDepth");
     const bool direct = m_sParameters.getValue("Direct") != 0;
     const size_t n_counts = (size_t)(maxPathLength + 2) * 4, n_work = (size_t)2 * (maxPathLength + 2);
-    const size_t n_mat = (size_t)(maxPathLength + 2) * 32;
-    if (counts_.n < n_counts) { counts_.alloc(n_counts); work_.alloc(n_work); mat_counts_.alloc(n_mat); }
-    Q.counts = counts_.p; Q.work = work_.p; Q.mat_counts = mat_counts_.p;
+    const size_t n_class = (size_t)(maxPathLength + 2) * 8;
+    if (counts_.n < n_counts) { counts_.alloc(n_counts); work_.alloc(n_work); class_counts_.alloc(n_class); }
+    Q.counts = counts_.p; Q.work = work_.p; Q.class_counts = class_counts_.p;
     const dev_scene& S = m_pScene->S;
     const launch_ctx lc{ stream, grid_blocks, m_sParameters.getValue("AlphaTest") != 0 && S.alpha_maps != 0 };
     pass_params P{};
@@ -669,9 +662,6 @@ void WavefrontPathTracer::DoRender(Image* I, const float* d_t1p, const float* d_
     P.batch = n_batch;
     P.width = w; P.height = h; P.tile_rank = shard_rank; P.tile_world = shard_world; P.n_local_pixels = n_local_pixels;
     P.direct = direct ? 1 : 0; P.max_path_length = maxPathLength; P.rr_start_depth = rrStart;
-    P.sort_materials = (m_sParameters.getValue("SortMaterials") != 0 && S.shade_features != 0) ? 1 : 0;
-    P.block_sort = m_sParameters.getValue("BlockSort") != 0 ? 1 : 0;
-    P.sort_octants = m_sParameters.getValue("SortOctants") != 0 ? 1 : 0;
     P.block_counts = pass_block_counts_; P.max_block_count = pass_max_block_count_;
     P.wavefront_rules = m_sParameters.getValue("PathSemantics") == 1 ? 1 : 0; P.u16_bary = m_sParameters.getValue("U16Barycentrics") != 0 ? 1 : 0;
     P.depth_buffer = depth_buffer_; P.depth_w = depth_w_; P.depth_h = depth_h_; P.depth_near = m_pScene->near_depth; P.depth_far = m_pScene->far_depth;
@@ -683,7 +673,7 @@ void WavefrontPathTracer::DoRender(Image* I, const float* d_t1p, const float* d_
     if (!pass_block_counts_) P.stage = ensureStage(n_batch);
     P.stray_stage = (batch_variance_ && P.stage) ? stray_stage_.p : nullptr;
     if (pass_block_counts_ && pass_paths_ > capacity) throw std::runtime_error("ray queue overflow: the block sampler asks for more samples in one pass than the queues hold (DoubleRayBuffer.h:86-89)");
-    CTL_HIP(hipMemsetAsync(mat_counts_.p, 0, n_mat * sizeof(uint32_t), stream));
+    CTL_HIP(hipMemsetAsync(class_counts_.p, 0, n_class * sizeof(uint32_t), stream));
     CTL_HIP(hipMemsetAsync(counts_.p, 0, n_counts * sizeof(uint32_t), stream));
     CTL_HIP(hipMemsetAsync(work_.p, 0, n_work * sizeof(uint32_t), stream));
     timer.begin(stream, 0); launch_raygen(lc, S, Q, P); timer.end(stream);
@@ -695,10 +685,10 @@ void WavefrontPathTracer::DoRender(Image* I, const float* d_t1p, const float* d_
         shadow_launches++;
     };
     const bool fuse = !counting && direct && m_sParameters.getValue("FuseTraversal") != 0;
-    // closest-hit traversals of a flattened scene leave the BSDF model of every hit in Q.mat_key (device_scene.h hit_key_out) for the shade kernel's regrouping; the counting
-    // kernels and the device-wide material sort (which writes its own keys there) do without
+    // closest-hit traversals of a flattened scene leave the BSDF model of every hit in Q.mat_key (device_scene.h hit_key_out) for the shade kernel's regrouping and the model-class lists;
+    // the counting kernels do without
     P.model_classes = (S.shade_features != 0 && m_sParameters.getValue("ShadeByModelClass") != 0) ? 1 : 0;
-    dev_scene Sk = S; Sk.hit_key_out = (S.flat_leaf_keys && (S.shade_features == 0 || P.model_classes) && !counting && !P.sort_materials && P.block_sort) ? Q.mat_key : nullptr;   // (k_shade_full keys its regrouping by model AND material index)
+    dev_scene Sk = S; Sk.hit_key_out = (S.flat_leaf_keys && (S.shade_features == 0 || P.model_classes) && !counting) ? Q.mat_key : nullptr;   // (k_shade_full keys its regrouping by model AND material index)
     P.key_from_traversal = Sk.hit_key_out ? 1 : 0;
     if (!P.key_from_traversal) P.model_classes = 0;
     if (P.model_classes && !class_order_.p) { class_order_.alloc((size_t)capacity * 5); for (int c = 0; c < 5; c++) Q.class_order[c] = class_order_.p + (size_t)c * capacity; }

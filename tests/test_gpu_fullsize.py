@@ -165,7 +165,7 @@ def test_bathroom_workload_at_full_size(gpu, orc):
     """synthetic-bathroom (the stand-in for BASELINE config 5: rough plastic / conductor / dielectric, coating, textures, height map, environment
     emitter) at 1920x1080, depth 8, through the full shade kernel:
       * two bands of rows rendered by the oracle equal the same rows of the GPU frame (per pixel where paths are short, band mean at full depth);
-      * the workgroup-local regrouping of the shade kernel (BlockSort) and the device-wide material sort only reorder work: same frame, same rays;
+      * the one kernel with every model (ShadeByModelClass off) instead of a launch per model class only reorders work: same frame, same rays;
       * 2 x (1 pass) accumulates to the same sums as 2 passes; the megakernel plugin renders the same frame."""
     gpu.api.set_cache_dir(os.environ.get("CTL_CACHE_DIR") or os.path.join(os.environ.get("TMPDIR", "/tmp"), "ctl_amd_cache"))
     sc = scenes.synthetic_bathroom(W, H)
@@ -195,7 +195,7 @@ def test_bathroom_workload_at_full_size(gpu, orc):
             assert (g == w).all(axis=2).mean() >= 0.97, (depth, y0, float((g == w).all(axis=2).mean()))
     base, rays = render(gpu, gpu.WavefrontPathTracer, flat, tables)
     assert rays > 4 * W * H
-    for params in (dict(BlockSort=False), dict(SortMaterials=True), dict(ShadeByModelClass=False)):
+    for params in (dict(ShadeByModelClass=False),):
         other, rays_o = render(gpu, gpu.WavefrontPathTracer, flat, tables, **params)
         assert rays_o == rays
         assert np.array_equal(other[..., 6], base[..., 6])

@@ -138,13 +138,13 @@ def test_synthetic_bathroom_workload(gpu, orc):
 
 
 def test_queue_ordering_options_do_not_change_the_image(gpu, orc):
-    """FuseTraversal (path rays of a bounce and shadow rays of the previous one in one persistent launch, or in two), BlockSort (each workgroup of the full shade kernel regroups its paths by BSDF model), ShadeByModelClass (one shade launch per model class of the scene, or the one kernel with every model), SortMaterials (shade in BSDF-model order) and SortOctants (append new rays grouped by direction octant) only reorder work:
-    same frame (up to the order of the float atomics) and same ray count as the default order"""
+    """FuseTraversal (path rays of a bounce and shadow rays of the previous one in one persistent launch, or in two) and ShadeByModelClass (one shade launch per model class of the scene, or the one kernel with every model, which regroups the paths of each workgroup by BSDF model) only reorder work:
+    same frame (up to the order of the float atomics) and same ray count as the default order.  The ordering options that were measured, lost and removed (EXPERIMENTS.md) are unknown keys now."""
     sc = scenes.synthetic_bathroom(96, 54, n_instances=60, subdiv=2)
     scene = gpu.Scene(sc.desc, flatten=True)
     tables = orc.sequence_tables(3)
     out = []
-    for params in (dict(), dict(SortMaterials=True), dict(SortOctants=True), dict(SortMaterials=True, SortOctants=True), dict(BlockSort=False), dict(BlockSort=False, SortMaterials=True), dict(FuseTraversal=False), dict(ShadeByModelClass=False), dict(ShadeByModelClass=False, BlockSort=False)):
+    for params in (dict(), dict(FuseTraversal=False), dict(ShadeByModelClass=False)):
         tr = gpu.WavefrontPathTracer(); p = tr.getParameters(); p.setValue("MaxPathLength", 6)
         for k, v in params.items():
             p.setValue(k, v)
@@ -157,6 +157,9 @@ def test_queue_ordering_options_do_not_change_the_image(gpu, orc):
         assert rays == out[0][1]
         assert np.array_equal(got[..., 6], out[0][0][..., 6])
         assert np.allclose(got[..., :3], out[0][0][..., :3], rtol=1e-5, atol=1e-5)
+    for name in ("SortMaterials", "SortOctants", "BlockSort"):
+        with pytest.raises(gpu.CtlError, match="Unknown parameter key"):
+            p.setValue(name, True)
 
 
 def test_mitsuba_xml_scene(gpu, orc, tmp_path):
