@@ -200,8 +200,9 @@ def set_cache_dir(directory):
     _check(lib.ctl_set_cache_dir(None if directory is None else str(directory).encode()))
 
 
-FLAT_Q4, FLAT_F4, FLAT_F2, FLAT_Q8 = 0, 1, 2, 3          # CTL_FLAT_* node formats of the flattened BVH
-FLAT_FORMATS = {"q4": FLAT_Q4, "f4": FLAT_F4, "f2": FLAT_F2, "q8": FLAT_Q8}
+FLAT_Q4, FLAT_Q8 = 0, 3                                    # CTL_FLAT_* node formats of the flattened BVH
+FLAT_F4, FLAT_F2 = 1, 2                                    # retired numbers, kept as names only: the library answers them with CTL_ERR_UNSUPPORTED and FLAT_FORMATS does not offer them
+FLAT_FORMATS = {"q4": FLAT_Q4, "q8": FLAT_Q8}
 DEFAULT_FLAT_FORMAT = "q4"                                 # what Scene(desc, flatten=True) builds when no format is named (csrc/flatten.cpp default_flat_format)
 
 
@@ -679,7 +680,7 @@ class Scene:
     """The scene resident in HBM (UpdateKernel, Kernel/TraceHelper.cu:182-217)."""
 
     def __init__(self, desc, flatten=False, flat_format=None, reduced_rough_transmittance=False):
-        """flat_format: None = the library default (Q4, or $CTL_FLAT_FORMAT), else FLAT_Q4 / FLAT_F4 / FLAT_F2 or one of the strings q4 / f4 / f2.
+        """flat_format: None = the library default (Q4, or $CTL_FLAT_FORMAT), else FLAT_Q4 / FLAT_Q8 or one of the strings q4 / q8.
         reduced_rough_transmittance: CTL_SCENE_REDUCED_ROUGH_TRANSMITTANCE (faster rough plastic, equal to the reference's lookup up to rounding only)"""
         self._h = C.c_void_p()
         self._keepalive = desc

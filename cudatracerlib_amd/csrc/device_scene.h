@@ -80,7 +80,7 @@ struct dev_scene {
     int flat_root;
     int flat_compact;            // Q4: the child links are implied by the layout (flat4_node::links), a step loads 48 of the node's 64 B
     int inst_w_one;              // every node's inverse transform has w33 == 1.0f exactly (x / 1 == x: the traversal skips the division)
-    int flat_format;             // flat_format of flatten.h: 0 Q4 (64-B quantised 4-wide), 1 F4 (128-B fp32 4-wide), 2 F2 (64-B fp32 2-wide)
+    int flat_format;             // flat_format of flatten.h: 0 Q4 (64-B quantised 4-wide), 3 Q8 (128-B quantised 8-wide); 1 and 2 are retired
     int flat_leaf_keys;          // the device copy of the leaf entries carries the BSDF model of the entry's material (bsdf_type & 15) in bits 28..31 of its index word (tracer.hip; host arrays and the cache do not)
     unsigned char* hit_key_out;  // per launch (the tracer's copy of this struct): where a closest-hit traversal leaves that model (CTL_BSDF_*, all >= 1) per ray (0 = miss), for the shade kernel's regrouping; else nullptr
     int flat_top_cached;         // Q4 with implied links: the first this-many nodes of flat_nodes (the top of the tree, stored breadth-first) are kept in LDS by every traversal workgroup (traverse_flat.h kTopCache)

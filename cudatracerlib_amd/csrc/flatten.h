@@ -25,8 +25,7 @@ static_assert(sizeof(flat_leaf) == 128, "flat leaf entry is one 128-B line");
 // node formats (one per flat_scene; the traversal kernels are instantiated per format)
 enum flat_format : int {
     kFlatQ4 = 0,   // 4-wide, 64 B, child boxes quantised to 8 bits against the node's own box
-    kFlatF4 = 1,   // 4-wide, 128 B (one L2 line), fp32 child boxes stored plane-major
-    kFlatF2 = 2,   // 2-wide, 64 B, fp32 child boxes: the reference's BVHNodeData layout (Engine/TriIntersectorData.h:42-117)
+                   // 1, 2: retired (the fp32 formats F4 / F2, EXPERIMENTS.md)
     kFlatQ8 = 3,   // 8-wide, 128 B (one L2 line, 96 B used), 8-bit child boxes, one-triangle leaf slots, octant-ordered slots (flat8.h)
 };
 
@@ -88,22 +87,10 @@ inline bool flat4_encode_links(const int32_t child[4], const uint32_t counts[4],
     return true;
 }
 
-// F4.  Plane-major so that a lane picks the near / far plane of all four children by ADDRESS (the sign of its ray direction
-// selects lo or hi), not by four selects per axis: lo_x[4] hi_x[4] lo_y[4] hi_y[4] lo_z[4] hi_z[4] child[4] pad[4].
-// A missing child has an inverted box (lo = +FLT_MAX, hi = -FLT_MAX) and is never entered.
-struct flat4f_node {
-    float lo_x[4], hi_x[4], lo_y[4], hi_y[4], lo_z[4], hi_z[4];
-    int32_t child[4];      // >= 0: node index * 8 (float4 units); < 0: ~firstLeafEntry; 0x76543210: none
-    uint32_t pad[4];
-};
-static_assert(sizeof(flat4f_node) == 128, "fp32 wide node is one 128-B L2 line");
-
 struct flat_scene {
     int format = kFlatQ4;
     std::vector<flat8_node> nodes_q8;     // kFlatQ8; node 0 is the root
     std::vector<flat4_node> nodes;        // kFlatQ4; node 0 is the root
-    std::vector<flat4f_node> nodes_f4;    // kFlatF4
-    std::vector<ctl_bvh_node> nodes_f2;   // kFlatF2 (child >= 0: node index * 4)
     std::vector<flat_leaf> leaves;
     int max_depth = 0;                    // of the stored tree
     bool compact_links = true;            // Q4: every node's implied links (flat4_node::links) are valid; false -> the kernels read child[]
@@ -120,16 +107,19 @@ struct flat_scene {
         bool ready() const { return !level_nodes.empty(); }
         size_t bytes() const { return part_index.size() * 4 + part_boxes.size() * sizeof(refit_box) + xf0.size() * sizeof(ctl_float4x4) + (level_start.size() + level_nodes.size()) * 4; }
     } refit;
-    size_t node_bytes() const { return nodes.size() * sizeof(flat4_node) + nodes_f4.size() * sizeof(flat4f_node) + nodes_f2.size() * sizeof(ctl_bvh_node) + nodes_q8.size() * sizeof(flat8_node); }
-    int stack_need() const { return (format == kFlatF2 || format == kFlatQ8) ? max_depth + 2 : 3 * max_depth + 2; }   // traversal-stack entries a ray can need (Q8: one sibling group per level)
+    size_t node_bytes() const { return nodes.size() * sizeof(flat4_node) + nodes_q8.size() * sizeof(flat8_node); }
+    int stack_need() const { return format == kFlatQ8 ? max_depth + 2 : 3 * max_depth + 2; }   // traversal-stack entries a ray can need (Q8: one sibling group per level)
 };
 
-// false when the scene has no triangles or more than `max_triangles` instanced triangles
+// false when the scene has no triangles or more than `max_triangles` instanced triangles.  format: kFlatQ8, anything else builds kFlatQ4 — as does a scene that does not fit
+// the 8-wide format (2^24 nodes or more, or a leaf that still holds several entries at the builder's depth limit).  The retired numbers 1 and 2 are NOT refused here: every
+// caller that takes a format from outside refuses them first (capi.hip ctl_flat_bvh_build / ctl_flatten_probe, tracer.hip Scene::Scene)
 bool flatten_scene(const ctl_scene_desc& d, flat_scene& out, size_t max_triangles, int format = kFlatQ4);
 // Refit of a Q4 tree to the node transforms of `d` (flat_refit.h): same nodes / meshes as the description the tree was built from, links, masks and memory order
 // unchanged.  area_before_after (may be null): summed surface area of the nodes' boxes before and after, a SAH proxy.  Throws when the tree cannot be refitted.
 void refit_flat_scene(flat_scene& F, const ctl_scene_desc& d, double* area_before_after);
 double flat_scene_node_area(const flat_scene& F);   // Q4: sum over the nodes of the surface area of the box around their decoded child boxes
-int default_flat_format();   // kFlatQ4 unless $CTL_FLAT_FORMAT says q4 / f4 / f2 (measurement knob)
+int default_flat_format();   // kFlatQ4 unless $CTL_FLAT_FORMAT says q8 (measurement knob).  Changed with the retirement of F4 / F2: the knob's spellings f4 / f2, which made scene creation
+                             // answer CTL_ERR_UNSUPPORTED, are no longer known and give kFlatQ4 like any other unknown value
 
 }  // namespace ctl

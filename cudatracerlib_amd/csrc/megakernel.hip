@@ -11,6 +11,8 @@
 #include "mitsuba_loader.h"   // unsupported_error
 #include <climits>
 
+static_assert((int)ctl::kFmtQ4 == (int)ctl::kFlatQ4 && (int)ctl::kFmtQ8 == (int)ctl::kFlatQ8, "the kernels' format numbers (traverse_flat.h) are the flattener's (flatten.h)");
+
 namespace ctl {
 
 // single_stack_column, trace_single, light_sample_position and env_eval_differential: single_ray.h (shared with prim_tracer.hip); the tile order of the pixels:

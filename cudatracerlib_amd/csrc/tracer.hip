@@ -235,12 +235,11 @@ Scene::Scene(const ctl_scene_desc& d, bool flatten, int flat_format, bool reduce
     S.hit_key_out = nullptr; S.flat_leaf_keys = 0;
     S.flat_nodes = nullptr; S.flat_leaves = nullptr; S.flat_root = 0; S.flat_format = 0; S.flat_compact = 0; S.inst_w_one = 0; S.flat_top_cached = 0;
     if (flatten) {
-        // node format: Q4 (64-B 4-wide nodes with 8-bit child boxes) unless the caller or $CTL_FLAT_FORMAT asks for Q8; F4 / F2 are refused (DESIGN.md §3 has the measurements)
+        // node format: Q4 (64-B 4-wide nodes with 8-bit child boxes) unless the caller or $CTL_FLAT_FORMAT asks for Q8; the retired formats 1 and 2 (F4 / F2) are refused (EXPERIMENTS.md has the measurements)
+        if (flat_format == 1 || flat_format == 2) throw unsupported_error("ctl_scene_create: flat node formats 1 and 2 (F4 / F2) are retired: no traversal kernel reads them (EXPERIMENTS.md)");
         flat_scene F;
         if (flatten_scene(d, F, (size_t)1 << 30, flat_format < 0 ? default_flat_format() : flat_format)) {   // up to 2^30 instanced triangles (64 GiB of leaf entries)
             if (F.stack_need() + 2 > (F.format == kFlatQ8 ? kFlat8StackGroups : kStackSize)) throw std::runtime_error("ctl_scene_create: flattened BVH too deep for the traversal stack");
-            if (F.format != kFlatQ4 && F.format != kFlatQ8)
-                throw unsupported_error("ctl_scene_create: the F4 / F2 node formats are flatten-only (ctl_flat_bvh_build / api.FlatBvh): no traversal kernel reads them");
             if (F.format == kFlatQ4) flat_nodes_.upload((const float4*)F.nodes.data(), F.nodes.size() * 4);
             else flat_nodes_.upload((const float4*)F.nodes_q8.data(), F.nodes_q8.size() * 8);
             for (const flat_leaf& L : F.leaves) if (L.node >= d.n_nodes) throw std::runtime_error("ctl_scene_create: flattened leaf entry out of range");

@@ -25,7 +25,7 @@
 
 namespace ctl {
 
-enum { kFmtQ4 = 0, kFmtF4 = 1, kFmtF2 = 2, kFmtQ8 = 3 };   // = flat_format (flatten.h); Q8 has its own kernel body (traverse_flat8.h), F4 / F2 have no traversal kernel
+enum { kFmtQ4 = 0, kFmtQ8 = 3 };   // = kFlatQ4 / kFlatQ8 of flatten.h (megakernel.hip sees both headers and asserts it); Q8 has its own kernel body (traverse_flat8.h); 1 and 2 are retired
 
 #ifndef CTL_FLAT_LDS_ROWS
 #define CTL_FLAT_LDS_ROWS 23   // round 6: 23 rows + 1 spare = 24 KiB per 256-lane workgroup, SIX workgroups per CU (rounds 3-5: 19 rows, 20 KiB, seven).  Held to six by LDS padding the round-5 kernel

@@ -330,8 +330,7 @@ enum { CTL_SCENE_FLATTEN = 1,
         * scenes but are no longer equal to the bit, and textured scenes can exceed it at texture boundaries.  Without the flag every lookup is the reference's own arithmetic. */
        CTL_SCENE_REDUCED_ROUGH_TRANSMITTANCE = 2 };
 enum { CTL_FLAT_Q4 = 0,    /* 4-wide, 64-B nodes, 8-bit child boxes (default) */
-       CTL_FLAT_F4 = 1,    /* 4-wide, 128-B nodes, fp32 child boxes           */
-       CTL_FLAT_F2 = 2,    /* 2-wide, 64-B nodes in the reference's BVHNodeData layout */
+                           /* 1 and 2 are retired (the fp32 formats F4 / F2, EXPERIMENTS.md): CTL_ERR_UNSUPPORTED */
        CTL_FLAT_Q8 = 3 };  /* 8-wide, 128-B nodes, 8-bit child boxes, octant-ordered slots, one-triangle leaf slots (csrc/flat8.h) */
 #define CTL_SCENE_FLAT_FORMAT(f) ((((uint32_t)(f)) + 1u) << 8)
 int ctl_scene_create_ex(const ctl_scene_desc* desc, uint32_t flags, ctl_scene** out);

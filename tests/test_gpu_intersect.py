@@ -92,7 +92,24 @@ def check_flat(gpu, orc, desc, rays, any_hit, fmt):
     return got
 
 
-@pytest.mark.parametrize("fmt", ["q8", "q4"])   # f4 / f2 are flatten-only: no traversal kernel reads them
+def test_retired_formats_are_refused_and_the_scene_holds_the_host_tree(gpu):
+    """the retired node formats 1 and 2 (F4 / F2) are refused at scene creation, before anything is flattened; a Q4 and a Q8 scene created right after hold, byte for byte,
+    the arrays api.FlatBvh builds on the host"""
+    from cudatracerlib_amd import api
+    sc = scenes.cornell_box(32, 32, glass_sphere=True)          # (the description points into the scene object: keep it alive)
+    d = sc.desc
+    for fmt in (1, 2):
+        with pytest.raises(api.CtlError) as e:
+            gpu.Scene(d, flatten=True, flat_format=fmt)
+        assert e.value.code == -5 and "retired" in str(e.value)      # CTL_ERR_UNSUPPORTED
+    for fmt in (api.FLAT_Q4, api.FLAT_Q8):
+        dev, host = gpu.Scene(d, flatten=True, flat_format=fmt).flat_bvh(), api.FlatBvh(d, fmt)
+        assert dev.desc.format == host.desc.format == fmt
+        for name in ("nodes", "leaves", "child_links"):
+            assert getattr(dev, name)().tobytes() == getattr(host, name)().tobytes(), (fmt, name)
+
+
+@pytest.mark.parametrize("fmt", ["q8", "q4"])
 @pytest.mark.parametrize("any_hit", [False, True])
 def test_flattened_world_space_bvh(gpu, orc, any_hit, fmt):
     """CTL_SCENE_FLATTEN: one world-space BVH over all instanced triangles, every node format.  The tree only culls — each leaf entry is

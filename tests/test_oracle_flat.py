@@ -19,13 +19,13 @@ def rays_for(desc, n, seed):
     return r
 
 
-@pytest.mark.parametrize("fmt", [api.FLAT_Q8, api.FLAT_Q4, api.FLAT_F4, api.FLAT_F2])
+@pytest.mark.parametrize("fmt", [api.FLAT_Q8, api.FLAT_Q4])
 def test_flat_traversal_equals_two_level(orc, fmt):
     for sc, n in ((scenes.synthetic_sm(32, 32, n_instances=60, subdiv=2), 6000), (scenes.cornell_box(32, 32, glass_sphere=True), 4000)):
         d = sc.desc
         rays = rays_for(d, n, 5)
         fb = api.FlatBvh(d, fmt)
-        assert fb.desc.format == fmt and fb.desc.n_leaves > 0 and fb.desc.node_bytes == (128 if fmt in (api.FLAT_F4, api.FLAT_Q8) else 64)
+        assert fb.desc.format == fmt and fb.desc.n_leaves > 0 and fb.desc.node_bytes == (128 if fmt == api.FLAT_Q8 else 64)
         want, c2 = orc.intersect(d, rays, count=True)
         got, cf = orc.intersect(d, rays, count=True, flat=fb.desc)
         ties = (got["tri_idx"] != want["tri_idx"]) & (got["dist"] == want["dist"])
@@ -194,18 +194,34 @@ def test_layout_of_the_8_wide_nodes(orc):
         check_q8_layout(fb)
 
 
-def test_render_counts_in_flat_mode(orc):
+@pytest.mark.parametrize("fmt", [api.FLAT_Q4, api.FLAT_Q8])
+def test_render_counts_in_flat_mode(orc, fmt):
     """orc.render(flat=..., counts=...) renders the same image as the two-level oracle and reports per-ray node / triangle visits"""
     sc = scenes.cornell_box(24, 24, glass_sphere=True)
     d = sc.desc
     tables = orc.sequence_tables(1)
     want, rays = orc.render(d, 24, 24, n_passes=1, tables=tables, max_path_length=4)
-    fb = api.FlatBvh(d, api.FLAT_F4)
+    fb = api.FlatBvh(d, fmt)
     counts = {}
     got, rays_f = orc.render(d, 24, 24, n_passes=1, tables=tables, max_path_length=4, flat=fb.desc, counts=counts)
     assert rays == rays_f and np.array_equal(got[..., 6], want[..., 6])
     assert np.allclose(got[..., :3], want[..., :3], rtol=1e-6, atol=1e-7)
     assert counts["path_rays"] + counts["occ_rays"] == rays and counts["path_inner"] > counts["path_rays"] and counts["path_inst"] == 0
+
+
+@pytest.mark.parametrize("fmt", [1, 2])
+def test_retired_node_formats_are_refused(fmt):
+    """formats 1 and 2 (the fp32 formats F4 / F2) are retired: CTL_ERR_UNSUPPORTED with a message that says so and points to EXPERIMENTS.md, from both host entry points;
+    a format that never existed stays CTL_ERR_INVALID"""
+    sc = scenes.cornell_box(32, 32, glass_sphere=True)          # (the description points into the scene object: keep it alive)
+    d = sc.desc
+    for call in (lambda f: api.FlatBvh(d, f), lambda f: api.flatten_probe(d, f)):
+        with pytest.raises(api.CtlError) as e:
+            call(fmt)
+        assert e.value.code == -5 and "retired" in str(e.value) and "EXPERIMENTS.md" in str(e.value)
+        with pytest.raises(api.CtlError) as e:
+            call(4)
+        assert e.value.code == -1
 
 
 def test_sah_optimal_collapse_builds_a_valid_smaller_tree():
