@@ -9,6 +9,7 @@ from .api import (  # noqa: F401
     lib, CtlError, DynamicScene, Scene, Image, Comm, WavefrontPathTracer, PathTracer, PrimTracer, PathTrace_DrawMode, SequenceGenerator,
     ctl_material, ctl_texture, ctl_light, ctl_sensor, ctl_scene_desc, ctl_ray, ctl_hit, ctl_pixel_data,
     ctl_tracer_stats, ctl_traversal_counts, ctl_float4x4,
-    diffuse, dielectric, conductor, roughconductor, device_count, intersect, intersect_count,
+    diffuse, dielectric, conductor, roughconductor, device_count, intersect, intersect_count, intersect_ex, intersect_pair,
+    traversal_stack_histogram, traversal_lds_rows,
     FlatBvh, scene_desc_diff, DIFF_CAMERA, DIFF_MATERIALS, DIFF_LIGHTS, DIFF_TRANSFORMS, DIFF_TOPOLOGY,
 )

@@ -788,6 +788,53 @@ def trace_single_ray(scene, origin, direction, tmin=0.0, tmax=3.402823466e+38):
     return hit[0]
 
 
+ISECT_ANY_HIT, ISECT_ALPHA, ISECT_SINGLE = 1, 2, 4   # CTL_ISECT_*
+_HIT_DTYPE = [("dist", "f4"), ("node_idx", "i4"), ("tri_idx", "i4"), ("u", "f4"), ("v", "f4")]
+lib.ctl_intersect_ex.argtypes = [C.c_void_p, C.c_void_p, u32, C.c_void_p, u32]
+lib.ctl_intersect_pair.argtypes = [C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, u32]
+lib.ctl_traversal_stack_histogram.argtypes = [C.c_void_p, u32, C.c_int]
+lib.ctl_traversal_lds_rows.argtypes = [C.c_void_p]
+
+
+def intersect_ex(scene, rays, any_hit=False, alpha=False, single=False, flags=None):
+    """ctl_intersect_ex (TEST INFRASTRUCTURE): intersect() with a choice of kernel variant — alpha: the alpha-testing kernels (when the scene has alpha maps); single: the
+    single-ray traversal of the PathTracer / PrimTracer plugins (flattened scenes only; it alpha-tests whenever the scene has alpha maps).  flags: the raw CTL_ISECT_* word
+    instead of the three booleans.  A slot no kernel wrote comes back with tri_idx = node_idx = -2."""
+    r, rp = _rays_struct(rays)
+    hits = np.zeros(len(r), dtype=_HIT_DTYPE)
+    if flags is None:
+        flags = (ISECT_ANY_HIT if any_hit else 0) | (ISECT_ALPHA if alpha else 0) | (ISECT_SINGLE if single else 0)
+    _check(lib.ctl_intersect_ex(scene._h, rp, u32(len(r)), hits.ctypes.data_as(C.c_void_p), u32(flags)))
+    return hits
+
+
+def intersect_pair(scene, rays, shadow_rays, alpha=False, flags=None):
+    """ctl_intersect_pair (TEST INFRASTRUCTURE): the tracer's fused launch — closest hits of `rays`, then occlusion of `shadow_rays`, in one persistent launch.
+    Returns (hits, occ): the record array of intersect() and a uint32 array (1 occluded, 0 free; 0xffffffff: the slot was never written)."""
+    r, rp = _rays_struct(rays)
+    s, sp = _rays_struct(shadow_rays)
+    hits = np.zeros(len(r), dtype=_HIT_DTYPE); occ = np.zeros(len(s), np.uint32)
+    if flags is None:
+        flags = ISECT_ALPHA if alpha else 0
+    _check(lib.ctl_intersect_pair(scene._h, rp, u32(len(r)), hits.ctypes.data_as(C.c_void_p), sp, u32(len(s)), occ.ctypes.data_as(C.c_void_p), u32(flags)))
+    return hits, occ
+
+
+def traversal_stack_histogram(reset=False, n_bins=96):
+    """ctl_traversal_stack_histogram: rays of the counting traversals of flattened scenes so far (intersect_count, setCounting) by the deepest stack entry they used,
+    as a uint64 array of n_bins (the last bin collects everything deeper); reset clears the counters after reading them"""
+    h = np.zeros(n_bins, np.uint64)
+    _check(lib.ctl_traversal_stack_histogram(h.ctypes.data_as(C.c_void_p), u32(n_bins), 1 if reset else 0))
+    return h
+
+
+def traversal_lds_rows():
+    """ctl_traversal_lds_rows: stack entries a lane keeps in LDS, by kernel family (deeper entries live in scratch)"""
+    r = (u32 * 5)()
+    _check(lib.ctl_traversal_lds_rows(r))
+    return dict(zip(("two_level", "q4", "q8", "single_q4", "single_q8"), (int(x) for x in r)))
+
+
 def intersect_count(scene, rays, any_hit=False):
     r, rp = _rays_struct(rays)
     c = ctl_traversal_counts()

@@ -14,6 +14,7 @@
 #include <memory>
 #include "scene_cache.h"
 #include "shading_eval.h"
+#include "traversal_probe.h"
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -527,15 +528,18 @@ int ctl_tracer_read_pixel_variance(ctl_tracer* t, float* host_out) { CTL_REQUIRE
 int ctl_tracer_set_counting(ctl_tracer* t, int on) { CTL_REQUIRE(t, "null tracer"); CTL_TRY t->t->setCounting(on != 0); CTL_CATCH }
 
 // ---- intersect (row a7 on its own)
-static void run_intersect(Scene& sc, const float4* d_ro, const float4* d_rd, uint32_t n, float4* d_hit, int* d_node, uint32_t* d_occ, int any_hit, unsigned long long* d_counts, float* ms_out) {
+// alpha: the kernels alpha-test candidate hits, under the tracer's rule (the scene has alpha maps); single: the single-ray traversal (traversal_probe.h) instead of the wavefront kernel
+static void run_intersect(Scene& sc, const float4* d_ro, const float4* d_rd, uint32_t n, float4* d_hit, int* d_node, uint32_t* d_occ, int any_hit, unsigned long long* d_counts, float* ms_out,
+                          bool alpha = false, bool single = false) {
     dbuf<uint32_t> ctl; ctl.alloc(2);
     uint32_t h[2] = { n, 0 };
     CTL_HIP(hipMemcpy(ctl.p, h, sizeof(h), hipMemcpyHostToDevice));
     int dev = 0; hipDeviceProp_t prop; CTL_HIP(hipGetDevice(&dev)); CTL_HIP(hipGetDeviceProperties(&prop, dev));
-    launch_ctx lc{ nullptr, prop.multiProcessorCount * 8 };
+    launch_ctx lc{ nullptr, prop.multiProcessorCount * 8, alpha && sc.S.alpha_maps != 0 };
     hipEvent_t a, b; CTL_HIP(hipEventCreate(&a)); CTL_HIP(hipEventCreate(&b));
     CTL_HIP(hipEventRecord(a, nullptr));
-    if (d_counts) launch_intersect_count(lc, sc.S, d_ro, d_rd, ctl.p, ctl.p + 1, d_hit, d_node, nullptr, any_hit, d_counts);
+    if (single) launch_trace_single_probe(lc, sc.S, d_ro, d_rd, n, d_hit, d_node, any_hit);
+    else if (d_counts) launch_intersect_count(lc, sc.S, d_ro, d_rd, ctl.p, ctl.p + 1, d_hit, d_node, nullptr, any_hit, d_counts);
     else if (any_hit) launch_intersect_any(lc, sc.S, d_ro, d_rd, ctl.p, ctl.p + 1, d_occ, d_hit, d_node);
     else launch_intersect_closest(lc, sc.S, d_ro, d_rd, ctl.p, ctl.p + 1, d_hit, d_node);
     CTL_HIP(hipEventRecord(b, nullptr));
@@ -545,19 +549,32 @@ static void run_intersect(Scene& sc, const float4* d_ro, const float4* d_rd, uin
     if (ms_out) *ms_out = ms;
     (void)hipEventDestroy(a); (void)hipEventDestroy(b);
 }
-static void intersect_host(Scene& sc, const ctl_ray* rays, uint32_t n, ctl_hit* hits, int any_hit, ctl_traversal_counts* counts) {
+// the entry points that exist for the tests fill their device outputs with values no kernel writes, so that a ray that was never traced shows in the result
+constexpr int kPoisonIndex = -2; constexpr uint32_t kPoisonOcc = 0xffffffffu;
+static void upload_rays(const ctl_ray* rays, uint32_t n, dbuf<float4>& d_ro, dbuf<float4>& d_rd) {
     std::vector<float4> ro(n), rd(n);
     for (uint32_t i = 0; i < n; i++) { ro[i] = make_float4(rays[i].a[0], rays[i].a[1], rays[i].a[2], rays[i].a[3]); rd[i] = make_float4(rays[i].b[0], rays[i].b[1], rays[i].b[2], rays[i].b[3]); }
+    d_ro.upload(ro.data(), n); d_rd.upload(rd.data(), n);
+    CTL_HIP(hipStreamSynchronize(nullptr));   // the staging vectors end here
+}
+static void poison_hits(uint32_t n, dbuf<float4>& d_hit, dbuf<int>& d_node) {
+    const std::vector<float4> hh(n, make_float4(0.0f, 0.0f, 0.0f, __builtin_bit_cast(float, kPoisonIndex))); const std::vector<int> hn(n, kPoisonIndex);
+    d_hit.upload(hh.data(), n); d_node.upload(hn.data(), n);
+    CTL_HIP(hipStreamSynchronize(nullptr));
+}
+static void download_hits(uint32_t n, const dbuf<float4>& d_hit, const dbuf<int>& d_node, ctl_hit* hits) {
+    std::vector<float4> hh(n); std::vector<int> hn(n);
+    CTL_HIP(hipMemcpy(hh.data(), d_hit.p, (size_t)n * 16, hipMemcpyDeviceToHost)); CTL_HIP(hipMemcpy(hn.data(), d_node.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n; i++) { hits[i].dist = hh[i].x; hits[i].u = hh[i].y; hits[i].v = hh[i].z; hits[i].tri_idx = __builtin_bit_cast(int, hh[i].w); hits[i].node_idx = hn[i]; }
+}
+static void intersect_host(Scene& sc, const ctl_ray* rays, uint32_t n, ctl_hit* hits, int any_hit, ctl_traversal_counts* counts, bool alpha = false, bool single = false, bool poison = false) {
     dbuf<float4> d_ro, d_rd, d_hit; dbuf<int> d_node; dbuf<unsigned long long> d_cnt;
-    d_ro.upload(ro.data(), n); d_rd.upload(rd.data(), n); d_hit.alloc(n); d_node.alloc(n);
+    upload_rays(rays, n, d_ro, d_rd);
+    if (poison) poison_hits(n, d_hit, d_node); else { d_hit.alloc(n); d_node.alloc(n); }
     if (counts) { d_cnt.alloc(5); CTL_HIP(hipMemset(d_cnt.p, 0, 40)); }
     CTL_HIP(hipDeviceSynchronize());
-    run_intersect(sc, d_ro.p, d_rd.p, n, d_hit.p, d_node.p, nullptr, any_hit, counts ? d_cnt.p : nullptr, nullptr);
-    if (hits) {
-        std::vector<float4> hh(n); std::vector<int> hn(n);
-        CTL_HIP(hipMemcpy(hh.data(), d_hit.p, (size_t)n * 16, hipMemcpyDeviceToHost)); CTL_HIP(hipMemcpy(hn.data(), d_node.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-        for (uint32_t i = 0; i < n; i++) { hits[i].dist = hh[i].x; hits[i].u = hh[i].y; hits[i].v = hh[i].z; hits[i].tri_idx = __builtin_bit_cast(int, hh[i].w); hits[i].node_idx = hn[i]; }
-    }
+    run_intersect(sc, d_ro.p, d_rd.p, n, d_hit.p, d_node.p, nullptr, any_hit, counts ? d_cnt.p : nullptr, nullptr, alpha, single);
+    if (hits) download_hits(n, d_hit, d_node, hits);
     if (counts) { unsigned long long c[5]; CTL_HIP(hipMemcpy(c, d_cnt.p, 40, hipMemcpyDeviceToHost)); *counts = ctl_traversal_counts{ c[0], c[1], c[2], c[3], c[4] }; }
 }
 int ctl_trace_single_ray(ctl_scene* s, const ctl_ray* ray, ctl_hit* hit_out) { CTL_REQUIRE(s && ray && hit_out, "null argument"); return ctl_intersect(s, ray, 1, hit_out, 0); }
@@ -570,6 +587,37 @@ int ctl_intersect_count(ctl_scene* s, const ctl_ray* rays, uint32_t n, int any_h
     CTL_REQUIRE(s && rays && out, "null argument");
     CTL_TRY intersect_host(s->s, rays, n, nullptr, any_hit, out); CTL_CATCH
 }
+int ctl_intersect_ex(ctl_scene* s, const ctl_ray* rays, uint32_t n, ctl_hit* hits, uint32_t flags) {
+    CTL_REQUIRE(s && (rays || !n) && (hits || !n), "null argument");
+    CTL_REQUIRE(!(flags & ~(uint32_t)(CTL_ISECT_ANY_HIT | CTL_ISECT_ALPHA | CTL_ISECT_SINGLE)), "ctl_intersect_ex: unknown flag bits");
+    // (the PathTracer's own refusal, megakernel.hip InitializeScene: its traversal walks the flattened tree only)
+    if ((flags & CTL_ISECT_SINGLE) && !s->s.S.flat_nodes) return fail(CTL_ERR_UNSUPPORTED, "ctl_intersect_ex: CTL_ISECT_SINGLE needs a scene created with CTL_SCENE_FLATTEN");
+    if (!n) return CTL_OK;
+    CTL_TRY intersect_host(s->s, rays, n, hits, (flags & CTL_ISECT_ANY_HIT) ? 1 : 0, nullptr, (flags & CTL_ISECT_ALPHA) != 0, (flags & CTL_ISECT_SINGLE) != 0, true); CTL_CATCH
+}
+int ctl_intersect_pair(ctl_scene* s, const ctl_ray* rays, uint32_t n, ctl_hit* hits, const ctl_ray* shadow_rays, uint32_t sn, uint32_t* occ_out, uint32_t flags) {
+    CTL_REQUIRE(s && (rays || !n) && (hits || !n) && (shadow_rays || !sn) && (occ_out || !sn), "null argument");
+    CTL_REQUIRE(!(flags & ~(uint32_t)CTL_ISECT_ALPHA), "ctl_intersect_pair: only CTL_ISECT_ALPHA is accepted");
+    if (!n && !sn) return CTL_OK;
+    CTL_TRY
+        Scene& sc = s->s;
+        dbuf<float4> d_ro, d_rd, d_sro, d_srd, d_hit; dbuf<int> d_node; dbuf<uint32_t> d_occ, ctl;
+        upload_rays(rays, n, d_ro, d_rd); upload_rays(shadow_rays, sn, d_sro, d_srd);
+        poison_hits(n, d_hit, d_node);
+        const std::vector<uint32_t> po(sn, kPoisonOcc); d_occ.upload(po.data(), sn);
+        const uint32_t h[4] = { n, sn, 0u, 0u };   // the two queue lengths, then one ray cursor per queue, as tracer.hip hands them to the fused launch
+        ctl.upload(h, 4);
+        int dev = 0; hipDeviceProp_t prop; CTL_HIP(hipGetDevice(&dev)); CTL_HIP(hipGetDeviceProperties(&prop, dev));
+        const launch_ctx lc{ nullptr, prop.multiProcessorCount * 8, (flags & CTL_ISECT_ALPHA) != 0 && sc.S.alpha_maps != 0 };
+        CTL_HIP(hipDeviceSynchronize());
+        launch_intersect_pair(lc, sc.S, d_ro.p, d_rd.p, ctl.p, ctl.p + 2, d_hit.p, d_node.p, d_sro.p, d_srd.p, ctl.p + 1, ctl.p + 3, d_occ.p);
+        CTL_HIP(hipDeviceSynchronize());
+        CTL_HIP(hipGetLastError());
+        if (n) download_hits(n, d_hit, d_node, hits);
+        if (sn) CTL_HIP(hipMemcpy(occ_out, d_occ.p, (size_t)sn * 4, hipMemcpyDeviceToHost));
+    CTL_CATCH
+}
+int ctl_traversal_lds_rows(uint32_t out5[5]) { CTL_REQUIRE(out5, "null argument"); traversal_lds_rows(out5); return CTL_OK; }
 int ctl_intersect_device(ctl_scene* s, const void* d_ray_o, const void* d_ray_d, uint32_t n, void* d_hit4, void* d_hit_node, int any_hit, float* ms_out) {
     CTL_REQUIRE(s && d_ray_o && d_ray_d && d_hit4 && d_hit_node, "null argument");
     CTL_TRY run_intersect(s->s, (const float4*)d_ray_o, (const float4*)d_ray_d, n, (float4*)d_hit4, (int*)d_hit_node, nullptr, any_hit, nullptr, ms_out); CTL_CATCH

@@ -599,8 +599,24 @@ int ctl_tracer_set_counting(ctl_tracer* t, int on);
 /* __internal__IntersectBuffers (Kernel/TraceHelper.cu:736-746): n rays -> n hits; host pointers.
  * any_hit = 1 selects intersectKernel<true>. */
 int ctl_intersect(ctl_scene* s, const ctl_ray* rays, uint32_t n, ctl_hit* hits, int any_hit);
-/* TracerBase::TraceSingleRay(Ray, DynamicScene*) (Kernel/Tracer.cu:74-78): the closest hit of one ray (tmin = the scene's ray epsilon as the caller sets it in `ray`). */
+/* TracerBase::TraceSingleRay(Ray, DynamicScene*) (Kernel/Tracer.cu:74-78): the closest hit of one ray (tmin = the scene's ray epsilon as the caller sets it in `ray`).
+ * It is ctl_intersect with n = 1, i.e. it runs the WAVEFRONT kernel; the single-ray traversal the PathTracer and PrimTracer plugins run inside their kernels
+ * (csrc/single_ray.h) is reached with ctl_intersect_ex and CTL_ISECT_SINGLE. */
 int ctl_trace_single_ray(ctl_scene* s, const ctl_ray* ray, ctl_hit* hit_out);
+/* TEST INFRASTRUCTURE: every traversal kernel variant on a list of rays, so that the tests hold each to the oracle ray by ray (tests/test_gpu_traversal_variants.py).
+ * ctl_intersect_ex is ctl_intersect with a choice of variant:
+ *   CTL_ISECT_ANY_HIT  as any_hit of ctl_intersect
+ *   CTL_ISECT_ALPHA    the kernels that run Material::AlphaTest on candidate hits, under the tracers' rule: only when the scene has alpha maps
+ *   CTL_ISECT_SINGLE   the single-ray traversal (csrc/single_ray.h trace_single, what the PathTracer and PrimTracer plugins call per lane) from a probe kernel with one lane
+ *                      per ray.  It alpha-tests whenever the scene has alpha maps, with or without CTL_ISECT_ALPHA, and needs a scene created with CTL_SCENE_FLATTEN
+ *                      (CTL_ERR_UNSUPPORTED otherwise, as the PathTracer answers).
+ * ctl_intersect_pair is the tracer's fused launch (FuseTraversal): closest hits of `rays` into `hits`, then occlusion (1 / 0) of `shadow_rays` into `occ_out`, in ONE
+ * persistent launch with a ray cursor per queue.  flags: CTL_ISECT_ALPHA or 0.  n == 0 or sn == 0 is legal and still launches while the other is not.
+ * Both fill their device outputs before the launch with values no kernel writes (triangle -2, node -2, occlusion 0xffffffff): a ray that was never traced shows in the
+ * result.  Unknown flag bits and null pointers with a non-zero count are refused (CTL_ERR_INVALID) before anything is launched. */
+enum { CTL_ISECT_ANY_HIT = 1, CTL_ISECT_ALPHA = 2, CTL_ISECT_SINGLE = 4 };
+int ctl_intersect_ex(ctl_scene* s, const ctl_ray* rays, uint32_t n, ctl_hit* hits, uint32_t flags);
+int ctl_intersect_pair(ctl_scene* s, const ctl_ray* rays, uint32_t n, ctl_hit* hits, const ctl_ray* shadow_rays, uint32_t sn, uint32_t* occ_out, uint32_t flags);
 /* device-pointer variant (the layout the tracer itself uses): d_ray_o[n], d_ray_d[n] = float4 (origin,tmin) / (direction,tmax);
  * d_hit4[n] = float4 (t, u, v, triangle index bits, -1 = miss); d_hit_node[n] = int32.  Synchronous; ms_out (may be NULL) =
  * HIP-event time of the kernel launch. */
@@ -610,9 +626,11 @@ int ctl_intersect_device(ctl_scene* s, const void* d_ray_o, const void* d_ray_d,
 int ctl_intersect_count(ctl_scene* s, const ctl_ray* rays, uint32_t n, int any_hit, ctl_traversal_counts* out);
 
 /* Measurement: rays of all COUNTING traversals so far (ctl_intersect_count, ctl_tracer_set_counting) over the flattened BVH, by the deepest traversal-stack entry they
- * used; bin n_bins - 1 collects everything deeper.  The kernels keep the first 19 entries of a lane in LDS and deeper ones in scratch (csrc/traverse_flat.h): the
- * histogram says how often that happens.  reset != 0 clears it. */
+ * used; bin n_bins - 1 collects everything deeper.  The kernels keep the first entries of a lane in LDS and deeper ones in scratch (csrc/traverse_flat.h): the
+ * histogram says how often that happens.  reset != 0 clears it.
+ * ctl_traversal_lds_rows: how many entries that is, out5 = two-level kernel, Q4, Q8 (sibling groups), single-ray Q4, single-ray Q8 (groups); host only. */
 int ctl_traversal_stack_histogram(uint64_t* out, uint32_t n_bins, int reset);
+int ctl_traversal_lds_rows(uint32_t out5[5]);
 
 /* The shared fp32 transcendental functions of the shading code (cudatracerlib_amd/csrc/ctl_fmath.h; the oracle's -DORC_SHARED_MATH build runs the same source):
  * which = 0 sin, 1 cos, 2 tan, 3 acos, 4 atan, 5 atan2(x, y), 6 exp, 7 log, 8 log2, 9 pow(x, y); on_device = 0 evaluates on the host, 1 in a kernel — the two are

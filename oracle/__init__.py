@@ -45,6 +45,7 @@ def load(shared_math=False):
     o.orc_render.restype = u64
     o.orc_render.argtypes = [C.c_void_p, u32, u32, u32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, u32, u32, C.c_int]
     o.orc_intersect.argtypes = [C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    o.orc_intersect_ex.argtypes = [C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]; o.orc_intersect_ex.restype = None
     o.orc_set_flat_bvh.argtypes = [C.c_void_p]; o.orc_set_flat_bvh.restype = None
     o.orc_compute_partials.argtypes = [C.c_void_p] * 8
     o.orc_sensor_sample_ray_differential.argtypes = [C.c_void_p, f32, f32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -154,20 +155,23 @@ class Oracle:
         self.shared_math = shared_math
         self.lib = load(shared_math)
 
-    def intersect(self, desc, rays, any_hit=False, count=False, threads=8, alpha_test=False, flat=None, half_host_quirk=False):
+    def intersect(self, desc, rays, any_hit=False, count=False, threads=8, alpha_test=False, flat=None, half_host_quirk=False, stack_use=False):
         """flat: a ctl_flat_bvh_desc (cudatracerlib_amd.FlatBvh(...).desc) -> traverse the product's flattened BVH instead of the two-level structure.
-        half_host_quirk: the alpha test decodes the triangles' uv with half::ToFloat's host branch (as the reference compiled for the host does)"""
+        half_host_quirk: the alpha test decodes the triangles' uv with half::ToFloat's host branch (as the reference compiled for the host does)
+        stack_use: also return an int32 array (n, 2): per ray the deepest traversal-stack index it used and the index from which the subtree holding the reported hit was popped
+        (-1: reached by descent alone, or a miss), under the kernels' stack discipline of the structure walked (ocore.h StackUse).  Returned last."""
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
         hits = np.zeros(len(r), dtype=[("dist", "f4"), ("node_idx", "i4"), ("tri_idx", "i4"), ("u", "f4"), ("v", "f4")])
         cnt = (u64 * 5)()
         self.lib.orc_set_flat_bvh(C.addressof(flat) if flat is not None else None)
         try:
-            self.lib.orc_intersect(C.addressof(desc), r.ctypes.data, len(r), hits.ctypes.data, (1 if any_hit else 0) | (2 if alpha_test else 0) | (4 if half_host_quirk else 0), C.addressof(cnt) if count else None, threads)
+            su = np.zeros((len(r), 2), np.int32) if stack_use else None
+            self.lib.orc_intersect_ex(C.addressof(desc), r.ctypes.data, len(r), hits.ctypes.data, (1 if any_hit else 0) | (2 if alpha_test else 0) | (4 if half_host_quirk else 0), C.addressof(cnt) if count else None, threads,
+                                      su.ctypes.data if stack_use else None)
         finally:
             self.lib.orc_set_flat_bvh(None)
-        if count:
-            return hits, dict(n_inner=cnt[0], n_tri=cnt[1], n_inst=cnt[2])
-        return hits
+        out = (hits,) + ((dict(n_inner=cnt[0], n_tri=cnt[1], n_inst=cnt[2]),) if count else ()) + ((su,) if stack_use else ())
+        return out if len(out) > 1 else hits
 
     def render(self, desc, width, height, n_passes=1, tables=None, direct=True, max_path_length=8, rr_start=5, threads=8, rows=None, half_host_quirk=False, alpha_test=False, block_counts=None,
                flat=None, counts=None, partials=False, regularization=False, wavefront_rules=False, u16_barycentrics=False, omit_last_nee=False, zero_stop=None, pixel_rays=None):

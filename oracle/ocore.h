@@ -64,6 +64,11 @@ struct Hit {   // Kernel/TraceResult.h:18-35
     bool hasHit() const { return tri != UINT32_MAX; }
     void init() { dist = FLT_MAX; tri = UINT32_MAX; node = UINT32_MAX; u = v = 0; }
 };
+// Which traversal-stack entries a ray used, under the kernels' stack discipline (flat Q4: every entered child but the nearest is pushed; Q8: one sibling group per level while
+// siblings wait; two-level: top-level entries, the instance's exit marker, then the mesh's entries, in one stack).  deepest: the highest index written.  hit_from: the index of the
+// entry popped last before the reported hit was accepted, i.e. the entry whose subtree holds the hit; -1 when the hit was reached by descent alone or the ray misses.
+// The kernels postpone leaves, so their hit distance can shrink later than here and they may go deeper: these figures qualify a test input, they are not what a kernel must report.
+struct StackUse { int deepest = 0, hit_from = -1, last_pop = -1; void push(int i) { if (i > deepest) deepest = i; } void pop(int i) { last_pop = i; } void accept() { hit_from = last_pop; } };
 struct TravCounts { uint64_t n_inner = 0, n_tri = 0, n_inst = 0; std::vector<uint32_t>* node_log = nullptr; std::vector<uint32_t>* entry_log = nullptr; };   // logs (flattened Q4 traversal only): which node / leaf entry each step looked at (orc_packet_union_probe)
 
 // Math/MathFunc.h:443-444 — integer min/max on float bit patterns; for tmin >= 0 and non-NaN inputs the decision
@@ -81,16 +86,17 @@ inline float spanEnd(float a0, float a1, float b0, float b1, float c0, float c1,
 // wavefront path (TraceHelper.cu:469-476) — only culling differs, never the accepted hit.
 template <typename CLB>
 inline bool tracerayTemplate(V3 ori, V3 dir, float& rayT, float node_tmin, const CLB& clb, const float* nodes4, int bvhNodesOffset,
-                             int startNode, TravCounts* cnt, const bool* stop = nullptr) {
-    if (startNode < 0) return clb(~startNode);
+                             int startNode, TravCounts* cnt, const bool* stop = nullptr, StackUse* su = nullptr, int su_base = 0) {
+    if (startNode < 0) return clb(~startNode, su_base);
     bool found = false;
-    int stack[64]; stack[0] = EntrypointSentinel;
+    int stack[128]; stack[0] = EntrypointSentinel;   // (the product accepts scenes up to 96 entries deep, csrc/device_scene.h kStackSize)
     const float ooeps = exp2f(-80.0f);
     float idirx = 1.0f / (fabsf(dir.x) > ooeps ? dir.x : copysign_bits(ooeps, dir.x));
     float idiry = 1.0f / (fabsf(dir.y) > ooeps ? dir.y : copysign_bits(ooeps, dir.y));
     float idirz = 1.0f / (fabsf(dir.z) > ooeps ? dir.z : copysign_bits(ooeps, dir.z));
     float oodx = ori.x * idirx, oody = ori.y * idiry, oodz = ori.z * idirz;
     int sp = 0, leafAddr = 0, nodeAddr = startNode;
+    int leaf_from = -1, node_from = -1;   // StackUse: the entry popped last before the postponed leaf / the node in hand was reached (the reference's walk holds one leaf back while it pops on)
     while (nodeAddr != EntrypointSentinel && !(stop && *stop)) {
         while ((unsigned)nodeAddr < (unsigned)EntrypointSentinel) {
             const float* n = nodes4 + (size_t)(bvhNodesOffset + nodeAddr) * 4;
@@ -104,18 +110,20 @@ inline bool tracerayTemplate(V3 ori, V3 dir, float& rayT, float node_tmin, const
             const float c1max = spanEnd(c1lox, c1hix, c1loy, c1hiy, c1loz, c1hiz, rayT);
             int cx, cy; std::memcpy(&cx, n + 12, 4); std::memcpy(&cy, n + 13, 4);
             bool swp = (c1min < c0min), t0 = (c0max >= c0min), t1 = (c1max >= c1min);
-            if (!t0 && !t1) { nodeAddr = stack[sp]; sp--; }
+            if (!t0 && !t1) { if (su) su->pop(su_base + sp); nodeAddr = stack[sp]; sp--; }
             else {
                 nodeAddr = t0 ? cx : cy;
-                if (t0 && t1) { if (swp) std::swap(nodeAddr, cy); sp++; stack[sp] = cy; }
+                if (t0 && t1) { if (swp) std::swap(nodeAddr, cy); sp++; stack[sp] = cy; if (su) su->push(su_base + sp); }
             }
-            if (nodeAddr < 0 && leafAddr >= 0) { leafAddr = nodeAddr; nodeAddr = stack[sp]; sp--; }
+            if (nodeAddr < 0 && leafAddr >= 0) { leafAddr = nodeAddr; leaf_from = su ? su->last_pop : -1; if (su) su->pop(su_base + sp); nodeAddr = stack[sp]; sp--; }
             if (!(leafAddr >= 0)) break;   // host: mask = leafAddr >= 0 (BVHTraversal.h:209-213)
         }
         while (leafAddr < 0 && !(stop && *stop)) {
-            found |= clb(~leafAddr);
-            leafAddr = nodeAddr;
-            if (nodeAddr < 0) { nodeAddr = stack[sp]; sp--; }
+            if (su) { node_from = su->last_pop; su->last_pop = leaf_from; }   // the leaf is tested as reached from ITS entry, not from the one popped since
+            found |= clb(~leafAddr, su_base + sp);
+            if (su) su->last_pop = node_from;
+            leafAddr = nodeAddr; leaf_from = node_from;
+            if (nodeAddr < 0) { if (su) su->pop(su_base + sp); nodeAddr = stack[sp]; sp--; }
         }
     }
     return found;
@@ -148,7 +156,7 @@ inline const uint32_t g_top_probe_limits[8] = { 85u, 256u, 341u, 512u, 1365u, 54
 // The product's 8-wide node format (CTL_FLAT_Q8, cudatracerlib_amd/csrc/flat8.h): octant-ordered slots, one sibling group per level on the stack, the leaf slots a step hits
 // tested before its inner children are entered.  Same culling arithmetic as the 4-wide mirror below (8-bit boxes, the oriented slab as a fourth axis), restated.
 // $ORC_Q8_ORDER = dist (what-if): children nearest first by entry distance instead of by octant, to price the octant order.
-inline bool traceRayFlat8(const Scene& S, V3 ori, V3 dir, float tmin_tri, float tmax, bool any_hit, float node_tmin, Hit& res, TravCounts* cnt) {
+inline bool traceRayFlat8(const Scene& S, V3 ori, V3 dir, float tmin_tri, float tmax, bool any_hit, float node_tmin, Hit& res, TravCounts* cnt, StackUse* su = nullptr) {
     const ctl_scene_desc& g = S.d; const ctl_flat_bvh_desc& F = *S.flat;
     res.init(); res.dist = tmax;
     if (!F.n_nodes || !F.n_leaves) return false;
@@ -213,6 +221,7 @@ inline bool traceRayFlat8(const Scene& S, V3 ori, V3 dir, float tmin_tri, float 
             float t, u, v;
             if (woopIntersect(wt, o, d, tmin_tri, res.dist, t, u, v) && (!S.alpha_test || alphaSurvive(S, index >> 1, nodeIdx, u, v))) {
                 res.node = nodeIdx; res.tri = index >> 1; res.u = u; res.v = v; res.dist = t; found = true;
+                if (su) su->accept();
                 if (any_hit) return true;
             }
         }
@@ -227,16 +236,16 @@ inline bool traceRayFlat8(const Scene& S, V3 ori, V3 dir, float tmin_tri, float 
             continue;
         }
         const uint32_t ordered = ctl::flat8_to_order(inner, octinv);
-        if (ordered) { if (cur.hits) stack[++sp] = cur; cur = group{ base_b, imask, ordered }; }
-        else if (!cur.hits) { if (sp == 0) return found; cur = stack[sp--]; }
+        if (ordered) { if (cur.hits) { stack[++sp] = cur; if (su) su->push(sp); } cur = group{ base_b, imask, ordered }; }
+        else if (!cur.hits) { if (sp == 0) return found; if (su) su->pop(sp); cur = stack[sp--]; }
         const uint32_t bit = 31u - (uint32_t)__builtin_clz(cur.hits); cur.hits &= ~(1u << bit);
         const uint32_t slot = bit ^ octinv;
         node = (ctl::flat8_child_node(cur.base_b, cur.imask, slot) << 1) | ((cur.base_b >> (24 + slot)) & 1u);
     }
 }
 
-inline bool traceRayFlat(const Scene& S, V3 ori, V3 dir, float tmin_tri, float tmax, bool any_hit, float node_tmin, Hit& res, TravCounts* cnt) {
-    if (S.flat->format == CTL_FLAT_Q8) return traceRayFlat8(S, ori, dir, tmin_tri, tmax, any_hit, node_tmin, res, cnt);
+inline bool traceRayFlat(const Scene& S, V3 ori, V3 dir, float tmin_tri, float tmax, bool any_hit, float node_tmin, Hit& res, TravCounts* cnt, StackUse* su = nullptr) {
+    if (S.flat->format == CTL_FLAT_Q8) return traceRayFlat8(S, ori, dir, tmin_tri, tmax, any_hit, node_tmin, res, cnt, su);
     const ctl_scene_desc& g = S.d; const ctl_flat_bvh_desc& F = *S.flat;
     res.init(); res.dist = tmax;
     if (!F.n_nodes || !F.n_leaves) return false;
@@ -250,7 +259,7 @@ inline bool traceRayFlat(const Scene& S, V3 ori, V3 dir, float tmin_tri, float t
     // ORC_STACK_CULL=1 (what-if): every pushed child carries its entry distance and a pop that lies behind the hit found meanwhile is dropped —
     // the -DCTL_STACK_DIST=1 build of git show 8bbbae7:cudatracerlib_amd/csrc/experiments/traverse_flat_variants.h, measured and not shipped
     std::vector<float> sdist(stack.size(), -INFINITY); static const bool stack_cull = getenv("ORC_STACK_CULL") != nullptr;
-    auto pop = [&]() { for (;;) { const int n = stack[sp]; const float dn = sdist[sp]; sp--; if (!stack_cull || !(dn >= res.dist)) return n; } };
+    auto pop = [&]() { for (;;) { const int n = stack[sp]; const float dn = sdist[sp]; if (su) su->pop(sp); sp--; if (!stack_cull || !(dn >= res.dist)) return n; } };
     int node = 0; bool found = false;
     while (node != EntrypointSentinel) {
         if (node >= 0) {
@@ -307,6 +316,7 @@ inline bool traceRayFlat(const Scene& S, V3 ori, V3 dir, float tmin_tri, float t
             cswap(0, 1); cswap(2, 3); cswap(0, 2); cswap(1, 3); cswap(1, 2);
             int n_hit = 0; for (int k = 0; k < 4; k++) if (dd[k] < inf) n_hit++;
             for (int i = n_hit - 1; i >= 1; i--) { stack[++sp] = c[i]; sdist[sp] = dd[i]; }
+            if (su) su->push(sp);
             node = n_hit ? c[0] : pop();
         } else {
             const uint32_t* e = leaves + (size_t)(uint32_t)(~node) * 32;   // 128 B: Woop rows a, b, c, {globalTri << 1 | last, node, 0, 0}, then a copy of the node's inverse transform
@@ -319,6 +329,7 @@ inline bool traceRayFlat(const Scene& S, V3 ori, V3 dir, float tmin_tri, float t
             float t, u, v;
             if (woopIntersect(w, o, d, tmin_tri, res.dist, t, u, v) && (!S.alpha_test || alphaSurvive(S, index >> 1, nodeIdx, u, v))) {
                 res.node = nodeIdx; res.tri = index >> 1; res.u = u; res.v = v; res.dist = t; found = true;
+                if (su) su->accept();
                 if (any_hit) return true;
             }
             node = (index & 1) ? pop() : node - 1;
@@ -327,20 +338,20 @@ inline bool traceRayFlat(const Scene& S, V3 ori, V3 dir, float tmin_tri, float t
     return found;
 }
 
-inline bool traceRay(const Scene& S, V3 ori, V3 dir, float tmin_tri, float tmax, bool any_hit, float node_tmin, Hit& res, TravCounts* cnt = nullptr) {
-    if (S.flat) return traceRayFlat(S, ori, dir, tmin_tri, tmax, any_hit, node_tmin, res, cnt);
+inline bool traceRay(const Scene& S, V3 ori, V3 dir, float tmin_tri, float tmax, bool any_hit, float node_tmin, Hit& res, TravCounts* cnt = nullptr, StackUse* su = nullptr) {
+    if (S.flat) return traceRayFlat(S, ori, dir, tmin_tri, tmax, any_hit, node_tmin, res, cnt, su);
     const ctl_scene_desc& g = S.d;
     res.init(); res.dist = tmax;
     if (!g.n_nodes) return false;
     bool stop = false;
-    auto nodeClb = [&](int nodeIdx) -> bool {
+    auto nodeClb = [&](int nodeIdx, int top_sp) -> bool {
         if (stop) return false;
         if (cnt) cnt->n_inst++;
         const ctl_node& N = g.nodes[nodeIdx];
         const ctl_kernel_mesh& mesh = g.meshes[N.mesh_index];
         M44 modl; std::memcpy(modl.d, g.node_inv_transforms[nodeIdx].m, 64);
         V3 d = transformDir(modl, dir), o = transformPoint(modl, ori);
-        auto triClb = [&](int triIdx) -> bool {
+        auto triClb = [&](int triIdx, int) -> bool {
             if (stop) return false;
             bool found = false;
             for (int triAddr = triIdx;; triAddr++) {
@@ -350,17 +361,18 @@ inline bool traceRay(const Scene& S, V3 ori, V3 dir, float tmin_tri, float tmax,
                 float t, u, v;
                 if (woopIntersect(w, o, d, tmin_tri, res.dist, t, u, v) && (!S.alpha_test || alphaSurvive(S, (index >> 1) + mesh.tri_offset, nodeIdx, u, v))) {
                     res.node = nodeIdx; res.tri = (index >> 1) + mesh.tri_offset; res.u = u; res.v = v; res.dist = t;
-                    found = true;
+                    found = true; if (su) su->accept();
                     if (any_hit) { stop = true; break; }
                 }
                 if (index & 1) break;
             }
             return found;
         };
-        return tracerayTemplate(o, d, res.dist, node_tmin, triClb, (const float*)g.bvh_nodes, mesh.bvh_node_offset, 0, cnt, &stop);
+        if (su) su->push(top_sp + 1);   // the instance's exit marker takes the entry above the top level's; the mesh's own entries follow it
+        return tracerayTemplate(o, d, res.dist, node_tmin, triClb, (const float*)g.bvh_nodes, mesh.bvh_node_offset, 0, cnt, &stop, su, top_sp + 1);
     };
     // any-hit: `stop` ends both levels as intersectKernel<true> does (TraceHelper.cu:684-688)
-    return tracerayTemplate(ori, dir, res.dist, node_tmin, nodeClb, (const float*)g.scene_bvh_nodes, 0, g.scene_start_node, cnt, &stop);
+    return tracerayTemplate(ori, dir, res.dist, node_tmin, nodeClb, (const float*)g.scene_bvh_nodes, 0, g.scene_start_node, cnt, &stop, su, 0);
 }
 // per-thread traversal counters of a render in counting mode (orc_render_counts): [0] path rays, [1] occlusion rays
 struct RenderCounts { TravCounts c[2]; uint64_t rays[2] = { 0, 0 }; };

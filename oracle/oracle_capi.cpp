@@ -119,15 +119,17 @@ void orc_sensor_sample_rays(const ctl_sensor* s, float px, float py, float ax, f
 // The arrays are the product's (ctl_flat_bvh_arrays): "the CPU restatement in counting mode with the same BVH" (SURVEY §8d).
 static const ctl_flat_bvh_desc* g_flat = nullptr;
 void orc_set_flat_bvh(const ctl_flat_bvh_desc* f) { g_flat = f; }
-void orc_intersect(const ctl_scene_desc* desc, const ctl_ray* rays, uint32_t n, ctl_hit* hits, int any_hit, ctl_traversal_counts* counts, int n_threads) {
+// stack_use2 (optional): per ray {deepest stack index used, index the subtree of the reported hit was popped from or -1} (ocore.h StackUse)
+void orc_intersect_ex(const ctl_scene_desc* desc, const ctl_ray* rays, uint32_t n, ctl_hit* hits, int any_hit, ctl_traversal_counts* counts, int n_threads, int32_t* stack_use2) {
     Scene S; S.d = *desc; S.alpha_test = (any_hit & 2) != 0; S.half_host_quirk = (any_hit & 4) != 0; any_hit &= 1; S.flat = g_flat;   // bit 2: half::ToFloat's host branch in the alpha test's uv
     if (n_threads < 1) n_threads = 1;
     std::vector<TravCounts> tc(n_threads);
     auto work = [&](int tid) {
         for (uint32_t i = tid; i < n; i += n_threads) {
-            Hit h;
+            Hit h; StackUse su;
             traceRay(S, V3(rays[i].a[0], rays[i].a[1], rays[i].a[2]), V3(rays[i].b[0], rays[i].b[1], rays[i].b[2]), rays[i].a[3], rays[i].b[3], any_hit != 0, rays[i].a[3], h,
-                     counts ? &tc[tid] : nullptr);
+                     counts ? &tc[tid] : nullptr, stack_use2 ? &su : nullptr);
+            if (stack_use2) { stack_use2[2 * i] = su.deepest; stack_use2[2 * i + 1] = h.hasHit() ? su.hit_from : -1; }
             hits[i].dist = h.dist; hits[i].node_idx = (int32_t)h.node; hits[i].tri_idx = (int32_t)h.tri; hits[i].u = h.u; hits[i].v = h.v;
         }
     };
@@ -136,6 +138,9 @@ void orc_intersect(const ctl_scene_desc* desc, const ctl_ray* rays, uint32_t n, 
     work(0);
     for (auto& t : th) t.join();
     if (counts) { counts->n_inner = counts->n_tri = counts->n_inst = 0; for (auto& c : tc) { counts->n_inner += c.n_inner; counts->n_tri += c.n_tri; counts->n_inst += c.n_inst; } }
+}
+void orc_intersect(const ctl_scene_desc* desc, const ctl_ray* rays, uint32_t n, ctl_hit* hits, int any_hit, ctl_traversal_counts* counts, int n_threads) {
+    orc_intersect_ex(desc, rays, n, hits, any_hit, counts, n_threads, nullptr);
 }
 
 // ---- first-hit ray differentials and filtered texture lookup (probes for the tests)

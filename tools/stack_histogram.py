@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Traversal-stack depth of the bench workload's rays: one counting pass of bench.py's frame (synthetic-SM 1080p depth 8 by default), then
-ctl_traversal_stack_histogram — how many rays used which deepest stack entry, and how many went past the LDS rows (csrc/traverse_flat.h kFlatLdsRows = 19)."""
-import ctypes as C, os, sys
+ctl_traversal_stack_histogram — how many rays used which deepest stack entry, and how many went past the LDS rows (csrc/traverse_flat.h kFlatLdsRows, read from the library)."""
+import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import cudatracerlib_amd as ctl
@@ -15,13 +15,11 @@ if wl == "cornell-glass": w = h = 1024
 scene = ctl.Scene(sc.desc, flatten=True)
 tr = ctl.WavefrontPathTracer(); tr.getParameters().setValue("MaxPathLength", 8); tr.Resize(w, h); tr.InitializeScene(scene)
 img = ctl.Image(w, h)
-hist = (C.c_uint64 * 96)()
-ctl.lib.ctl_traversal_stack_histogram.argtypes = [C.c_void_p, C.c_uint32, C.c_int]
-ctl.api._check(ctl.lib.ctl_traversal_stack_histogram(hist, 96, 1))
+ctl.api.traversal_stack_histogram(reset=True)
 tr.setCounting(True); tr.DoPasses(img, 1, new_trace=True)
-ctl.api._check(ctl.lib.ctl_traversal_stack_histogram(hist, 96, 1))
-a = np.array(hist[:], np.float64); n = a.sum()
+a = ctl.api.traversal_stack_histogram(reset=True).astype(np.float64); n = a.sum()
+rows = ctl.api.traversal_lds_rows()["q4"]
 print("%s: %d rays (path + shadow) of one pass; deepest stack entry used -> share of rays" % (wl, int(n)))
 for d in range(96):
     if a[d]: print("  %2d  %9d  %7.4f %%" % (d, int(a[d]), 100 * a[d] / n))
-print("rays past the 19 LDS rows (entries in scratch): %d = %.5f %%; deepest: %d" % (int(a[19:].sum()), 100 * a[19:].sum() / n, int(np.nonzero(a)[0].max())))
+print("rays past the %d LDS rows (entries in scratch): %d = %.5f %%; deepest: %d" % (rows, int(a[rows:].sum()), 100 * a[rows:].sum() / n, int(np.nonzero(a)[0].max())))
