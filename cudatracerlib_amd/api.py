@@ -117,6 +117,7 @@ lib.ctl_image_device_ptr.argtypes = [C.c_void_p]
 for _n in ("ctl_builder_destroy", "ctl_scene_destroy", "ctl_image_destroy", "ctl_tracer_destroy", "ctl_sequence_generator_destroy", "ctl_comm_destroy", "ctl_flat_bvh_destroy"):
     getattr(lib, _n).restype = None
     getattr(lib, _n).argtypes = [C.c_void_p]
+lib.ctl_builder_update_mesh.argtypes = [C.c_void_p, u32, C.c_void_p, u32, C.c_void_p, u32, C.c_void_p, C.c_void_p]
 lib.ctl_device_malloc.argtypes = [C.c_size_t, C.POINTER(C.c_void_p)]
 lib.ctl_device_free.argtypes = [C.c_void_p]
 lib.ctl_memcpy_h2d.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -557,6 +558,7 @@ class DynamicScene:
         self._h = C.c_void_p()
         _check(lib.ctl_builder_create(C.byref(self._h)))
         self.desc = None
+        self.mesh_inputs = {}   # mesh index -> dict(positions, indices, normals, uvs) as add_mesh / UpdateMesh last took them: what a caller deforms
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -577,7 +579,21 @@ class DynamicScene:
         _check(lib.ctl_builder_add_mesh(self._h, _fp(P), u32(len(P)), None if I is None else I.ctypes.data_as(C.c_void_p), u32(n_tri),
                                         None if N is None else _fp(N), None if UV is None else _fp(UV),
                                         None if TM is None else TM.ctypes.data_as(C.c_void_p), arr, u32(len(mats)), C.byref(out)))
+        self.mesh_inputs[out.value] = dict(positions=P, indices=I, normals=N, uvs=UV)
         return out.value
+
+    def UpdateMesh(self, mesh, positions, indices=None, normals=None, uvs=None):
+        """ctl_builder_update_mesh — DynamicScene::AnimateMesh (DynamicScene.cpp:450-456) for a caller that supplies the positions: new vertex arrays for `mesh`, same
+        triangle count, arguments as add_mesh.  The mesh's triangle data, Woop rows, BVH boxes and box and the area lights on its nodes follow; UpdateScene() then
+        gives the deformed description, which Scene.update applies in place (DIFF_GEOMETRY)."""
+        P = _f32(positions, (-1, 3))
+        I = None if indices is None else np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1, 3)
+        n_tri = len(P) // 3 if I is None else len(I)
+        N = None if normals is None else _f32(normals, (-1, 3))
+        UV = None if uvs is None else _f32(uvs, (-1, 2))
+        _check(lib.ctl_builder_update_mesh(self._h, u32(mesh), _fp(P), u32(len(P)), None if I is None else I.ctypes.data_as(C.c_void_p), u32(n_tri),
+                                           None if N is None else _fp(N), None if UV is None else _fp(UV)))
+        self.mesh_inputs[mesh] = dict(positions=P, indices=I, normals=N, uvs=UV)
 
     def CreateNode(self, mesh_index, to_world=None):
         """DynamicScene::CreateNode + SetNodeTransform (DynamicScene.cpp:269-346)."""
@@ -690,9 +706,10 @@ class Scene:
         _check(lib.ctl_scene_create_ex(C.byref(desc), u32(flags), C.byref(self._h)))
 
     def update(self, desc):
-        """ctl_scene_update: applies what differs between the description the scene holds and `desc` — camera, materials, lights, node transforms (the
-        flattened Q4 tree is refitted on the device) — in place and returns the DIFF_* mask.  Raises CtlError(ERR_INVALID) when the topology differs (the
-        scene is untouched; .last_mask says what was found) and CtlError(ERR_UNSUPPORTED) for a transform change on a Q8 scene.  Start the next pass with new_trace."""
+        """ctl_scene_update: applies what differs between the description the scene holds and `desc` — camera, materials, lights, node transforms, the vertex
+        values of deformed meshes (DynamicScene.UpdateMesh; the flattened Q4 tree is refitted on the device) — in place and returns the DIFF_* mask.  Raises
+        CtlError(ERR_INVALID) when the topology differs (the scene is untouched; .last_mask says what was found) and CtlError(ERR_UNSUPPORTED) for a transform or
+        geometry change on a Q8 scene.  Start the next pass with new_trace."""
         mask = u32()
         code = lib.ctl_scene_update(self._h, C.byref(desc), C.byref(mask))
         self.last_mask = mask.value
@@ -718,7 +735,7 @@ class Scene:
             self._h = None
 
 
-DIFF_CAMERA, DIFF_MATERIALS, DIFF_LIGHTS, DIFF_TRANSFORMS, DIFF_TOPOLOGY = 1, 2, 4, 8, 16   # CTL_DIFF_*
+DIFF_CAMERA, DIFF_MATERIALS, DIFF_LIGHTS, DIFF_TRANSFORMS, DIFF_TOPOLOGY, DIFF_GEOMETRY = 1, 2, 4, 8, 16, 32   # CTL_DIFF_*
 ERR_INVALID, ERR_NO_DEVICE, ERR_UNSUPPORTED = -1, -2, -5
 
 

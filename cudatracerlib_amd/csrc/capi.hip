@@ -59,6 +59,10 @@ int ctl_builder_add_mesh(ctl_builder* b, const float* positions, uint32_t n_vert
     CTL_REQUIRE(b, "null builder");
     CTL_TRY uint32_t i = b->b.add_mesh(positions, n_vert, indices, n_tri, normals, uvs, tri_material, materials, n_mat); if (mesh_index_out) *mesh_index_out = i; CTL_CATCH
 }
+int ctl_builder_update_mesh(ctl_builder* b, uint32_t mesh_index, const float* positions, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri, const float* normals, const float* uvs) {
+    CTL_REQUIRE(b, "null builder");
+    CTL_TRY b->b.update_mesh(mesh_index, positions, n_vert, indices, n_tri, normals, uvs); CTL_CATCH
+}
 int ctl_builder_set_bvh_mode(ctl_builder* b, uint32_t mode) { CTL_REQUIRE(b && mode <= CTL_BVH_BINNED, "null builder or unknown mode"); b->b.bvh_mode = mode; return CTL_OK; }
 int ctl_builder_add_node(ctl_builder* b, uint32_t mesh_index, const ctl_float4x4* to_world, uint32_t* node_index_out) {
     CTL_REQUIRE(b, "null builder");
@@ -353,6 +357,7 @@ int ctl_flat_bvh_build(const ctl_scene_desc* desc, uint32_t format, ctl_flat_bvh
     CTL_TRY
         std::unique_ptr<ctl_flat_bvh> h(new ctl_flat_bvh());
         if (!flatten_scene(*desc, h->f, (size_t)1 << 30, (int)format)) throw std::runtime_error("ctl_flat_bvh_build: nothing to flatten");
+        if (h->f.format == kFlatQ4 && h->f.refit.ready()) hash_geometry(*desc, h->f.refit.geom);   // what ctl_flat_bvh_refit tells deformed meshes by
         *out = h.release();
     CTL_CATCH
 }

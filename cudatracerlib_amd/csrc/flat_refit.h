@@ -141,7 +141,8 @@ CTL_REFIT_HD void refit_entry_box(const float wa[4], const float wb[4], const fl
 
 // One node: cb[c] = the new box of every child that exists (bit c of `exist`).  Rewrites origin, the three step exponents and the six code words the way
 // flatten.cpp chooses them — origin = the node's own box's low corner, 2^(e - 127) the smallest power of two (strictly) above extent / 255, codes
-// rounded outwards, also under the fp32 evaluation origin + step * code — and returns the node's own box.  Slots without a child keep lo = 255, hi = 0.
+// rounded outwards, also under the fp32 evaluation origin + step * code — and returns the node's own box.  Slots without a child keep lo = 255, hi = 0, and so
+// does a child whose box is inverted.
 // words[0..9]: origin x y z, meta (e x, e y, e z, mask), qlo_x, qhi_x, qlo_y, qhi_y, qlo_z, qhi_z.
 CTL_REFIT_HD void refit_node_boxes(uint32_t words[10], uint32_t exist, const refit_box cb[4], refit_box& own) {
     for (int r = 0; r < 3; r++) { own.lo[r] = kRefitBig; own.hi[r] = -kRefitBig; }
@@ -149,6 +150,10 @@ CTL_REFIT_HD void refit_node_boxes(uint32_t words[10], uint32_t exist, const ref
         if (cb[c].lo[r] < own.lo[r]) own.lo[r] = cb[c].lo[r];
         if (cb[c].hi[r] > own.hi[r]) own.hi[r] = cb[c].hi[r];
     }
+    // a child with an inverted box — a leaf slot whose entries all collapsed (singular Woop matrices after a geometry update), a node under which nothing is left — keeps
+    // the codes of a missing child on every axis: nothing reaches it, and its +-kRefitBig never enters the conversions below
+    uint32_t empty = 0u;
+    for (int c = 0; c < 4; c++) if ((exist >> c) & 1u) for (int r = 0; r < 3; r++) if (!(cb[c].lo[r] <= cb[c].hi[r])) empty |= 1u << c;
     uint32_t meta = words[3] & 0xff000000u;
     for (int k = 0; k < 3; k++) {
         const float origin = own.lo[k];
@@ -168,7 +173,7 @@ CTL_REFIT_HD void refit_node_boxes(uint32_t words[10], uint32_t exist, const ref
         uint32_t wlo = 0u, whi = 0u;
         for (int c = 0; c < 4; c++) {
             long long lo = 255, hi = 0;
-            if ((exist >> c) & 1u) {
+            if (((exist >> c) & 1u) && !((empty >> c) & 1u)) {
                 const double dl = ((double)cb[c].lo[k] - (double)origin) * istep, dh = ((double)cb[c].hi[k] - (double)origin) * istep;
                 lo = (long long)dl; if ((double)lo > dl) lo--;        // floor
                 hi = (long long)dh; if ((double)hi < dh) hi++;        // ceil

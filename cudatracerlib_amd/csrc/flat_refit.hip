@@ -2,6 +2,13 @@
 // (flatten.cpp refit_flat_scene) runs too — same functions, same order of operations, so the device tree equals the host's byte for byte
 // (tests/test_gpu_scene_update.py).
 //
+//   k_deform_entries  a geometry update (CTL_DIFF_GEOMETRY), before k_refit_entries: one lane per leaf entry; the lane of an entry whose node instances a changed mesh copies the
+//                     three Woop rows of its triangle from the two-level leaf stream — which the update has re-uploaded, so the rows are the new ones — into the first 48 B of
+//                     the entry and marks the entry as standing for its whole triangle (part_index = kRefitNoPart: its clip box was cut from the triangle as it was).  Every
+//                     other lane leaves after the 16-B load of its index / node words.  The model / alpha bits and the box of the entry are k_refit_entries' work, which runs
+//                     next in stream order and reads what this kernel wrote.  The entry -> row mapping is a table per TRIANGLE (flatten.h triangle_woop_rows: 4 B per
+//                     triangle, made from woop_index on the first geometry update) instead of a word per ENTRY kept from creation: the entries already name their triangle,
+//                     so the flattened-tree cache and the creation path stay as they are.
 //   k_refit_entries   one lane per leaf entry: rows 0..2 and w33 of the node's new inverse transform into the entry, the model / alpha bits re-stamped if asked,
 //                     the entry's new world-space box into scratch.  A lane reads the first 64 B of its 128-B entry (four 16-B loads that share one line) and writes
 //                     the second 64 B; the arithmetic — a 4 x 4 inverse in double per entry — outweighs the traffic.
@@ -15,6 +22,22 @@
 namespace ctl {
 
 namespace {
+
+__global__ void __launch_bounds__(256) k_deform_entries(refit_device R, deform_device D) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= R.n_entries) return;
+    float4* __restrict__ E = R.leaves + (size_t)i * 8;
+    const float4 q3 = E[3];
+    const uint32_t index = __float_as_uint(q3.x), node = __float_as_uint(q3.y) & 0x7fffffffu;
+    if (node >= D.n_scene_nodes || !D.node_changed[node]) return;
+    const uint32_t tri = (R.leaf_keys ? (index & 0x0fffffffu) : index) >> 1;
+    if (tri >= D.n_tris) return;   // cannot happen in a tree the update has checked; never read outside the arrays
+    const uint32_t row = D.tri_row[tri];
+    if (row >= D.n_rows) return;
+    const float4* __restrict__ W = D.leaf_tris + (size_t)row * 4;
+    E[0] = W[0]; E[1] = W[1]; E[2] = W[2];
+    R.part_index[i] = kRefitNoPart;
+}
 
 __global__ void __launch_bounds__(256) k_refit_entries(refit_device R, int boxes) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -113,6 +136,11 @@ __global__ void __launch_bounds__(256) k_refit_area(const float4* __restrict__ n
 
 }  // namespace
 
+void launch_deform_entries(hipStream_t s, const refit_device& R, const deform_device& D) {
+    if (!R.n_entries) return;
+    hipLaunchKernelGGL(k_deform_entries, dim3((R.n_entries + 255u) / 256u), dim3(256), 0, s, R, D);
+    CTL_HIP(hipGetLastError());
+}
 void launch_refit_entries(hipStream_t s, const refit_device& R, bool boxes) {
     if (!R.n_entries) return;
     hipLaunchKernelGGL(k_refit_entries, dim3((R.n_entries + 255u) / 256u), dim3(256), 0, s, R, boxes ? 1 : 0);

@@ -852,16 +852,80 @@ double flat_scene_node_area(const flat_scene& F) {
     return a;
 }
 
+void triangle_woop_rows(const ctl_scene_desc& d, std::vector<uint32_t>& tri_row) {
+    const mesh_ranges R(d);
+    tri_row.assign(d.n_tri_data, 0xffffffffu);
+    for (uint32_t m = 0; m < d.n_meshes; m++)
+        for (uint32_t w = R.woop1[m]; w-- > R.woop0[m];) {   // backwards: the first reference in stream order stays
+            const size_t at = (size_t)d.meshes[m].bvh_index_offset + (w - R.woop0[m]);
+            if (at >= d.n_woop) continue;
+            const uint64_t tri = (uint64_t)d.meshes[m].tri_offset + (d.woop_index[at].index >> 1);
+            if (tri < d.n_tri_data) tri_row[tri] = w;
+        }
+}
+
+void flat_missing_triangles(const std::vector<flat_leaf>& leaves, uint32_t index_mask, const ctl_scene_desc& d, std::vector<uint32_t>& missing) {
+    std::vector<uint8_t> has(d.n_tri_data, 0), instanced(d.n_meshes, 0);
+    for (const flat_leaf& L : leaves) { const uint32_t tri = (L.index & index_mask) >> 1; if (tri < d.n_tri_data) has[tri] = 1; }
+    for (uint32_t k = 0; k < d.n_nodes; k++) if (d.nodes[k].mesh_index < d.n_meshes) instanced[d.nodes[k].mesh_index] = 1;
+    const mesh_ranges R(d);
+    missing.clear();
+    for (uint32_t m = 0; m < d.n_meshes; m++) if (instanced[m]) for (uint32_t t = R.tri0[m]; t < R.tri1[m]; t++) if (!has[t]) missing.push_back(t);
+    std::sort(missing.begin(), missing.end());
+}
+
+int mesh_gaining_a_triangle(const ctl_scene_desc& d, const std::vector<uint32_t>& missing, const std::vector<uint32_t>& tri_row, const std::vector<uint8_t>& mesh_changed) {
+    if (missing.empty()) return -1;
+    const mesh_ranges R(d);
+    for (uint32_t m = 0; m < d.n_meshes; m++) {
+        if (!mesh_changed[m]) continue;
+        for (auto it = std::lower_bound(missing.begin(), missing.end(), R.tri0[m]); it != missing.end() && *it < R.tri1[m]; ++it) {
+            const uint32_t row = *it < tri_row.size() ? tri_row[*it] : 0xffffffffu;
+            double v[3][3];
+            if (row < d.n_woop && woop_vertices(d.woop[row], v)) return (int)m;
+        }
+    }
+    return -1;
+}
+
 // The host refit: the yardstick of the kernels in flat_refit.hip, which run the same functions of flat_refit.h in the same order.
 void refit_flat_scene(flat_scene& F, const ctl_scene_desc& d, double* area_before_after) {
     if (F.format != kFlatQ4) throw unsupported_error("refit: only the Q4 node format can be refitted");
     if (!F.refit.ready() || F.refit.part_index.size() != F.leaves.size()) throw std::runtime_error("refit: the tree carries no refit data");
     if (d.n_nodes != F.refit.xf0.size()) throw std::runtime_error("refit: the description has another number of nodes than the tree was built from");
-    if (area_before_after) area_before_after[0] = flat_scene_node_area(F);
     std::vector<double> P((size_t)d.n_nodes * 12);
     for (uint32_t k = 0; k < d.n_nodes; k++)
         if (!refit_carry_matrix(d.node_transforms[k].m, F.refit.xf0[k].m, &P[(size_t)k * 12])) throw std::runtime_error("refit: singular node transform");
     for (const flat_leaf& L : F.leaves) if (L.node >= d.n_nodes) throw std::runtime_error("refit: leaf entry out of range");
+    // deformed meshes (ctl_scene_update's CTL_DIFF_GEOMETRY): found by their value hashes; everything that can refuse runs before the first byte is written
+    std::vector<uint8_t> mesh_changed; std::vector<uint32_t> tri_row; geometry_hashes geom; bool deformed = false;
+    if (!F.refit.geom.empty()) {
+        hash_geometry(d, geom);
+        if (!geom.same_structure(F.refit.geom)) throw std::runtime_error("refit: the topology of the description differs from the one the tree was built from");
+        mesh_changed.assign(d.n_meshes, 0);
+        for (uint32_t m = 0; m < d.n_meshes; m++) if (!geom.same_values(F.refit.geom, m)) { mesh_changed[m] = 1; deformed = true; }
+    }
+    if (deformed) {
+        for (uint32_t k = 0; k < d.n_nodes; k++) if (d.nodes[k].mesh_index >= d.n_meshes) throw std::runtime_error("refit: node references a missing mesh");
+        triangle_woop_rows(d, tri_row);
+        std::vector<uint32_t> missing; flat_missing_triangles(F.leaves, 0xffffffffu, d, missing);
+        const int m = mesh_gaining_a_triangle(d, missing, tri_row, mesh_changed);
+        if (m >= 0) throw std::runtime_error("refit: mesh " + std::to_string(m) + " has a triangle that was degenerate when the tree was built and no longer is: the tree has no leaf entry for it");
+        for (const flat_leaf& L : F.leaves) if (mesh_changed[d.nodes[L.node].mesh_index] && ((L.index >> 1) >= d.n_tri_data || tri_row[L.index >> 1] >= d.n_woop)) throw std::runtime_error("refit: leaf entry without a Woop row");
+    }
+    if (area_before_after) area_before_after[0] = flat_scene_node_area(F);
+    if (deformed) {
+        parallel_for(F.leaves.size(), [&](size_t i0, size_t i1) {
+            for (size_t i = i0; i < i1; i++) {
+                flat_leaf& L = F.leaves[i];
+                if (!mesh_changed[d.nodes[L.node].mesh_index]) continue;
+                const ctl_woop_tri& w = d.woop[tri_row[L.index >> 1]];
+                std::memcpy(L.a, w.a, 16); std::memcpy(L.b, w.b, 16); std::memcpy(L.c, w.c, 16);
+                F.refit.part_index[i] = kRefitNoPart;   // the clip box was cut from the triangle as it was: the entry stands for the whole triangle from now on
+            }
+        });
+    }
+    if (!F.refit.geom.empty()) F.refit.geom = geom;
     std::vector<refit_box> ebox(F.leaves.size()), nbox(F.nodes.size());
     parallel_for(F.leaves.size(), [&](size_t i0, size_t i1) {
         for (size_t i = i0; i < i1; i++) {

@@ -9,6 +9,7 @@
 #include "../../include/ctl_amd.h"
 #include "flat8.h"
 #include "flat_refit.h"
+#include "geometry_hash.h"
 #include <vector>
 #include <cstddef>
 
@@ -104,6 +105,10 @@ struct flat_scene {
         std::vector<refit_box> part_boxes;      // world space, at creation
         std::vector<ctl_float4x4> xf0;          // node transforms at creation
         std::vector<uint32_t> level_start, level_nodes;   // node ids grouped by depth: level l = level_nodes[level_start[l] .. level_start[l + 1])
+        // the geometry of the description the tree holds (geometry_hash.h): a refit compares the per-mesh value hashes of its description with these to find the meshes
+        // whose vertices moved.  Not made by flatten_scene (a pass over every geometry array that creation makes anyway, for the scene's snapshot): ctl_flat_bvh_build
+        // and ctl_scene_read_flat_bvh fill it; while it is empty a refit takes the geometry as unchanged
+        geometry_hashes geom;
         bool ready() const { return !level_nodes.empty(); }
         size_t bytes() const { return part_index.size() * 4 + part_boxes.size() * sizeof(refit_box) + xf0.size() * sizeof(ctl_float4x4) + (level_start.size() + level_nodes.size()) * 4; }
     } refit;
@@ -117,7 +122,17 @@ struct flat_scene {
 bool flatten_scene(const ctl_scene_desc& d, flat_scene& out, size_t max_triangles, int format = kFlatQ4);
 // Refit of a Q4 tree to the node transforms of `d` (flat_refit.h): same nodes / meshes as the description the tree was built from, links, masks and memory order
 // unchanged.  area_before_after (may be null): summed surface area of the nodes' boxes before and after, a SAH proxy.  Throws when the tree cannot be refitted.
+// ... and, where F.refit.geom says that meshes of `d` have other vertex values than the tree holds (a deformed mesh: same counts, woop_index and links), to those: the
+// entries of such a mesh get their triangle's new Woop rows and stand for the WHOLE triangle from then on (part_index = kRefitNoPart) before the boxes are made.
 void refit_flat_scene(flat_scene& F, const ctl_scene_desc& d, double* area_before_after);
+// What a refit to new vertex values needs of a description, shared by the host refit and ctl_scene_update:
+//   triangle_woop_rows      per triangle of tri_data one row of the Woop stream that stands for it (the first in stream order; every reference of a triangle holds the same
+//                           rows), 0xffffffff for a triangle no leaf of its mesh BVH references
+//   flat_missing_triangles  the triangles of instanced meshes that have NO leaf entry, ascending: gather_references dropped them (singular Woop matrix)
+//   mesh_gaining_a_triangle the first changed mesh in which such a triangle is regular in `d` — the tree has no entry to put it in —, or -1
+void triangle_woop_rows(const ctl_scene_desc& d, std::vector<uint32_t>& tri_row);
+void flat_missing_triangles(const std::vector<flat_leaf>& leaves, uint32_t index_mask, const ctl_scene_desc& d, std::vector<uint32_t>& missing);
+int mesh_gaining_a_triangle(const ctl_scene_desc& d, const std::vector<uint32_t>& missing, const std::vector<uint32_t>& tri_row, const std::vector<uint8_t>& mesh_changed);
 double flat_scene_node_area(const flat_scene& F);   // Q4: sum over the nodes of the surface area of the box around their decoded child boxes
 int default_flat_format();   // kFlatQ4 unless $CTL_FLAT_FORMAT says q8 (measurement knob).  Changed with the retirement of F4 / F2: the knob's spellings f4 / f2, which made scene creation
                              // answer CTL_ERR_UNSUPPORTED, are no longer known and give kFlatQ4 like any other unknown value

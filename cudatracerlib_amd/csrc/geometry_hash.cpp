@@ -1,0 +1,60 @@
+// geometry_hash.cpp — hash_geometry / mesh_ranges (geometry_hash.h): host arithmetic over a description.
+#include "geometry_hash.h"
+#include "scene_cache.h"
+#include <algorithm>
+#include <utility>
+
+namespace ctl {
+
+namespace {
+void ranges_of(const std::vector<uint32_t>& start, uint32_t count, std::vector<uint32_t>& first, std::vector<uint32_t>& last) {
+    const size_t n = start.size();
+    std::vector<std::pair<uint32_t, uint32_t>> order(n);
+    for (size_t m = 0; m < n; m++) order[m] = { std::min(start[m], count), (uint32_t)m };
+    std::sort(order.begin(), order.end());
+    first.assign(n, 0u); last.assign(n, 0u);
+    for (size_t r = 0; r < n; r++) { first[order[r].second] = order[r].first; last[order[r].second] = r + 1 < n ? order[r + 1].first : count; }
+}
+}  // namespace
+
+mesh_ranges::mesh_ranges(const ctl_scene_desc& d) {
+    std::vector<uint32_t> s(d.n_meshes);
+    for (uint32_t m = 0; m < d.n_meshes; m++) s[m] = d.meshes[m].tri_offset;
+    ranges_of(s, d.n_tri_data, tri0, tri1);
+    for (uint32_t m = 0; m < d.n_meshes; m++) s[m] = d.meshes[m].bvh_tri_offset / 3;
+    ranges_of(s, d.n_woop, woop0, woop1);
+    for (uint32_t m = 0; m < d.n_meshes; m++) s[m] = d.meshes[m].bvh_node_offset / 4;
+    ranges_of(s, d.n_bvh_nodes, node0, node1);
+}
+
+void hash_geometry(const ctl_scene_desc& d, geometry_hashes& out) {
+    const mesh_ranges R(d);
+    content_hash S; std::vector<content_hash> V(d.n_meshes);
+    uint32_t tri_front = d.n_tri_data, woop_front = d.n_woop, node_front = d.n_bvh_nodes;
+    for (uint32_t m = 0; m < d.n_meshes; m++) { tri_front = std::min(tri_front, R.tri0[m]); woop_front = std::min(woop_front, R.woop0[m]); node_front = std::min(node_front, R.node0[m]); }
+    S.add_value(d.n_tri_data); S.add_value(d.n_woop); S.add_value(d.n_bvh_nodes);
+    if (tri_front) S.add(d.tri_data, (size_t)tri_front * sizeof(ctl_triangle_data));
+    if (woop_front) S.add(d.woop, (size_t)woop_front * sizeof(ctl_woop_tri));
+    if (node_front) S.add(d.bvh_nodes, (size_t)node_front * sizeof(ctl_bvh_node));
+    if (d.n_woop) S.add(d.woop_index, (size_t)d.n_woop * sizeof(ctl_woop_index));
+    static_assert(sizeof(ctl_bvh_node) == 64, "Aila-Laine node: 48 B of boxes, 16 B of links");
+    for (uint32_t m = 0; m < d.n_meshes; m++) {
+        content_hash& H = V[m];
+        if (R.tri1[m] > R.tri0[m]) H.add(d.tri_data + R.tri0[m], (size_t)(R.tri1[m] - R.tri0[m]) * sizeof(ctl_triangle_data));
+        if (R.woop1[m] > R.woop0[m]) H.add(d.woop + R.woop0[m], (size_t)(R.woop1[m] - R.woop0[m]) * sizeof(ctl_woop_tri));
+        for (uint32_t i = R.node0[m]; i < R.node1[m]; i++) { H.add(&d.bvh_nodes[i], 48); S.add(&d.bvh_nodes[i].child0, 16); }
+    }
+    for (uint32_t i = 0; i < d.n_images; i++) if (d.images[i].texels) S.add(d.images[i].texels, (size_t)d.images[i].width * d.images[i].height * 4);
+    const int have_rt = d.rough_transmittance ? 1 : 0; S.add_value(have_rt);
+    if (d.rough_transmittance) for (int i = 0; i < 3; i++) {
+        const ctl_rough_transmittance& t = d.rough_transmittance[i];
+        S.add_value(t.eta_samples); S.add_value(t.alpha_samples); S.add_value(t.theta_samples); S.add_value(t.eta_min); S.add_value(t.eta_max); S.add_value(t.alpha_min); S.add_value(t.alpha_max);
+        const int have = (t.trans && t.diff_trans) ? 1 : 0; S.add_value(have);
+        if (have) { S.add(t.trans, (size_t)2 * t.eta_samples * t.alpha_samples * t.theta_samples * 4); S.add(t.diff_trans, (size_t)2 * t.eta_samples * t.alpha_samples * 4); }
+    }
+    S.digest(out.structure);
+    out.values.resize((size_t)d.n_meshes * 2);
+    for (uint32_t m = 0; m < d.n_meshes; m++) V[m].digest(&out.values[(size_t)m * 2]);
+}
+
+}  // namespace ctl

@@ -1,0 +1,31 @@
+// geometry_hash.h — what a scene keeps of the geometry arrays of the description it was made from (scene_update.hip), and what ctl_scene_desc_diff tells
+// CTL_DIFF_GEOMETRY from CTL_DIFF_TOPOLOGY by: one 128-bit hash of the STRUCTURE and one per mesh of the VALUES, made in a single pass over the arrays.
+//   structure   the counts, woop_index, the links of the mesh BVH nodes (child0, child1, parent, pad), texels, transmittance tables — and whatever part of the
+//               triangle / Woop / node arrays lies in front of the first mesh's range
+//   values[m]   mesh m's ranges of tri_data and woop, and the float boxes (the first 48 B) of its bvh_nodes
+// A description whose structure hash (and counts, meshes, node -> mesh / material assignment) equals the scene's differs from it in geometry VALUES at most, and
+// the per-mesh hashes say in which meshes: the ones an update re-uploads and whose leaf entries it rewrites.
+#pragma once
+#include "../../include/ctl_amd.h"
+#include <cstdint>
+#include <vector>
+
+namespace ctl {
+
+// [first, last) of every mesh in the three geometry arrays: a mesh's range ends where the next one (by offset) starts, the last one's at the array's end;
+// offsets beyond an array are held to its end, so that a range never reaches outside
+struct mesh_ranges {
+    std::vector<uint32_t> tri0, tri1, woop0, woop1, node0, node1;
+    explicit mesh_ranges(const ctl_scene_desc& d);
+};
+
+struct geometry_hashes {
+    uint64_t structure[2] = { 0, 0 };
+    std::vector<uint64_t> values;   // two words per mesh
+    bool same_structure(const geometry_hashes& o) const { return structure[0] == o.structure[0] && structure[1] == o.structure[1] && values.size() == o.values.size(); }
+    bool same_values(const geometry_hashes& o, size_t m) const { return values[2 * m] == o.values[2 * m] && values[2 * m + 1] == o.values[2 * m + 1]; }
+    bool empty() const { return values.empty() && !structure[0] && !structure[1]; }
+};
+void hash_geometry(const ctl_scene_desc& d, geometry_hashes& out);
+
+}  // namespace ctl

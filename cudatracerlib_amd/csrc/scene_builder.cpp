@@ -117,6 +117,40 @@ static void compute_vertex_normals(const float* V, const uint32_t* I, uint32_t n
     for (uint32_t a = 0; a < nv; a++) N[a] = normalize(N[a]);
 }
 
+// Mesh::CompileMesh (Engine/Mesh.cpp:216-272): the TriangleData of every triangle into out[0 .. n_tri), its box into boxes[] and the mesh's box.  One function for
+// add_mesh and update_mesh: a mesh updated to new arrays holds the bytes a fresh add_mesh of those arrays compiles
+static void compile_triangles(const float* positions, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri, const float* normals, const float* uvs, const uint8_t* tri_material, uint32_t n_mat,
+                              bool flip_normals, bool face_normals, float max_smooth_angle, ctl_triangle_data* out, aabb* boxes, aabb& box) {
+    std::vector<f3> comp;
+    if (!normals || flip_normals) compute_vertex_normals(positions, indices, n_vert, n_tri, comp, flip_normals);   // Mesh.cpp:216-217
+    auto vidx = [&](uint32_t ti, int j) { return indices ? indices[ti * 3 + j] : ti * 3 + j; };
+    auto vtx = [&](uint32_t i) { return f3(positions[3 * i], positions[3 * i + 1], positions[3 * i + 2]); };
+    box.reset();
+    for (uint32_t ti = 0; ti < n_tri; ti++) {   // Mesh::CompileMesh (Engine/Mesh.cpp:225-272)
+        f3 p[3], n[3]; f2 t[3];
+        boxes[ti].reset();
+        for (int j = 0; j < 3; j++) {
+            uint32_t l = vidx(ti, j);
+            if (l >= n_vert) throw std::runtime_error("ctl_builder_add_mesh: vertex index out of range");
+            p[j] = vtx(l);
+            t[j] = uvs ? f2{ uvs[2 * l], uvs[2 * l + 1] } : f2{ 0.0f, 0.0f };
+            n[j] = (normals && !flip_normals) ? normalize(f3(normals[3 * l], normals[3 * l + 1], normals[3 * l + 2])) : comp[l];
+            float pp[3] = { p[j].x, p[j].y, p[j].z };
+            boxes[ti].grow(pp); box.grow(pp);
+        }
+        if (face_normals || max_smooth_angle != 0) {   // Mesh.cpp:247-267
+            f3 n_face = normalize(cross(p[0] - p[1], p[2] - p[1]));
+            if (flip_normals) n_face = -n_face;
+            bool use_face = face_normals;
+            if (!face_normals) for (int j = 0; j < 3; j++) if (acosf(dot(n_face, n[j])) > max_smooth_angle) use_face = true;
+            if (use_face) n[0] = n[1] = n[2] = n_face;
+        }
+        uint32_t mi = tri_material ? tri_material[ti] : 0;
+        if (mi >= n_mat) throw std::runtime_error("ctl_builder_add_mesh: triangle material index out of range");
+        tri_data_pack(out[ti], p, n, t, mi);
+    }
+}
+
 uint32_t scene_builder::add_mesh(const float* positions, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri, const float* normals,
                                  const float* uvs, const uint8_t* tri_material, const ctl_material* materials, uint32_t n_mat,
                                  bool flip_normals, bool face_normals, float max_smooth_angle) {
@@ -151,36 +185,11 @@ uint32_t scene_builder::add_mesh(const float* positions, uint32_t n_vert, const 
             return finish_mesh(mr);
         }
     }
-    std::vector<f3> comp;
-    if (!normals || flip_normals) compute_vertex_normals(positions, indices, n_vert, n_tri, comp, flip_normals);   // Mesh.cpp:216-217
-    auto vidx = [&](uint32_t ti, int j) { return indices ? indices[ti * 3 + j] : ti * 3 + j; };
-    auto vtx = [&](uint32_t i) { return f3(positions[3 * i], positions[3 * i + 1], positions[3 * i + 2]); };
-    mr.box.reset();
     std::vector<aabb> boxes(n_tri);
     tri.resize(mr.tri_offset + n_tri);
-    for (uint32_t ti = 0; ti < n_tri; ti++) {   // Mesh::CompileMesh (Engine/Mesh.cpp:225-272)
-        f3 p[3], n[3]; f2 t[3];
-        boxes[ti].reset();
-        for (int j = 0; j < 3; j++) {
-            uint32_t l = vidx(ti, j);
-            if (l >= n_vert) throw std::runtime_error("ctl_builder_add_mesh: vertex index out of range");
-            p[j] = vtx(l);
-            t[j] = uvs ? f2{ uvs[2 * l], uvs[2 * l + 1] } : f2{ 0.0f, 0.0f };
-            n[j] = (normals && !flip_normals) ? normalize(f3(normals[3 * l], normals[3 * l + 1], normals[3 * l + 2])) : comp[l];
-            float pp[3] = { p[j].x, p[j].y, p[j].z };
-            boxes[ti].grow(pp); mr.box.grow(pp);
-        }
-        if (face_normals || max_smooth_angle != 0) {   // Mesh.cpp:247-267
-            f3 n_face = normalize(cross(p[0] - p[1], p[2] - p[1]));
-            if (flip_normals) n_face = -n_face;
-            bool use_face = face_normals;
-            if (!face_normals) for (int j = 0; j < 3; j++) if (acosf(dot(n_face, n[j])) > max_smooth_angle) use_face = true;
-            if (use_face) n[0] = n[1] = n[2] = n_face;
-        }
-        uint32_t mi = tri_material ? tri_material[ti] : 0;
-        if (mi >= n_mat) throw std::runtime_error("ctl_builder_add_mesh: triangle material index out of range");
-        tri_data_pack(tri[mr.tri_offset + ti], p, n, t, mi);
-    }
+    compile_triangles(positions, n_vert, indices, n_tri, normals, uvs, tri_material, n_mat, flip_normals, face_normals, max_smooth_angle, tri.data() + mr.tri_offset, boxes.data(), mr.box);
+    auto vidx = [&](uint32_t ti, int j) { return indices ? indices[ti * 3 + j] : ti * 3 + j; };
+    auto vtx = [&](uint32_t i) { return f3(positions[3 * i], positions[3 * i + 1], positions[3 * i + 2]); };
     // ConstructBVH (Engine/MeshLoader/BVHBuilderHelper.cpp:116-147): max leaf size 8
     bvh_result R;
     if (use_sbvh) build_sbvh(positions, indices, n_tri, 8, R);   // the reference's own tree: SplitBVHBuilder with spatial splits
@@ -222,6 +231,67 @@ uint32_t scene_builder::finish_mesh(const mesh_rec& mr) {
     return (uint32_t)meshes.size() - 1;
 }
 
+// DynamicScene::AnimateMesh (Engine/DynamicScene.cpp:450-456; AnimatedMesh::k_ComputeState, Engine/AnimatedMesh.cpp:163-184) for a host that supplies the vertex
+// positions: the TriangleData and the Woop rows of the mesh from the new arrays, its BVH REFITTED (links, the leaves' references and their order stay; a spatial-split
+// reference's clipped box gives way to the whole triangle's: the tree culls less well, never wrongly), its box, and the shape sets of the area lights on its nodes.
+// Everything that can refuse the arrays runs before the first byte is written.  The geometry cache is neither read nor written.
+void scene_builder::update_mesh(uint32_t mesh_index, const float* positions, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri, const float* normals, const float* uvs) {
+    if (mesh_index >= mesh_info.size()) throw std::runtime_error("ctl_builder_update_mesh: bad mesh index");
+    mesh_rec& mr = mesh_info[mesh_index];
+    if (!positions || n_tri != mr.n_tris) throw std::runtime_error("ctl_builder_update_mesh: mesh " + std::to_string(mesh_index) + " has " + std::to_string(mr.n_tris) + " triangles; an update keeps the triangle count");
+    if (!indices && n_vert != n_tri * 3) throw std::runtime_error("ctl_builder_update_mesh: triangle soup needs n_vert == 3*n_tri");
+    if (indices) for (size_t i = 0; i < (size_t)n_tri * 3; i++) if (indices[i] >= n_vert) throw std::runtime_error("ctl_builder_update_mesh: vertex index out of range");
+    for (uint32_t i = 0; i < mr.n_woop; i++) if ((widx[mr.woop_offset + i].index >> 1) >= n_tri) throw std::runtime_error("ctl_builder_update_mesh: the mesh's leaf references are out of range");
+    std::vector<uint8_t> tri_material(n_tri);   // the materials stay those of the mesh as added (TriangleData::getMatIndex)
+    for (uint32_t ti = 0; ti < n_tri; ti++) tri_material[ti] = (uint8_t)((tri[mr.tri_offset + ti].nor_mat_extra[1] >> 16) & 0xffu);
+    std::vector<ctl_triangle_data> compiled(n_tri); std::vector<aabb> boxes(n_tri); aabb box;
+    compile_triangles(positions, n_vert, indices, n_tri, normals, uvs, tri_material.data(), 256, false, false, 0.0f, compiled.data(), boxes.data(), box);
+    std::copy(compiled.begin(), compiled.end(), tri.begin() + mr.tri_offset);
+    mr.box = box;
+    auto vidx = [&](uint32_t ti, int j) { return indices ? indices[ti * 3 + j] : ti * 3 + j; };
+    auto vtx = [&](uint32_t i) { return f3(positions[3 * i], positions[3 * i + 1], positions[3 * i + 2]); };
+    for (uint32_t i = 0; i < mr.n_woop; i++) {   // createLeafNode (BVHBuilderHelper.cpp:51-62)
+        const uint32_t t = widx[mr.woop_offset + i].index >> 1;
+        woop_set_data(woop[mr.woop_offset + i], vtx(vidx(t, 0)), vtx(vidx(t, 1)), vtx(vidx(t, 2)));
+    }
+    // the child boxes, bottom-up: the builders emit a node's children after the node, so the reverse index order visits them first
+    ctl_bvh_node* N = bvh.data() + mr.node_offset;
+    auto child_box = [&](int code, aabb& b) -> bool {   // false: no child, or a link this mesh does not hold (the box stays as built)
+        if (code == 0x76543210) return false;
+        b.reset();
+        if (code >= 0) {
+            const uint32_t k = (uint32_t)code / 4;
+            if (k >= mr.n_nodes) return false;
+            const ctl_bvh_node& c = N[k];
+            if (c.child0 != 0x76543210) { const float lo[3] = { c.a[0], c.a[2], c.c[0] }, hi[3] = { c.a[1], c.a[3], c.c[1] }; b.grow(lo); b.grow(hi); }
+            if (c.child1 != 0x76543210) { const float lo[3] = { c.b[0], c.b[2], c.c[2] }, hi[3] = { c.b[1], c.b[3], c.c[3] }; b.grow(lo); b.grow(hi); }
+            return true;
+        }
+        for (uint32_t e = (uint32_t)~code; e < mr.n_woop; e++) {
+            const uint32_t w = widx[mr.woop_offset + e].index;
+            b.grow(boxes[w >> 1]);
+            if (w & 1u) break;
+        }
+        return true;
+    };
+    for (uint32_t v = mr.n_nodes; v-- > 0;) {
+        ctl_bvh_node& n = N[v]; aabb b;
+        if (child_box(n.child0, b)) { n.a[0] = b.lo[0]; n.a[1] = b.hi[0]; n.a[2] = b.lo[1]; n.a[3] = b.hi[1]; n.c[0] = b.lo[2]; n.c[1] = b.hi[2]; }
+        if (child_box(n.child1, b)) { n.b[0] = b.lo[0]; n.b[1] = b.hi[0]; n.b[2] = b.lo[1]; n.b[3] = b.hi[1]; n.c[2] = b.lo[2]; n.c[3] = b.hi[2]; }
+    }
+    for (uint32_t k = 0; k < nodes.size(); k++) if (nodes[k].mesh_index == mesh_index) recalculate_node_lights(k);
+}
+
+// the shape sets of a node's area lights from its current transform and its mesh's current triangles
+void scene_builder::recalculate_node_lights(uint32_t node_index) {
+    const ctl_node& N = nodes[node_index];
+    for (uint32_t k = 0; k < N.n_lights && k < 2; k++) {
+        if (N.lights[k] >= lights.size()) continue;
+        ctl_light& L = lights[N.lights[k]];
+        if (L.type == CTL_LIGHT_DIFFUSE && L.node_idx == node_index && L.count) L.sum_area = recalculate_shape_set(node_index, L.area_dist_index, L.triangles_index, L.count);
+    }
+}
+
 uint32_t scene_builder::add_node(uint32_t mesh_index, const ctl_float4x4* to_world) {
     if (mesh_index >= meshes.size()) throw std::runtime_error("ctl_builder_add_node: bad mesh index");
     const mesh_rec& mr = mesh_info[mesh_index];
@@ -251,12 +321,7 @@ void scene_builder::set_node_transform(uint32_t node_index, const ctl_float4x4& 
     ctl_float4x4 inv; mat_inverse(m.m, inv.m);
     if (inv.m[12] != 0.0f || inv.m[13] != 0.0f || inv.m[14] != 0.0f || !(inv.m[15] > 0.0f)) throw std::runtime_error("set_node_transform: node transform is singular");
     xf[node_index] = m; ixf[node_index] = inv;
-    const ctl_node& N = nodes[node_index];
-    for (uint32_t k = 0; recalculate_lights && k < N.n_lights && k < 2; k++) {
-        if (N.lights[k] >= lights.size()) continue;
-        ctl_light& L = lights[N.lights[k]];
-        if (L.type == CTL_LIGHT_DIFFUSE && L.node_idx == node_index && L.count) L.sum_area = recalculate_shape_set(node_index, L.area_dist_index, L.triangles_index, L.count);
-    }
+    if (recalculate_lights) recalculate_node_lights(node_index);
 }
 // `mat->bsdf = ...; mat->bsdf.As()->m_enableTwoSided = ...` of BsdfParser::apply_bsdf (ObjectParser.h:996-1010): replaces the BSDF
 // of one of the node's materials and keeps its NodeLightIndex

@@ -46,6 +46,9 @@ struct scene_builder {
     uint32_t add_mesh(const float* positions, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri, const float* normals, const float* uvs,
                       const uint8_t* tri_material, const ctl_material* materials, uint32_t n_mat,
                       bool flip_normals = false, bool face_normals = false, float max_smooth_angle = 0.0f);   // Mesh::CompileMesh options (Mesh.cpp:199)
+    // new vertex arrays for a mesh, same triangle count (ctl_builder_update_mesh): TriangleData, Woop rows, the mesh BVH's boxes, the mesh box, the area lights of its nodes
+    void update_mesh(uint32_t mesh_index, const float* positions, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri, const float* normals, const float* uvs);
+    void recalculate_node_lights(uint32_t node_index);   // ShapeSet::Recalculate of every area light of a node
     uint32_t add_node(uint32_t mesh_index, const ctl_float4x4* to_world);
     void set_node_transform(uint32_t node_index, const ctl_float4x4& to_world, bool recalculate_lights = false);
     float recalculate_shape_set(uint32_t node_index, uint32_t cdf_off, uint32_t tri_off, uint32_t count);   // ShapeSet::Recalculate of one area light in the anim blob

@@ -107,7 +107,7 @@ void check_scene_desc(const ctl_scene_desc& d, uint32_t parts, const char* who) 
     if (parts & (CTL_DIFF_TRANSFORMS | CTL_DIFF_TOPOLOGY)) check_nodes(d, parts, who);
     if (parts & CTL_DIFF_LIGHTS) check_lights(d, who);
     if (parts & CTL_DIFF_MATERIALS) check_materials(d, who);
-    if (parts & (CTL_DIFF_TRANSFORMS | CTL_DIFF_TOPOLOGY)) check_traversal_stack(d, !creating, who);
+    if (parts & (CTL_DIFF_TRANSFORMS | CTL_DIFF_TOPOLOGY | CTL_DIFF_GEOMETRY)) check_traversal_stack(d, !creating, who);   // (a geometry update brings the mesh BVHs anew: what creation checks of them)
     if ((parts & CTL_DIFF_CAMERA) && (d.camera.type < CTL_SENSOR_SPHERICAL || d.camera.type > CTL_SENSOR_TELECENTRIC))
         refuse(who, creating ? "unknown sensor type " + std::to_string(d.camera.type) : std::string("unknown sensor type"));   // (creation has always named the value, an update never has)
 }

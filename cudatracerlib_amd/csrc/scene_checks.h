@@ -11,6 +11,7 @@ constexpr uint32_t kCheckAllParts = CTL_DIFF_CAMERA | CTL_DIFF_MATERIALS | CTL_D
 // whose other parts are those of a description that was checked already):
 //   CTL_DIFF_TOPOLOGY    a scene has nodes, a node names a mesh — only creation can meet these, and CTL_DIFF_TOPOLOGY in `parts` says that creation is asking
 //   CTL_DIFF_TRANSFORMS  affine node transforms; the scene BVH fits the traversal stack next to the deepest mesh BVH (check_traversal_stack)
+//   CTL_DIFF_GEOMETRY    the mesh BVHs next to the scene BVH on the traversal stack (check_traversal_stack): what creation checks of the arrays a geometry update brings
 //   CTL_DIFF_LIGHTS      env_map_index, light types, the lights' image indices
 //   CTL_DIFF_MATERIALS   texture types and image indices, map kind, alpha state, BSDF type, nested BSDFs, distributions and their transmittance tables
 //   CTL_DIFF_CAMERA      the sensor type

@@ -6,29 +6,14 @@
 #include "flatten.h"
 #include "flat_refit.h"
 #include "scene_checks.h"
+#include "geometry_hash.h"
 #include "scene_cache.h"
 #include "mitsuba_loader.h"   // unsupported_error
 #include <cstring>
 
 namespace ctl {
 
-void scene_geometry_hash(const ctl_scene_desc& d, uint64_t out[2]) {
-    content_hash H;
-    H.add_value(d.n_tri_data); if (d.n_tri_data) H.add(d.tri_data, (size_t)d.n_tri_data * sizeof(ctl_triangle_data));
-    H.add_value(d.n_woop); if (d.n_woop) { H.add(d.woop, (size_t)d.n_woop * sizeof(ctl_woop_tri)); H.add(d.woop_index, (size_t)d.n_woop * sizeof(ctl_woop_index)); }
-    H.add_value(d.n_bvh_nodes); if (d.n_bvh_nodes) H.add(d.bvh_nodes, (size_t)d.n_bvh_nodes * sizeof(ctl_bvh_node));
-    for (uint32_t i = 0; i < d.n_images; i++) if (d.images[i].texels) H.add(d.images[i].texels, (size_t)d.images[i].width * d.images[i].height * 4);
-    const int have_rt = d.rough_transmittance ? 1 : 0; H.add_value(have_rt);
-    if (d.rough_transmittance) for (int i = 0; i < 3; i++) {
-        const ctl_rough_transmittance& t = d.rough_transmittance[i];
-        H.add_value(t.eta_samples); H.add_value(t.alpha_samples); H.add_value(t.theta_samples); H.add_value(t.eta_min); H.add_value(t.eta_max); H.add_value(t.alpha_min); H.add_value(t.alpha_max);
-        const int have = (t.trans && t.diff_trans) ? 1 : 0; H.add_value(have);
-        if (have) { H.add(t.trans, (size_t)2 * t.eta_samples * t.alpha_samples * t.theta_samples * 4); H.add(t.diff_trans, (size_t)2 * t.eta_samples * t.alpha_samples * 4); }
-    }
-    H.digest(out);
-}
-
-uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const uint64_t* a_geometry_hash) {
+uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const geometry_hashes* a_geometry, geometry_hashes* b_geometry) {
     auto same = [](const void* x, const void* y, size_t bytes) { return bytes == 0 || (x && y && std::memcmp(x, y, bytes) == 0); };
     uint32_t mask = 0;
     // topology first: the counts decide whether the arrays can be compared at all
@@ -45,14 +30,15 @@ uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const
         const ctl_mipmap &x = a.images[i], &y = b.images[i];
         if (x.width != y.width || x.height != y.height || x.texel_type != y.texel_type || x.wrap_mode != y.wrap_mode || x.filter_mode != y.filter_mode) mask |= CTL_DIFF_TOPOLOGY;
     }
-    if (a_geometry_hash) {
-        uint64_t hb[2]; scene_geometry_hash(b, hb);
-        if (hb[0] != a_geometry_hash[0] || hb[1] != a_geometry_hash[1]) mask |= CTL_DIFF_TOPOLOGY;
-    } else if (!(mask & CTL_DIFF_TOPOLOGY)) {
-        uint64_t ha[2], hb[2];
-        if (!same(a.tri_data, b.tri_data, (size_t)a.n_tri_data * sizeof(ctl_triangle_data)) || !same(a.woop, b.woop, (size_t)a.n_woop * sizeof(ctl_woop_tri)) ||
-            !same(a.woop_index, b.woop_index, (size_t)a.n_woop * sizeof(ctl_woop_index)) || !same(a.bvh_nodes, b.bvh_nodes, (size_t)a.n_bvh_nodes * sizeof(ctl_bvh_node))) mask |= CTL_DIFF_TOPOLOGY;
-        else { scene_geometry_hash(a, ha); scene_geometry_hash(b, hb); if (ha[0] != hb[0] || ha[1] != hb[1]) mask |= CTL_DIFF_TOPOLOGY; }   // texels and transmittance tables
+    // the geometry arrays, one pass over each description's: another structure (woop_index, the mesh BVHs' links, texels, transmittance tables) is topology, other
+    // VALUES in some mesh (triangle data, Woop rows, the mesh BVHs' boxes) are CTL_DIFF_GEOMETRY
+    {
+        geometry_hashes ha, hb_local; geometry_hashes& hb = b_geometry ? *b_geometry : hb_local;
+        if (!a_geometry) hash_geometry(a, ha);
+        const geometry_hashes& ga = a_geometry ? *a_geometry : ha;
+        hash_geometry(b, hb);
+        if (!hb.same_structure(ga)) mask |= CTL_DIFF_TOPOLOGY;
+        else for (uint32_t m = 0; m < b.n_meshes; m++) if (!hb.same_values(ga, m)) { mask |= CTL_DIFF_GEOMETRY; break; }
     }
     if (std::memcmp(&a.camera, &b.camera, sizeof(ctl_sensor)) != 0) mask |= CTL_DIFF_CAMERA;
     if (!same(a.materials, b.materials, (size_t)a.n_materials * sizeof(ctl_material))) mask |= CTL_DIFF_MATERIALS;
@@ -67,14 +53,15 @@ uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const
 
 Scene::~Scene() {}
 
-void Scene::snapshot(const ctl_scene_desc& d) {
+void Scene::snapshot(const ctl_scene_desc& d, const geometry_hashes* geom) {
     std::unique_ptr<desc_snapshot> s(new desc_snapshot());
     s->meshes.assign(d.meshes, d.meshes + d.n_meshes); s->nodes.assign(d.nodes, d.nodes + d.n_nodes); s->materials.assign(d.materials, d.materials + d.n_materials);
     s->lights.assign(d.lights, d.lights + d.n_lights_buf); s->anim.assign(d.anim, d.anim + d.n_anim_bytes); s->top.assign(d.scene_bvh_nodes, d.scene_bvh_nodes + d.n_scene_bvh_nodes);
     s->xf.assign(d.node_transforms, d.node_transforms + d.n_nodes); s->ixf.assign(d.node_inv_transforms, d.node_inv_transforms + d.n_nodes);
     s->images.assign(d.images, d.images + d.n_images); for (auto& m : s->images) m.texels = nullptr;
-    if (snap_) { s->geometry_hash[0] = snap_->geometry_hash[0]; s->geometry_hash[1] = snap_->geometry_hash[1]; }   // after an update: the geometry is the one already hashed
-    else scene_geometry_hash(d, s->geometry_hash);
+    if (geom) s->geom = *geom;                    // after an update: the pass that found the difference made them
+    else if (snap_) s->geom = snap_->geom;
+    else hash_geometry(d, s->geom);
     s->d = d;
     s->d.tri_data = nullptr; s->d.woop = nullptr; s->d.woop_index = nullptr; s->d.bvh_nodes = nullptr;
     s->d.meshes = s->meshes.data(); s->d.nodes = s->nodes.data(); s->d.materials = s->materials.data(); s->d.lights = s->lights.data(); s->d.anim = s->anim.data();
@@ -87,7 +74,7 @@ void Scene::snapshot(const ctl_scene_desc& d) {
 
 // The refit (and / or the re-stamp of the entries' material bits) of the device tree; the null stream, between two synchronisations: ordered after every trace that
 // was launched and before the next
-void Scene::refit_flat(const ctl_scene_desc& d, bool boxes, bool restamp, ctl_scene_update_stats* st) {
+void Scene::refit_flat(const ctl_scene_desc& d, bool boxes, bool restamp, const std::vector<uint8_t>* mesh_changed, ctl_scene_update_stats* st) {
     refit_device R{};
     R.nodes = flat_nodes_.p; R.leaves = flat_leaves_.p; R.n_nodes = (uint32_t)flat_n_nodes_; R.n_entries = (uint32_t)flat_n_entries_; R.compact = S.flat_compact;
     R.part_index = refit_part_index_.p; R.part_boxes = refit_part_boxes_.p; R.inst = inst_.p; R.inst_fwd = inst_fwd_.p;
@@ -107,6 +94,15 @@ void Scene::refit_flat(const ctl_scene_desc& d, bool boxes, bool restamp, ctl_sc
     CTL_HIP(hipEventCreate(&ev.a)); CTL_HIP(hipEventCreate(&ev.b));
     hipEvent_t a = ev.a, b = ev.b;
     CTL_HIP(hipEventRecord(a, nullptr));
+    if (mesh_changed) {   // the entries of the deformed meshes take their new Woop rows and become whole, then every entry is refitted as after a transform change
+        std::vector<uint32_t> rows, changed(d.n_nodes);
+        if (!refit_tri_row_.p) { triangle_woop_rows(d, rows); refit_tri_row_.upload(rows.data(), rows.size()); }   // woop_index is structure: the table holds for every later update
+        for (uint32_t k = 0; k < d.n_nodes; k++) changed[k] = (*mesh_changed)[d.nodes[k].mesh_index];
+        refit_node_changed_.upload(changed.data(), changed.size());
+        CTL_HIP(hipStreamSynchronize(nullptr));   // `changed` and `rows` are pageable: the copies have left them
+        const deform_device D{ refit_node_changed_.p, d.n_nodes, refit_tri_row_.p, d.n_tri_data, leaf_tris_.p, d.n_woop };
+        launch_deform_entries(nullptr, R, D);
+    }
     launch_refit_entries(nullptr, R, true);
     const size_t n_levels = refit_.level_start.size() - 1;
     for (size_t l = n_levels; l-- > 0;) launch_refit_level(nullptr, R, refit_level_nodes_.p + refit_.level_start[l], refit_.level_start[l + 1] - refit_.level_start[l]);
@@ -119,19 +115,59 @@ void Scene::refit_flat(const ctl_scene_desc& d, bool boxes, bool restamp, ctl_sc
     st->node_area_before = area[0]; st->node_area_after = area[1]; st->refit_ms = ms; st->refit_levels = (uint32_t)n_levels;
 }
 
+// One mesh's ranges of the two-level arrays, laid out as the constructor lays them out (tracer.hip), into the SAME allocations: tracers keep their pointers.  Synchronous
+// copies from pageable memory.
+void Scene::upload_mesh_geometry(const ctl_scene_desc& d, const mesh_ranges& R, uint32_t m) {
+    const ctl_kernel_mesh& km = d.meshes[m];
+    if (R.tri1[m] > R.tri0[m]) CTL_HIP(hipMemcpy(tri_data_.p + (size_t)R.tri0[m] * 2, d.tri_data + R.tri0[m], (size_t)(R.tri1[m] - R.tri0[m]) * sizeof(ctl_triangle_data), hipMemcpyHostToDevice));
+    if (R.node1[m] > R.node0[m]) CTL_HIP(hipMemcpy(bot_nodes_.p + (size_t)R.node0[m] * 4, d.bvh_nodes + R.node0[m], (size_t)(R.node1[m] - R.node0[m]) * sizeof(ctl_bvh_node), hipMemcpyHostToDevice));
+    const uint32_t first = R.woop0[m], last = R.woop1[m];
+    if (last <= first) return;
+    std::vector<float4> tmp((size_t)(last - first) * 4);
+    for (uint32_t w = first; w < last; w++) {
+        const ctl_woop_tri& t = d.woop[w];
+        const size_t o = (size_t)(w - first) * 4, at = (size_t)km.bvh_index_offset + (w - first);
+        tmp[o + 0] = make_float4(t.a[0], t.a[1], t.a[2], t.a[3]);
+        tmp[o + 1] = make_float4(t.b[0], t.b[1], t.b[2], t.b[3]);
+        tmp[o + 2] = make_float4(t.c[0], t.c[1], t.c[2], t.c[3]);
+        const uint32_t idx = at < d.n_woop ? d.woop_index[at].index : 1u;
+        tmp[o + 3] = make_float4(__builtin_bit_cast(float, idx), 0, 0, 0);
+    }
+    CTL_HIP(hipMemcpy(leaf_tris_.p + (size_t)first * 4, tmp.data(), tmp.size() * sizeof(float4), hipMemcpyHostToDevice));
+}
+
 uint32_t Scene::update(const ctl_scene_desc& d, ctl_scene_update_stats* stats) {
     require_device();
     if (!snap_) throw std::runtime_error("ctl_scene_update: the scene holds no description");
-    const uint32_t mask = scene_desc_diff(snap_->d, d, snap_->geometry_hash);
+    geometry_hashes geom;
+    const uint32_t mask = scene_desc_diff(snap_->d, d, &snap_->geom, &geom);
     last_mask_ = mask;
     if (mask == 0) { last_update_ = ctl_scene_update_stats{}; if (stats) *stats = last_update_; return 0; }   // nothing differs: no synchronisation, no tracer is stalled
     if (mask & CTL_DIFF_TOPOLOGY) throw std::runtime_error("ctl_scene_update: the topology of the scene differs (geometry arrays, counts, node -> mesh / material assignment, images or transmittance tables): re-create the scene");
-    const bool refit = (mask & CTL_DIFF_TRANSFORMS) && flattened();
-    if (refit && S.flat_format != kFlatQ4) throw unsupported_error("ctl_scene_update: the Q8 node format is not refitted; a transform change needs a scene in the default format (or a new scene)");
+    const bool refit = (mask & (CTL_DIFF_TRANSFORMS | CTL_DIFF_GEOMETRY)) && flattened();
+    if (refit && S.flat_format != kFlatQ4) throw unsupported_error("ctl_scene_update: the Q8 node format is not refitted; a transform or geometry change needs a scene in the default format (or a new scene)");
     if (refit && refit_.level_start.size() < 2) throw unsupported_error("ctl_scene_update: the flattened tree carries no refit data");
     // Everything that can refuse the new description runs before anything is written, and before a tracer is stalled.  A transform change brings a new scene BVH: its
     // links must stay inside the array (creation is more lenient there, scene_checks.h) and its depth fit next to the mesh BVHs of creation (the geometry hash matched)
     check_scene_desc(d, mask, "ctl_scene_update");
+    std::vector<uint8_t> mesh_changed;   // CTL_DIFF_GEOMETRY: the meshes whose value hash differs
+    const mesh_ranges ranges(d);
+    if (mask & CTL_DIFF_GEOMETRY) {
+        mesh_changed.assign(d.n_meshes, 0);
+        for (uint32_t m = 0; m < d.n_meshes; m++) mesh_changed[m] = geom.same_values(snap_->geom, m) ? 0 : 1;
+        // the arrays were sized by creation and the counts agree; a range the re-upload writes must still lie inside them
+        for (uint32_t m = 0; m < d.n_meshes; m++) if (mesh_changed[m] && ((size_t)ranges.tri1[m] * 2 > tri_data_.n || (size_t)ranges.woop1[m] * 4 > leaf_tris_.n || (size_t)ranges.node1[m] * 4 > bot_nodes_.n))
+            throw std::runtime_error("ctl_scene_update: mesh " + std::to_string(m) + " reaches outside the scene's geometry arrays");
+        if (flattened() && !flat_missing_tris_.empty()) {
+            // a triangle that gather_references dropped at creation (singular Woop matrix) and that is regular now: the tree has no leaf entry to put it in
+            std::vector<uint32_t> rows; triangle_woop_rows(d, rows);
+            const int m = mesh_gaining_a_triangle(d, flat_missing_tris_, rows, mesh_changed);
+            if (m >= 0) {
+                last_mask_ |= CTL_DIFF_TOPOLOGY;
+                throw std::runtime_error("ctl_scene_update: mesh " + std::to_string(m) + " has a triangle that was degenerate when the scene was flattened and no longer is: the flattened tree has no leaf entry for it; re-create the scene");
+            }
+        }
+    }
     ctl_scene_update_stats st{}; st.mask = mask;
     CTL_HIP(hipDeviceSynchronize());   // no trace reads the arrays any more
     const uint32_t had_alpha_maps = S.alpha_maps;
@@ -150,12 +186,16 @@ uint32_t Scene::update(const ctl_scene_desc& d, ctl_scene_update_stats* stats) {
         upload_top_level(d); upload_instances(d);
         if (flattened()) S.inst_w_one = inverse_transforms_have_w_one(d);
     }
+    if (mask & CTL_DIFF_GEOMETRY) {
+        for (uint32_t m = 0; m < d.n_meshes; m++) if (mesh_changed[m]) upload_mesh_geometry(d, ranges, m);
+        if (flattened()) restamp = true;   // the entries' model / alpha bits come from tri_data: re-stamped from the new one
+    }
     CTL_HIP(hipDeviceSynchronize());
     bind(d);
     if (mask & CTL_DIFF_CAMERA) set_camera(d);
-    if (refit || restamp) { refit_flat(d, refit, restamp, &st); st.restamped = restamp ? 1u : 0u; }
+    if (refit || restamp) { refit_flat(d, refit, restamp, (mask & CTL_DIFF_GEOMETRY) ? &mesh_changed : nullptr, &st); st.restamped = restamp ? 1u : 0u; }
     last_update_ = st;
-    snapshot(d);
+    snapshot(d, &geom);
     if (stats) *stats = st;
     return mask;
 }
@@ -184,6 +224,14 @@ void Scene::read_flat_bvh(flat_scene& F) {
     }
     F.nodes.resize(flat_n_nodes_);
     CTL_HIP(hipMemcpy(F.nodes.data(), flat_nodes_.p, flat_n_nodes_ * sizeof(flat4_node), hipMemcpyDeviceToHost));
+    if (refit_part_index_.p && refit_part_index_.n == flat_n_entries_) {   // the refit side data as the device holds it: a geometry update turns split references into whole entries
+        F.refit.part_index.resize(flat_n_entries_);
+        CTL_HIP(hipMemcpy(F.refit.part_index.data(), refit_part_index_.p, flat_n_entries_ * 4, hipMemcpyDeviceToHost));
+        F.refit.part_boxes = refit_.part_boxes; F.refit.xf0 = refit_.xf0; F.refit.level_start = refit_.level_start;
+        F.refit.level_nodes.resize(refit_level_nodes_.n);
+        if (refit_level_nodes_.n) CTL_HIP(hipMemcpy(F.refit.level_nodes.data(), refit_level_nodes_.p, refit_level_nodes_.n * 4, hipMemcpyDeviceToHost));
+        F.refit.geom = snap_->geom;
+    }
     F.child_links.assign(flat_n_nodes_ * 4, 0x76543210);
     for (size_t i = 0; i < flat_n_nodes_; i++) {
         const flat4_node& n = F.nodes[i];

@@ -32,16 +32,16 @@ template <typename T> struct dbuf {   // tracked device allocation (Base/CudaMem
     void upload(const T* h, size_t count, hipStream_t s = 0) { if (count > n) alloc(count); if (count) CTL_HIP(hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, s)); }
 };
 
-// ctl_scene_desc_diff: the CTL_DIFF_* bits of what differs between two descriptions.  a_geometry_hash: when given, `a` is a snapshot without its geometry arrays
-// (triangles, Woop rows, mesh BVHs, texels, transmittance tables) and they are compared through scene_geometry_hash(b) instead
-uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const uint64_t* a_geometry_hash = nullptr);
-void scene_geometry_hash(const ctl_scene_desc& d, uint64_t out[2]);
+// ctl_scene_desc_diff: the CTL_DIFF_* bits of what differs between two descriptions.  a_geometry: when given, `a` is a snapshot without its geometry arrays
+// (triangles, Woop rows, mesh BVHs, texels, transmittance tables) and they are compared through the hashes of geometry_hash.h instead.  b_geometry (may be null)
+// receives the hashes of `b` where the function made them (always when a_geometry is given and the counts agree): the ONE pass over b's geometry arrays of an update
+uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const geometry_hashes* a_geometry = nullptr, geometry_hashes* b_geometry = nullptr);
 // the host copy of a description that a scene keeps to diff an update against (scene_update.hip)
 struct desc_snapshot {
     ctl_scene_desc d{};   // pointers into the vectors below; the geometry arrays are null
     std::vector<ctl_kernel_mesh> meshes; std::vector<ctl_node> nodes; std::vector<ctl_material> materials; std::vector<ctl_light> lights; std::vector<uint8_t> anim;
     std::vector<ctl_bvh_node> top; std::vector<ctl_float4x4> xf, ixf; std::vector<ctl_mipmap> images;
-    uint64_t geometry_hash[2] = { 0, 0 };
+    geometry_hashes geom;   // structure + per-mesh values (geometry_hash.h)
 };
 
 // dev_scene::inst_w_one of a flattened scene: every node transform affine with w == 1 exactly (what add_node produces), so the kernels skip the load of w and the division by it
@@ -75,12 +75,16 @@ private:
     void set_shading_state(const shading_state& s) { S.shade_features = s.features; S.shade_models = s.models; S.alpha_maps = s.alpha_maps; }   // derive_shading_state (device_scene.h)
     void bind(const ctl_scene_desc& d);                   // device pointers and the scalars of the description into S
     void set_camera(const ctl_scene_desc& d);
-    void snapshot(const ctl_scene_desc& d);               // host copy of the description an update diffs against (the geometry arrays as a hash)
-    void refit_flat(const ctl_scene_desc& d, bool boxes, bool restamp, ctl_scene_update_stats* stats);
+    void snapshot(const ctl_scene_desc& d, const geometry_hashes* geom = nullptr);   // host copy of the description an update diffs against (the geometry arrays as hashes; geom: already made)
+    // mesh_changed (may be null): per mesh, whether its vertex values differ (CTL_DIFF_GEOMETRY): the entries of those meshes get their new Woop rows first
+    void refit_flat(const ctl_scene_desc& d, bool boxes, bool restamp, const std::vector<uint8_t>* mesh_changed, ctl_scene_update_stats* stats);
+    void upload_mesh_geometry(const ctl_scene_desc& d, const mesh_ranges& R, uint32_t mesh);   // the two-level arrays of one mesh, re-laid-out as the constructor does, into the same allocations
     bool reduced_rough_transmittance_ = false;
     ctl_scene_update_stats last_update_{}; uint32_t last_mask_ = 0;
     std::unique_ptr<desc_snapshot> snap_;
     flat_scene::refit_side refit_;   // host part: xf0, level_start
+    std::vector<uint32_t> flat_missing_tris_;   // triangles of instanced meshes without a leaf entry (flatten.h flat_missing_triangles): a geometry update cannot bring them back
+    dbuf<uint32_t> refit_tri_row_, refit_node_changed_;   // made by the first geometry update: triangle -> row of leaf_tris_ (triangle_woop_rows); per node, whether its mesh changed
     std::vector<int32_t> flat_child_links_;
     size_t flat_n_nodes_ = 0, flat_n_entries_ = 0, flat_slab_nodes_ = 0; int flat_max_depth_ = 0; bool flat_root_slab_ = false;
     dbuf<uint32_t> refit_part_index_, refit_level_nodes_; dbuf<refit_box> refit_part_boxes_, refit_ebox_, refit_nbox_; dbuf<double> refit_carry_, refit_area_;
@@ -125,13 +129,17 @@ private:
 // flat_refit.hip: the refit of the Q4 tree on the device, the arithmetic of flat_refit.h.  Plain launches on `s`, deepest level first; no kernel waits for another workgroup.
 struct refit_device {
     float4* nodes; float4* leaves; uint32_t n_nodes, n_entries; int compact;
-    const uint32_t* part_index; const refit_box* part_boxes; const double* carry;   // side data; carry = P per scene node (12 doubles)
+    uint32_t* part_index; const refit_box* part_boxes; const double* carry;   // side data; carry = P per scene node (12 doubles).  k_deform_entries writes part_index
     const float4* inst; const float4* inst_fwd;                                       // the scene's node transforms, as the two-level traversal keeps them
     refit_box* ebox; refit_box* nbox;                                                 // scratch: the new box of every entry / node
     // re-stamp of the model nibble (index bits 28..31) and the alpha bit (node bit 31) of every entry from node_info + tri_data + the materials;
     // restamp: 0 = leave the bits alone, else the NUMBER of materials (a material index beyond it is never read)
     int restamp, leaf_keys, alpha_maps; const uint4* tri_data; const uint4* node_info; const ctl_material* mats;
 };
+// a geometry update (k_deform_entries): the entries of the nodes marked in node_changed take rows 0..2 of their triangle from the two-level leaf stream (leaf_tris, 64-B
+// stride, already holding the new values), through tri_row (triangle -> row), and stand for their whole triangle from then on
+struct deform_device { const uint32_t* node_changed; uint32_t n_scene_nodes; const uint32_t* tri_row; uint32_t n_tris; const float4* leaf_tris; uint32_t n_rows; };
+void launch_deform_entries(hipStream_t s, const refit_device& R, const deform_device& D);
 void launch_refit_entries(hipStream_t s, const refit_device& R, bool boxes);
 void launch_refit_level(hipStream_t s, const refit_device& R, const uint32_t* level_nodes, uint32_t count);
 void launch_refit_area(hipStream_t s, const float4* nodes, uint32_t n_nodes, double* sum_out);   // adds the nodes' box areas to *sum_out

@@ -244,6 +244,7 @@ Scene::Scene(const ctl_scene_desc& d, bool flatten, int flat_format, bool reduce
             else flat_nodes_.upload((const float4*)F.nodes_q8.data(), F.nodes_q8.size() * 8);
             for (const flat_leaf& L : F.leaves) if (L.node >= d.n_nodes) throw std::runtime_error("ctl_scene_create: flattened leaf entry out of range");
             S.flat_leaf_keys = 0;
+            if (F.format == kFlatQ4 && F.refit.ready()) flat_missing_triangles(F.leaves, 0xffffffffu, d, flat_missing_tris_);   // what a geometry update cannot bring back (scene_update.hip); before the bits below are stamped
             // The DEVICE copy of the entries carries the BSDF model of each entry's material in bits 28..31 of its index word (the host arrays, the cache and the oracle's view stay
             // as flatten.cpp made them): a closest-hit traversal leaves it per ray (dev_scene::hit_key_out) and the shade kernel regroups its lanes by it without the
             // hit -> node -> triangle -> material chain of dependent loads that made the regrouping cost more than it won.

@@ -313,6 +313,16 @@ int ctl_builder_finalize(ctl_builder* b, ctl_scene_desc* out);
  * sets recalculated (ShapeSet::triData::Recalculate, Engine/ShapeSet.cu:11-23); the next ctl_builder_finalize rebuilds the scene BVH, the scene box, ray_trace_eps
  * and the box-dependent lights from the new transforms. */
 int ctl_builder_set_node_transform(ctl_builder* b, uint32_t node_index, const ctl_float4x4* to_world);
+/* DynamicScene::AnimateMesh (Engine/DynamicScene.cpp:450-456; AnimatedMesh::k_ComputeState, Engine/AnimatedMesh.cpp:163-184) for a host that computes the vertex positions
+ * itself (skinning, simulation): new vertex arrays for mesh `mesh_index`, with the argument conventions and compile options of ctl_builder_add_mesh (indices == NULL: a
+ * triangle soup, normals == NULL: computed, uvs == NULL).  n_tri must be the mesh's triangle count; the materials and the per-triangle material indices stay those of the
+ * mesh as added.  Rewritten for that mesh only: its TriangleData (the bytes a fresh ctl_builder_add_mesh of the new arrays compiles), every Woop row, the boxes of its BVH
+ * nodes bottom-up — links, leaf references and their order stay; a spatial-split reference's clipped box gives way to the whole triangle's, so the tree culls less well
+ * but never wrongly —, the mesh's box, and the shape sets of the area lights on the nodes that instance it.  The next ctl_builder_finalize rebuilds the scene BVH, the scene
+ * box, ray_trace_eps and the box-dependent lights.  ctl_scene_update applies the result in place (CTL_DIFF_GEOMETRY).  The geometry cache is neither read nor written.
+ * CTL_ERR_INVALID (a bad mesh index, another triangle count, an index out of range) leaves the builder untouched. */
+int ctl_builder_update_mesh(ctl_builder* b, uint32_t mesh_index, const float* positions, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri,
+                            const float* normals, const float* uvs);
 
 /* ------------------------------------------------------------------- scenes */
 typedef struct ctl_scene ctl_scene;
@@ -342,12 +352,16 @@ enum { CTL_DIFF_CAMERA = 1,       /* ctl_scene_desc::camera                     
        CTL_DIFF_MATERIALS = 2,    /* the contents of `materials`                                                                                   */
        CTL_DIFF_LIGHTS = 4,       /* lights, anim blob, num_lights, light_indices, light_cdf, env_map_index, the nodes' light slots                 */
        CTL_DIFF_TRANSFORMS = 8,   /* node_transforms, node_inv_transforms, the scene BVH and its start node, box_min / box_max, ray_trace_eps       */
-       CTL_DIFF_TOPOLOGY = 16 };  /* anything else: triangle / Woop / mesh-BVH arrays, any count but the lights', meshes, node -> mesh / material
-                                     assignment, images, rough-transmittance tables                                                               */
+       CTL_DIFF_TOPOLOGY = 16,    /* anything else: any count but the lights', woop_index, the mesh BVHs' links, meshes, node -> mesh / material assignment,
+                                     images, rough-transmittance tables                                                                           */
+       CTL_DIFF_GEOMETRY = 32 };  /* only VALUES of the geometry arrays: the contents of tri_data and woop and the float boxes of bvh_nodes — a deformed mesh
+                                     (ctl_builder_update_mesh) — with everything CTL_DIFF_TOPOLOGY names equal                                    */
 int ctl_scene_desc_diff(const ctl_scene_desc* a, const ctl_scene_desc* b, uint32_t* mask_out);
 /* Everything ctl_scene_create and ctl_scene_update refuse a description for that can be judged from the description alone (host only, no device call): node transforms,
  * sensor, lights, textures, materials, the depth of the two-level BVH.  parts == 0: as ctl_scene_create checks; else the CTL_DIFF_* parts to check, as ctl_scene_update
  * checks the parts it found changed (CTL_DIFF_TOPOLOGY among them: as creation checks them).  CTL_ERR_INVALID and ctl_last_error() name the first rule broken.
+ * CTL_DIFF_GEOMETRY is not a part this call takes (CTL_ERR_INVALID, as for any unknown bit): what an update checks of a deformed mesh — its BVH next to the scene BVH on the
+ * traversal stack — is what parts = CTL_DIFF_TRANSFORMS checks, and the range and leaf-entry rules need the scene itself.
  * state_out (may be NULL): dev_scene's shade_features (the kShade* bits of csrc/device_scene.h), shade_models (bit m: some material has bsdf_type m) and alpha_maps. */
 int ctl_scene_desc_check(const ctl_scene_desc* desc, uint32_t parts, uint32_t state_out[3]);
 /* Applies everything that differs between the description `scene` holds and `new_desc`, except topology, in place; *mask_out (may be NULL) = the CTL_DIFF_* bits found.
@@ -355,10 +369,16 @@ int ctl_scene_desc_check(const ctl_scene_desc* desc, uint32_t parts, uint32_t st
  * Transforms: the two-level arrays are re-uploaded and the flattened Q4 tree is REFITTED on the device (csrc/flat_refit.h: links, masks and memory order stay, every
  * box is recomputed, oriented slabs are neutralised) — the traversal still returns the reference's (t, u, v, triangle, node) bit for bit, a refitted tree only culls
  * less well than a rebuilt one the further the nodes moved.  Synchronous; call between passes and start the next one with new_trace.
+ * Geometry (CTL_DIFF_GEOMETRY): the tri_data, Woop and BVH-node ranges of the meshes whose values differ are re-uploaded into the same allocations; in the flattened Q4
+ * tree the leaf entries of those meshes get their triangle's new Woop rows on the device and stand for the whole triangle from then on (a split reference's clip box was
+ * cut from the triangle as it was), then the tree is refitted as for a transform change — once, also when transforms and lights changed in the same call.
  *   CTL_ERR_NO_DEVICE    no device (checked first)
- *   CTL_ERR_INVALID      CTL_DIFF_TOPOLOGY is set: the scene is untouched, re-create it
- *   CTL_ERR_UNSUPPORTED  CTL_DIFF_TRANSFORMS on a CTL_FLAT_Q8 scene (the measurement format is not refitted); camera / material / light updates work there
- * The scene keeps its own host copy of the description (the geometry arrays as a hash): new_desc's pointers are not kept. */
+ *   CTL_ERR_INVALID      CTL_DIFF_TOPOLOGY is set: the scene is untouched, re-create it.  Also, with CTL_DIFF_TOPOLOGY added to *mask_out, a CTL_DIFF_GEOMETRY update of a
+ *                        flattened scene in which a triangle that was degenerate at creation (singular Woop matrix: it has no leaf entry) is regular now;
+ *                        ctl_last_error() names the mesh.  The other direction is fine: a triangle that collapses keeps its entry and can never be hit
+ *   CTL_ERR_UNSUPPORTED  CTL_DIFF_TRANSFORMS or CTL_DIFF_GEOMETRY on a CTL_FLAT_Q8 scene (the measurement format is not refitted); camera / material / light updates work there
+ * The scene keeps its own host copy of the description (the geometry arrays as hashes: one of their structure, one per mesh of their values, which tell an update WHICH
+ * meshes changed): new_desc's pointers are not kept. */
 int ctl_scene_update(ctl_scene* scene, const ctl_scene_desc* new_desc, uint32_t* mask_out);
 /* Report of the last ctl_scene_update: summed surface area of the flattened tree's node boxes before and after a refit (a SAH proxy: a host re-creates the scene when
  * the ratio says the tree has degraded — the library has no policy), both 0 when the update did not refit; HIP-event time of the refit kernels. */
@@ -383,15 +403,19 @@ typedef struct {
     uint32_t compact;                /* CTL_FLAT_Q4: 1 = the kernels derive the links from the layout (flat4_node::links) and the nodes' last 16 B hold oriented slabs; CTL_FLAT_Q8: always 1 */
     uint32_t root_slab;              /* the root node carries a slab (Q4: bit 0 of the link a traversal starts with; Q8: the root's q5 is loaded)            */
     uint64_t n_slab_nodes;           /* nodes that carry an oriented slab (flat_slab.h)                                                  */
-    /* the refit side data of a built CTL_FLAT_Q4 tree (csrc/flat_refit.h; NULL / 0 otherwise, and for a tree read back from a scene): per leaf entry UINT32_MAX or the
-     * index of its clip box — the entry is a split reference —, and the clip boxes {lo xyz, hi xyz} in world space as they were when the tree was built */
+    /* the refit side data of a CTL_FLAT_Q4 tree (csrc/flat_refit.h; NULL / 0 otherwise), built or read back from a scene: per leaf entry UINT32_MAX or the index of its
+     * clip box — the entry is a split reference —, and the clip boxes {lo xyz, hi xyz} in world space as they were when the tree was built.  A geometry refit sets the
+     * entries of the deformed meshes to UINT32_MAX */
     const uint32_t* part_index; const float* part_boxes; uint64_t n_part_boxes;
 } ctl_flat_bvh_desc;
 int ctl_flat_bvh_build(const ctl_scene_desc* desc, uint32_t format, ctl_flat_bvh** out);
 int ctl_flat_bvh_arrays(const ctl_flat_bvh* h, ctl_flat_bvh_desc* out);
 void ctl_flat_bvh_destroy(ctl_flat_bvh* h);
 /* The refit of ctl_scene_update on the arrays of a CTL_FLAT_Q4 handle, host only, with the same arithmetic (csrc/flat_refit.h): the yardstick of the device kernels.
- * new_desc = the description the handle was built from with other node transforms.  Other formats: CTL_ERR_UNSUPPORTED. */
+ * new_desc = the description the handle was built from with other node transforms and / or other vertex values in some meshes (ctl_builder_update_mesh; the handle
+ * tells them by the per-mesh hashes it keeps): the entries of those meshes take their new Woop rows and become whole, which the part_index of ctl_flat_bvh_arrays
+ * shows afterwards.  CTL_ERR_INVALID where ctl_scene_update would refuse the geometry (another structure, a degenerate triangle that is regular now).
+ * Other formats: CTL_ERR_UNSUPPORTED. */
 int ctl_flat_bvh_refit(ctl_flat_bvh* h, const ctl_scene_desc* new_desc);
 /* The flattened tree of a CTL_SCENE_FLATTEN scene copied back from HBM into a handle for ctl_flat_bvh_arrays, with the BSDF-model bits (28..31 of the index word)
  * and the alpha bit (31 of the node word) that ctl_scene_create_ex stamps into the device copy removed: the arrays the test oracle traverses. */

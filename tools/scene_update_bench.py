@@ -10,6 +10,12 @@ Per workload, on one GPU, in one process:
      once with the cache warm for the NEW transforms (its best case);
   3. Mrays/s of the WavefrontPathTracer (depth 8) on the refitted tree against a freshly built tree of the same description, for three motions of one node
      (M1 small move, M2 rotation + non-uniform scale, M3 a move across a third of the scene), next to the surface-area ratio ctl_scene_get_update_stats reports.
+  4. a one-mesh deformation (DynamicScene.UpdateMesh: a ripple along the normals, 4 % of the mesh radius, on the mesh of the moved node): wall time around
+     UpdateMesh + ctl_builder_finalize + ctl_scene_update, median of 10, and the refit kernels' HIP-event time; against what a host without CTL_DIFF_GEOMETRY pays in
+     the same run — the scene built again in a new builder with the cache warm for every untouched mesh, ctl_builder_add_mesh of the deformed arrays (cold: a new
+     content hash) and ctl_scene_create_ex (the flattened tree is necessarily cold too); and the refitted tree's Mrays/s and node-area ratio against a fresh tree.
+     A workload that comes from a Mitsuba file has no vertex arrays on the Python side: the mesh's triangles are taken back from its Woop rows as a triangle soup.
+--only deform runs step 4 (and the camera update of step 1) alone.
 One JSON line per workload is appended to --out; --results appends a section to that Markdown file.  bench.py is not involved.
 """
 import argparse
@@ -73,6 +79,66 @@ def mrays(scene, args):
     return (t1.rays_total - t0.rays_total) / max(1e-9, t1.seconds_total - t0.seconds_total) / 1e6
 
 
+def mesh_soup(d, mesh):
+    """the triangles of one mesh of a description as a soup (3 * n_tri, 3) float32: the vertices back from the Woop rows (TriIntersectorData::getData), one row per triangle"""
+    M = d.view("meshes", np.uint32, d.n_meshes, 5)
+    first = int(M[mesh, 2] // 3); later = np.sort(M[:, 2] // 3); later = later[later > first]
+    last = int(later[0]) if len(later) else d.n_woop
+    tris = d.view("woop_index", np.uint32, d.n_woop, 1)[int(M[mesh, 3]):int(M[mesh, 3]) + last - first, 0] >> 1
+    _, pick = np.unique(tris, return_index=True)             # sorted by triangle id: triangle t of the mesh is row pick[t]
+    R = d.view("woop", np.float32, d.n_woop, 12)[first:last][pick].astype(np.float64).reshape(-1, 3, 4)
+    A = np.zeros((len(R), 4, 4)); A[:, 0] = R[:, 1]; A[:, 1] = R[:, 2]; A[:, 2] = R[:, 0]; A[:, 2, 3] *= -1; A[:, 3, 3] = 1
+    Ai = np.linalg.inv(A)
+    v2 = Ai[:, :3, 3]
+    return np.stack([v2 + Ai[:, :3, 0], v2 + Ai[:, :3, 1], v2], axis=1).reshape(-1, 3).astype(np.float32)
+
+
+def ripple(P, k=0):
+    """D1 of tests/scene_deform_cases.py: along the direction from the mesh's centre, amplitude 4 % of its radius; k shifts the phase (every step of a timing loop differs)"""
+    P = np.asarray(P, np.float64)
+    c = 0.5 * (P.min(axis=0) + P.max(axis=0)); Q = P - c
+    radius = np.linalg.norm(Q, axis=1).max()
+    n = Q / np.maximum(np.linalg.norm(Q, axis=1, keepdims=True), 1e-30)
+    return (P + n * (0.04 * radius * np.sin(5.0 * Q[:, 0] / radius + 3.0 * Q[:, 1] / radius + 0.7 + 0.37 * k))[:, None]).astype(np.float32)
+
+
+def deformation(workload, args, sc, scene, node, rec):
+    d = sc.desc
+    mesh = int(d.view("nodes", np.uint32, d.n_nodes, 6)[node, 0])
+    inp = sc.mesh_inputs.get(mesh)
+    P0, I, N, UV = (inp["positions"], inp["indices"], inp["normals"], inp["uvs"]) if inp else (mesh_soup(d, mesh), None, None, None)
+    rec["deformed_mesh"] = mesh; rec["deformed_triangles"] = int(len(I) if I is not None else len(P0) // 3)
+    rec["deformed_instances"] = int((d.view("nodes", np.uint32, d.n_nodes, 6)[:, 0] == mesh).sum())
+    refit = []
+
+    def deform(k):
+        sc.UpdateMesh(mesh, ripple(P0, k), I, normals=N, uvs=UV); assert scene.update(sc.UpdateScene()) & api.DIFF_GEOMETRY; refit.append(scene.update_stats()["refit_ms"])
+    rec["update_deform_ms"] = timed(deform)
+    rec["deform_refit_kernels_ms"] = float(np.median(refit))
+    P1 = ripple(P0, 100)
+    sc.UpdateMesh(mesh, P1, I, normals=N, uvs=UV); scene.update(sc.UpdateScene())
+    st = scene.update_stats()
+    r = mrays(scene, args)
+    # what the same change costs without CTL_DIFF_GEOMETRY: the cache is warmed by a first build of the untouched scene; then a new builder (every untouched mesh from
+    # the cache), the deformed arrays compiled (cold) and the scene created (the flattened tree cold)
+    with tempfile.TemporaryDirectory() as cache:
+        api.set_cache_dir(cache)
+        warm = build(workload, args); del warm
+        t = time.perf_counter()
+        again = build(workload, args)
+        cold = api.DynamicScene(); cold.add_mesh(P1, I, normals=N, uvs=UV)
+        rec["recreate_deformed_builder_ms"] = (time.perf_counter() - t) * 1e3
+        again.UpdateMesh(mesh, P1, I, normals=N, uvs=UV); again.UpdateScene()     # (not timed: stands in for the new builder holding the deformed mesh)
+        t = time.perf_counter(); fresh = ctl.Scene(again.desc, flatten=True); rec["recreate_deformed_create_ms"] = (time.perf_counter() - t) * 1e3
+        api.set_cache_dir(None)
+    rec["recreate_deformed_ms"] = rec["recreate_deformed_builder_ms"] + rec["recreate_deformed_create_ms"]
+    f = mrays(fresh, args)
+    del fresh
+    rec["traversal_deformed"] = dict(refit_mrays=r, fresh_mrays=f, ratio=r / f, node_area_before=st["node_area_before"], node_area_after=st["node_area_after"],
+                                     area_ratio=st["node_area_after"] / st["node_area_before"], refit_ms=st["refit_ms"])
+    rec["deform_faster_than_recreate"] = bool(rec["update_deform_ms"] < rec["recreate_deformed_ms"])
+
+
 def timed(f, n=10):
     ts = []
     for k in range(n):
@@ -96,6 +162,9 @@ def run(workload, args):
     def camera(k):
         s = api.ctl_sensor.from_buffer_copy(cam0); s.to_world[3] += 0.001 * size[0] * (k + 1); sc.setSensor(s); assert scene.update(sc.UpdateScene()) == api.DIFF_CAMERA
     rec["update_camera_ms"] = timed(camera)
+    if args.only == "deform":
+        deformation(workload, args, sc, scene, node, rec)
+        return rec
 
     def material(k):
         sc.desc.materials[0].tex[0].value[0] = 0.3 + 0.01 * k; assert scene.update(sc.desc) == api.DIFF_MATERIALS
@@ -132,10 +201,27 @@ def run(workload, args):
         rec["traversal"][which] = dict(refit_mrays=r, fresh_mrays=f, ratio=r / f, node_area_before=st["node_area_before"], node_area_after=st["node_area_after"],
                                        area_ratio=st["node_area_after"] / st["node_area_before"], refit_ms=st["refit_ms"])
     rec["faster_than_warm_recreate"] = bool(rec["update_transform_ms"] < rec["recreate_warmcache_ms"])
+    sc.SetNodeTransform(node, X0.astype(np.float32)); scene.update(sc.UpdateScene())
+    deformation(workload, args, sc, scene, node, rec)
     return rec
 
 
+def markdown_deform(recs):
+    out = ["", "## Deforming one mesh in place (tools/scene_update_bench.py)", "",
+           "| workload | deformed mesh (triangles x instances) | update: camera | one-mesh deformation (refit kernels) | re-create: new builder + add_mesh | + ctl_scene_create_ex | re-create, total |", "|---|---|---|---|---|---|---|"]
+    for r in recs:
+        out.append("| %s | %d x %d | %.2f ms | %.2f ms (%.2f ms) | %.0f ms | %.0f ms | %.0f ms |" % (r["workload"], r["deformed_triangles"], r["deformed_instances"], r["update_camera_ms"], r["update_deform_ms"],
+                   r["deform_refit_kernels_ms"], r["recreate_deformed_builder_ms"], r["recreate_deformed_create_ms"], r["recreate_deformed_ms"]))
+    out += ["", "| workload | change | refitted tree | fresh tree | ratio | node-area ratio (SAH proxy) |", "|---|---|---|---|---|---|"]
+    for r in recs:
+        t = r["traversal_deformed"]
+        out.append("| %s | D1 | %.0f Mrays/s | %.0f Mrays/s | %.3f | %.3f |" % (r["workload"], t["refit_mrays"], t["fresh_mrays"], t["ratio"], t["area_ratio"]))
+    return "\n".join(out) + "\n"
+
+
 def markdown(recs):
+    if "update_transform_ms" not in recs[0]:
+        return markdown_deform(recs)
     out = ["", "## In-place scene updates (tools/scene_update_bench.py)", "",
            "| workload | entries | update: camera | material | material + re-stamp | one-node transform (refit kernels) | re-create, no cache | re-create, warm cache |", "|---|---|---|---|---|---|---|---|"]
     for r in recs:
@@ -145,7 +231,7 @@ def markdown(recs):
     for r in recs:
         for m, t in r["traversal"].items():
             out.append("| %s | %s | %.0f Mrays/s | %.0f Mrays/s | %.3f | %.3f |" % (r["workload"], m, t["refit_mrays"], t["fresh_mrays"], t["ratio"], t["area_ratio"]))
-    return "\n".join(out) + "\n"
+    return "\n".join(out) + "\n" + markdown_deform(recs)
 
 
 def main():
@@ -156,6 +242,7 @@ def main():
     ap.add_argument("--depth", type=int, default=8); ap.add_argument("--passes", type=int, default=4)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scene_update.jsonl"))
     ap.add_argument("--results", default=None)
+    ap.add_argument("--only", default=None, choices=["deform"], help="deform: the camera update and the one-mesh deformation alone")
     args = ap.parse_args()
     if ctl.device_count() < 1:
         raise SystemExit("scene_update_bench needs a HIP device")
