@@ -45,6 +45,15 @@
 #define CTL_SHADE_CLASSED 0
 #endif
 #define CTL_HAS_KEY(k) ((((unsigned)(CTL_SHADE_KEYS)) >> (k)) & 1u)
+// CTL_SHADE_PARK (the basic build): per-lane words that live long and are touched seldom — the radiance, the throughput, the pixel position, the pass number, the next
+// direction — wait in LDS (s_park[word][lane]) instead of in registers while the hit point is set up and the BSDF and the light are evaluated; the code takes them out where it
+// needs them and puts them back.  A lane reads only what it wrote itself, so the parking needs no barrier of its own.  Every floating-point operation and its order stay.
+#ifndef CTL_SHADE_PARK
+#define CTL_SHADE_PARK 0
+#endif
+#if CTL_SHADE_PARK && CTL_SHADE_WAVEFRONT_RULES
+#error "CTL_SHADE_PARK is written for the default path rules"
+#endif
 #include "kernels.h"
 #include "shading.h"
 #include "compaction.h"
@@ -52,9 +61,22 @@
 namespace ctl {
 
 // ------------------------------------------------------------------------------------------------ shading
+#if CTL_SHADE_PARK
+// the lane's own index, opaque to the compiler: a read through it is not forwarded from the store that parked the word (forwarding would keep the word in its register)
+__device__ __forceinline__ uint32_t park_lane() { uint32_t t = threadIdx.x; asm volatile("" : "+v"(t)); return t; }
+#define CTL_PARK3(k, v) (s_park[k][threadIdx.x] = (v).x, s_park[(k) + 1][threadIdx.x] = (v).y, s_park[(k) + 2][threadIdx.x] = (v).z)
+#define CTL_UNPARK3(k, v) ((v) = f3(s_park[k][park_lane()], s_park[(k) + 1][park_lane()], s_park[(k) + 2][park_lane()]))
+#else
+#define CTL_PARK3(k, v) ((void)0)
+#define CTL_UNPARK3(k, v) ((void)0)
+#endif
+enum { kParkCl = 0, kParkCf = 3, kParkNewD = 6, kParkPx = 9, kParkPass = 11, kParkWords = 12 };
 // One lane = one queued path vertex.  `depth` is the megakernel's 1-based depth of this vertex.
 __global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERNEL(dev_scene S, wave_queues Q, pass_params P, int depth, ctl_pixel_data* __restrict__ image) {
     __shared__ uint32_t s_cnt[3][kWideBlock / 64]; __shared__ uint32_t s_base[3];
+#if CTL_SHADE_PARK
+    __shared__ float s_park[kParkWords][CTL_SHADE_BLOCK];
+#endif
 #if CTL_SHADE_LDS_TABLES
     scene_tables_to_lds<CTL_SHADE_BLOCK>(S);   // emitter records, anim blob, normal table: LDS for the whole launch (shading.h scene_lights / scene_anim / scene_normal_lut)
 #endif
@@ -128,6 +150,9 @@ __global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERN
             pixel = __float_as_uint(rad.w);
             const uint32_t packed = __float_as_uint(nor.w);
             pass_b = (packed >> 16) & 0xffu;
+#if CTL_SHADE_PARK
+            s_park[kParkPx][threadIdx.x] = px.x; s_park[kParkPx + 1][threadIdx.x] = px.y; s_park[kParkPass][threadIdx.x] = __uint_as_float(pass_b);
+#endif
             const uint32_t n1 = CTL_SAMPLER_NUM_SEQUENCES * CTL_SAMPLER_SEQUENCE_LENGTH;
             sampler rng{ P.t1 + pass_b * n1, P.t2 + pass_b * n1, pixel, packed & 0xffu, (packed >> 8) & 0xffu };
             bool specularBounce = ((packed >> 24) & kFlagSpecular) != 0;
@@ -138,6 +163,7 @@ __global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERN
             // (deferred `cl += cf * UniformSampleOneLight(...)`, PathTracer.cu:81-82)
             const uint32_t sidx = __float_as_uint(pend.w);
             if (sidx != kNoShadow && !occ_prev[sidx]) cl = cl + f3(pend.x, pend.y, pend.z);
+            CTL_PARK3(kParkCl, cl); CTL_PARK3(kParkCf, cf);
             const f3 r_o(ro.x, ro.y, ro.z), r_d(rd.x, rd.y, rd.z);
             const int tri = __float_as_int(hit.w);
             if (depth == 1 && P.depth_buffer) {   // IDepthTracer: g_DepthImageWPT.Store(x, y, res.m_fDist) at pathDepth 0 (WavefrontPathTracer.cu:76-77, Kernel/Tracer.h:16-31)
@@ -179,7 +205,9 @@ __global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERN
 #if CTL_SHADE_WAVEFRONT_RULES
                     cl = cl + misWeight * light_eval(S, light, b.dg.P, b.dg.sys.n, -r_d) * cf;   // payload.L += misWeight * res.Le(...) * payload.throughput (WavefrontPathTracer.cu:99): the OTHER order than PathTrace's — one ulp in 1 % of the pixels (round 6, tools/r06_diag_wf.py)
 #else
+                    CTL_UNPARK3(kParkCl, cl); CTL_UNPARK3(kParkCf, cf);
                     cl = cl + misWeight * cf * light_eval(S, light, b.dg.P, b.dg.sys.n, -r_d);   // cl += misWeight * cf * r2.Le(...) (PathTracer.cu:76)
+                    CTL_PARK3(kParkCl, cl);
 #endif
                 }
 #if CTL_SHADE_WAVEFRONT_RULES
@@ -222,6 +250,7 @@ __global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERN
                 // what the continuation needs of the sampled record is taken now: next-event estimation below re-uses the record itself (a copy of it costs ~45 registers)
                 new_o = b.dg.P; new_d = b.dg.sys.to_world(b.wo);
                 specularBounce = (b.sampled_type & kEDelta) != 0;
+                CTL_PARK3(kParkNewD, new_d);
                 if (P.direct && (mat.combined_type & kESmooth)) {
                     // UniformSampleOneLight + EstimateDirect (Kernel/TraceAlgorithms.cu:44-101), occlusion deferred.
                     // `cl += cf * UniformSampleOneLight(...)` (PathTracer.cu:81-82) is executed WHATEVER the estimate is — no light, a zero light sample, a zero BSDF value, an occluded
@@ -245,6 +274,7 @@ __global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERN
                                         const float directPdf = (dr.measure == kMeasureArea ? dr.pdf * dr.dist / fabsf(dot(dr.n, dr.d)) : dr.pdf) * lpdf;
                                         weight = power_heuristic(directPdf, bp);
                                     }
+                                    CTL_UNPARK3(kParkCf, cf);
                                     directF = cf * sdiv(value * bsdfVal * weight, lpdf);
                                     want_shadow = true;
                                     sh_org = dr.ref; sh_dir = dr.d; sh_tmax = dr.dist - S.eps;   // Occluded(r, 0, dist) (KernelDynamicScene.cu:70-80)
@@ -253,7 +283,8 @@ __global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERN
                         }
                     }
                 }
-                if (P.direct && (mat.combined_type & kESmooth)) cl = cl + cf * f3(0.0f);   // the zero estimate of `cl += cf * UniformSampleOneLight(...)` (see above): at the NEE site itself it cost the rough-plastic class kernel 16 B of scratch and synthetic-bathroom 1.3 %, here 0.3 %
+                CTL_UNPARK3(kParkCf, cf);
+                if (P.direct && (mat.combined_type & kESmooth)) { CTL_UNPARK3(kParkCl, cl); cl = cl + cf * f3(0.0f); CTL_PARK3(kParkCl, cl); }   // the zero estimate of `cl += cf * UniformSampleOneLight(...)` (see above): at the NEE site itself it cost the rough-plastic class kernel 16 B of scratch and synthetic-bathroom 1.3 %, here 0.3 %
                 cf = cf * f;
                 alive = true;
                 // a path whose throughput became exactly zero cannot contribute any more (the reference keeps tracing it
@@ -275,12 +306,14 @@ __global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERN
                     const float direct_pdf = env_pdf_direct(S, light, r_d) * pdf_emitter(S, S.env_map_index);
                     misWeight = power_heuristic(brdf_scattering_pdf, direct_pdf);
                 }
+                CTL_UNPARK3(kParkCl, cl); CTL_UNPARK3(kParkCf, cf);
                 cl = cl + misWeight * cf * env_eval(S, light, r_d);
+                CTL_PARK3(kParkCl, cl);
             }
 #endif
             // a miss without an environment map still executes `cl += misWeight * cf * EvalEnvironment(r)` with EvalEnvironment == Spectrum(0) (PathTracer.cu:99-111,
             // KernelDynamicScene.cu:54-60): nothing for a finite throughput, NaN for a NaN / infinite one — the sample is then dropped by AddSample, as in the reference
-            else if (CTL_HAS_KEY(0) && tri < 0) cl = cl + cf * f3(0.0f);
+            else if (CTL_HAS_KEY(0) && tri < 0) { CTL_UNPARK3(kParkCl, cl); CTL_UNPARK3(kParkCf, cf); cl = cl + cf * f3(0.0f); CTL_PARK3(kParkCl, cl); }
             terminated = !alive;
             specular = specularBounce; bsdf_pdf_out = brdf_scattering_pdf; d1 = rng.d1; d2 = rng.d2;
         }
@@ -288,8 +321,12 @@ __global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERN
         const block_slots bs = block_append3(n_shadow, want_shadow, n_next, alive, n_final, terminated && want_shadow, s_cnt, s_base);
         const uint32_t sslot = bs.s[0], nslot = bs.s[1], fslot = bs.s[2];
         if (!active) continue;
+#if CTL_SHADE_PARK
+        CTL_UNPARK3(kParkCl, cl); px = make_float2(s_park[kParkPx][park_lane()], s_park[kParkPx + 1][park_lane()]); pass_b = __float_as_uint(s_park[kParkPass][park_lane()]);
+#endif
         if (want_shadow) { sh_o[sslot] = make_float4(sh_org.x, sh_org.y, sh_org.z, S.eps); sh_d[sslot] = make_float4(sh_dir.x, sh_dir.y, sh_dir.z, sh_tmax); }
         if (alive) {
+            CTL_UNPARK3(kParkNewD, new_d);
             B.ray_o[nslot] = make_float4(new_o.x, new_o.y, new_o.z, S.eps);
             B.ray_d[nslot] = make_float4(new_d.x, new_d.y, new_d.z, 3.402823466e+38f);
             B.thr[nslot] = make_float4(cf.x, cf.y, cf.z, bsdf_pdf_out);

@@ -3,8 +3,10 @@
 # Usage: tools/kernel_resources.sh [kernels shade_full shade_basic megakernel]
 cd "$(dirname "$0")/.." || exit 1
 units=${*:-kernels shade_full shade_basic megakernel}
+# the flags of the library that ships (cudatracerlib_amd/build.py), not a copy of them
+FLAGS=$(python3 -c "import runpy; print(' '.join(runpy.run_path('cudatracerlib_amd/build.py')['FLAGS']))") || exit 1
 for f in $units; do
-  /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -ffp-contract=off -munsafe-fp-atomics $KRES_FLAGS -c cudatracerlib_amd/csrc/$f.hip -o /tmp/kres_$$.o \
+  ${HIPCC:-/opt/rocm/bin/hipcc} $FLAGS $KRES_FLAGS -c cudatracerlib_amd/csrc/$f.hip -o /tmp/kres_$$.o \
       -Rpass-analysis=kernel-resource-usage 2>&1 |
     awk -v unit="$f" '
       /Function Name:/ { name=$0; sub(/.*Function Name: /, "", name); sub(/ \[-Rpass.*/, "", name) }
