@@ -11,5 +11,5 @@ from .api import (  # noqa: F401
     ctl_tracer_stats, ctl_traversal_counts, ctl_float4x4,
     diffuse, dielectric, conductor, roughconductor, device_count, intersect, intersect_count, intersect_ex, intersect_pair,
     traversal_stack_histogram, traversal_lds_rows,
-    FlatBvh, scene_desc_diff, DIFF_CAMERA, DIFF_MATERIALS, DIFF_LIGHTS, DIFF_TRANSFORMS, DIFF_TOPOLOGY, DIFF_GEOMETRY,
+    FlatBvh, scene_desc_diff, DIFF_CAMERA, DIFF_MATERIALS, DIFF_LIGHTS, DIFF_TRANSFORMS, DIFF_TOPOLOGY, DIFF_GEOMETRY, skin_mesh_host,
 )

@@ -118,6 +118,12 @@ for _n in ("ctl_builder_destroy", "ctl_scene_destroy", "ctl_image_destroy", "ctl
     getattr(lib, _n).restype = None
     getattr(lib, _n).argtypes = [C.c_void_p]
 lib.ctl_builder_update_mesh.argtypes = [C.c_void_p, u32, C.c_void_p, u32, C.c_void_p, u32, C.c_void_p, C.c_void_p]
+lib.ctl_scene_bind_skin.argtypes = [C.c_void_p, u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, u32, C.c_void_p, C.c_void_p, u32]
+lib.ctl_scene_animate_mesh.argtypes = [C.c_void_p, u32, C.c_void_p, C.c_void_p, f32, C.c_void_p]
+lib.ctl_scene_get_skin_ms.argtypes = [C.c_void_p, C.POINTER(f32)]
+lib.ctl_scene_read_mesh_geometry.argtypes = [C.c_void_p, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.ctl_scene_unbind_skin.argtypes = [C.c_void_p, u32]
+lib.ctl_skin_mesh_host.argtypes = [C.c_void_p, u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p, f32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 lib.ctl_device_malloc.argtypes = [C.c_size_t, C.POINTER(C.c_void_p)]
 lib.ctl_device_free.argtypes = [C.c_void_p]
 lib.ctl_memcpy_h2d.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -704,6 +710,9 @@ class Scene:
         if flat_format is not None:
             flags |= (FLAT_FORMATS.get(flat_format, flat_format) + 1) << 8
         _check(lib.ctl_scene_create_ex(C.byref(desc), u32(flags), C.byref(self._h)))
+        # (triangles, Woop rows) per mesh, taken while the description is certainly alive: the sizes read_mesh_geometry's buffers must have (an update keeps them)
+        self._mesh_counts = mesh_counts(desc)
+        self._skins = {}   # mesh -> dict(n_vert, n_bones) of the bound meshes
 
     def update(self, desc):
         """ctl_scene_update: applies what differs between the description the scene holds and `desc` — camera, materials, lights, node transforms, the vertex
@@ -723,6 +732,48 @@ class Scene:
         _check(lib.ctl_scene_get_update_stats(self._h, C.byref(st)))
         return {k: getattr(st, k) for k, _ in st._fields_}
 
+    def bind_skin(self, mesh, rest_positions, indices, bone_indices, bone_weights, n_bones, rest_normals=None):
+        """ctl_scene_bind_skin: binds `mesh` to a rest pose (arrays as DynamicScene.add_mesh takes them; indices None: a soup; rest_normals None: computed once) and to
+        its bone bytes, uint8 (n_vert, 8) each.  The mesh is device-owned until unbind_skin."""
+        a = _skin_arrays(rest_positions, rest_normals, indices, bone_indices, bone_weights)
+        _check(lib.ctl_scene_bind_skin(self._h, u32(mesh), a["P"].ctypes.data, _ptr(a["N"]), u32(len(a["P"])), _ptr(a["I"]), u32(a["n_tri"]), a["BI"].ctypes.data, a["BW"].ctypes.data, u32(n_bones)))
+        self._skins[mesh] = dict(n_vert=len(a["P"]), n_bones=n_bones)
+
+    def animate_mesh(self, mesh, bones0, bones1=None, lerp=0.0):
+        """ctl_scene_animate_mesh: poses a bound mesh from (n_bones, 4, 4) row-major bone matrices; bones1 None: bones0.  Returns the update-stats dict plus skin_ms, the
+        HIP-event time of the three pose kernels.  Start the next pass with new_trace."""
+        B0 = np.ascontiguousarray(bones0, np.float32).reshape(-1, 16)
+        B1 = None if bones1 is None else np.ascontiguousarray(bones1, np.float32).reshape(-1, 16)
+        n = self._skins.get(mesh, {}).get("n_bones")
+        if n is not None and (len(B0) != n or (B1 is not None and len(B1) != n)):
+            raise ValueError("animate_mesh: %d bone matrices for a skin of %d bones" % (len(B0), n))
+        st = ctl_scene_update_stats()
+        _check(lib.ctl_scene_animate_mesh(self._h, u32(mesh), B0.ctypes.data, _ptr(B1), f32(lerp), C.addressof(st)))
+        out = {k: getattr(st, k) for k, _ in st._fields_}
+        ms = f32(); _check(lib.ctl_scene_get_skin_ms(self._h, C.byref(ms))); out["skin_ms"] = ms.value
+        return out
+
+    def read_mesh_geometry(self, mesh, vertices=False):
+        """ctl_scene_read_mesh_geometry: dict(tri (n_tri, 8) uint32, woop (n_rows, 12) uint32) as HBM holds them — any mesh of any scene — and, with vertices=True
+        (a bound, posed mesh), positions and normals (n_vert, 3) float32 of the last pose"""
+        if not 0 <= mesh < len(self._mesh_counts):
+            raise CtlError(ERR_INVALID, "read_mesh_geometry: bad mesh index")
+        n_tri, n_rows = self._mesh_counts[mesh]
+        tri = np.zeros((n_tri, 8), np.uint32); woop = np.zeros((n_rows, 12), np.uint32)
+        P = N = None
+        if vertices:
+            if mesh not in self._skins:
+                raise CtlError(ERR_INVALID, "read_mesh_geometry: mesh %d is not bound" % mesh)
+            n_vert = self._skins[mesh]["n_vert"]
+            P = np.zeros((n_vert, 3), np.float32); N = np.zeros((n_vert, 3), np.float32)
+        _check(lib.ctl_scene_read_mesh_geometry(self._h, u32(mesh), _ptr(P), _ptr(N), tri.ctypes.data, woop.ctypes.data))
+        return dict(positions=P, normals=N, tri=tri, woop=woop)
+
+    def unbind_skin(self, mesh):
+        """ctl_scene_unbind_skin: the next update(desc) sees the mesh as changed (DIFF_GEOMETRY) and restores the description's values"""
+        _check(lib.ctl_scene_unbind_skin(self._h, u32(mesh)))
+        self._skins.pop(mesh, None)
+
     def flat_bvh(self):
         """ctl_scene_read_flat_bvh: the device tree copied back as a FlatBvh, without the model / alpha bits stamped into the device copy"""
         h = C.c_void_p()
@@ -741,6 +792,50 @@ ERR_INVALID, ERR_NO_DEVICE, ERR_UNSUPPORTED = -1, -2, -5
 
 class ctl_scene_update_stats(C.Structure):
     _fields_ = [("node_area_before", C.c_double), ("node_area_after", C.c_double), ("refit_ms", f32), ("refit_levels", u32), ("mask", u32), ("restamped", u32)]
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _skin_arrays(rest_positions, rest_normals, indices, bone_indices, bone_weights):
+    P = _f32(rest_positions, (-1, 3))
+    N = None if rest_normals is None else _f32(rest_normals, (-1, 3))
+    I = None if indices is None else np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1, 3)
+    BI = np.ascontiguousarray(bone_indices, dtype=np.uint8).reshape(-1, 8); BW = np.ascontiguousarray(bone_weights, dtype=np.uint8).reshape(-1, 8)
+    if len(BI) != len(P) or len(BW) != len(P) or (N is not None and len(N) != len(P)):
+        raise ValueError("skin arrays: one row per vertex")
+    return dict(P=P, N=N, I=I, BI=BI, BW=BW, n_tri=len(P) // 3 if I is None else len(I))
+
+
+def skin_mesh_host(desc, mesh, rest_positions, indices, bone_indices, bone_weights, n_bones, bones0, bones1=None, lerp=0.0, rest_normals=None, n_rows=None):
+    """ctl_skin_mesh_host (host only): the yardstick of Scene.animate_mesh + read_mesh_geometry — dict(positions, normals (n_vert, 3) float32, tri (n_tri, 8) uint32,
+    woop (n_rows, 12) uint32); n_rows: the mesh's rows of the Woop stream (default: counted from the description's mesh offsets)"""
+    a = _skin_arrays(rest_positions, rest_normals, indices, bone_indices, bone_weights)
+    B0 = np.ascontiguousarray(bones0, np.float32).reshape(-1, 16)
+    B1 = None if bones1 is None else np.ascontiguousarray(bones1, np.float32).reshape(-1, 16)
+    if len(B0) != n_bones or (B1 is not None and len(B1) != n_bones):
+        raise ValueError("skin_mesh_host: %d bone matrices for %d bones" % (len(B0), n_bones))
+    if n_rows is None:
+        n_rows = mesh_counts(desc)[mesh][1] if 0 <= mesh < desc.n_meshes else 0
+    P = np.zeros((len(a["P"]), 3), np.float32); N = np.zeros_like(P); tri = np.zeros((a["n_tri"], 8), np.uint32); woop = np.zeros((n_rows, 12), np.uint32)
+    _check(lib.ctl_skin_mesh_host(C.addressof(desc), u32(mesh), a["P"].ctypes.data, _ptr(a["N"]), u32(len(a["P"])), _ptr(a["I"]), u32(a["n_tri"]), a["BI"].ctypes.data, a["BW"].ctypes.data,
+                                  u32(n_bones), B0.ctypes.data, _ptr(B1), f32(lerp), P.ctypes.data, N.ctypes.data, tri.ctypes.data, woop.ctypes.data))
+    return dict(positions=P, normals=N, tri=tri, woop=woop)
+
+
+def mesh_counts(desc):
+    """[(triangles, rows of the Woop stream)] per mesh of a description: a mesh's range ends where the next one (by offset) starts, the last one's at the array's end
+    (csrc/geometry_hash.h mesh_ranges).  One sort per array."""
+    if not desc.n_meshes:
+        return []
+    M = desc.view("meshes", np.uint32, desc.n_meshes, 5).astype(np.int64)
+
+    def lengths(start, total):
+        start = np.minimum(start, total); order = np.argsort(start, kind="stable")
+        end = np.empty_like(start); end[order] = np.append(start[order][1:], total)
+        return end - start
+    return list(zip(lengths(M[:, 0], desc.n_tri_data).tolist(), lengths(M[:, 2] // 3, desc.n_woop).tolist()))
 
 
 def scene_desc_diff(a, b):

@@ -8,6 +8,7 @@
 #include "scene_checks.h"
 #include "mitsuba_loader.h"
 #include "flatten.h"
+#include "mesh_skin.h"
 #include "material_factory.h"
 #include "material_textures.h"
 #include "image_io.h"
@@ -332,6 +333,36 @@ int ctl_scene_update(ctl_scene* scene, const ctl_scene_desc* new_desc, uint32_t*
     return rc;
 }
 int ctl_scene_get_update_stats(ctl_scene* scene, ctl_scene_update_stats* out) { CTL_REQUIRE(scene && out, "null argument"); *out = scene->s.last_update(); return CTL_OK; }
+// ---- skinned meshes (mesh_skin.hip)
+static const char* kNoDevice = "no HIP device: the MI355X path tracer has no CPU fallback";
+int ctl_scene_bind_skin(ctl_scene* scene, uint32_t mesh_index, const float* rest_positions, const float* rest_normals, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri,
+                        const uint8_t* bone_indices, const uint8_t* bone_weights, uint32_t n_bones) {
+    if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
+    CTL_REQUIRE(scene, "null scene");
+    CTL_TRY scene->s.bind_skin(mesh_index, rest_positions, rest_normals, n_vert, indices, n_tri, bone_indices, bone_weights, n_bones); CTL_CATCH
+}
+int ctl_scene_animate_mesh(ctl_scene* scene, uint32_t mesh_index, const ctl_float4x4* bones0, const ctl_float4x4* bones1, float lerp, ctl_scene_update_stats* stats_out) {
+    if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
+    CTL_REQUIRE(scene && bones0, "null argument");
+    CTL_TRY scene->s.animate_mesh(mesh_index, bones0, bones1, lerp, stats_out); CTL_CATCH
+}
+int ctl_scene_get_skin_ms(ctl_scene* scene, float* ms_out) { CTL_REQUIRE(scene && ms_out, "null argument"); *ms_out = scene->s.last_skin_ms(); return CTL_OK; }
+int ctl_scene_read_mesh_geometry(ctl_scene* scene, uint32_t mesh_index, float* positions_out, float* normals_out, ctl_triangle_data* tri_data_out, ctl_woop_tri* woop_out) {
+    if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
+    CTL_REQUIRE(scene, "null scene");
+    CTL_TRY scene->s.read_mesh_geometry(mesh_index, positions_out, normals_out, tri_data_out, woop_out); CTL_CATCH
+}
+int ctl_scene_unbind_skin(ctl_scene* scene, uint32_t mesh_index) {
+    if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
+    CTL_REQUIRE(scene, "null scene");
+    CTL_TRY scene->s.unbind_skin(mesh_index); CTL_CATCH
+}
+int ctl_skin_mesh_host(const ctl_scene_desc* desc, uint32_t mesh_index, const float* rest_positions, const float* rest_normals, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri,
+                       const uint8_t* bone_indices, const uint8_t* bone_weights, uint32_t n_bones, const ctl_float4x4* bones0, const ctl_float4x4* bones1, float lerp,
+                       float* positions_out, float* normals_out, ctl_triangle_data* tri_data_out, ctl_woop_tri* woop_out) {
+    CTL_REQUIRE(desc, "null description");
+    CTL_TRY skin_mesh_host(*desc, mesh_index, rest_positions, rest_normals, n_vert, indices, n_tri, bone_indices, bone_weights, n_bones, bones0, bones1, lerp, positions_out, normals_out, tri_data_out, woop_out); CTL_CATCH
+}
 int ctl_flat_bvh_refit(ctl_flat_bvh* h, const ctl_scene_desc* new_desc) { CTL_REQUIRE(h && new_desc, "null argument"); CTL_TRY refit_flat_scene(h->f, *new_desc, nullptr); CTL_CATCH }
 int ctl_scene_read_flat_bvh(ctl_scene* scene, ctl_flat_bvh** out) {
     CTL_REQUIRE(scene && out, "null argument");

@@ -27,7 +27,7 @@ mesh_ranges::mesh_ranges(const ctl_scene_desc& d) {
     ranges_of(s, d.n_bvh_nodes, node0, node1);
 }
 
-void hash_geometry(const ctl_scene_desc& d, geometry_hashes& out) {
+void hash_geometry(const ctl_scene_desc& d, geometry_hashes& out, const std::vector<uint8_t>* skip_values) {
     const mesh_ranges R(d);
     content_hash S; std::vector<content_hash> V(d.n_meshes);
     uint32_t tri_front = d.n_tri_data, woop_front = d.n_woop, node_front = d.n_bvh_nodes;
@@ -40,6 +40,8 @@ void hash_geometry(const ctl_scene_desc& d, geometry_hashes& out) {
     static_assert(sizeof(ctl_bvh_node) == 64, "Aila-Laine node: 48 B of boxes, 16 B of links");
     for (uint32_t m = 0; m < d.n_meshes; m++) {
         content_hash& H = V[m];
+        const bool skip = skip_values && m < skip_values->size() && (*skip_values)[m];
+        if (skip) { for (uint32_t i = R.node0[m]; i < R.node1[m]; i++) S.add(&d.bvh_nodes[i].child0, 16); continue; }
         if (R.tri1[m] > R.tri0[m]) H.add(d.tri_data + R.tri0[m], (size_t)(R.tri1[m] - R.tri0[m]) * sizeof(ctl_triangle_data));
         if (R.woop1[m] > R.woop0[m]) H.add(d.woop + R.woop0[m], (size_t)(R.woop1[m] - R.woop0[m]) * sizeof(ctl_woop_tri));
         for (uint32_t i = R.node0[m]; i < R.node1[m]; i++) { H.add(&d.bvh_nodes[i], 48); S.add(&d.bvh_nodes[i].child0, 16); }
@@ -54,7 +56,10 @@ void hash_geometry(const ctl_scene_desc& d, geometry_hashes& out) {
     }
     S.digest(out.structure);
     out.values.resize((size_t)d.n_meshes * 2);
-    for (uint32_t m = 0; m < d.n_meshes; m++) V[m].digest(&out.values[(size_t)m * 2]);
+    for (uint32_t m = 0; m < d.n_meshes; m++) {
+        if (skip_values && m < skip_values->size() && (*skip_values)[m]) { out.values[(size_t)m * 2] = out.values[(size_t)m * 2 + 1] = 0; continue; }
+        V[m].digest(&out.values[(size_t)m * 2]);
+    }
 }
 
 }  // namespace ctl

@@ -24,8 +24,12 @@ struct geometry_hashes {
     std::vector<uint64_t> values;   // two words per mesh
     bool same_structure(const geometry_hashes& o) const { return structure[0] == o.structure[0] && structure[1] == o.structure[1] && values.size() == o.values.size(); }
     bool same_values(const geometry_hashes& o, size_t m) const { return values[2 * m] == o.values[2 * m] && values[2 * m + 1] == o.values[2 * m + 1]; }
+    // a mesh whose values in HBM are no description's any more (ctl_scene_unbind_skin): the two words no digest is expected to give, so that every later comparison
+    // finds the mesh changed; hash_geometry writes the same words for a mesh it was told to skip, and a diff that ignores a mesh carries them forward.  Idempotent.
+    void invalidate_values(size_t m) { if (values.size() > 2 * m + 1) values[2 * m] = values[2 * m + 1] = 0; }
     bool empty() const { return values.empty() && !structure[0] && !structure[1]; }
 };
-void hash_geometry(const ctl_scene_desc& d, geometry_hashes& out);
+// skip_values (may be null, else one byte per mesh): the value ranges of a marked mesh are not read and its two words are 0
+void hash_geometry(const ctl_scene_desc& d, geometry_hashes& out, const std::vector<uint8_t>* skip_values = nullptr);
 
 }  // namespace ctl

@@ -8,37 +8,15 @@
 #include <cstdlib>
 #include <string>
 #include "ctl_math.h"
+#include "mesh_skin.h"
 #include <cstring>
 #include <algorithm>
 #include <stdexcept>
 
 namespace ctl {
 
-// float4x4::inverse (Math/float4x4.h:132-193) — cofactor expansion in the reference's expression order
-void mat_inverse(const float* Q, float* out) {
-#define M(i, j) Q[(i) * 4 + (j)]
-    float m00 = M(0, 0), m01 = M(0, 1), m02 = M(0, 2), m03 = M(0, 3), m10 = M(1, 0), m11 = M(1, 1), m12 = M(1, 2), m13 = M(1, 3);
-    float m20 = M(2, 0), m21 = M(2, 1), m22 = M(2, 2), m23 = M(2, 3), m30 = M(3, 0), m31 = M(3, 1), m32 = M(3, 2), m33 = M(3, 3);
-#undef M
-    float v0 = m20 * m31 - m21 * m30, v1 = m20 * m32 - m22 * m30, v2 = m20 * m33 - m23 * m30;
-    float v3 = m21 * m32 - m22 * m31, v4 = m21 * m33 - m23 * m31, v5 = m22 * m33 - m23 * m32;
-    float t00 = +(v5 * m11 - v4 * m12 + v3 * m13), t10 = -(v5 * m10 - v2 * m12 + v1 * m13);
-    float t20 = +(v4 * m10 - v2 * m11 + v0 * m13), t30 = -(v3 * m10 - v1 * m11 + v0 * m12);
-    float invDet = 1 / (t00 * m00 + t10 * m01 + t20 * m02 + t30 * m03);
-    float d00 = t00 * invDet, d10 = t10 * invDet, d20 = t20 * invDet, d30 = t30 * invDet;
-    float d01 = -(v5 * m01 - v4 * m02 + v3 * m03) * invDet, d11 = +(v5 * m00 - v2 * m02 + v1 * m03) * invDet;
-    float d21 = -(v4 * m00 - v2 * m01 + v0 * m03) * invDet, d31 = +(v3 * m00 - v1 * m01 + v0 * m02) * invDet;
-    v0 = m10 * m31 - m11 * m30; v1 = m10 * m32 - m12 * m30; v2 = m10 * m33 - m13 * m30;
-    v3 = m11 * m32 - m12 * m31; v4 = m11 * m33 - m13 * m31; v5 = m12 * m33 - m13 * m32;
-    float d02 = +(v5 * m01 - v4 * m02 + v3 * m03) * invDet, d12 = -(v5 * m00 - v2 * m02 + v1 * m03) * invDet;
-    float d22 = +(v4 * m00 - v2 * m01 + v0 * m03) * invDet, d32 = -(v3 * m00 - v1 * m01 + v0 * m02) * invDet;
-    v0 = m21 * m10 - m20 * m11; v1 = m22 * m10 - m20 * m12; v2 = m23 * m10 - m20 * m13;
-    v3 = m22 * m11 - m21 * m12; v4 = m23 * m11 - m21 * m13; v5 = m23 * m12 - m22 * m13;
-    float d03 = -(v5 * m01 - v4 * m02 + v3 * m03) * invDet, d13 = +(v5 * m00 - v2 * m02 + v1 * m03) * invDet;
-    float d23 = -(v4 * m00 - v2 * m01 + v0 * m03) * invDet, d33 = +(v3 * m00 - v1 * m01 + v0 * m02) * invDet;
-    float r[16] = { d00, d01, d02, d03, d10, d11, d12, d13, d20, d21, d22, d23, d30, d31, d32, d33 };
-    std::memcpy(out, r, sizeof(r));
-}
+// float4x4::inverse (Math/float4x4.h:132-193): the one restatement is mesh_skin.h's, which the device runs too
+void mat_inverse(const float* Q, float* out) { float r[16]; mat4_inverse(Q, r); std::memcpy(out, r, sizeof(r)); }
 void mat_mul(const float* l, const float* r, float* o) {   // float4x4.h:373-381
     float t[16];
     for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) { float s = 0.0f; for (int k = 0; k < 4; k++) s += l[i * 4 + k] * r[k * 4 + j]; t[i * 4 + j] = s; }
@@ -48,11 +26,8 @@ static m34 as_m34(const float* m) { m34 r; std::memcpy(r.r, m, 48); return r; }
 
 // Woop rows from the three vertices (Engine/TriIntersectorData.cu:5-18)
 void woop_set_data(ctl_woop_tri& w, f3 a, f3 b, f3 c) {
-    f3 e0 = a - c, e1 = b - c, n = cross(a - c, b - c);
-    float m[16] = { e0.x, e1.x, n.x, c.x, e0.y, e1.y, n.y, c.y, e0.z, e1.z, n.z, c.z, 0, 0, 0, 1 }, inv[16];
-    mat_inverse(m, inv);
-    w.a[0] = inv[8]; w.a[1] = inv[9]; w.a[2] = inv[10]; w.a[3] = -inv[11];
-    for (int j = 0; j < 4; j++) { w.b[j] = inv[j]; w.c[j] = inv[4 + j]; }
+    float r[12]; woop_rows_from_vertices(r, a, b, c);
+    std::memcpy(w.a, r, 16); std::memcpy(w.b, r + 4, 16); std::memcpy(w.c, r + 8, 16);
 }
 // and back (Engine/TriIntersectorData.cu:20-32) — area lights take their vertices from this round trip
 void woop_get_data(const ctl_woop_tri& w, f3& v0, f3& v1, f3& v2) {
@@ -65,26 +40,11 @@ void woop_get_data(const ctl_woop_tri& w, f3& v0, f3& v1, f3& v2) {
 
 // TriangleData::setUvSetData + setData (Engine/TriangleData.cu:18-65)
 static void tri_data_pack(ctl_triangle_data& T, const f3 p[3], const f3 n[3], const f2 t[3], uint32_t mat_index) {
-    std::memset(&T, 0, sizeof(T));
-    T.nor_mat_extra[1] = (mat_index & 0xff) << 16;
-    for (int i = 0; i < 3; i++) T.uv[i] = (uint32_t)float_to_half(t[i].x) | ((uint32_t)float_to_half(t[i].y) << 16);
-    auto h = [](uint32_t bits) { return half_to_float((uint16_t)bits); };
-    f2 t0{ h(T.uv[0]), h(T.uv[0] >> 16) }, t1{ h(T.uv[1]), h(T.uv[1] >> 16) }, t2{ h(T.uv[2]), h(T.uv[2] >> 16) };
-    f3 dP1 = p[1] - p[0], dP2 = p[2] - p[0];
-    f2 dUV1{ t1.x - t0.x, t1.y - t0.y }, dUV2{ t2.x - t0.x, t2.y - t0.y };
-    float determinant = dUV1.x * dUV2.y - dUV1.y * dUV2.x;
-    f3 dpdu, dpdv;
-    if (determinant == 0) { f3 a, b, nn = normalize(cross(dP1, dP2)); coordinate_system(nn, a, b); dpdu = a; dpdv = b; }
-    else {
-        float invDet = 1.0f / determinant;
-        dpdu = ((dUV2.y * dP1 - dUV1.y * dP2) * invDet);
-        dpdv = ((-dUV2.x * dP1 + dUV1.x * dP2) * invDet);
-    }
-    uint32_t ax = float_to_half(dpdu.x), ay = float_to_half(dpdu.y), az = float_to_half(dpdu.z);
-    uint32_t bx = float_to_half(dpdv.x), by = float_to_half(dpdv.y), bz = float_to_half(dpdv.z);
-    T.nor_mat_extra[0] = (uint32_t)normal_to_uchar2(n[0]) | ((uint32_t)normal_to_uchar2(n[1]) << 16);
-    T.nor_mat_extra[1] = (uint32_t)normal_to_uchar2(n[2]) | (T.nor_mat_extra[1] & 0xffff0000);
-    T.dpdu_dpdv[0] = ax | (ay << 16); T.dpdu_dpdv[1] = az | (bx << 16); T.dpdu_dpdv[2] = by | (bz << 16);
+    uint32_t uv[3], words[8];
+    for (int i = 0; i < 3; i++) uv[i] = (uint32_t)float_to_half(t[i].x) | ((uint32_t)float_to_half(t[i].y) << 16);
+    tri_data_words<false>(words, p, n, uv, mat_index);   // mesh_skin.h; the normal codec over libm, as these arrays always were
+    static_assert(sizeof(ctl_triangle_data) == sizeof(words), "TriangleData is eight words");
+    std::memcpy(&T, words, sizeof(words));
 }
 
 // shading normal of a triangle at barycentrics (1/3,1/3) under `l2w` — the dg.sys.n of TriangleData::fillDG
@@ -104,7 +64,7 @@ static f3 tri_data_center_normal(const ctl_triangle_data& T, const m34& l2w) {
 // Mesh::ComputeVertexNormals (Engine/Mesh.cpp:151-190), "sphere inscribed polytope" weights
 static aabb box_transform(const aabb& b, const float* m);
 
-static void compute_vertex_normals(const float* V, const uint32_t* I, uint32_t nv, uint32_t nt, std::vector<f3>& N, bool flip = false) {
+void compute_vertex_normals(const float* V, const uint32_t* I, uint32_t nv, uint32_t nt, std::vector<f3>& N, bool flip) {
     N.assign(nv, f3(0.0f));
     auto vtx = [&](uint32_t i) { return f3(V[3 * i], V[3 * i + 1], V[3 * i + 2]); };
     const float flip_coeff = flip ? -1.0f : 1.0f;

@@ -10,6 +10,8 @@ namespace ctl {
 void mat_inverse(const float* m16, float* out16);   // float4x4::inverse (Math/float4x4.h:132-193)
 void mat_mul(const float* l16, const float* r16, float* out16);
 void woop_set_data(ctl_woop_tri& w, f3 a, f3 b, f3 c);
+// Mesh::ComputeVertexNormals (Engine/Mesh.cpp:151-190); I == nullptr: a triangle soup.  Also what ctl_scene_bind_skin makes of a rest pose without normals
+void compute_vertex_normals(const float* V, const uint32_t* I, uint32_t nv, uint32_t nt, std::vector<f3>& N, bool flip = false);
 void woop_get_data(const ctl_woop_tri& w, f3& v0, f3& v1, f3& v2);
 
 struct mesh_rec { uint32_t tri_offset, n_tris, node_offset, n_nodes, woop_offset, n_woop, mat_offset, n_mat; aabb box; int max_depth; };

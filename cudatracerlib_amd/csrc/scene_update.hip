@@ -13,7 +13,7 @@
 
 namespace ctl {
 
-uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const geometry_hashes* a_geometry, geometry_hashes* b_geometry) {
+uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const geometry_hashes* a_geometry, geometry_hashes* b_geometry, const std::vector<uint8_t>* ignore_values) {
     auto same = [](const void* x, const void* y, size_t bytes) { return bytes == 0 || (x && y && std::memcmp(x, y, bytes) == 0); };
     uint32_t mask = 0;
     // topology first: the counts decide whether the arrays can be compared at all
@@ -36,7 +36,9 @@ uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const
         geometry_hashes ha, hb_local; geometry_hashes& hb = b_geometry ? *b_geometry : hb_local;
         if (!a_geometry) hash_geometry(a, ha);
         const geometry_hashes& ga = a_geometry ? *a_geometry : ha;
-        hash_geometry(b, hb);
+        if (ignore_values && ignore_values->size() != b.n_meshes) ignore_values = nullptr;
+        hash_geometry(b, hb, ignore_values);   // the ranges of an ignored mesh are not read
+        if (ignore_values && hb.values.size() == ga.values.size()) for (uint32_t m = 0; m < b.n_meshes; m++) if ((*ignore_values)[m]) { hb.values[2 * m] = ga.values[2 * m]; hb.values[2 * m + 1] = ga.values[2 * m + 1]; }
         if (!hb.same_structure(ga)) mask |= CTL_DIFF_TOPOLOGY;
         else for (uint32_t m = 0; m < b.n_meshes; m++) if (!hb.same_values(ga, m)) { mask |= CTL_DIFF_GEOMETRY; break; }
     }
@@ -140,7 +142,9 @@ uint32_t Scene::update(const ctl_scene_desc& d, ctl_scene_update_stats* stats) {
     require_device();
     if (!snap_) throw std::runtime_error("ctl_scene_update: the scene holds no description");
     geometry_hashes geom;
-    const uint32_t mask = scene_desc_diff(snap_->d, d, &snap_->geom, &geom);
+    std::vector<uint8_t> device_owned;   // the bound meshes (mesh_skin.hip): their values are the device's, whatever the description says
+    if (!skins_.empty()) { device_owned.assign(snap_->d.n_meshes, 0); for (const auto& kv : skins_) if (kv.first < device_owned.size()) device_owned[kv.first] = 1; }
+    const uint32_t mask = scene_desc_diff(snap_->d, d, &snap_->geom, &geom, device_owned.empty() ? nullptr : &device_owned);
     last_mask_ = mask;
     if (mask == 0) { last_update_ = ctl_scene_update_stats{}; if (stats) *stats = last_update_; return 0; }   // nothing differs: no synchronisation, no tracer is stalled
     if (mask & CTL_DIFF_TOPOLOGY) throw std::runtime_error("ctl_scene_update: the topology of the scene differs (geometry arrays, counts, node -> mesh / material assignment, images or transmittance tables): re-create the scene");

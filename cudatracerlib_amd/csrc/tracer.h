@@ -35,7 +35,9 @@ template <typename T> struct dbuf {   // tracked device allocation (Base/CudaMem
 // ctl_scene_desc_diff: the CTL_DIFF_* bits of what differs between two descriptions.  a_geometry: when given, `a` is a snapshot without its geometry arrays
 // (triangles, Woop rows, mesh BVHs, texels, transmittance tables) and they are compared through the hashes of geometry_hash.h instead.  b_geometry (may be null)
 // receives the hashes of `b` where the function made them (always when a_geometry is given and the counts agree): the ONE pass over b's geometry arrays of an update
-uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const geometry_hashes* a_geometry = nullptr, geometry_hashes* b_geometry = nullptr);
+// ignore_values (may be null): per mesh, non-zero = the VALUES of that mesh are not compared (a device-owned mesh, mesh_skin.hip): b's hash of it is a's
+uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const geometry_hashes* a_geometry = nullptr, geometry_hashes* b_geometry = nullptr, const std::vector<uint8_t>* ignore_values = nullptr);
+struct skin_binding;   // mesh_skin.hip
 // the host copy of a description that a scene keeps to diff an update against (scene_update.hip)
 struct desc_snapshot {
     ctl_scene_desc d{};   // pointers into the vectors below; the geometry arrays are null
@@ -61,6 +63,13 @@ public:
     uint32_t last_mask() const { return last_mask_; }   // the CTL_DIFF_* bits the last update() found, also when it refused
     const ctl_scene_update_stats& last_update() const { return last_update_; }
     void read_flat_bvh(flat_scene& out);   // the device tree copied back, un-stamped: what flatten_scene handed to the upload, after any refit
+    // skinned meshes (mesh_skin.hip; ctl_scene_bind_skin, ctl_scene_animate_mesh, ctl_scene_read_mesh_geometry, ctl_scene_unbind_skin).  A bound mesh is device-owned: update()
+    // neither compares nor uploads its values
+    void bind_skin(uint32_t mesh, const float* rest_positions, const float* rest_normals, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri, const uint8_t* bone_indices, const uint8_t* bone_weights, uint32_t n_bones);
+    void unbind_skin(uint32_t mesh);
+    void animate_mesh(uint32_t mesh, const ctl_float4x4* bones0, const ctl_float4x4* bones1, float lerp, ctl_scene_update_stats* stats);
+    void read_mesh_geometry(uint32_t mesh, float* positions_out, float* normals_out, ctl_triangle_data* tri_data_out, ctl_woop_tri* woop_out);
+    float last_skin_ms() const { return last_skin_ms_; }   // HIP-event time of the three pose kernels of the last animate_mesh
     dev_scene S{};
     uint32_t n_nodes = 0;
     float box_min[3] = { 0, 0, 0 }, box_max[3] = { 0, 0, 0 };   // KernelDynamicScene::m_sBox
@@ -80,6 +89,7 @@ private:
     void refit_flat(const ctl_scene_desc& d, bool boxes, bool restamp, const std::vector<uint8_t>* mesh_changed, ctl_scene_update_stats* stats);
     void upload_mesh_geometry(const ctl_scene_desc& d, const mesh_ranges& R, uint32_t mesh);   // the two-level arrays of one mesh, re-laid-out as the constructor does, into the same allocations
     bool reduced_rough_transmittance_ = false;
+    std::map<uint32_t, std::shared_ptr<skin_binding>> skins_; float last_skin_ms_ = 0;   // the bound meshes
     ctl_scene_update_stats last_update_{}; uint32_t last_mask_ = 0;
     std::unique_ptr<desc_snapshot> snap_;
     flat_scene::refit_side refit_;   // host part: xf0, level_start

@@ -384,6 +384,47 @@ int ctl_scene_update(ctl_scene* scene, const ctl_scene_desc* new_desc, uint32_t*
  * the ratio says the tree has degraded — the library has no policy), both 0 when the update did not refit; HIP-event time of the refit kernels. */
 typedef struct { double node_area_before, node_area_after; float refit_ms; uint32_t refit_levels; uint32_t mask; uint32_t restamped; } ctl_scene_update_stats;
 int ctl_scene_get_update_stats(ctl_scene* scene, ctl_scene_update_stats* out);
+/* ---- skinned meshes: the reference's AnimatedMesh::k_ComputeState with g_ComputeVertices / g_ComputeTriangles (Engine/AnimatedMesh.{h,cpp,cu}) — the host hands over bone
+ * matrices, the device does the rest (csrc/mesh_skin.h, mesh_skin.hip; INTEGRATION.md "Skinned meshes").  The calls act on a scene, not on the builder.
+ *
+ * ctl_scene_bind_skin binds mesh `mesh_index` of the scene to a rest pose and uploads the arrays once.  rest_positions, rest_normals and indices follow the conventions of
+ * ctl_builder_add_mesh: indices == NULL is a triangle soup (n_vert == 3 * n_tri); rest_normals == NULL means Mesh::ComputeVertexNormals of the rest pose, once, on the host.
+ * bone_indices and bone_weights are uint8[n_vert][8], the bytes of AnimatedVertex::m_cBoneIndices / m_fBoneWeights in memory order; a weight is byte / 255.0f and all eight
+ * influences are always summed, as d_Compute does (weights need not sum to 255: TransformPoint divides by w).  Refusals come before anything is allocated:
+ *   CTL_ERR_NO_DEVICE    no device (checked first)
+ *   CTL_ERR_INVALID      a bad mesh index, another triangle count than the mesh's, a vertex index out of range, n_bones of 0 or above 256, an index byte >= n_bones (under a
+ *                        zero weight too: the matrix is still read)
+ *   CTL_ERR_UNSUPPORTED  a scene that is not a flattened CTL_FLAT_Q4 scene with refit data; a mesh whose nodes carry an area light (their shape sets are host work:
+ *                        ctl_builder_update_mesh); a mesh with a triangle that was degenerate when the scene was flattened (it has no leaf entry)
+ * A bound mesh is DEVICE-OWNED: ctl_scene_update neither compares nor uploads its values, whatever new_desc holds for it, and never reports CTL_DIFF_GEOMETRY for it — a
+ * camera, material or transform update during an animation keeps the pose and stays cheap.  Binding a bound mesh again replaces the binding.
+ *
+ * ctl_scene_animate_mesh poses a bound mesh: n_bones ctl_float4x4 per pose, row-major like the node transforms; bones1 == NULL means bones0; the vertex is
+ * lerp(M0 p, M1 p, lerp) with M = the weighted sum of its eight bone matrices.  Three kernels write the skinned vertices, the mesh's TriangleData (uv words and material bytes
+ * stay) and every Woop row of its leaf stream; then the flattened tree's entries of the nodes that instance the mesh take the new rows and the tree is refitted, as after a
+ * CTL_DIFF_GEOMETRY update.  A matrix entry or a lerp that is not finite, or a mesh that is not bound: CTL_ERR_INVALID, before the device is touched.  Synchronous, like
+ * ctl_scene_update: call it between passes and start the next pass with new_trace.  stats_out (may be NULL) as ctl_scene_get_update_stats reports it (mask = CTL_DIFF_GEOMETRY);
+ * ctl_scene_get_skin_ms: the HIP-event time of the three pose kernels of the last call (refit_ms is the flat-tree half).
+ * What a pose leaves alone: the scene box, ray_trace_eps and the box-dependent lights stay as created — a host whose character leaves the scene box re-creates the scene, or
+ * runs a host update (ctl_builder_update_mesh) —, and so do the nodes of the mesh's two-level BVH, which a flattened scene never traverses.
+ *
+ * ctl_scene_read_mesh_geometry copies back what HBM holds (any pointer may be NULL): positions_out / normals_out float[n_vert][3], the skinned vertices of the last pose
+ * (CTL_ERR_INVALID unless the mesh is bound and posed); tri_data_out and woop_out, the mesh's ranges of tri_data and of the Woop rows, for any mesh of any scene.
+ *
+ * ctl_scene_unbind_skin frees the binding and hands the mesh back to the description: its value hash is invalid from then on, so the next ctl_scene_update sees the mesh as
+ * changed (CTL_DIFF_GEOMETRY) and restores the description's values.
+ *
+ * ctl_skin_mesh_host is the yardstick, host only: `desc` = the description the scene was made from, the bind arguments, the pose; returns the positions, the normals, the
+ * mesh's TriangleData and its Woop rows through the same functions the kernels run (csrc/mesh_skin.h), bit for bit what ctl_scene_read_mesh_geometry reads back. */
+int ctl_scene_bind_skin(ctl_scene* scene, uint32_t mesh_index, const float* rest_positions, const float* rest_normals, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri,
+                        const uint8_t* bone_indices, const uint8_t* bone_weights, uint32_t n_bones);
+int ctl_scene_animate_mesh(ctl_scene* scene, uint32_t mesh_index, const ctl_float4x4* bones0, const ctl_float4x4* bones1, float lerp, ctl_scene_update_stats* stats_out);
+int ctl_scene_get_skin_ms(ctl_scene* scene, float* ms_out);
+int ctl_scene_read_mesh_geometry(ctl_scene* scene, uint32_t mesh_index, float* positions_out, float* normals_out, ctl_triangle_data* tri_data_out, ctl_woop_tri* woop_out);
+int ctl_scene_unbind_skin(ctl_scene* scene, uint32_t mesh_index);
+int ctl_skin_mesh_host(const ctl_scene_desc* desc, uint32_t mesh_index, const float* rest_positions, const float* rest_normals, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri,
+                       const uint8_t* bone_indices, const uint8_t* bone_weights, uint32_t n_bones, const ctl_float4x4* bones0, const ctl_float4x4* bones1, float lerp,
+                       float* positions_out, float* normals_out, ctl_triangle_data* tri_data_out, ctl_woop_tri* woop_out);
 /* On-disk cache of compiled geometry — the role of the reference's .xmsh files (Engine/Mesh.cpp:46-98,199-290; DynamicScene::CreateNode
  * compiles a mesh only when its .xmsh is missing).  With a directory set, ctl_builder_add_mesh stores / reloads a compiled mesh
  * (TriangleData, BVH nodes, Woop rows) and CTL_SCENE_FLATTEN stores / reloads the flattened BVH, both keyed by a hash of their

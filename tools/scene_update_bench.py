@@ -16,6 +16,10 @@ Per workload, on one GPU, in one process:
      content hash) and ctl_scene_create_ex (the flattened tree is necessarily cold too); and the refitted tree's Mrays/s and node-area ratio against a fresh tree.
      A workload that comes from a Mitsuba file has no vertex arrays on the Python side: the mesh's triangles are taken back from its Woop rows as a triangle soup.
 --only deform runs step 4 (and the camera update of step 1) alone.
+  5. (--only skin) a pose change of the same mesh under four bones (position bands along its long axis, blended weights), median of 10 each, in one run:
+     (a) the host path: DynamicScene.UpdateMesh + ctl_builder_finalize + ctl_scene_update with the positions and normals skinned BEFOREHAND (ctl_skin_mesh_host, not timed);
+     (b) ctl_scene_animate_mesh on the mesh bound with ctl_scene_bind_skin (the bind is timed once, apart): wall time and the HIP-event times of the three pose kernels
+         and of the refit.  After (b) a camera update on the bound scene is timed too: the bound mesh is neither hashed nor compared.
 One JSON line per workload is appended to --out; --results appends a section to that Markdown file.  bench.py is not involved.
 """
 import argparse
@@ -139,6 +143,68 @@ def deformation(workload, args, sc, scene, node, rec):
     rec["deform_faster_than_recreate"] = bool(rec["update_deform_ms"] < rec["recreate_deformed_ms"])
 
 
+def skin_pose(c, axis, k):
+    """four bone matrices of pose k: small rotations about the mesh centre that grow along the band, plus a stretch; the mesh stays within a few percent of its rest box"""
+    out = np.tile(np.eye(4), (4, 1, 1))
+    for b in range(4):
+        lin = rot(axis, 0.02 * (b - 1.5) * (1 + 0.3 * np.sin(0.9 * k + b))) @ np.diag([1.0, 1.0 - 0.01 * b, 1.0 + 0.005 * b])
+        out[b, :3, :3] = lin; out[b, :3, 3] = c - lin @ c
+    return out.astype(np.float32)
+
+
+def skinning(workload, args, sc, scene, node, rec):
+    d = sc.desc
+    mesh = int(d.view("nodes", np.uint32, d.n_nodes, 6)[node, 0])
+    inp = sc.mesh_inputs.get(mesh)
+    P0, I, N, UV = (inp["positions"], inp["indices"], inp["normals"], inp["uvs"]) if inp else (mesh_soup(d, mesh), None, None, None)
+    P0 = np.ascontiguousarray(P0, np.float32)
+    rec["skinned_mesh"] = mesh; rec["skinned_triangles"] = int(len(I) if I is not None else len(P0) // 3); rec["skinned_vertices"] = int(len(P0))
+    rec["skinned_instances"] = int((d.view("nodes", np.uint32, d.n_nodes, 6)[:, 0] == mesh).sum())
+    lo, hi = P0.min(axis=0).astype(np.float64), P0.max(axis=0).astype(np.float64)
+    c = 0.5 * (lo + hi); ax = int(np.argmax(hi - lo)); axis = np.eye(3)[(ax + 1) % 3]
+    t = (P0[:, ax] - lo[ax]) / max(hi[ax] - lo[ax], 1e-30) * 3.0
+    b0 = np.minimum(np.floor(t).astype(np.int64), 2)
+    BI = np.zeros((len(P0), 8), np.uint8); BW = np.zeros((len(P0), 8), np.uint8)
+    BI[:, 0] = b0; BI[:, 1] = b0 + 1; BW[:, 1] = np.clip(np.round((t - b0) * 255.0), 0, 255); BW[:, 0] = 255 - BW[:, 1]
+    n = 10
+    poses = [(skin_pose(c, axis, k), skin_pose(c, axis, k + 0.5), 0.25) for k in range(n + 1)]
+    # (a) the host path, with the vertices skinned beforehand: ctl_skin_mesh_host makes the very positions and normals (b) leaves in HBM
+    skinned = [api.skin_mesh_host(d, mesh, P0, I, BI, BW, 4, B0, B1, lerp, rest_normals=N) for B0, B1, lerp in poses[:n]]
+    refit_a = []
+
+    def host_path(k):
+        sc.UpdateMesh(mesh, skinned[k]["positions"], I, normals=skinned[k]["normals"], uvs=UV); assert scene.update(sc.UpdateScene()) & api.DIFF_GEOMETRY; refit_a.append(scene.update_stats()["refit_ms"])
+    rec["skin_host_path_ms"] = timed(host_path, n)
+    rec["skin_host_path_refit_kernels_ms"] = float(np.median(refit_a))
+    del skinned
+    # (b) the device path
+    tb = time.perf_counter(); scene.bind_skin(mesh, P0, I, BI, BW, 4, rest_normals=N); rec["skin_bind_ms"] = (time.perf_counter() - tb) * 1e3
+    scene.animate_mesh(mesh, *poses[n])          # (first launch of the kernels: not timed)
+    stats = []
+
+    def device_path(k):
+        stats.append(scene.animate_mesh(mesh, *poses[k]))
+    rec["skin_animate_ms"] = timed(device_path, n)
+    rec["skin_kernels_ms"] = float(np.median([s["skin_ms"] for s in stats])); rec["skin_refit_kernels_ms"] = float(np.median([s["refit_ms"] for s in stats]))
+    cam0 = api.ctl_sensor.from_buffer_copy(d.camera)
+
+    def camera(k):
+        s = api.ctl_sensor.from_buffer_copy(cam0); s.to_world[3] += 0.0007 * (k + 1); sc.setSensor(s); assert scene.update(sc.UpdateScene()) == api.DIFF_CAMERA
+    rec["skin_bound_camera_update_ms"] = timed(camera, n)
+    rec["skin_mrays"] = mrays(scene, args)
+    rec["skin_faster_than_host_path"] = bool(rec["skin_animate_ms"] < rec["skin_host_path_ms"])
+
+
+def markdown_skin(recs):
+    out = ["", "## Skinned meshes: a pose from bone matrices (tools/scene_update_bench.py --only skin)", "",
+           "| workload | skinned mesh (triangles x instances) | (a) UpdateMesh + finalize + ctl_scene_update, vertices skinned beforehand (refit kernels) | (b) ctl_scene_animate_mesh, wall | pose kernels | refit kernels | bind, once | camera update, mesh bound |",
+           "|---|---|---|---|---|---|---|---|"]
+    for r in recs:
+        out.append("| %s | %d x %d | %.2f ms (%.2f ms) | %.2f ms | %.3f ms | %.2f ms | %.0f ms | %.2f ms |" % (r["workload"], r["skinned_triangles"], r["skinned_instances"], r["skin_host_path_ms"],
+                   r["skin_host_path_refit_kernels_ms"], r["skin_animate_ms"], r["skin_kernels_ms"], r["skin_refit_kernels_ms"], r["skin_bind_ms"], r["skin_bound_camera_update_ms"]))
+    return "\n".join(out) + "\n"
+
+
 def timed(f, n=10):
     ts = []
     for k in range(n):
@@ -164,6 +230,9 @@ def run(workload, args):
     rec["update_camera_ms"] = timed(camera)
     if args.only == "deform":
         deformation(workload, args, sc, scene, node, rec)
+        return rec
+    if args.only == "skin":
+        skinning(workload, args, sc, scene, node, rec)
         return rec
 
     def material(k):
@@ -220,6 +289,8 @@ def markdown_deform(recs):
 
 
 def markdown(recs):
+    if "skin_animate_ms" in recs[0]:
+        return markdown_skin(recs)
     if "update_transform_ms" not in recs[0]:
         return markdown_deform(recs)
     out = ["", "## In-place scene updates (tools/scene_update_bench.py)", "",
@@ -242,7 +313,7 @@ def main():
     ap.add_argument("--depth", type=int, default=8); ap.add_argument("--passes", type=int, default=4)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scene_update.jsonl"))
     ap.add_argument("--results", default=None)
-    ap.add_argument("--only", default=None, choices=["deform"], help="deform: the camera update and the one-mesh deformation alone")
+    ap.add_argument("--only", default=None, choices=["deform", "skin"], help="deform: the camera update and the one-mesh deformation alone; skin: the camera update and the pose change of a bound mesh against the host path")
     args = ap.parse_args()
     if ctl.device_count() < 1:
         raise SystemExit("scene_update_bench needs a HIP device")
