@@ -89,6 +89,21 @@ class ctl_tracer_stats(C.Structure):
                 ("closest_counts", ctl_traversal_counts), ("any_counts", ctl_traversal_counts), ("fused_launches", u64), ("fused_shadow_rays", u64), ("fused_closest_rays", u64), ("ms_fused", C.c_double)]
 
 
+PHASE_HG, PHASE_ISOTROPIC, PHASE_KAJIYA_KAY, PHASE_RAYLEIGH = 1, 2, 3, 4   # CTL_PHASE_*
+VOLUME_HOMOGENEOUS = 1
+PARSE_EXTERIOR_MEDIA, PARSE_INTERIOR_MEDIA = 1, 2   # CTL_PARSE_*
+MAX_VOL_COUNT = 16
+
+
+class ctl_phase_function(C.Structure):
+    _fields_ = [("type", u32), ("g", f32), ("ks", f32), ("kd", f32), ("exponent", f32), ("normalization", f32)]
+
+
+class ctl_volume(C.Structure):
+    _fields_ = [("type", u32), ("phase", ctl_phase_function), ("volume_to_world", ctl_float4x4), ("world_to_volume", ctl_float4x4),
+                ("sig_a", f32 * 3), ("sig_s", f32 * 3), ("le", f32 * 3)]
+
+
 class ctl_scene_desc(C.Structure):
     _fields_ = [("tri_data", C.c_void_p), ("n_tri_data", u32), ("woop", C.c_void_p), ("n_woop", u32), ("woop_index", C.c_void_p),
                 ("bvh_nodes", C.c_void_p), ("n_bvh_nodes", u32), ("meshes", C.c_void_p), ("n_meshes", u32), ("nodes", C.c_void_p), ("n_nodes", u32),
@@ -97,7 +112,8 @@ class ctl_scene_desc(C.Structure):
                 ("node_transforms", C.c_void_p), ("node_inv_transforms", C.c_void_p), ("env_map_index", u32),
                 ("box_min", f32 * 3), ("box_max", f32 * 3), ("camera", ctl_sensor), ("num_lights", u32),
                 ("light_indices", u32 * MAX_NUM_LIGHTS), ("light_cdf", f32 * MAX_NUM_LIGHTS), ("ray_trace_eps", f32),
-                ("images", C.POINTER(ctl_mipmap)), ("n_images", u32), ("rough_transmittance", C.POINTER(ctl_rough_transmittance))]
+                ("images", C.POINTER(ctl_mipmap)), ("n_images", u32), ("rough_transmittance", C.POINTER(ctl_rough_transmittance)),
+                ("volumes", C.POINTER(ctl_volume)), ("n_volumes", u32)]
 
     # numpy views of the reference-layout arrays (host memory owned by the builder)
     def view(self, name, dtype, count, width):
@@ -108,6 +124,7 @@ class ctl_scene_desc(C.Structure):
         return np.frombuffer(buf, dtype=dtype).reshape(count, width)
 
 
+assert C.sizeof(ctl_volume) == 192 and C.sizeof(ctl_phase_function) == 24
 assert C.sizeof(ctl_texture) == 48 and C.sizeof(ctl_material) == 384 and C.sizeof(ctl_pixel_data) == 28 and C.sizeof(ctl_hit) == 20
 
 lib.ctl_last_error.restype = C.c_char_p
@@ -143,6 +160,10 @@ lib.ctl_builder_add_distant_light.argtypes = [C.c_void_p, C.POINTER(f32), C.POIN
 lib.ctl_builder_add_image.argtypes = [C.c_void_p, C.c_void_p, u32, u32, u32, u32, u32, C.POINTER(u32)]
 lib.ctl_builder_set_environment_map.argtypes = [C.c_void_p, u32, C.POINTER(f32), C.c_void_p]
 lib.ctl_builder_set_camera_lookat.argtypes = [C.c_void_p, C.POINTER(f32), C.POINTER(f32), C.POINTER(f32), f32, u32, u32]
+lib.ctl_volume_update.argtypes = [C.POINTER(ctl_volume)]
+lib.ctl_builder_create_volume.argtypes = [C.c_void_p, C.POINTER(ctl_volume), C.POINTER(u32)]
+lib.ctl_builder_set_volume.argtypes = [C.c_void_p, u32, C.POINTER(ctl_volume)]
+lib.ctl_volume_eval.argtypes = [C.c_void_p, i32, C.c_void_p, u32, C.c_void_p, i32]
 
 
 def _check(code):
@@ -546,6 +567,81 @@ def blend(index0, nested0, index1, nested1, weight=0.5):
 
 
 # ---------------------------------------------------------------- DynamicScene (Engine/DynamicScene.h:70-187, loader-facing subset)
+def phase_isotropic():
+    p = ctl_phase_function(); p.type = PHASE_ISOTROPIC
+    return p
+
+
+def phase_hg(g):
+    """HGPhaseFunction(g), |g| < 1"""
+    p = ctl_phase_function(); p.type = PHASE_HG; p.g = float(g)
+    return p
+
+
+def phase_rayleigh():
+    p = ctl_phase_function(); p.type = PHASE_RAYLEIGH
+    return p
+
+
+def phase_kajiya_kay(ks=0.4, kd=0.2, exponent=4.0):
+    """KajiyaKayPhaseFunction(ks, kd, e); the normalisation is derived by volume_update / CreateVolume"""
+    p = ctl_phase_function(); p.type = PHASE_KAJIYA_KAY; p.ks, p.kd, p.exponent = float(ks), float(kd), float(exponent)
+    return p
+
+
+def _rgb3(v):
+    a = np.broadcast_to(np.asarray(v, np.float32), (3,))
+    return (f32 * 3)(*[float(x) for x in a])
+
+
+def homogeneous_volume(volume_to_world, sigma_a, sigma_s, phase=None, le=0.0):
+    """HomogeneousVolumeDensity(func, ToWorld, sa, ss, e): the unit cube under volume_to_world (4x4, row-major), with its derived fields (volume_update)"""
+    v = ctl_volume(); v.type = VOLUME_HOMOGENEOUS
+    v.phase = phase if phase is not None else phase_isotropic()
+    v.volume_to_world.m[:] = [float(x) for x in np.asarray(volume_to_world, np.float32).reshape(16)]
+    v.sig_a, v.sig_s, v.le = _rgb3(sigma_a), _rgb3(sigma_s), _rgb3(le)
+    return volume_update(v)
+
+
+def volume_update(v):
+    """ctl_volume_update: world_to_volume and the Kajiya-Kay normalisation from the primary fields (host only); returns v"""
+    _check(lib.ctl_volume_update(C.byref(v)))
+    return v
+
+
+def box_to_volume_matrix(box_min, box_max):
+    """the volume_to_world that maps the unit cube onto an axis-aligned box: Translate(min) % Scale(max - min), as the Mitsuba loader builds it"""
+    lo, hi = np.asarray(box_min, np.float32), np.asarray(box_max, np.float32)
+    m = np.zeros((4, 4), np.float32)
+    m[0, 0], m[1, 1], m[2, 2] = (hi - lo)
+    m[:3, 3] = lo
+    m[3, 3] = 1
+    return m
+
+
+VEVAL_QUERY_FLOATS, VEVAL_RESULT_FLOATS = 10, 17
+(VEVAL_REGION_INTERSECT, VEVAL_INTERSECT, VEVAL_REGION_TAU, VEVAL_TAU, VEVAL_REGION_SAMPLE_DISTANCE, VEVAL_SAMPLE_DISTANCE, VEVAL_SAMPLE_VOLUME, VEVAL_PHASE_EVAL,
+ VEVAL_PHASE_SAMPLE, VEVAL_P, VEVAL_SAMPLE, VEVAL_TRANSMITTANCE, VEVAL_EVAL_TRANSMITTANCE) = range(13)   # CTL_VEVAL_*
+
+
+def volumes_desc(volumes):
+    """a description that holds nothing but `volumes` (a list of ctl_volume): what volume_eval reads.  The array is kept alive by the returned object"""
+    d = ctl_scene_desc()
+    arr = (ctl_volume * max(1, len(volumes)))(*volumes)
+    d.volumes = C.cast(arr, C.POINTER(ctl_volume)); d.n_volumes = len(volumes)
+    d._keep = arr
+    return d
+
+
+def volume_eval(desc, what, queries, on_device=False):
+    """ctl_volume_eval: the participating-media functions (csrc/volume.h) one call per query row ((n, 10) float32; a [volume] index as the bits of its float) ->
+    (n, 17) float32.  on_device=False runs on the host and needs no GPU (the yardstick); True runs one small kernel.  Layouts: include/ctl_amd.h CTL_VEVAL_*."""
+    q = np.ascontiguousarray(queries, np.float32).reshape(-1, VEVAL_QUERY_FLOATS)
+    out = np.zeros((len(q), VEVAL_RESULT_FLOATS), np.float32)
+    _check(lib.ctl_volume_eval(C.addressof(desc), i32(what), q.ctypes.data, u32(len(q)), out.ctypes.data, i32(1 if on_device else 0)))
+    return out
+
+
 def decode_image_file(path):
     """ctl_decode_image_file: (H, W, 3) float32 for HDR / PFM / EXR files, (H, W, 4) uint8 otherwise; rows top-down"""
     w, h, fl = u32(0), u32(0), i32(0)
@@ -678,14 +774,30 @@ class DynamicScene:
             m = ctl_float4x4(); m.m[:] = [float(x) for x in np.asarray(to_world, np.float32).reshape(16)]
         _check(lib.ctl_builder_set_environment_map(self._h, u32(image), (f32 * 3)(*scale), C.byref(m) if m is not None else None))
 
+    def CreateVolume(self, volume):
+        """DynamicScene::CreateVolume(VolumeRegion) (DynamicScene.cpp:787-792): a ctl_volume (homogeneous_volume(...)), at most MAX_VOL_COUNT; returns its index.
+        UpdateScene() then hands the media out in desc.volumes; only the PathTracer plugin renders them."""
+        idx = u32()
+        _check(lib.ctl_builder_create_volume(self._h, C.byref(volume), C.byref(idx)))
+        return idx.value
+
+    def SetVolume(self, index, volume):
+        """replace volume `index` (the host edits the region CreateVolume returned); Scene.update applies the next description in place (DIFF_VOLUMES)"""
+        _check(lib.ctl_builder_set_volume(self._h, u32(index), C.byref(volume)))
+
     def setSensor(self, sensor):
         """the camera as a ctl_sensor struct (ctl_builder_set_camera), e.g. another scene's desc.camera"""
         _check(lib.ctl_builder_set_camera(self._h, C.byref(sensor)))
 
-    def ParseMitsubaScene(self, path, width=-1, height=-1):
-        """ParseMitsubaScene (Engine/SceneLoader/Mitsuba/MitsubaLoader.h:13)."""
+    def ParseMitsubaScene(self, path, width=-1, height=-1, exterior_media=False, interior_media=False):
+        """ParseMitsubaScene (Engine/SceneLoader/Mitsuba/MitsubaLoader.h:13).  exterior_media / interior_media: its create_exterior_bssrdf / create_interior_bssrdf
+        (ctl_parse_mitsuba_scene_ex): a shape without a BSDF whose exterior / interior is a homogeneous medium becomes a volume and is removed."""
         w, h = i32(width), i32(height)
-        _check(lib.ctl_parse_mitsuba_scene(self._h, path.encode(), C.byref(w), C.byref(h)))
+        flags = (PARSE_EXTERIOR_MEDIA if exterior_media else 0) | (PARSE_INTERIOR_MEDIA if interior_media else 0)
+        if flags:
+            _check(lib.ctl_parse_mitsuba_scene_ex(self._h, path.encode(), C.byref(w), C.byref(h), u32(flags)))
+        else:
+            _check(lib.ctl_parse_mitsuba_scene(self._h, path.encode(), C.byref(w), C.byref(h)))
         return w.value, h.value
 
     def UpdateScene(self):
@@ -786,7 +898,7 @@ class Scene:
             self._h = None
 
 
-DIFF_CAMERA, DIFF_MATERIALS, DIFF_LIGHTS, DIFF_TRANSFORMS, DIFF_TOPOLOGY, DIFF_GEOMETRY = 1, 2, 4, 8, 16, 32   # CTL_DIFF_*
+DIFF_CAMERA, DIFF_MATERIALS, DIFF_LIGHTS, DIFF_TRANSFORMS, DIFF_TOPOLOGY, DIFF_GEOMETRY, DIFF_VOLUMES = 1, 2, 4, 8, 16, 32, 64   # CTL_DIFF_*
 ERR_INVALID, ERR_NO_DEVICE, ERR_UNSUPPORTED = -1, -2, -5
 
 

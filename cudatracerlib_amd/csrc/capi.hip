@@ -16,6 +16,7 @@
 #include "scene_cache.h"
 #include "shading_eval.h"
 #include "traversal_probe.h"
+#include "volume_eval.h"
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -30,7 +31,13 @@ struct ctl_scene {
 };
 struct ctl_flat_bvh { flat_scene f; };
 struct ctl_image { Image img; ctl_image(uint32_t w, uint32_t h) : img(w, h) {} };
-struct ctl_tracer { std::unique_ptr<TracerBase> t; };
+// wavefront / scene: the WavefrontPathTracer has no medium code and refuses a scene with participating media here, when the scene is handed over and when a pass starts
+// (scene_volumes.h; the PathTracer and the PrimTracer judge that themselves; WavefrontPathTracer is declared in tracer.h, whose text the committed counter profile's hash covers).
+// `scene` is only ever looked up, never dereferenced, and only while the registry still knows it under `scene_id`: a destroyed scene, or a new one at its address, is not judged
+struct ctl_tracer {
+    std::unique_ptr<TracerBase> t; bool wavefront = false; const Scene* scene = nullptr; uint64_t scene_id = 0;
+    void refuse_media() const { if (wavefront && scene && scene_id && scene_volumes_id(scene) == scene_id) refuse_volumes(scene, "WavefrontPathTracer"); }
+};
 struct ctl_sequence_generator { sequence_generator g; };
 
 static thread_local std::string g_err;
@@ -115,10 +122,21 @@ int ctl_builder_set_camera_lookat(ctl_builder* b, const float pos[3], const floa
 }
 int ctl_builder_set_camera(ctl_builder* b, const ctl_sensor* sensor) { CTL_REQUIRE(b && sensor, "null argument"); CTL_TRY b->b.set_camera(*sensor); CTL_CATCH }
 int ctl_builder_set_node_transform(ctl_builder* b, uint32_t node_index, const ctl_float4x4* to_world) { CTL_REQUIRE(b && to_world, "null argument"); CTL_TRY b->b.set_node_transform(node_index, *to_world, true); CTL_CATCH }
+int ctl_builder_create_volume(ctl_builder* b, const ctl_volume* volume, uint32_t* index_out) {
+    CTL_REQUIRE(b && volume, "null argument");
+    CTL_TRY uint32_t i = b->b.create_volume(*volume); if (index_out) *index_out = i; CTL_CATCH
+}
+int ctl_builder_set_volume(ctl_builder* b, uint32_t index, const ctl_volume* volume) { CTL_REQUIRE(b && volume, "null argument"); CTL_TRY b->b.set_volume(index, *volume); CTL_CATCH }
 int ctl_builder_finalize(ctl_builder* b, ctl_scene_desc* out) { CTL_REQUIRE(b && out, "null argument"); CTL_TRY b->b.finalize(*out); CTL_CATCH }
 
 int ctl_material_update(ctl_material* m) {   // (a weight from an IMAGE texture's average is final after ctl_builder_finalize, material_textures.h)
     CTL_REQUIRE(m, "null argument"); CTL_REQUIRE(material_update(*m), "unknown bsdf_type"); material_update_textures(*m, image_set()); return CTL_OK;
+}
+int ctl_volume_update(ctl_volume* v) { CTL_REQUIRE(v, "null argument"); CTL_TRY volume_update(*v); CTL_CATCH }
+// ---- the participating-media functions (volume.h) one call per query, on the host or by a kernel (volume_eval.hip)
+int ctl_volume_eval(const ctl_scene_desc* desc, int32_t what, const float* queries, uint32_t n, float* out, int32_t on_device) {
+    CTL_REQUIRE(desc && (n == 0 || (queries && out)), "null argument");
+    CTL_TRY volume_eval(*desc, what, queries, n, out, on_device != 0); CTL_CATCH
 }
 float ctl_fresnel_diffuse_reflectance(float eta) { return fresnel_diffuse_reflectance(eta); }
 // ---- the shared transcendental functions (ctl_fmath.h), evaluated on the host or by a kernel: the parity tests hold the two bit-identical
@@ -411,6 +429,10 @@ int ctl_parse_mitsuba_scene(ctl_builder* b, const char* xml_path, int32_t* width
     CTL_REQUIRE(b && xml_path, "null argument");
     CTL_TRY parse_mitsuba_scene(b->b, xml_path, width_inout, height_inout); CTL_CATCH
 }
+int ctl_parse_mitsuba_scene_ex(ctl_builder* b, const char* xml_path, int32_t* width_inout, int32_t* height_inout, uint32_t flags) {
+    CTL_REQUIRE(b && xml_path, "null argument");
+    CTL_TRY parse_mitsuba_scene(b->b, xml_path, width_inout, height_inout, flags); CTL_CATCH
+}
 int ctl_decode_image_file(const char* path, uint32_t* width, uint32_t* height, int32_t* is_float, float* rgb, uint8_t* rgba8) {
     CTL_REQUIRE(path && width && height && is_float, "null argument");
     CTL_TRY
@@ -527,7 +549,7 @@ int ctl_tracer_create(const char* plugin, ctl_tracer** out) {
     const bool wave = !std::strcmp(plugin, "WavefrontPathTracer") || !std::strcmp(plugin, "PT_Wave"), mega = !std::strcmp(plugin, "PathTracer") || !std::strcmp(plugin, "PT");   // main.cpp:91-96
     const bool prim = !std::strcmp(plugin, "PrimTracer") || !std::strcmp(plugin, "direct");
     if (!wave && !mega && !prim) return fail(CTL_ERR_UNSUPPORTED, std::string("unknown tracer plugin: ") + plugin);
-    CTL_TRY ctl_tracer* t = new ctl_tracer(); try { if (wave) t->t.reset(new WavefrontPathTracer()); else if (mega) t->t.reset(new PathTracer()); else t->t.reset(new PrimTracer()); } catch (...) { delete t; throw; } *out = t; CTL_CATCH
+    CTL_TRY ctl_tracer* t = new ctl_tracer(); try { t->wavefront = wave; if (wave) t->t.reset(new WavefrontPathTracer()); else if (mega) t->t.reset(new PathTracer()); else t->t.reset(new PrimTracer()); } catch (...) { delete t; throw; } *out = t; CTL_CATCH
 }
 void ctl_tracer_destroy(ctl_tracer* t) { delete t; }
 int ctl_tracer_set_param_bool(ctl_tracer* t, const char* key, int value) { CTL_REQUIRE(t && key, "null argument"); CTL_TRY t->t->getParameters().setValue(key, value ? 1 : 0, TracerParameter::Bool); CTL_CATCH }
@@ -540,11 +562,11 @@ int ctl_tracer_get_param_float(ctl_tracer* t, const char* key, float* value_out)
 int ctl_tracer_set_param_enum(ctl_tracer* t, const char* key, const char* value_name) { CTL_REQUIRE(t && key && value_name, "null argument"); CTL_TRY t->t->getParameters().setEnumByName(key, value_name); CTL_CATCH }
 int ctl_tracer_get_param_int(ctl_tracer* t, const char* key, int* value_out) { CTL_REQUIRE(t && key && value_out, "null argument"); CTL_TRY *value_out = t->t->getParameters().getValue(key); CTL_CATCH }
 int ctl_tracer_resize(ctl_tracer* t, uint32_t width, uint32_t height) { CTL_REQUIRE(t && width && height, "bad argument"); CTL_TRY t->t->Resize(width, height); CTL_CATCH }
-int ctl_tracer_initialize_scene(ctl_tracer* t, ctl_scene* s) { CTL_REQUIRE(t && s, "null argument"); CTL_TRY t->t->InitializeScene(&s->s); CTL_CATCH }
+int ctl_tracer_initialize_scene(ctl_tracer* t, ctl_scene* s) { CTL_REQUIRE(t && s, "null argument"); CTL_TRY if (t->wavefront) refuse_volumes(&s->s, "WavefrontPathTracer"); t->t->InitializeScene(&s->s); t->scene = &s->s; t->scene_id = scene_volumes_id(&s->s); CTL_CATCH }
 int ctl_tracer_set_tile_shard(ctl_tracer* t, uint32_t rank, uint32_t world) { CTL_REQUIRE(t, "null tracer"); CTL_TRY t->t->setTileShard(rank, world); CTL_CATCH }
 int ctl_tracer_set_sampler_tables(ctl_tracer* t, const float* tables_1d, const float* tables_2d) { CTL_REQUIRE(t && tables_1d && tables_2d, "null argument"); CTL_TRY t->t->setSamplerTables(tables_1d, tables_2d); CTL_CATCH }
-int ctl_tracer_do_pass(ctl_tracer* t, ctl_image* img, int new_trace) { CTL_REQUIRE(t && img, "null argument"); CTL_TRY t->t->DoPass(&img->img, new_trace != 0); CTL_CATCH }
-int ctl_tracer_do_passes(ctl_tracer* t, ctl_image* img, int new_trace, uint32_t n_passes) { CTL_REQUIRE(t && img, "null argument"); CTL_TRY t->t->DoPasses(&img->img, new_trace != 0, n_passes); CTL_CATCH }
+int ctl_tracer_do_pass(ctl_tracer* t, ctl_image* img, int new_trace) { CTL_REQUIRE(t && img, "null argument"); CTL_TRY t->refuse_media(); t->t->DoPass(&img->img, new_trace != 0); CTL_CATCH }
+int ctl_tracer_do_passes(ctl_tracer* t, ctl_image* img, int new_trace, uint32_t n_passes) { CTL_REQUIRE(t && img, "null argument"); CTL_TRY t->refuse_media(); t->t->DoPasses(&img->img, new_trace != 0, n_passes); CTL_CATCH }
 int ctl_tracer_reserve_passes(ctl_tracer* t, uint32_t n) { CTL_REQUIRE(t, "null tracer"); CTL_TRY t->t->reservePasses(n); CTL_CATCH }
 int ctl_tracer_set_block_weight(ctl_tracer* t, uint32_t bx, uint32_t by, float w) { CTL_REQUIRE(t, "null tracer"); CTL_TRY t->t->setBlockWeight(bx, by, w); CTL_CATCH }
 int ctl_tracer_get_block_counts(ctl_tracer* t, uint8_t* out, uint32_t n) {

@@ -9,6 +9,7 @@
 #include "tracer.h"
 #include "single_ray.h"
 #include "mitsuba_loader.h"   // unsupported_error
+#include "scene_volumes.h"
 #include <climits>
 
 static_assert((int)ctl::kFmtQ4 == (int)ctl::kFlatQ4 && (int)ctl::kFmtQ8 == (int)ctl::kFlatQ8, "the kernels' format numbers (traverse_flat.h) are the flattener's (flatten.h)");
@@ -18,11 +19,15 @@ namespace ctl {
 // single_stack_column, trace_single, light_sample_position and env_eval_differential: single_ray.h (shared with prim_tracer.hip); the tile order of the pixels:
 // kernels.h tile_order_pixel
 
-// pathKernel2<DIRECT> + PathTrace<DIRECT> (Integrators/PathTracer.cu:182-194, 10-113), no participating media
+// pathKernel2<DIRECT> + PathTrace<DIRECT> (Integrators/PathTracer.cu:182-194, 10-113).  MEDIA = false: a scene without participating media (k_path_trace: the code it
+// always was); MEDIA = true: the medium half of PathTrace (:17-58) from the volume table V (volume.h) — the distance draw, the medium vertex's next-event estimation and
+// phase-function scattering, the surface NEE attenuated by Transmittance (k_path_trace_media, launched only for a scene that has volumes)
 #ifndef CTL_MEGA_WAVES
 #define CTL_MEGA_WAVES 2
 #endif
-__global__ __launch_bounds__(256, CTL_MEGA_WAVES) void k_path_trace(dev_scene S, pass_params P, ctl_pixel_data* __restrict__ image, unsigned long long* __restrict__ ray_count) {
+template <bool MEDIA> struct media_state { vol::medium_rec rec = vol::zero_rec(); bool in_medium = false; };   // PathTrace's mRec lives across the bounces
+template <> struct media_state<false> {};
+template <bool MEDIA> __device__ __forceinline__ void path_trace(const dev_scene S, const pass_params P, const vol::table V, ctl_pixel_data* __restrict__ image, unsigned long long* __restrict__ ray_count) {
     const uint32_t tiles_x = (P.width + 63) / 64;
     const uint32_t n_total = P.n_local_pixels * P.batch;
     const uint32_t n1 = CTL_SAMPLER_NUM_SEQUENCES * CTL_SAMPLER_SEQUENCE_LENGTH;
@@ -42,11 +47,56 @@ __global__ __launch_bounds__(256, CTL_MEGA_WAVES) void k_path_trace(dev_scene S,
         f3 cl(0.0f), cf(1.0f), last_nor(0.0f);
         int depth = 0; bool specularBounce = false, had_hit = false;
         float brdf_scattering_pdf = 0;
+        media_state<MEDIA> ms;
         while (depth++ < P.max_path_length) {
             float t, u, v; int tri, node;
             had_hit = trace_single<false>(S, r_o, r_d, S.eps, 3.402823466e+38f, t, u, v, tri, node);
             rays++;
+            if constexpr (MEDIA) {
+                vol::medium_rec& mRec = ms.rec;   // PathTracer.cu:22-52.  r2.m_fDist of a miss is TraceResult::Init's FLT_MAX; the WHOLE segment [0, m_fDist] goes into sampleDistance
+                const float dist = had_hit ? t : 3.402823466e+38f;
+                float minT, maxT;
+                const bool isInMedium = ms.in_medium = vol::intersect(V, r_o, r_d, 0.0f, dist, minT, maxT);
+                // the distance draw is consumed whenever HasVolumes() && isInMedium, whatever the outcome
+                if (V.n > 0 && isInMedium && vol::sample_distance(V, r_o, r_d, 0.0f, dist, rng.next1(), mRec)) {
+                    cf = cf * sdiv(mRec.sigmaS * mRec.transmittance, mRec.pdfSuccess);
+                    if (P.direct) {   // sampleAttenuatedEmitterDirect from DirectSamplingRecord(mRec.p, 0) (KernelDynamicScene.cu:98-123): ONE 2-D draw picks the emitter and, rescaled, samples it
+                        direct_rec dr; dr.ref = mRec.p; dr.refN = f3(0.0f); dr.p = f3(0.0f); dr.pdf = 0.0f;
+                        f2 sl = rng.next2();
+                        f3 value(0.0f);
+                        float lpdf; const int li2 = sample_emitter_reuse(S, lpdf, sl.x);
+                        if (li2 >= 0) {
+                            value = light_sample_direct(S, scene_lights(S)[li2], dr, sl);
+                            if (dr.pdf != 0) { dr.pdf *= lpdf; value = sdiv(value, lpdf); } else value = f3(0.0f);
+                        }
+                        value = value * vol::eval_transmittance(V, dr.ref, dr.p);
+                        if (!is_zero(value)) {
+                            const float p = vol::phase_p(V, mRec.p, -r_d, dr.d);
+                            if (p != 0) {
+                                float st, su, sv; int stri, snode;
+                                rays++;
+                                if (!trace_single<true>(S, dr.ref, dr.d, S.eps, dr.dist - S.eps, st, su, sv, stri, snode)) {   // Occluded(Ray(ref, d), 0, dist)
+                                    const float weight = power_heuristic(dr.pdf, p);   // the phase value serves as f and as pdf
+                                    cl = cl + cf * value * p * weight;
+                                }
+                            }
+                        }
+                    }
+                    f3 wo(0.0f); float ppdf;   // no region found by Sample: weight 0 (the reference then follows an unset direction with a zero throughput; the cut below ends the path)
+                    cf = cf * vol::phase_sample_aggregate(V, mRec.p, -r_d, wo, ppdf, rng.next2());
+                    r_d = wo; r_o = mRec.p;
+                    // brdf_scattering_pdf, last_nor and specularBounce keep their values from the last surface: the next emission's MIS weight and the roulette use them stale
+                    if (is_zero(cf)) break;
+                    if (depth > P.rr_start_depth && !specularBounce) {
+                        const float q = max3c(cf);
+                        if (rng.next1() >= q) break;
+                        cf = sdiv(cf, q);
+                    }
+                    continue;
+                }
+            }
             if (!had_hit) break;
+            if constexpr (MEDIA) { if (ms.in_medium) cf = cf * sdiv(ms.rec.transmittance, ms.rec.pdfFailure); }
             bsdf_rec b; b.eta = 1.0f; b.sampled_type = 0; b.type_mask = kEAll;
             b.dg.P = r_o + t * r_d;
             fill_dg(S, u, v, tri, node, b.dg);
@@ -82,7 +132,8 @@ __global__ __launch_bounds__(256, CTL_MEGA_WAVES) void k_path_trace(dev_scene S,
                             if (!trace_single<true>(S, dr.ref, dr.d, S.eps, dr.dist - S.eps, st, su, sv, stri, snode)) {   // Occluded(r, 0, dist)
                                 float weight = 1.0f;
                                 if (dr.measure != kMeasureDiscrete) weight = power_heuristic((dr.measure == kMeasureArea ? dr.pdf * dr.dist / fabsf(dot(dr.n, dr.d)) : dr.pdf) * lpdf, bsdf_pdf_top(mat, b2));
-                                cl = cl + cf * sdiv(value * bsdfVal * weight, lpdf);
+                                if constexpr (MEDIA) cl = cl + cf * sdiv((value * bsdfVal * weight) * vol::transmittance(V, dr.ref, dr.d, 0.0f, dr.dist), lpdf);   // EstimateDirect(..., attenuated = true) (TraceAlgorithms.cu:66-67)
+                                else cl = cl + cf * sdiv(value * bsdfVal * weight, lpdf);
                             }
                         }
                     }
@@ -110,6 +161,13 @@ __global__ __launch_bounds__(256, CTL_MEGA_WAVES) void k_path_trace(dev_scene S,
     // one atomic per wave
     for (int off = 32; off > 0; off >>= 1) rays += __shfl_down(rays, off, 64);
     if ((threadIdx.x & 63) == 0 && rays) atomicAdd(ray_count, rays);
+}
+__global__ __launch_bounds__(256, CTL_MEGA_WAVES) void k_path_trace(dev_scene S, pass_params P, ctl_pixel_data* __restrict__ image, unsigned long long* __restrict__ ray_count) {
+    path_trace<false>(S, P, vol::table{}, image, ray_count);
+}
+// the volume table is an argument of this kernel alone; its regions stay in global memory and are indexed wave-uniformly
+__global__ __launch_bounds__(256, CTL_MEGA_WAVES) void k_path_trace_media(dev_scene S, pass_params P, vol::table V, ctl_pixel_data* __restrict__ image, unsigned long long* __restrict__ ray_count) {
+    path_trace<true>(S, P, V, image, ray_count);
 }
 
 // ---- PathTraceRegularization<DIRECT> (Integrators/PathTracer.cu:115-173): the plugin with Regularization = true
@@ -226,6 +284,7 @@ PathTracer::PathTracer() {
 }
 void PathTracer::InitializeScene(Scene* s) {
     if (!s->S.flat_nodes) throw unsupported_error("PathTracer (megakernel): the scene must be created with CTL_SCENE_FLATTEN");
+    if (m_sParameters.getValue("Regularization")) refuse_volumes(s, "PathTracer with Regularization = true (PathTraceRegularization)");
     Tracer<true>::InitializeScene(s);
 }
 void PathTracer::Resize(unsigned int _w, unsigned int _h) {
@@ -237,6 +296,8 @@ void PathTracer::Resize(unsigned int _w, unsigned int _h) {
 void PathTracer::DoRender(Image* I, const float* d_t1, const float* d_t2, unsigned int n_batch) {
     // the reference's megakernel renders a block once per mention by the sampler, i.e. the SAME sample twice; only the wavefront plugin honours block samplers here
     if (pass_block_counts_) throw unsupported_error("PathTracer (megakernel): block samplers other than Uniform are served by the WavefrontPathTracer plugin only");
+    if (m_sParameters.getValue("Regularization")) refuse_volumes(m_pScene, "PathTracer with Regularization = true (PathTraceRegularization)");
+    const vol::table V = scene_volume_table(m_pScene);   // read per pass: ctl_scene_update may have changed the media since InitializeScene
     pass_params P{};
     P.t1 = d_t1; P.t2 = (const float2*)d_t2; P.batch = n_batch; P.width = w; P.height = h; P.tile_rank = shard_rank; P.tile_world = shard_world; P.n_local_pixels = n_local_pixels;
     P.direct = m_sParameters.getValue("Direct"); P.max_path_length = m_sParameters.getValue("MaxPathLength"); P.rr_start_depth = m_sParameters.getValue("RRStartDepth");
@@ -253,8 +314,8 @@ void PathTracer::DoRender(Image* I, const float* d_t1, const float* d_t2, unsign
         CTL_HIP(hipMemcpyAsync(mollifier_.p, m.data(), n_batch * sizeof(float), hipMemcpyHostToDevice, stream));
         CTL_HIP(hipStreamSynchronize(stream));   // `m` is pageable and leaves scope
         hipLaunchKernelGGL(k_path_trace_regularization, dim3(grid_blocks), dim3(256), 0, stream, m_pScene->S, P, (const float*)mollifier_.p, I->device(), count_.p);
-    } else
-    hipLaunchKernelGGL(k_path_trace, dim3(grid_blocks), dim3(256), 0, stream, m_pScene->S, P, I->device(), count_.p);
+    } else if (V.n) hipLaunchKernelGGL(k_path_trace_media, dim3(grid_blocks), dim3(256), 0, stream, m_pScene->S, P, V, I->device(), count_.p);
+    else hipLaunchKernelGGL(k_path_trace, dim3(grid_blocks), dim3(256), 0, stream, m_pScene->S, P, I->device(), count_.p);
     timer.end(stream);
     CTL_HIP(hipMemcpyAsync(&host_count_, count_.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     CTL_HIP(hipStreamSynchronize(stream));
@@ -269,7 +330,9 @@ void PathTracer::DebugInternal(Image* I, unsigned int x, unsigned int y, const f
     P.direct = 1; P.max_path_length = m_sParameters.getValue("MaxPathLength"); P.rr_start_depth = m_sParameters.getValue("RRStartDepth");
     P.debug_out = debug_.p; P.debug_x = x; P.debug_y = y;
     CTL_HIP(hipMemsetAsync(count_.p, 0, sizeof(unsigned long long), stream));
-    hipLaunchKernelGGL(k_path_trace, dim3(1), dim3(256), 0, stream, m_pScene->S, P, I->device(), count_.p);
+    const vol::table V = scene_volume_table(m_pScene);
+    if (V.n) hipLaunchKernelGGL(k_path_trace_media, dim3(1), dim3(256), 0, stream, m_pScene->S, P, V, I->device(), count_.p);
+    else hipLaunchKernelGGL(k_path_trace, dim3(1), dim3(256), 0, stream, m_pScene->S, P, I->device(), count_.p);
     CTL_HIP(hipMemcpyAsync(rgb, debug_.p, 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
     CTL_HIP(hipStreamSynchronize(stream));
 }

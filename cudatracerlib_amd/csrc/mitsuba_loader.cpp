@@ -9,6 +9,8 @@
 #include "mesh_io.h"
 #include "material_factory.h"
 #include "sequence_generator.h"   // xorwow = CudaRNG
+#include "volume_eval.h"          // volume_update
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -64,6 +66,9 @@ struct loader {
     std::map<std::string, uint32_t> image_cache;     // file path -> image index
     std::map<uint32_t, std::vector<float>> mesh_emission;   // OBJ "Ke" per mesh material
     std::map<uint32_t, uint32_t> node_mesh;
+    uint32_t flags = 0;                              // CTL_PARSE_*: create_exterior_bssrdf / create_interior_bssrdf of ParseMitsubaScene
+    std::map<std::string, ctl_volume> ref_medium;    // media with an id, as parsed
+    std::vector<uint32_t> nodes_to_remove;           // ParserState::nodes_to_remove: the shapes that only carried a medium
     int film_w = 768, film_h = 576; bool have_film = false, have_sensor = false;
     mat4 id_matrix = identity();   // assume_rotated_coords = false (main.cpp passes false)
 
@@ -362,6 +367,43 @@ struct loader {
         const std::vector<float>& E = mesh_emission[node_mesh[node]];
         for (size_t m = 0; m * 3 + 2 < E.size(); m++) if (E[m * 3] != 0 || E[m * 3 + 1] != 0 || E[m * 3 + 2] != 0) B.add_area_light(node, (uint32_t)m, &E[m * 3]);
     }
+    // PhaseFunctionParser::parse (ObjectParser.h:134-171)
+    ctl_phase_function parse_phase(const xml_node& n) {
+        ctl_phase_function F{}; const std::string T = n.attr("type");
+        if (T == "isotropic") F.type = CTL_PHASE_ISOTROPIC;
+        else if (T == "hg") { F.type = CTL_PHASE_HG; F.g = prop_f(n, "g"); }
+        else if (T == "rayleigh") F.type = CTL_PHASE_RAYLEIGH;
+        else if (T == "kkay") { F.type = CTL_PHASE_KAJIYA_KAY; F.ks = prop_f(n, "ks", 0.4f); F.kd = prop_f(n, "kd", 0.2f); F.exponent = prop_f(n, "e", 4.0f); }
+        else bad("invalid PhaseFunction type : " + T);
+        return F;
+    }
+    // MediumParser::parse / homogeneous (ObjectParser.h:173-227).  As written: a <ref> returns the medium AS IT WAS PARSED, with the transform of that parse — a top-level
+    // <medium id> is parsed with the identity, so a shape that refers to it gets a volume over the unit cube, not over the scene box.  false: skipped (lenient mode)
+    bool parse_medium(const xml_node& n, const mat4& to_world, ctl_volume& out) {
+        if (is_ref(n)) { auto it = ref_medium.find(n.attr("id")); if (it == ref_medium.end()) bad("unknown reference : " + n.attr("id")); out = it->second; return true; }
+        const std::string T = n.attr("type");
+        if (T == "heterogeneous") { unsupported("heterogeneous medium (VolumeGrid)"); return false; }
+        if (T != "homogeneous") bad("invalid VolumeRegion type : " + T);
+        ctl_volume V{}; V.type = CTL_VOLUME_HOMOGENEOUS; V.phase.type = CTL_PHASE_ISOTROPIC;
+        if (const xml_node* ph = n.child("phase")) V.phase = parse_phase(*ph);
+        rgb sigma_a(0.0f), sigma_s(0.0f);
+        if (n.property("material")) { unsupported("medium material presets (MaterialLibrary)"); return false; }
+        if (n.property("sigmaT") || n.property("albedo")) {
+            const rgb sigma_t = n.property("sigmaT") ? parse_color(*n.property("sigmaT")) : rgb(1.0f), albedo = n.property("albedo") ? parse_color(*n.property("albedo")) : rgb(1.0f);
+            sigma_s = rgb(albedo.r * sigma_t.r, albedo.g * sigma_t.g, albedo.b * sigma_t.b);
+            sigma_a = rgb(sigma_t.r - sigma_s.r, sigma_t.g - sigma_s.g, sigma_t.b - sigma_s.b);
+        } else if (n.property("sigmaA") || n.property("sigmaS")) {
+            if (n.property("sigmaA")) sigma_a = parse_color(*n.property("sigmaA"));
+            if (n.property("sigmaS")) sigma_s = parse_color(*n.property("sigmaS"));
+        }
+        const float sc = prop_f(n, "scale", 1.0f);
+        V.sig_a[0] = sigma_a.r * sc; V.sig_a[1] = sigma_a.g * sc; V.sig_a[2] = sigma_a.b * sc;
+        V.sig_s[0] = sigma_s.r * sc; V.sig_s[1] = sigma_s.g * sc; V.sig_s[2] = sigma_s.b * sc;   // le = 0: the loader never passes an emission
+        std::memcpy(V.volume_to_world.m, to_world.m, 64);
+        volume_update(V);   // R.Update()
+        if (n.has_attr("id")) ref_medium[n.attr("id")] = V;
+        out = V; return true;
+    }
     void parse_generic(uint32_t node, const xml_node& n, const mat4& local = identity(), bool in_coord = false) {   // :1031-1102
         const mat4 T = n.property("toWorld") ? parse_matrix(*n.property("toWorld")) : (in_coord ? identity() : id_matrix);
         ctl_float4x4 m; std::memcpy(m.m, mul(T, local).m, 64);
@@ -373,9 +415,24 @@ struct loader {
             const rgb e = parse_color(*r); const float rad[3] = { e.r, e.g, e.b };
             B.add_area_light(node, 0, rad);
         }
-        if (const xml_node* b = n.child("bsdf")) apply_bsdf(*b, node);
-        for (const xml_node& c : n.children) if (c.lname() == "ref" && (!c.has_attr("name") || c.attr("name") == "bsdf")) apply_bsdf(c, node);
-        if (n.property("interior") || n.property("exterior")) { /* media are only created when the caller asks for BSSRDFs (main.cpp passes false) */ }
+        bool has_bsdf = false;
+        if (const xml_node* b = n.child("bsdf")) { apply_bsdf(*b, node); has_bsdf = true; }
+        for (const xml_node& c : n.children) if (c.lname() == "ref" && (!c.has_attr("name") || c.attr("name") == "bsdf")) { apply_bsdf(c, node); has_bsdf = true; }
+        // create_bssrdf (:1066-1101): media are only created when the caller asks for them (main.cpp passes false, false).  A shape WITHOUT a BSDF becomes a volume over
+        // the scene box as it stands at this point of the parse — this shape's node included — and its node is removed when the parse ends
+        bool delete_node = false;
+        auto create_bssrdf = [&](const char* prop) {
+            const xml_node* m = n.property(prop);
+            if (!m) return;
+            const aabb box = B.scene_box();
+            const mat4 obj_mat = mul(translate(box.lo[0], box.lo[1], box.lo[2]), scale(box.hi[0] - box.lo[0], box.hi[1] - box.lo[1], box.hi[2] - box.lo[2]));
+            if (has_bsdf) { unsupported("a medium on a shape that has a BSDF (Material::bssrdf)"); return; }
+            ctl_volume V;
+            if (parse_medium(*m, obj_mat, V)) { B.create_volume(V); delete_node = true; }
+        };
+        if (flags & CTL_PARSE_EXTERIOR_MEDIA) create_bssrdf("exterior");
+        if (flags & CTL_PARSE_INTERIOR_MEDIA) create_bssrdf("interior");
+        if (delete_node) nodes_to_remove.push_back(node);
     }
     mat4 node_transform(uint32_t node) const { mat4 r; std::memcpy(r.m, B.xf[node].m, 64); return r; }
     void assign_instance(uint32_t src, const mat4& m) {   // ShapegroupData::assign (:1127-1145): new node of the same mesh with the source's BSDF
@@ -606,18 +663,24 @@ void loader::parse_file(const std::string& file) {
         else if (t == "bsdf") parse_bsdf(n, 0);
         else if (t == "shape") parse_shape(n);
         else if (t == "texture") parse_texture(n);
-        else if (t == "medium") unsupported("<medium>");
+        else if (t == "medium") { if (!flags) unsupported("<medium>"); else { ctl_volume V; (void)parse_medium(n, identity(), V); } }   // MediumParser::parse(n, S): kept for a later <ref>
         // other elements (integrator, ...) are ignored, as in the reference
     }
 }
 
 } // namespace
 
-void parse_mitsuba_scene(scene_builder& b, const char* xml_path, int32_t* width_inout, int32_t* height_inout) {
+void parse_mitsuba_scene(scene_builder& b, const char* xml_path, int32_t* width_inout, int32_t* height_inout, uint32_t flags) {
+    if (flags & ~(uint32_t)(CTL_PARSE_EXTERIOR_MEDIA | CTL_PARSE_INTERIOR_MEDIA)) throw std::runtime_error("ctl_parse_mitsuba_scene_ex: unknown flag bits");
     const std::string path(xml_path);
     const size_t s = path.find_last_of("/\\");
     loader L(b, s == std::string::npos ? "." : path.substr(0, s));
+    L.flags = flags;
     L.parse_file(path);
+    // MitsubaLoader.cpp:68-70: scene.DeleteNode for every shape that only carried a medium, highest index first so that the others keep theirs
+    std::sort(L.nodes_to_remove.begin(), L.nodes_to_remove.end());
+    L.nodes_to_remove.erase(std::unique(L.nodes_to_remove.begin(), L.nodes_to_remove.end()), L.nodes_to_remove.end());
+    for (size_t k = L.nodes_to_remove.size(); k-- > 0;) b.remove_node(L.nodes_to_remove[k]);
     if (!L.have_sensor) throw std::runtime_error("ParseMitsubaScene: the scene has no <sensor>");
     int w = L.film_w, h = L.film_h;
     if (width_inout && height_inout && *width_inout > 0 && *height_inout > 0) {   // caller override of the film size (main.cpp resizes the tracer, not the sensor)

@@ -9,5 +9,6 @@ namespace ctl {
 struct io_error : std::runtime_error { using std::runtime_error::runtime_error; };
 struct unsupported_error : std::runtime_error { using std::runtime_error::runtime_error; };
 // width/height: in = override (<= 0: take the film size of the file), out = the size used
-void parse_mitsuba_scene(scene_builder& b, const char* xml_path, int32_t* width_inout, int32_t* height_inout);
+// flags: CTL_PARSE_* (create_exterior_bssrdf / create_interior_bssrdf of ParseMitsubaScene); 0 = no media are created and <medium> is refused
+void parse_mitsuba_scene(scene_builder& b, const char* xml_path, int32_t* width_inout, int32_t* height_inout, uint32_t flags = 0);
 }

@@ -9,6 +9,7 @@
 #include <string>
 #include "ctl_math.h"
 #include "mesh_skin.h"
+#include "volume_eval.h"
 #include <cstring>
 #include <algorithm>
 #include <stdexcept>
@@ -546,6 +547,25 @@ static aabb box_transform(const aabb& b, const float* m) {
     return o;
 }
 
+uint32_t scene_builder::create_volume(const ctl_volume& v) {
+    if (volumes.size() >= CTL_MAX_VOL_COUNT) throw std::runtime_error("ctl_builder_create_volume: the aggregate holds at most " + std::to_string(CTL_MAX_VOL_COUNT) + " volumes (KernelAggregateVolume::MAX_VOL_COUNT)");
+    ctl_volume c = v; volume_update(c);
+    volumes.push_back(c);
+    return (uint32_t)volumes.size() - 1;
+}
+void scene_builder::set_volume(uint32_t index, const ctl_volume& v) {
+    if (index >= volumes.size()) throw std::runtime_error("ctl_builder_set_volume: bad volume index");
+    ctl_volume c = v; volume_update(c);
+    volumes[index] = c;
+}
+
+void scene_builder::remove_node(uint32_t i) {
+    if (i >= nodes.size()) throw std::runtime_error("remove_node: bad node index");
+    if (nodes[i].n_lights) throw std::runtime_error("remove_node: node " + std::to_string(i) + " carries area lights");
+    nodes.erase(nodes.begin() + i); xf.erase(xf.begin() + i); ixf.erase(ixf.begin() + i);
+    for (auto& L : lights) if (L.type == CTL_LIGHT_DIFFUSE && L.node_idx != 0xffffffffu && L.node_idx > i) L.node_idx--;
+}
+
 void scene_builder::finalize(ctl_scene_desc& out) {
     if (nodes.empty()) throw std::runtime_error("ctl_builder_finalize: scene has no nodes");
     if (!have_camera) throw std::runtime_error("ctl_builder_finalize: no camera set");
@@ -589,6 +609,7 @@ void scene_builder::finalize(ctl_scene_desc& out) {
     }
     for (int i = 0; i < 3; i++) { rt[i].trans = rt_trans[i].empty() ? nullptr : rt_trans[i].data(); rt[i].diff_trans = rt_diff[i].empty() ? nullptr : rt_diff[i].data(); }
     out.rough_transmittance = have_rt ? rt : nullptr;
+    out.volumes = volumes.empty() ? nullptr : volumes.data(); out.n_volumes = (uint32_t)volumes.size();
     {   // the light that depends on the scene box: InfiniteLight::Update (SceneTypes/Light.h:318-325)
         f3 lo(scene.lo[0], scene.lo[1], scene.lo[2]), hi(scene.hi[0], scene.hi[1], scene.hi[2]);
         f3 center = (lo + hi) * 0.5f;   // AABB::Center (Math/AABB.h)

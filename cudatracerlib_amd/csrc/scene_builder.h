@@ -37,6 +37,7 @@ struct scene_builder {
     bool have_rt = false;
     ctl_sensor camera{};
     bool have_camera = false;
+    std::vector<ctl_volume> volumes;                   // DynamicScene::m_pVolumes
 
     // mesh BVH builder: CTL_BVH_SBVH = the reference's SplitBVHBuilder restated (sbvh_builder.cpp, identical arrays), CTL_BVH_BINNED = binned
     // SAH without spatial splits (bvh_builder.cpp, threaded), CTL_BVH_AUTO = SBVH up to kSbvhAutoLimit = 65536 triangles (its sweep sorts the
@@ -68,6 +69,12 @@ struct scene_builder {
     void load_rough_transmittance(uint32_t slot, const char* path);
     void set_camera_lookat(const float pos[3], const float target[3], const float up[3], float fov_degrees, uint32_t w, uint32_t h);
     void set_camera(const ctl_sensor& s);
+    // DynamicScene::CreateVolume(VolumeRegion) (Engine/DynamicScene.cpp:787-792) / an edit of the region it returned; the derived fields are recomputed (ctl_volume_update)
+    uint32_t create_volume(const ctl_volume& v);
+    void set_volume(uint32_t index, const ctl_volume& v);
+    // DynamicScene::DeleteNode (Engine/DynamicScene.cpp:380-384) for a node without lights (the loader's medium-only shapes): the nodes behind it move up one index, the
+    // area lights of those nodes follow; the node's material copies stay in the array, unreferenced
+    void remove_node(uint32_t node_index);
     void finalize(ctl_scene_desc& out);
 };
 

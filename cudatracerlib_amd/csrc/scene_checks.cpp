@@ -2,6 +2,7 @@
 #include "scene_checks.h"
 #include "device_scene.h"   // kStackSize and the BSDF model classifiers
 #include <algorithm>
+#include <cmath>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -80,6 +81,27 @@ void check_materials(const ctl_scene_desc& d, const char* who) {
     }
 }
 
+// participating media (CTL_DIFF_VOLUMES): what csrc/volume.h takes for granted
+void check_volumes(const ctl_scene_desc& d, const char* who) {
+    if (d.n_volumes > CTL_MAX_VOL_COUNT) refuse(who, std::to_string(d.n_volumes) + " volumes; the aggregate holds at most " + std::to_string(CTL_MAX_VOL_COUNT) + " (KernelAggregateVolume::MAX_VOL_COUNT)");
+    if (d.n_volumes && !d.volumes) refuse(who, "n_volumes without a volumes array");
+    for (uint32_t i = 0; i < d.n_volumes; i++) {
+        const ctl_volume& V = d.volumes[i]; const std::string vi = "volume " + std::to_string(i) + ": ";
+        if (V.type != CTL_VOLUME_HOMOGENEOUS) refuse(who, vi + "volume type " + std::to_string(V.type) + " has no HIP implementation (homogeneous media only)");
+        for (int k = 0; k < 9; k++) {
+            const float c = k < 3 ? V.sig_a[k] : (k < 6 ? V.sig_s[k - 3] : V.le[k - 6]);
+            if (!std::isfinite(c) || c < 0.0f) refuse(who, vi + "sig_a, sig_s and le must be finite and non-negative");
+        }
+        for (int k = 0; k < 16; k++) if (!std::isfinite(V.volume_to_world.m[k])) refuse(who, vi + "volume_to_world is not finite");
+        for (int k = 0; k < 16; k++) if (!std::isfinite(V.world_to_volume.m[k])) refuse(who, vi + "volume_to_world is not invertible (world_to_volume is not finite; ctl_volume_update derives it)");
+        const ctl_phase_function& F = V.phase;
+        if (F.type < CTL_PHASE_HG || F.type > CTL_PHASE_RAYLEIGH) refuse(who, vi + "unknown phase function type " + std::to_string(F.type));
+        if (F.type == CTL_PHASE_HG && !(std::fabs(F.g) < 1.0f)) refuse(who, vi + "the Henyey-Greenstein g must lie in (-1, 1)");
+        if (F.type == CTL_PHASE_KAJIYA_KAY && !(std::isfinite(F.ks) && std::isfinite(F.kd) && std::isfinite(F.exponent) && std::isfinite(F.normalization)))
+            refuse(who, vi + "the Kajiya-Kay ks, kd, exponent and normalization must be finite");
+    }
+}
+
 }  // namespace
 
 void check_traversal_stack(const ctl_scene_desc& d, bool strict_top_level, const char* who) {
@@ -108,6 +130,7 @@ void check_scene_desc(const ctl_scene_desc& d, uint32_t parts, const char* who) 
     if (parts & CTL_DIFF_LIGHTS) check_lights(d, who);
     if (parts & CTL_DIFF_MATERIALS) check_materials(d, who);
     if (parts & (CTL_DIFF_TRANSFORMS | CTL_DIFF_TOPOLOGY | CTL_DIFF_GEOMETRY)) check_traversal_stack(d, !creating, who);   // (a geometry update brings the mesh BVHs anew: what creation checks of them)
+    if (parts & (CTL_DIFF_VOLUMES | CTL_DIFF_TOPOLOGY)) check_volumes(d, who);
     if ((parts & CTL_DIFF_CAMERA) && (d.camera.type < CTL_SENSOR_SPHERICAL || d.camera.type > CTL_SENSOR_TELECENTRIC))
         refuse(who, creating ? "unknown sensor type " + std::to_string(d.camera.type) : std::string("unknown sensor type"));   // (creation has always named the value, an update never has)
 }

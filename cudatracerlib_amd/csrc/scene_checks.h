@@ -5,7 +5,7 @@
 
 namespace ctl {
 
-constexpr uint32_t kCheckAllParts = CTL_DIFF_CAMERA | CTL_DIFF_MATERIALS | CTL_DIFF_LIGHTS | CTL_DIFF_TRANSFORMS | CTL_DIFF_TOPOLOGY;   // what creation checks
+constexpr uint32_t kCheckAllParts = CTL_DIFF_CAMERA | CTL_DIFF_MATERIALS | CTL_DIFF_LIGHTS | CTL_DIFF_TRANSFORMS | CTL_DIFF_TOPOLOGY | CTL_DIFF_VOLUMES;   // what creation checks
 
 // Throws std::runtime_error(who + ": " + what) for the first rule that `d` breaks among the rules of `parts` (CTL_DIFF_* bits: an update passes the mask it found,
 // whose other parts are those of a description that was checked already):
@@ -15,6 +15,8 @@ constexpr uint32_t kCheckAllParts = CTL_DIFF_CAMERA | CTL_DIFF_MATERIALS | CTL_D
 //   CTL_DIFF_LIGHTS      env_map_index, light types, the lights' image indices
 //   CTL_DIFF_MATERIALS   texture types and image indices, map kind, alpha state, BSDF type, nested BSDFs, distributions and their transmittance tables
 //   CTL_DIFF_CAMERA      the sensor type
+//   CTL_DIFF_VOLUMES     at most CTL_MAX_VOL_COUNT volumes; finite, non-negative coefficients; a finite matrix with a finite inverse; a known phase function, |g| < 1,
+//                        finite Kajiya-Kay terms (creation checks these too)
 // What needs the flattened tree (a leaf's material index, the flattened depth, the node format) is checked where the tree is made (tracer.hip).
 void check_scene_desc(const ctl_scene_desc& d, uint32_t parts, const char* who);
 

@@ -9,7 +9,10 @@
 #include "geometry_hash.h"
 #include "scene_cache.h"
 #include "mitsuba_loader.h"   // unsupported_error
+#include "scene_volumes.h"
 #include <cstring>
+#include <map>
+#include <mutex>
 
 namespace ctl {
 
@@ -19,7 +22,8 @@ uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const
     // topology first: the counts decide whether the arrays can be compared at all
     if (a.n_tri_data != b.n_tri_data || a.n_woop != b.n_woop || a.n_bvh_nodes != b.n_bvh_nodes || a.n_meshes != b.n_meshes || a.n_nodes != b.n_nodes || a.n_materials != b.n_materials ||
         a.n_images != b.n_images || (a.rough_transmittance != nullptr) != (b.rough_transmittance != nullptr))
-        return CTL_DIFF_TOPOLOGY | ((std::memcmp(&a.camera, &b.camera, sizeof(ctl_sensor)) != 0) ? CTL_DIFF_CAMERA : 0u);
+        return CTL_DIFF_TOPOLOGY | ((std::memcmp(&a.camera, &b.camera, sizeof(ctl_sensor)) != 0) ? CTL_DIFF_CAMERA : 0u) |
+               ((a.n_volumes != b.n_volumes || !same(a.volumes, b.volumes, (size_t)a.n_volumes * sizeof(ctl_volume))) ? (uint32_t)CTL_DIFF_VOLUMES : 0u);
     if (!same(a.meshes, b.meshes, (size_t)a.n_meshes * sizeof(ctl_kernel_mesh))) mask |= CTL_DIFF_TOPOLOGY;
     for (uint32_t k = 0; k < a.n_nodes; k++) {
         const ctl_node &x = a.nodes[k], &y = b.nodes[k];
@@ -50,10 +54,48 @@ uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const
     if (!same(a.node_transforms, b.node_transforms, (size_t)a.n_nodes * sizeof(ctl_float4x4)) || !same(a.node_inv_transforms, b.node_inv_transforms, (size_t)a.n_nodes * sizeof(ctl_float4x4)) ||
         a.scene_start_node != b.scene_start_node || a.n_scene_bvh_nodes != b.n_scene_bvh_nodes || !same(a.scene_bvh_nodes, b.scene_bvh_nodes, (size_t)a.n_scene_bvh_nodes * sizeof(ctl_bvh_node)) ||
         std::memcmp(a.box_min, b.box_min, 12) != 0 || std::memcmp(a.box_max, b.box_max, 12) != 0 || std::memcmp(&a.ray_trace_eps, &b.ray_trace_eps, 4) != 0) mask |= CTL_DIFF_TRANSFORMS;
+    if (a.n_volumes != b.n_volumes || !same(a.volumes, b.volumes, (size_t)a.n_volumes * sizeof(ctl_volume))) mask |= CTL_DIFF_VOLUMES;
     return mask;
 }
 
-Scene::~Scene() {}
+// ---- the scenes' volume tables (scene_volumes.h): device table, host copy (what the snapshot's `volumes` points at) and the kernel argument, per scene
+namespace {
+struct scene_volumes { dbuf<ctl_volume> dev; std::vector<ctl_volume> host; vol::table T{}; uint64_t id = 0; };
+std::mutex g_volumes_mutex;
+// never destroyed: a scene that is still alive when the process ends must not free device memory during static destruction, after the runtime may have gone
+std::map<const Scene*, std::unique_ptr<scene_volumes>>& g_volumes = *new std::map<const Scene*, std::unique_ptr<scene_volumes>>();
+uint64_t g_next_volumes_id = 1;
+// the description's media into the scene's table, synchronously, when they differ from what it holds; returns the host copy (null without media)
+const ctl_volume* store_volumes(const Scene* s, const ctl_scene_desc& d) {
+    std::lock_guard<std::mutex> lock(g_volumes_mutex);
+    std::unique_ptr<scene_volumes>& e = g_volumes[s];
+    const bool fresh = !e;
+    if (fresh) { e.reset(new scene_volumes()); e->id = g_next_volumes_id++; e->dev.alloc(CTL_MAX_VOL_COUNT); CTL_HIP(hipMemset(e->dev.p, 0, CTL_MAX_VOL_COUNT * sizeof(ctl_volume))); }
+    const size_t n = d.n_volumes;   // (<= CTL_MAX_VOL_COUNT: check_scene_desc)
+    if (fresh || n != e->host.size() || (n && std::memcmp(e->host.data(), d.volumes, n * sizeof(ctl_volume)) != 0)) {
+        e->host.assign(d.volumes, d.volumes + n);
+        if (n) CTL_HIP(hipMemcpy(e->dev.p, e->host.data(), n * sizeof(ctl_volume), hipMemcpyHostToDevice));
+        e->T = vol::make_table(e->dev.p, (uint32_t)n);
+    }
+    return e->host.empty() ? nullptr : e->host.data();
+}
+}  // namespace
+vol::table scene_volume_table(const Scene* s) {
+    std::lock_guard<std::mutex> lock(g_volumes_mutex);
+    auto it = g_volumes.find(s);
+    return it == g_volumes.end() ? vol::table{} : it->second->T;
+}
+uint64_t scene_volumes_id(const Scene* s) {
+    std::lock_guard<std::mutex> lock(g_volumes_mutex);
+    auto it = g_volumes.find(s);
+    return it == g_volumes.end() ? 0 : it->second->id;
+}
+void refuse_volumes(const Scene* s, const char* who) {
+    const uint32_t n = s ? scene_volume_table(s).n : 0;
+    if (n) throw unsupported_error(std::string(who) + ": the scene has participating media (" + std::to_string(n) + " volumes), which only the PathTracer plugin with Regularization = false renders");
+}
+
+Scene::~Scene() { std::lock_guard<std::mutex> lock(g_volumes_mutex); g_volumes.erase(this); }
 
 void Scene::snapshot(const ctl_scene_desc& d, const geometry_hashes* geom) {
     std::unique_ptr<desc_snapshot> s(new desc_snapshot());
@@ -61,6 +103,8 @@ void Scene::snapshot(const ctl_scene_desc& d, const geometry_hashes* geom) {
     s->lights.assign(d.lights, d.lights + d.n_lights_buf); s->anim.assign(d.anim, d.anim + d.n_anim_bytes); s->top.assign(d.scene_bvh_nodes, d.scene_bvh_nodes + d.n_scene_bvh_nodes);
     s->xf.assign(d.node_transforms, d.node_transforms + d.n_nodes); s->ixf.assign(d.node_inv_transforms, d.node_inv_transforms + d.n_nodes);
     s->images.assign(d.images, d.images + d.n_images); for (auto& m : s->images) m.texels = nullptr;
+    // the media: creation and every update end here, after the device has been synchronised — the table is written in place (no re-creation, no refit)
+    s->d.volumes = store_volumes(this, d);
     if (geom) s->geom = *geom;                    // after an update: the pass that found the difference made them
     else if (snap_) s->geom = snap_->geom;
     else hash_geometry(d, s->geom);

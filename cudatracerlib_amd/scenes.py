@@ -159,6 +159,19 @@ def cornell_box(width=256, height=256, glass_sphere=False, extra_materials=False
     return sc
 
 
+def fog_box(width=256, height=256, sigma_a=0.0005, sigma_s=0.002, phase=None, fraction=(1.0, 1.0, 1.0), glass_sphere=False):
+    """The Cornell box plus ONE homogeneous medium over the scene box (sigma_a / sigma_s: a scalar or rgb, per scene unit — the box is ~550 units wide; phase: an
+    api.phase_*(), default isotropic).  fraction: the part of the scene box, from its minimum corner, that the medium fills per axis — (1, 0.5, 1) is fog over the
+    lower half.  Only the PathTracer plugin renders it.  The builder is returned after UpdateScene(); .volume is the ctl_volume, .volume_index its slot."""
+    sc = cornell_box(width, height, glass_sphere=glass_sphere)
+    lo = np.array(sc.desc.box_min, np.float32); hi = np.array(sc.desc.box_max, np.float32)
+    hi = (lo + (hi - lo) * np.asarray(fraction, np.float32)).astype(np.float32)
+    sc.volume = api.homogeneous_volume(api.box_to_volume_matrix(lo, hi), sigma_a, sigma_s, phase)
+    sc.volume_index = sc.CreateVolume(sc.volume)
+    sc.UpdateScene()
+    return sc
+
+
 def _rotation(rs):
     q = rs.normal(size=4); q /= np.linalg.norm(q)
     w, x, y, z = q
@@ -168,6 +181,7 @@ def _rotation(rs):
 
 
 # ---- scene descriptions: one description, two ways into the library ------------------------------------------------------------------
+# (optionally volumes: [ ctl_volume ], participating media, which build_scene creates and export_mitsuba refuses.)
 # A description is a plain dict { meshes: [ {V, F, N | None, material} ], nodes: [ (mesh, 4x4 | None) ], lights: [ (node, radiance) ], camera: (pos, target, up,
 # fov_deg, w, h) } with material = ("diffuse", rgb) | ("roughconductor", alpha, eta, k)  (GGX, visible-normal sampling).
 # build_scene() feeds it to the builder API (DynamicScene); export_mitsuba() writes it as a Mitsuba-0.5 scene (scene.xml + meshes.serialized) that
@@ -191,6 +205,8 @@ def build_scene(desc, sensor=None):
     sc.setCamera(pos, target, up, fov, w, h)
     if sensor is not None:
         sc.setSensor(sensor)
+    for v in desc.get("volumes", ()):   # participating media: ctl_volume records (api.homogeneous_volume)
+        sc.CreateVolume(v)
     sc.UpdateScene()
     return sc
 
@@ -238,6 +254,8 @@ def _serialized_mesh(V, F, N):
 def export_mitsuba(desc, directory, name="scene.xml"):
     """writes <directory>/<name> and <directory>/meshes.serialized; returns the path of the XML file.  Every mesh needs explicit normals (with_explicit_normals)."""
     import os, struct
+    if desc.get("volumes"):
+        raise ValueError("export_mitsuba: a scene with participating media is not exported")
     os.makedirs(directory, exist_ok=True)
     blobs, offsets, pos = [], [], 0
     for m in desc["meshes"]:

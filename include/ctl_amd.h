@@ -217,6 +217,25 @@ typedef struct {
 
 #define CTL_MAX_NUM_LIGHTS 16      /* Engine/KernelDynamicScene.h:26 */
 
+/* Participating media (SceneTypes/Volumes.{h,cu}, SceneTypes/PhaseFunction.{h,cu}).  ids = the reference's TYPE_FUNC ids. */
+enum { CTL_PHASE_HG = 1, CTL_PHASE_ISOTROPIC = 2, CTL_PHASE_KAJIYA_KAY = 3, CTL_PHASE_RAYLEIGH = 4 };
+typedef struct {
+    uint32_t type;             /* CTL_PHASE_*                                                                    */
+    float g;                   /* HGPhaseFunction::m_g, |g| < 1                                                  */
+    float ks, kd, exponent;    /* KajiyaKayPhaseFunction::m_ks, m_kd, m_exponent                                 */
+    float normalization;       /* DERIVED: KajiyaKayPhaseFunction::m_normalization (ctl_volume_update)           */
+} ctl_phase_function;          /* 24 B */
+enum { CTL_VOLUME_HOMOGENEOUS = 1 };   /* HomogeneousVolumeDensity; VolumeGrid (2) is not carried */
+#define CTL_MAX_VOL_COUNT 16       /* KernelAggregateVolume::MAX_VOL_COUNT */
+/* A region is the unit cube [0,1]^3 under volume_to_world (BaseVolumeRegion); its coefficients hold inside and are 0 outside. */
+typedef struct {
+    uint32_t type;                     /* CTL_VOLUME_*                                                           */
+    ctl_phase_function phase;          /* BaseVolumeRegion::Func                                                 */
+    ctl_float4x4 volume_to_world;      /* BaseVolumeRegion::VolumeToWorld                                        */
+    ctl_float4x4 world_to_volume;      /* DERIVED: VolumeToWorld.inverse() (BaseVolumeRegion::Update; ctl_volume_update) */
+    float sig_a[3], sig_s[3], le[3];   /* absorption, scattering, emission (the path tracer never reads le)      */
+} ctl_volume;                          /* 192 B */
+
 /* Engine/KernelDynamicScene.h:28-109 restated with plain pointers (HOST memory). */
 typedef struct {
     const ctl_triangle_data* tri_data;   uint32_t n_tri_data;     /* m_sTriData       */
@@ -242,6 +261,7 @@ typedef struct {
     float ray_trace_eps;                      /* m_rayTraceEps = 1e-4 * |box diagonal| (DynamicScene.cpp:587) */
     const ctl_mipmap* images;            uint32_t n_images;       /* m_sTexData (level 0) */
     const ctl_rough_transmittance* rough_transmittance;           /* [3] or NULL (needed by roughplastic only) */
+    const ctl_volume* volumes;           uint32_t n_volumes;      /* m_sVolume (KernelAggregateVolume): at most CTL_MAX_VOL_COUNT regions; NULL / 0 = no participating media */
 } ctl_scene_desc;
 
 /* BSDF::Update() (SceneTypes/BSDF_Simple.h:255-264 plastic, :298-304 roughplastic, :332-337 phong, :371-376 ward; BSDF_Complex.h:37-44 coating, :117-125
@@ -250,6 +270,10 @@ typedef struct {
  * luminance (constant and checkerboard textures; an image texture's average is the caller's, as ImageTexture::Average reads the coarsest MIP level).
  * Host only.  A caller converting the reference's own objects copies their fields instead and does not need this. */
 int ctl_material_update(ctl_material* m);
+/* BaseVolumeRegion::Update + KajiyaKayPhaseFunction::Update (SceneTypes/Volumes.h:31-34, PhaseFunction.cu:64-77): recomputes a volume's DERIVED fields from its primary
+ * ones — world_to_volume = float4x4::inverse of volume_to_world, and for a Kajiya-Kay phase function the normalisation by the reference's 1000-step Simpson sum (with the
+ * shared fp32 functions of csrc/ctl_fmath.h).  Host only.  An unknown phase or volume type: CTL_ERR_INVALID. */
+int ctl_volume_update(ctl_volume* v);
 /* FresnelHelper::fresnelDiffuseReflectance(eta, false) as above. */
 float ctl_fresnel_diffuse_reflectance(float eta);
 
@@ -306,6 +330,11 @@ int ctl_builder_load_rough_transmittance(ctl_builder* b, uint32_t slot, const ch
 int ctl_builder_set_camera_lookat(ctl_builder* b, const float pos[3], const float target[3], const float up[3],
                                   float fov_degrees, uint32_t width, uint32_t height);
 int ctl_builder_set_camera(ctl_builder* b, const ctl_sensor* sensor);
+/* DynamicScene::CreateVolume(VolumeRegion) (Engine/DynamicScene.cpp:787-792): adds a participating medium, at most CTL_MAX_VOL_COUNT; ctl_builder_set_volume replaces one
+ * (the host edits the region CreateVolume returned).  The derived fields are recomputed as ctl_volume_update does; the next ctl_builder_finalize hands the array out and
+ * ctl_scene_update applies it in place (CTL_DIFF_VOLUMES).  Only the PathTracer plugin renders media; the other plugins refuse a scene that has any. */
+int ctl_builder_create_volume(ctl_builder* b, const ctl_volume* volume, uint32_t* index_out);
+int ctl_builder_set_volume(ctl_builder* b, uint32_t index, const ctl_volume* volume);
 /* DynamicScene::UpdateScene + getKernelSceneData (DynamicScene.cpp:480-589): builds the scene BVH and fills
  * `out` with pointers that stay valid until the builder is destroyed or finalized again. */
 int ctl_builder_finalize(ctl_builder* b, ctl_scene_desc* out);
@@ -354,8 +383,9 @@ enum { CTL_DIFF_CAMERA = 1,       /* ctl_scene_desc::camera                     
        CTL_DIFF_TRANSFORMS = 8,   /* node_transforms, node_inv_transforms, the scene BVH and its start node, box_min / box_max, ray_trace_eps       */
        CTL_DIFF_TOPOLOGY = 16,    /* anything else: any count but the lights', woop_index, the mesh BVHs' links, meshes, node -> mesh / material assignment,
                                      images, rough-transmittance tables                                                                           */
-       CTL_DIFF_GEOMETRY = 32 };  /* only VALUES of the geometry arrays: the contents of tri_data and woop and the float boxes of bvh_nodes — a deformed mesh
+       CTL_DIFF_GEOMETRY = 32,    /* only VALUES of the geometry arrays: the contents of tri_data and woop and the float boxes of bvh_nodes — a deformed mesh
                                      (ctl_builder_update_mesh) — with everything CTL_DIFF_TOPOLOGY names equal                                    */
+       CTL_DIFF_VOLUMES = 64 };   /* `volumes` / `n_volumes`: the participating media, and nothing else                                            */
 int ctl_scene_desc_diff(const ctl_scene_desc* a, const ctl_scene_desc* b, uint32_t* mask_out);
 /* Everything ctl_scene_create and ctl_scene_update refuse a description for that can be judged from the description alone (host only, no device call): node transforms,
  * sensor, lights, textures, materials, the depth of the two-level BVH.  parts == 0: as ctl_scene_create checks; else the CTL_DIFF_* parts to check, as ctl_scene_update
@@ -463,6 +493,15 @@ int ctl_flat_bvh_refit(ctl_flat_bvh* h, const ctl_scene_desc* new_desc);
 int ctl_scene_read_flat_bvh(ctl_scene* scene, ctl_flat_bvh** out);
 /* ParseMitsubaScene (Engine/SceneLoader/Mitsuba/MitsubaLoader.h:13): fills a builder from a Mitsuba-0.5 XML file. */
 int ctl_parse_mitsuba_scene(ctl_builder* b, const char* xml_path, int32_t* width_inout, int32_t* height_inout);
+/* The same with ParseMitsubaScene's create_exterior_bssrdf / create_interior_bssrdf (flags = 0: ctl_parse_mitsuba_scene, which creates no media and refuses <medium>).
+ * With a flag set, ObjectParser.h:1066-1101 and MediumParser::homogeneous (:177-214) as written: a shape WITHOUT a BSDF whose `exterior` / `interior` is a homogeneous
+ * medium — inline, or a <ref> to a <medium id=...> — creates a volume and has its node removed when the parse ends.  An inline medium lies over the scene box as it
+ * stands at that point of the parse (Translate(box.min) % Scale(box.Size()), the shape's own node included); a referenced medium keeps the transform it was parsed with,
+ * the identity for a top-level <medium>: the reference resolves the <ref> before it looks at the transform.  sigmaA / sigmaS or sigmaT / albedo, scale, and
+ * <phase type="isotropic|hg|rayleigh|kkay">.  Refused (CTL_ERR_UNSUPPORTED; skipped under CTL_LOADER_LENIENT): material= presets (MaterialLibrary), heterogeneous media,
+ * a medium on a shape that has a BSDF (Material::bssrdf).  Unknown flag bits: CTL_ERR_INVALID. */
+enum { CTL_PARSE_EXTERIOR_MEDIA = 1, CTL_PARSE_INTERIOR_MEDIA = 2 };
+int ctl_parse_mitsuba_scene_ex(ctl_builder* b, const char* xml_path, int32_t* width_inout, int32_t* height_inout, uint32_t flags);
 /* The bitmap reader behind the loader's textures and environment maps (the reference goes through FreeImage, Engine/MIPMap.cu:542-592): PNG, JPEG
  * (sequential and progressive), BMP, TGA, PNM, PFM, Radiance HDR, OpenEXR (scanline; NONE / RLE / ZIPS / ZIP).  Rows top-down.  *is_float = 1: `rgb`
  * receives 3 floats per pixel; 0: `rgba8` receives 4 bytes per pixel.  With both buffers NULL only the size and kind are returned. */
@@ -729,6 +768,29 @@ enum { CTL_EVAL_BSDF_SAMPLE = 0,      /* [material] wi(3) sample(2) uv(2)       
        CTL_EVAL_ALPHA_TEST = 11 };    /* [material] uv(2), each representable in half precision -> 1 / 0: Material::AlphaTest as the traversal asks it (alpha_survives), through one synthetic triangle per query whose vertices carry the uv; every build */
 int ctl_shading_eval(const ctl_scene* scene, int32_t build, int32_t what, const ctl_material* materials, uint32_t n_materials,
                      uint32_t n, const float* queries, uint32_t query_stride, float* out, uint32_t out_stride);
+
+/* TEST INFRASTRUCTURE: the participating-media functions (csrc/volume.h) one call per query, after ctl_shading_eval and ctl_shared_math_eval.  `desc` supplies volumes /
+ * n_volumes (nothing else of it is read; the derived fields must be current: ctl_volume_update, or a description from the builder).  on_device = 0 runs the functions
+ * on the host and needs no GPU — the yardstick; 1 runs one small kernel, one lane per query (CTL_ERR_NO_DEVICE without a device).  The two are bit-identical.
+ * A query row is CTL_VEVAL_QUERY_FLOATS floats, a result row CTL_VEVAL_RESULT_FLOATS floats, unused ones 0; a [volume] index travels as the BITS of its float and is
+ * checked against n_volumes before anything runs (CTL_ERR_INVALID, as for a description the validator refuses or an unknown `what`).  No reference counterpart. */
+#define CTL_VEVAL_QUERY_FLOATS 10
+#define CTL_VEVAL_RESULT_FLOATS 17
+enum { CTL_VEVAL_REGION_INTERSECT = 0,        /* [volume] o(3) d(3) minT maxT        -> hit t0 t1 (0 0 on a miss)                          (BaseVolumeRegion::IntersectP)            */
+       CTL_VEVAL_INTERSECT = 1,               /* o(3) d(3) minT maxT                 -> hit t0 t1 (FLT_MAX, -FLT_MAX on a miss)            (KernelAggregateVolume::IntersectP)       */
+       CTL_VEVAL_REGION_TAU = 2,              /* [volume] o(3) d(3) minT maxT        -> tau(3)                                             (HomogeneousVolumeDensity::tau)           */
+       CTL_VEVAL_TAU = 3,                     /* o(3) d(3) minT maxT                 -> tau(3)                                             (KernelAggregateVolume::tau)              */
+       CTL_VEVAL_REGION_SAMPLE_DISTANCE = 4,  /* [volume] o(3) d(3) minT maxT sample -> success t p(3) transmittance(3) sigmaA(3) sigmaS(3) pdfSuccess pdfSuccessRev pdfFailure, into a
+                                                 record of zeros                                                                           (HomogeneousVolumeDensity::sampleDistance) */
+       CTL_VEVAL_SAMPLE_DISTANCE = 5,         /* o(3) d(3) minT maxT sample          -> the same row                                       (KernelAggregateVolume::sampleDistance)   */
+       CTL_VEVAL_SAMPLE_VOLUME = 6,           /* o(3) d(3) minT maxT sample          -> region index (-1: none), the sample after sampleReuse, pdf (sampleVolume, with ffsn)         */
+       CTL_VEVAL_PHASE_EVAL = 7,              /* [volume] wi(3) wo(3)                -> value, of the region's phase function              (PhaseFunction::Evaluate)                 */
+       CTL_VEVAL_PHASE_SAMPLE = 8,            /* [volume] wi(3) sample(2)            -> weight pdf wo(3)                                   (PhaseFunction::Sample(pRec, pdf, sample)) */
+       CTL_VEVAL_P = 9,                       /* p(3) wi(3) wo(3)                    -> value                                              (KernelAggregateVolume::p)                */
+       CTL_VEVAL_SAMPLE = 10,                 /* p(3) wi(3) sample(2)                -> weight pdf wo(3), pdf and wo 0 where no region is found (KernelAggregateVolume::Sample)      */
+       CTL_VEVAL_TRANSMITTANCE = 11,          /* o(3) d(3) tmin tmax                 -> T(3)                                               (Transmittance, TraceAlgorithms.cu:22-31) */
+       CTL_VEVAL_EVAL_TRANSMITTANCE = 12 };   /* p1(3) p2(3)                         -> T(3)                                               (KernelDynamicScene::evalTransmittance)   */
+int ctl_volume_eval(const ctl_scene_desc* desc, int32_t what, const float* queries, uint32_t n, float* out, int32_t on_device);
 
 /* device memory helpers so that Python callers need no HIP binding */
 int ctl_device_malloc(size_t bytes, void** out);

@@ -1,0 +1,300 @@
+"""Participating media, the host half (no GPU): the restatement's surface half against the oracle's render; ctl_volume_eval(on_device = 0) — csrc/volume.h on the host —
+against the numpy restatement tests/volume_ref.py, every function, every row bit for bit; the restatement against closed forms in float64; builder, validator and
+diff.  The volume sets and the queries: volume_cases.py."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import volume_ref
+from cudatracerlib_amd import api, scenes
+from volume_cases import SETS, make_set, queries, same_rows, FUNCTIONS
+
+f32 = np.float32
+
+
+@pytest.fixture(scope="module")
+def box_scene():
+    return scenes.cornell_box(24, 16)
+
+
+def test_path_trace_without_volumes_is_the_oracle_render(orc_sm, box_scene):
+    """path_trace with NO volumes equals Oracle(shared_math=True).render in every pixel, bit for bit: cornell_box(24, 16), 2 passes, max path length 6.  Validates the
+    restatement's surface half (draw order, getBsdfSample, emission MIS, UniformSampleOneLight, roulette, AddSample) against code that exists already."""
+    d = box_scene.desc
+    tables = orc_sm.sequence_tables(2)
+    zero_stop = np.zeros((16, 24, 7), np.float32)
+    want, rays = orc_sm.render(d, 24, 16, n_passes=2, tables=tables, max_path_length=6, zero_stop=zero_stop)
+    want = want + zero_stop   # the samples of paths the reference walks on with a zero throughput and then drops (none expected here; the library ends such paths)
+    count = []
+    got = volume_ref.path_trace(orc_sm, d, [], 24, 16, tables, direct=True, max_path_length=6, rr_start=5, ray_count=count)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    assert count[0] == rays
+
+
+@pytest.mark.parametrize("what", sorted(FUNCTIONS))
+def test_volume_eval_host_equals_the_restatement(orc_sm, what):
+    """ctl_volume_eval(on_device = 0) against volume_ref, every row bit for bit, NaN for NaN: 1024 seeded queries per volume set, 4096 per function over the four
+    sets (the numpy restatement is what bounds the count), plus the branch points of each set (volume_cases.queries)."""
+    n_rows = 0
+    for name in SETS:
+        vols = make_set(name)
+        d = api.volumes_desc(vols)
+        q = queries(name, vols, what, 1024)
+        got = api.volume_eval(d, what, q, on_device=False)
+        want = volume_ref.eval_rows(volume_ref.Volumes(orc_sm, vols), what, q)
+        bad = same_rows(got, want)
+        assert not bad, "%s on set %s: %d of %d rows differ, first %s\n got %s\nwant %s\nquery %s" % (FUNCTIONS[what], name, len(bad), len(q), bad[0], got[bad[0]], want[bad[0]], q[bad[0]])
+        n_rows += len(q)
+    assert n_rows >= 4096
+
+
+def test_rayleigh_sample_is_nan_and_kept(orc_sm):
+    """RayleighPhaseFunction::Sample takes pow of a negative base: the NaN propagates into wo and the pdf, in the library as in the restatement"""
+    vols = make_set("two")
+    ri = [i for i, v in enumerate(vols) if v.phase.type == api.PHASE_RAYLEIGH][0]
+    q = np.zeros((1, 10), np.float32); q[0, 0] = np.array([ri], np.uint32).view(np.float32)[0]; q[0, 1:4] = (0, 0, 1); q[0, 4:6] = (0.3, 0.6)
+    got = api.volume_eval(api.volumes_desc(vols), api.VEVAL_PHASE_SAMPLE, q)
+    assert got[0, 0] == 1 and np.isnan(got[0, 1:5]).all()
+
+
+def _ulp(x):
+    return np.spacing(np.abs(np.float32(x))).astype(np.float64)
+
+
+def test_restatement_absorbing_slab_closed_form(orc_sm):
+    """Transmittance and evalTransmittance of an absorbing slab against exp(-sigma_t d) in float64, independent of the code under test.
+    The slab is the cube [0, 4]^3 (volume_to_world = Scale(4): its inverse, the local ray and the slab distances are exact in fp32) and the rays run along an axis
+    from dyadic origins, so ray(t0) - ray(t1) and its length d are exact.  What rounds: sigma_a + sigma_s is taken as its fp32 value; tau = d * sigma_t (half an ulp of
+    x = tau, i.e. a relative error <= 2^-24 in x, which exp turns into a relative error <= |x| 2^-24 <= |x| ulp of the result); exp itself (<= 1 ulp, tests/test_fmath.py).
+    With |x| <= 2.8 here: <= 1 + 2.8 < 4 ulp of the fp32 result."""
+    rs = np.random.RandomState(5)
+    m = np.diag([4, 4, 4, 1]).astype(np.float32)
+    for k in range(64):
+        sig = rs.uniform(0.01, 0.7, 3).astype(np.float32)
+        vols = [api.homogeneous_volume(m, sig, 0.0)]
+        V = volume_ref.Volumes(orc_sm, vols)
+        axis = k % 3
+        o = np.array([1.5, 2.25, 0.75], np.float32); o[axis] = -2.0 if k % 2 else 1.0   # from outside (d = 4) or from inside (d = 3)
+        dvec = np.zeros(3, np.float32); dvec[axis] = 1
+        dist = 4.0 if k % 2 else 3.0
+        exact = np.exp(-(sig.astype(np.float64)) * dist)
+        T = V.transmittance(o, dvec, f32(0), f32(64))
+        assert (np.abs(T.astype(np.float64) - exact) <= 4 * _ulp(T)).all(), (k, T, exact)
+        p2 = o.copy(); p2[axis] = 8.0   # evalTransmittance: d = (p2 - p1) / l is the same axis exactly
+        T2 = V.eval_transmittance(o, p2)
+        assert (np.abs(T2.astype(np.float64) - exact) <= 4 * _ulp(T2)).all(), (k, T2, exact)
+
+
+def test_restatement_phase_functions_integrate_to_one(orc_sm):
+    """Isotropic and Henyey-Greenstein Evaluate integrate to 1 over the sphere: 2 pi * Gauss-Legendre (256 nodes in mu = cos theta, fp32-rounded, wi = +z so that
+    dot(wi, wo) = mu exactly) of the restatement's fp32 values, summed in float64.  The quadrature itself is exact to ~1e-16 (the integrand is analytic in an ellipse
+    with rho = 1.43 at g = 0.7).
+    Isotropic: the value is fl(1 / fl(4 fl(pi))), three roundings of which 4 * pi is exact: <= 1.5 ulp, so the bound is 4 ulp of 1.
+    HG: p = c (1 - g^2) / (temp sqrt(temp)), temp = 1 + g^2 + 2 g mu.  temp is a sum with cancellation: each of g^2, 1 + g^2, 2 g mu and temp rounds, an absolute error
+    <= 2^-24 A with A = g^2 + (1 + g^2) + 2 g + (1 + g)^2; p carries 1.5 times temp's relative error plus <= 3.5 2^-24 from 1 - g^2 (two roundings), the product with c,
+    sqrt, temp * sqrt and the division.  Integrated: 2 pi int p (1.5 A 2^-24 / temp + 3.5 2^-24) dmu = 2^-24 (3.5 + 1.5 A I), I = 2 pi int p / temp dmu
+    = (1 - g^2) / (6 g) ((1 - g)^-3 - (1 + g)^-3).  The fp32 rounding of the nodes moves each by <= 2^-25: 2 pi int |p'| 2^-25 dmu = 2^-24 N,
+    N = ((1 + g) / (1 - g)^2 - (1 - g) / (1 + g)^2) / 4.  Bound: 2^-24 (3.5 + 1.5 A I + N) — 4 ulp of 1 would need I small, i.e. g near 0; the figure is derived, not measured."""
+    x, w = np.polynomial.legendre.leggauss(256)
+    mu = x.astype(np.float32)
+    V = volume_ref.Volumes(orc_sm, [api.homogeneous_volume(np.eye(4), 0.0, 1.0, api.phase_isotropic()), api.homogeneous_volume(np.eye(4), 0.0, 1.0, api.phase_hg(0.7)),
+                                    api.homogeneous_volume(np.eye(4), 0.0, 1.0, api.phase_hg(-0.3))])
+    wi = np.array([0, 0, 1], np.float32)
+    for F in V.v:
+        vals = np.array([V.phase_eval(F, wi, np.array([np.sqrt(f32(1) - m * m), 0, m], np.float32)) for m in mu], np.float64)
+        total = 2 * np.pi * np.dot(w, vals)
+        if F["type"] == api.PHASE_ISOTROPIC:
+            bound = 4 * 2.0 ** -23
+        else:
+            g = abs(float(F["g"]))
+            A = g * g + (1 + g * g) + 2 * g + (1 + g) ** 2
+            I = (1 - g * g) / (6 * g) * ((1 - g) ** -3 - (1 + g) ** -3)
+            N = ((1 + g) / (1 - g) ** 2 - (1 - g) / (1 + g) ** 2) / 4
+            bound = 2.0 ** -24 * (3.5 + 1.5 * A * I + N)
+        assert abs(total - 1) <= bound, (F["type"], float(F["g"]), total - 1, bound)
+
+
+# ---------------------------------------------------------------------------------------------------------------- builder, validator, diff
+def test_builder_round_trip_and_derived_fields(orc_sm):
+    sc = scenes.fog_box(24, 16, sigma_a=(0.001, 0.002, 0.003), sigma_s=0.004, phase=api.phase_kajiya_kay(0.4, 0.2, 4.0), fraction=(1, 0.5, 1))
+    d = sc.desc
+    assert d.n_volumes == 1
+    v = d.volumes[0]
+    assert v.type == api.VOLUME_HOMOGENEOUS and v.phase.type == api.PHASE_KAJIYA_KAY
+    assert np.allclose(list(v.sig_a), (0.001, 0.002, 0.003)) and np.allclose(list(v.sig_s), 0.004) and list(v.le) == [0, 0, 0]
+    m = np.array(list(v.volume_to_world.m), np.float32).reshape(4, 4)
+    lo, hi = np.array(d.box_min, np.float32), np.array(d.box_max, np.float32)
+    assert np.array_equal(m[:3, 3], lo) and np.array_equal(np.diag(m)[:3], ((hi - lo) * np.array([1, 0.5, 1], np.float32)).astype(np.float32))
+    im = np.array(list(v.world_to_volume.m), np.float64).reshape(4, 4)
+    assert np.allclose(im @ m.astype(np.float64), np.eye(4), atol=1e-5)
+    # KajiyaKayPhaseFunction::Update, restated: the 1000-step Simpson sum in fp32 with the shared functions
+    M = volume_ref.Math(orc_sm)
+    PI = volume_ref.PI
+    step = f32(PI / f32(1000)); mm = f32(4); theta = step; acc = f32(0)
+    for _ in range(1, 1000):
+        value = f32(M.pow(M.cos(f32(theta - f32(PI / f32(2)))), f32(4.0)) * M.sin(theta))
+        acc = f32(acc + f32(value * mm)); theta = f32(theta + step); mm = f32(f32(6) - mm)
+    want = f32(f32(1) / f32(f32(f32(f32(acc * step) / f32(3)) * f32(2)) * PI))
+    assert f32(v.phase.normalization).view(np.uint32) == want.view(np.uint32)
+    # SetVolume replaces it; a second finalize hands the new one out
+    sc.SetVolume(0, api.homogeneous_volume(m, 0.0, 0.01, api.phase_hg(-0.9)))
+    d2 = sc.UpdateScene()
+    assert d2.volumes[0].phase.type == api.PHASE_HG and f32(d2.volumes[0].phase.g) == f32(-0.9)
+    with pytest.raises(api.CtlError):
+        sc.SetVolume(3, sc.volume)
+    assert scenes.cornell_box(24, 16).desc.n_volumes == 0
+
+
+def test_builder_holds_sixteen_volumes():
+    sc = scenes.cornell_box(24, 16)
+    for k in range(16):
+        assert sc.CreateVolume(api.homogeneous_volume(np.eye(4), 0.1, 0.1)) == k
+    with pytest.raises(api.CtlError, match="at most 16"):
+        sc.CreateVolume(api.homogeneous_volume(np.eye(4), 0.1, 0.1))
+
+
+def _desc_with(base, vols):
+    d = api.ctl_scene_desc()
+    C.memmove(C.addressof(d), C.addressof(base), C.sizeof(d))
+    arr = (api.ctl_volume * max(1, len(vols)))(*vols)
+    d.volumes = C.cast(arr, C.POINTER(api.ctl_volume)); d.n_volumes = len(vols)
+    d._keep = arr
+    return d
+
+
+@pytest.mark.parametrize("rule", ["count", "negative", "nan", "matrix_nan", "singular", "phase", "g", "kajiya"])
+def test_validator_refuses(box_scene, rule):
+    good = api.homogeneous_volume(api.box_to_volume_matrix((0, 0, 0), (10, 10, 10)), 0.1, 0.2, api.phase_hg(0.5))
+
+    def copy(v):
+        c = api.ctl_volume(); C.memmove(C.addressof(c), C.addressof(v), C.sizeof(c)); return c
+    v = copy(good); vols = [v]; message = None
+    if rule == "count":
+        vols = [copy(good) for _ in range(17)]; message = "at most 16"
+    elif rule == "negative":
+        v.sig_s[1] = -0.5; message = "finite and non-negative"
+    elif rule == "nan":
+        v.sig_a[2] = float("nan"); message = "finite and non-negative"
+    elif rule == "matrix_nan":
+        v.volume_to_world.m[5] = float("inf"); message = "volume_to_world is not finite"
+    elif rule == "singular":
+        v.volume_to_world.m[0] = 0.0; api.volume_update(v); message = "not invertible"
+    elif rule == "phase":
+        v.phase.type = 9; message = "unknown phase function type 9"
+    elif rule == "g":
+        v.phase.g = 1.0; message = r"g must lie in \(-1, 1\)"
+    elif rule == "kajiya":
+        v.phase.type = api.PHASE_KAJIYA_KAY; v.phase.ks = float("inf"); message = "Kajiya-Kay"
+    d = _desc_with(box_scene.desc, vols)
+    for parts in (0, api.DIFF_VOLUMES):
+        with pytest.raises(api.CtlError, match=message):
+            api.scene_desc_check(d, parts)
+    with pytest.raises(api.CtlError, match=message):   # the call-by-call entry judges its description the same way
+        api.volume_eval(d, api.VEVAL_TAU, np.zeros((1, 10), np.float32))
+    api.scene_desc_check(_desc_with(box_scene.desc, [copy(good)]), api.DIFF_VOLUMES)
+
+
+def test_diff_reports_volumes_alone(box_scene):
+    base = box_scene.desc
+    v = api.homogeneous_volume(api.box_to_volume_matrix((0, 0, 0), (10, 10, 10)), 0.1, 0.2)
+    w = api.homogeneous_volume(api.box_to_volume_matrix((0, 0, 0), (10, 10, 10)), 0.1, 0.25)
+    a, b, c = _desc_with(base, []), _desc_with(base, [v]), _desc_with(base, [w])
+    assert api.scene_desc_diff(a, a) == 0 and api.scene_desc_diff(b, b) == 0
+    assert api.scene_desc_diff(a, b) == api.DIFF_VOLUMES      # 0 -> 1 volumes
+    assert api.scene_desc_diff(b, c) == api.DIFF_VOLUMES      # other coefficients
+    assert api.scene_desc_diff(b, _desc_with(base, [v, w])) == api.DIFF_VOLUMES
+    other = scenes.cornell_box(24, 16)
+    other.setCamera((278, 273, -700), (278, 273, 0), (0, 1, 0), 39.3077, 24, 16); other.UpdateScene()
+    assert api.scene_desc_diff(b, _desc_with(other.desc, [v])) == api.DIFF_CAMERA   # nothing else reports it
+    assert api.DIFF_VOLUMES == 64
+
+
+def test_geometry_cache_hash_does_not_see_volumes(box_scene):
+    fog = scenes.fog_box(24, 16)
+    assert api.flatten_probe(box_scene.desc) == api.flatten_probe(fog.desc)
+
+
+# ---------------------------------------------------------------------------------------------------------------- export, Mitsuba loader
+def test_export_mitsuba_refuses_a_scene_with_volumes(tmp_path):
+    """a scene description (scenes.build_scene's dict) may carry volumes: build_scene creates them, export_mitsuba raises"""
+    V, F = scenes.icosphere(1)
+    desc = dict(meshes=[dict(V=V, F=F, N=V, material=("diffuse", (0.5, 0.5, 0.5)))], nodes=[(0, None)], lights=[], camera=((0, 0, -4), (0, 0, 0), (0, 1, 0), 40.0, 16, 12),
+                volumes=[api.homogeneous_volume(api.box_to_volume_matrix((-1, -1, -1), (1, 1, 1)), 0.1, 0.3, api.phase_hg(0.2))])
+    sc = scenes.build_scene(desc)
+    assert sc.desc.n_volumes == 1 and f32(sc.desc.volumes[0].phase.g) == f32(0.2)
+    with pytest.raises(ValueError, match="participating media"):
+        scenes.export_mitsuba(desc, str(tmp_path))
+    del desc["volumes"]
+    scenes.export_mitsuba(desc, str(tmp_path))
+
+
+_SENSOR = '<sensor type="perspective"><float name="fov" value="40"/><transform name="toWorld"><lookat origin="0, 0, -9" target="0, 0, 0" up="0, 1, 0"/></transform></sensor>'
+_HAZE = ('<medium type="homogeneous" id="haze"><rgb name="sigmaT" value="0.4, 0.2, 0.1"/><rgb name="albedo" value="0.5, 0.5, 0.25"/><float name="scale" value="2"/>'
+         '<phase type="hg"><float name="g" value="0.5"/></phase></medium>')
+_ROOM = '<shape type="cube"><transform name="toWorld"><scale x="2" y="1" z="3"/></transform><bsdf type="diffuse"/></shape>'   # [-2, 2] x [-1, 1] x [-3, 3]
+_INLINE = ('<shape type="cube"><transform name="toWorld"><translate x="5"/></transform><medium name="interior" type="homogeneous">'
+           '<rgb name="sigmaA" value="0.1, 0.2, 0.3"/><rgb name="sigmaS" value="0.4, 0.5, 0.6"/><phase type="kkay"/></medium></shape>')   # [4, 6] x [-1, 1] x [-1, 1]
+_BY_REF = '<shape type="cube"><ref name="interior" id="haze"/></shape>'
+_LATER = '<shape type="cube"><transform name="toWorld"><translate y="10"/></transform><bsdf type="diffuse"/></shape>'       # enlarges the scene box AFTER the media were made
+
+
+def _parse(tmp_path, body, **flags):
+    p = tmp_path / "m.xml"
+    p.write_text('<scene version="0.5.0">%s%s</scene>' % (_SENSOR, body))
+    sc = api.DynamicScene()
+    sc.ParseMitsubaScene(str(p), 32, 24, **flags)
+    return sc, sc.UpdateScene()
+
+
+def test_loader_without_flags_behaves_as_before(tmp_path):
+    with pytest.raises(api.CtlError) as e:
+        _parse(tmp_path, _HAZE + _ROOM)
+    assert e.value.code == -5 and "ParseMitsubaScene: <medium> is not supported by this build (set CTL_LOADER_LENIENT=1 to skip it)" in str(e.value)
+    sc, d = _parse(tmp_path, _ROOM + _INLINE)   # a shape's interior is dropped, the shape stays
+    assert d.n_volumes == 0 and d.n_nodes == 2
+
+
+def test_loader_creates_volumes_from_shapes_without_a_bsdf(tmp_path):
+    """ObjectParser.h:1066-1101 + MediumParser::homogeneous with create_interior_bssrdf: a box room, a BSDF-less shape with an inline interior, another that refers to a
+    top-level <medium id>, then a shape that enlarges the scene box.  The inline medium lies over the scene box AS IT STOOD when its shape was parsed (room + that shape);
+    the referenced one keeps the identity it was parsed with at the top level (the reference resolves the <ref> before it looks at the transform); both nodes are removed."""
+    sc, d = _parse(tmp_path, _HAZE + _ROOM + _INLINE + _BY_REF + _LATER, interior_media=True)
+    assert d.n_volumes == 2 and d.n_nodes == 2
+    a, b = d.volumes[0], d.volumes[1]
+    want = np.array([[8, 0, 0, -2], [0, 2, 0, -1], [0, 0, 6, -3], [0, 0, 0, 1]], np.float32)   # Translate(box.min) % Scale(box.Size()), box = [-2, 6] x [-1, 1] x [-3, 3]
+    assert np.array_equal(np.array(list(a.volume_to_world.m), np.float32).reshape(4, 4), want)
+    assert np.array_equal(np.array(list(a.world_to_volume.m), np.float32), np.array(list(api.homogeneous_volume(want, 0, 0).world_to_volume.m), np.float32))
+    assert np.array_equal(np.array(list(a.sig_a), np.float32), np.array([0.1, 0.2, 0.3], np.float32)) and np.array_equal(np.array(list(a.sig_s), np.float32), np.array([0.4, 0.5, 0.6], np.float32))
+    assert list(a.le) == [0, 0, 0] and a.type == api.VOLUME_HOMOGENEOUS
+    kk = api.volume_update(api.homogeneous_volume(np.eye(4), 0, 0, api.phase_kajiya_kay(0.4, 0.2, 4.0)))
+    assert a.phase.type == api.PHASE_KAJIYA_KAY and (f32(a.phase.ks), f32(a.phase.kd), f32(a.phase.exponent)) == (f32(0.4), f32(0.2), f32(4.0))
+    assert f32(a.phase.normalization).view(np.uint32) == f32(kk.phase.normalization).view(np.uint32)
+    assert np.array_equal(np.array(list(b.volume_to_world.m), np.float32).reshape(4, 4), np.eye(4, dtype=np.float32))
+    st = np.array([0.4, 0.2, 0.1], np.float32); al = np.array([0.5, 0.5, 0.25], np.float32)
+    ss = (al * st).astype(np.float32); sa = (st - ss).astype(np.float32)      # sigma_s = albedo * sigma_t, sigma_a = sigma_t - sigma_s, then * scale
+    assert np.array_equal(np.array(list(b.sig_s), np.float32), (ss * f32(2)).astype(np.float32)) and np.array_equal(np.array(list(b.sig_a), np.float32), (sa * f32(2)).astype(np.float32))
+    assert b.phase.type == api.PHASE_HG and f32(b.phase.g) == f32(0.5)
+    api.scene_desc_check(d)
+    # the two shapes that stay are the room and the later cube, in that order
+    xf = d.view("node_transforms", np.float32, d.n_nodes, 16)
+    assert xf[1][7] == 9.0 and xf[0][7] == -1.0   # toWorld % (Scale(2) % Translate(-0.5)): the cube's own mapping of the unit cube onto [-1, 1]^3 is folded in
+    # the other flag looks at `exterior` only: nothing is created, every shape stays; the top-level medium is parsed and kept
+    sc2, d2 = _parse(tmp_path, _HAZE + _ROOM + _INLINE + _BY_REF, exterior_media=True)
+    assert d2.n_volumes == 0 and d2.n_nodes == 3
+    sc3, d3 = _parse(tmp_path, _ROOM + _INLINE.replace('"interior"', '"exterior"'), exterior_media=True)
+    assert d3.n_volumes == 1 and d3.n_nodes == 1
+
+
+@pytest.mark.parametrize("case", ["bsdf", "heterogeneous", "preset"])
+def test_loader_still_refuses(tmp_path, case):
+    body = {"bsdf": _ROOM + '<shape type="cube"><bsdf type="diffuse"/><medium name="interior" type="homogeneous"/></shape>',
+            "heterogeneous": _ROOM + '<shape type="cube"><medium name="interior" type="heterogeneous"/></shape>',
+            "preset": _ROOM + '<shape type="cube"><medium name="interior" type="homogeneous"><string name="material" value="Skin1"/></medium></shape>'}[case]
+    with pytest.raises(api.CtlError) as e:
+        _parse(tmp_path, body, interior_media=True)
+    assert e.value.code == -5 and "not supported by this build" in str(e.value) and {"bsdf": "BSDF", "heterogeneous": "heterogeneous", "preset": "MaterialLibrary"}[case] in str(e.value)
+    with pytest.raises(api.CtlError, match="unknown flag bits"):
+        p = tmp_path / "f.xml"; p.write_text('<scene version="0.5.0">%s%s</scene>' % (_SENSOR, _ROOM))
+        w, h = C.c_int32(8), C.c_int32(8)
+        api._check(api.lib.ctl_parse_mitsuba_scene_ex(api.DynamicScene()._h, str(p).encode(), C.byref(w), C.byref(h), C.c_uint32(4)))
