@@ -7,7 +7,7 @@
 // A render points the reference's globals at the product's compiled scene (ctl_scene_desc):
 //   g_SceneDataHost        meshes, BVH arrays, nodes, materials, lights (rebuilt from the flat descriptors the way INTEGRATION.md's converter maps them back:
 //                          ref_bsdf_all_of, ref_material_of, ref_light_of), the anim blob, TriangleData, images, the light CDF, the camera, m_rayTraceEps,
-//                          doAlphaMapping, an empty volume aggregate
+//                          doAlphaMapping, the volume aggregate (ref_volume_driver.cpp ref_bind_volumes; empty for a scene without media)
 //   t_nodesA / t_SceneNodes the node arrays the host traversal reads (the generated unit's two hand-written pointers)
 //   g_SamplerDataHost      a SequenceSamplerData laid out over one pass's sequence tables (element * num_sequences + sequence, Kernel/Sampler_device.h:20-24),
 //                          rebound per pass; its members are private and its constructor allocates, so the object is laid out in raw storage in the member order of
@@ -46,6 +46,7 @@ void ref_light_of(const ctl_scene_desc* d, const ctl_light& L, Light& out);     
 void ref_bsdf_all_of(const ctl_material* mats, uint32_t idx, BSDFALL& out);            // ref_bsdf_driver.cpp
 Material ref_material_of(const ctl_material& M);                                       // ref_material_driver.cpp
 Image* ref_image_view(void* raw, size_t raw_size, void* pixels, int w, int h);         // ref_image_driver.cpp
+void ref_bind_volumes(const ctl_volume* v, uint32_t n);                                // ref_volume_driver.cpp
 
 namespace {
 struct sync_buffer_layout { void* vptr; int location; unsigned length; void* host; void* device; };
@@ -88,7 +89,7 @@ void bind_path_scene(const ctl_scene_desc* d, bool alpha) {
     S.m_sSceneBVH.m_pNodes = (BVHNodeData*)const_cast<ctl_bvh_node*>(d->scene_bvh_nodes);
     S.m_sSceneBVH.m_pNodeTransforms = (float4x4*)const_cast<ctl_float4x4*>(d->node_transforms);
     S.m_sSceneBVH.m_pInvNodeTransforms = (float4x4*)const_cast<ctl_float4x4*>(d->node_inv_transforms);
-    S.m_sVolume.m_uVolumeCount = 0;
+    ref_bind_volumes(d->volumes, d->n_volumes);   // m_sVolume: the scene's regions, built by the reference's own constructors (none: the count is 0)
     S.m_sBox = AABB(Vec3f(d->box_min[0], d->box_min[1], d->box_min[2]), Vec3f(d->box_max[0], d->box_max[1], d->box_max[2]));
     S.doAlphaMapping = alpha;
     S.m_rayTraceEps = d->ray_trace_eps;

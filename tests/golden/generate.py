@@ -972,8 +972,138 @@ def gen_pipeline(r):
     np.savez_compressed(os.path.join(HERE, "pipeline.npz"), **out)
 
 
+def gen_volumes(r):
+    """The participating-media functions run by the reference's own code (oracle/ref_volume_driver.cpp: SceneTypes/Volumes.cu and PhaseFunction.cu built whole) over the
+    sets and query rows of tests/volume_cases.py: per (function, set) of golden_pairs() the query rows (GOLDEN_ROWS seeded ones plus the branch points), the reference's
+    result rows in ctl_volume_eval's layout, and the mask of the rows that were sent.  A row in which sampleVolume would index past its table is never sent (the
+    reference reads whatever follows m_pVolumes there): decided from the restatement tests/volume_ref.py BEFORE the call, and kept under SENT_CAP per function and set —
+    on the set `four` every row is sent.  Per set also the digest of the volume table and Kajiya-Kay's m_normalization as the reference's constructor computes it."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import volume_cases as K
+    import volume_ref
+    from cudatracerlib_amd import api
+    r.ref_volume_eval.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]; r.ref_volume_eval.restype = C.c_int
+    r.ref_kajiya_kay_normalization.argtypes = [f32, f32, f32]; r.ref_kajiya_kay_normalization.restype = f32
+    orc = oracle.Oracle()
+    out = {}
+    sets = {}
+    for name in K.GOLDEN_SETS:
+        vols = K.make_set(name)
+        norm = np.array([r.ref_kajiya_kay_normalization(f32(v.phase.ks), f32(v.phase.kd), f32(v.phase.exponent)) if v.phase.type == api.PHASE_KAJIYA_KAY else 0.0 for v in vols], np.float32)
+        out[name + "_digest"] = np.array(K.table_digest(vols)); out[name + "_kk_normalization"] = norm
+        sets[name] = (vols, volume_ref.Volumes(orc, K.with_normalization(vols, norm)))
+    four_masks = set()
+    for what, name in K.golden_pairs():
+        vols, V = sets[name]
+        q = K.queries(name, vols, what, K.GOLDEN_ROWS)
+        sent, masks = K.sent_mask(V, what, q)
+        assert 1.0 - sent.mean() <= K.SENT_CAP, "%s on %s: %.1f %% of the rows are kept from the reference" % (K.FUNCTIONS[what], name, 100 * (1 - sent.mean()))
+        if name == "four":
+            assert sent.all(), "%s on four: the layout lets a ray's mask index past the table (masks %s)" % (K.FUNCTIONS[what], sorted(masks))
+            four_masks |= masks
+        d = api.volumes_desc(vols)
+        res = np.zeros((len(q), 17), np.float32)
+        assert r.ref_volume_eval(d.volumes, d.n_volumes, what, q.ctypes.data, len(q), sent.ctypes.data, res.ctypes.data) == 0, (what, name)
+        assert not res[sent == 0].any()
+        k = "%d_%s" % (what, name)
+        out[k + "_q"] = q; out[k + "_out"] = res; out[k + "_sent"] = sent
+    assert four_masks <= {0, 2, 3, 7, 11} and {2, 3, 7, 11} <= four_masks, sorted(four_masks)   # the masks volume_cases.py states for `four`
+    np.savez_compressed(os.path.join(HERE, "volumes.npz"), **out)
+    assert os.path.getsize(os.path.join(HERE, "volumes.npz")) < os.path.getsize(os.path.join(HERE, "pathtrace.npz"))
+
+
+MEDIA_PASSES, MEDIA_MAX_PATH_LENGTH, MEDIA_RR_START = 2, 6, 3
+# A case's passes use the table sets first, first + 1 of a fresh SequenceGenerator.  `first` is 0 unless some pixel of the case then takes an emission MIS weight with
+# PathTrace's uninitialised last_nor (a path that reaches the emitter, Direct on, after medium vertices only: Integrators/PathTracer.cu:21,71); then it is the first
+# window in which no pixel does — found with the restatement's counter (volume_ref.path_trace, undefined[..., 2]) and asserted again whenever the fixture is recorded.
+MEDIA_FIRST_PASS = {"half_box_direct": 1, "isotropic_direct": 2, "two_regions_direct": 1, "isotropic_50x33": 2}
+
+
+def pathtrace_media_cases():
+    """the media fixture's cases: (key, scene builder, width, height, DIRECT, first table set).  2 passes, MaxPathLength 6, RRStartDepth 3 (roulette runs after a medium vertex, with the
+    stale specularBounce).  The four media of tests/test_gpu_volume.py at 48 x 32 with Direct on and off; `two_regions`: the whole box isotropic plus its lower half
+    HG -0.5, built with CreateVolume on cornell_box — the masks 1 and 3 occur (both index region 1, as written) and p weights two phase functions; one 50 x 33 frame,
+    neither dimension a multiple of the wave or tile size; `clear_*`: the same scene without media, what the sanity test holds the media frames against."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from cudatracerlib_amd import api, scenes
+    from test_gpu_volume import MEDIA
+
+    def fog(name, w, h):
+        m = MEDIA[name]
+        return lambda: scenes.fog_box(w, h, sigma_a=m["sigma_a"], sigma_s=m["sigma_s"], phase=api.phase_hg(m["phase"][1]) if m["phase"] else None, fraction=m["fraction"])
+
+    def two_regions():
+        sc = scenes.cornell_box(48, 32)
+        lo = np.array(sc.desc.box_min, np.float32); hi = np.array(sc.desc.box_max, np.float32)
+        sc.CreateVolume(api.homogeneous_volume(api.box_to_volume_matrix(lo, hi), 0.0005, 0.002, api.phase_isotropic()))
+        sc.CreateVolume(api.homogeneous_volume(api.box_to_volume_matrix(lo, (lo + (hi - lo) * np.array([1, 0.5, 1], np.float32)).astype(np.float32)), 0.0004, (0.003, 0.002, 0.0012), api.phase_hg(-0.5)))
+        sc.UpdateScene()
+        return sc
+    cases = [("%s_%s" % (name, "direct" if direct else "nodirect"), fog(name, 48, 32), 48, 32, direct) for name in sorted(MEDIA) for direct in (True, False)]
+    cases += [("two_regions_direct", two_regions, 48, 32, True), ("isotropic_50x33", fog("isotropic", 50, 33), 50, 33, True)]
+    cases = [c + (MEDIA_FIRST_PASS.get(c[0], 0),) for c in cases]
+    clear = sorted({(clear_case_of(c), c[2], c[3], c[4], c[5]) for c in cases})
+    return cases + [(key, (lambda w=w, h=h: scenes.cornell_box(w, h)), w, h, direct, first) for key, w, h, direct, first in clear]
+
+
+def clear_case_of(case):
+    """the key of the case without media that a media case is held against: the same frame size, Direct setting and tables"""
+    return "clear_%dx%d_%s_%d" % (case[2], case[3], "direct" if case[4] else "nodirect", case[5])
+
+
+def pathtrace_media_tables(first):
+    """the sampler tables of a media case: table sets first .. first + MEDIA_PASSES - 1 of a fresh SequenceGenerator"""
+    return pathtrace_tables(first + MEDIA_PASSES)[first:]
+
+
+def pathtrace_media_digest(d, tables):
+    """pathtrace_input_digest plus the volume table"""
+    import hashlib
+    import volume_cases as K
+    return hashlib.sha256((pathtrace_input_digest(d, tables) + K.table_digest([d.volumes[i] for i in range(d.n_volumes)])).encode()).hexdigest()
+
+
+def media_volumes(d):
+    """the regions of a compiled scene as the glibc restatement takes them (no Kajiya-Kay among these cases: the derived fields are the product's)"""
+    return [d.volumes[i] for i in range(d.n_volumes)]
+
+
+def gen_pathtrace_media(r):
+    """PathTrace<DIRECT> with participating media run by the reference's own code (ref_pathtrace_render, the aggregate bound by oracle/ref_volume_driver.cpp) over the
+    cases of pathtrace_media_cases(): rgb sums, weightSum, rays per pixel, input digest.  Before a case goes to the reference the restatement
+    (volume_ref.path_trace, glibc oracle, the reference's rules) renders it and counts, per pixel, the places where the reference's behaviour is undefined — a read
+    of a medium record nothing has written, a sampleVolume index past the table, an emission MIS weight taken with PathTrace's uninitialised last_nor; a case is recorded only when all three counts are zero in EVERY pixel.  (A path whose throughput is exactly zero walks on in the
+    reference along a direction nothing has set: that changes no radiance, only the recorded ray counts of such pixels — tests/test_oracle_volume.py says how they are held.)"""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import volume_ref
+    r.ref_pathtrace_render.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    r.ref_pathtrace_render.restype = C.c_int
+    orc = oracle.Oracle()
+    out = {}
+    for key, make, w, h, direct, first in pathtrace_media_cases():
+        sc = make(); d = sc.desc
+        tables = pathtrace_media_tables(first)
+        t1 = np.ascontiguousarray(np.concatenate([t[0] for t in tables])); t2 = np.ascontiguousarray(np.concatenate([t[1] for t in tables]))
+        if d.n_volumes:
+            undefined = np.zeros((h, w, 6), np.int32)
+            volume_ref.path_trace(orc, d, media_volumes(d), w, h, tables, direct=direct, max_path_length=MEDIA_MAX_PATH_LENGTH, rr_start=MEDIA_RR_START, reference_rules=True, undefined=undefined)
+            assert not undefined[..., :3].any(), "%s: %d pixels reach undefined behaviour of the reference (unwritten record reads %d, indices past the table %d, unwritten last_nor reads %d): choose another case or window" % (
+                key, undefined[..., :3].any(axis=2).sum(), undefined[..., 0].sum(), undefined[..., 1].sum(), undefined[..., 2].sum())
+        px = np.zeros((h, w, 7), np.float32); rays = np.zeros((h, w), np.uint32)
+        assert r.ref_pathtrace_render(C.addressof(d), w, h, MEDIA_PASSES, t1.ctypes.data, t2.ctypes.data, int(direct), 0, MEDIA_MAX_PATH_LENGTH, MEDIA_RR_START, 0, px.ctypes.data, rays.ctypes.data) == 0, key
+        assert (px[..., 3:6] == 0).all() and rays.max() < 65536 and px[..., 6].sum() > 0.9 * w * h * MEDIA_PASSES and px[..., :3].mean() > 1e-3, key
+        out[key + "_rgb"] = np.ascontiguousarray(px[..., :3]); out[key + "_weight"] = np.ascontiguousarray(px[..., 6])
+        out[key + "_rays"] = rays.astype(np.uint16); out[key + "_digest"] = np.array(pathtrace_media_digest(d, tables))
+    np.savez_compressed(os.path.join(HERE, "pathtrace_media.npz"), **out)
+    assert os.path.getsize(os.path.join(HERE, "pathtrace_media.npz")) < os.path.getsize(os.path.join(HERE, "pathtrace.npz"))
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["pipeline"]:      # only this fixture
+    if sys.argv[1:] == ["volumes"]:         # only this fixture
+        gen_volumes(oracle.load_ref())
+    elif sys.argv[1:] == ["pathtrace_media"]:   # only this fixture
+        gen_pathtrace_media(oracle.load_ref())
+    elif sys.argv[1:] == ["pipeline"]:      # only this fixture
         gen_pipeline(oracle.load_ref())
     elif sys.argv[1:] == ["pathtrace"]:     # only this fixture (the others stay byte-identical)
         gen_pathtrace(oracle.load_ref())
@@ -1027,3 +1157,5 @@ if __name__ == "__main__":
         gen_primtracer(oracle.load_ref())
         gen_image(oracle.load_ref())
         gen_pipeline(oracle.load_ref())
+        gen_volumes(oracle.load_ref())
+        gen_pathtrace_media(oracle.load_ref())

@@ -1,6 +1,8 @@
 """Participating media on the device: ctl_volume_eval in a kernel against the host yardstick bit for bit; PathTracer frames of scenes.fog_box against the per-pixel
 restatement tests/volume_ref.path_trace (which tests/test_volume_host.py pins on the oracle's render and on the host yardstick); ctl_tracer_debug_pixel; in-place
-updates of the volume table; the plugins that refuse media."""
+updates of the volume table; the plugins that refuse media.
+The restatement itself is pinned on the reference's own Volumes.cu / PhaseFunction.cu / PathTrace by tests/test_oracle_volume.py (tests/golden/volumes.npz,
+pathtrace_media.npz), and tests/test_gpu_volume_golden.py holds the device to those fixtures directly."""
 import numpy as np
 import pytest
 

@@ -1,6 +1,7 @@
 """Participating media, the host half (no GPU): the restatement's surface half against the oracle's render; ctl_volume_eval(on_device = 0) — csrc/volume.h on the host —
 against the numpy restatement tests/volume_ref.py, every function, every row bit for bit; the restatement against closed forms in float64; builder, validator and
-diff.  The volume sets and the queries: volume_cases.py."""
+diff.  The volume sets and the queries: volume_cases.py.
+What pins the restatement itself on the reference's own code (and ctl_volume_eval on the reference's rows directly): tests/test_oracle_volume.py."""
 import ctypes as C
 
 import numpy as np

@@ -6,6 +6,9 @@ SETS:  one      one volume over the Cornell box (HG 0.7, coloured sigma_s)
        two      two overlapping volumes with different phase functions (Rayleigh; Kajiya-Kay under a rotation, whose WorldBound() is larger than the region)
        sixteen  a 4 x 4 grid of regions, all four phase functions, with the coefficient corner cases: sig_s = 0, sig_t = 0, one zero channel, a density whose
                 transmittance falls under 1e-8, g = 0 and |g| = 0.9
+       four     (GOLDEN_SETS only: the fixture recorded from the reference, tests/golden/volumes.npz) four regions laid out so that sampleVolume's index — ffsn's bit
+                MASK, as written — stays inside the table for every ray: region 0 the Cornell box, region 1 a box around every ray origin, regions 2 and 3 two small
+                cubes in opposite corners that no ray of the population crosses both.  The masks that occur are 2 (index 2), 3 (index 1), 7 and 11 (index 1 or 2)
 queries(set, volumes, what, n): n seeded rows plus the branch points of that function."""
 import numpy as np
 
@@ -15,6 +18,8 @@ f32 = np.float32
 BOX_LO = np.array([0.0, 0.0, 0.0], np.float32)
 BOX_HI = np.array([556.0, 548.8, 559.2], np.float32)
 SETS = ("one", "half", "two", "sixteen")
+GOLDEN_SETS = SETS + ("four",)
+GOLDEN_ROWS = 256   # seeded rows per function and set in tests/golden/volumes.npz (plus the branch points)
 FUNCTIONS = {api.VEVAL_REGION_INTERSECT: "region IntersectP", api.VEVAL_INTERSECT: "aggregate IntersectP", api.VEVAL_REGION_TAU: "region tau", api.VEVAL_TAU: "aggregate tau",
              api.VEVAL_REGION_SAMPLE_DISTANCE: "region sampleDistance", api.VEVAL_SAMPLE_DISTANCE: "aggregate sampleDistance", api.VEVAL_SAMPLE_VOLUME: "sampleVolume",
              api.VEVAL_PHASE_EVAL: "phase Evaluate", api.VEVAL_PHASE_SAMPLE: "phase Sample", api.VEVAL_P: "aggregate p", api.VEVAL_SAMPLE: "aggregate Sample",
@@ -47,6 +52,11 @@ def make_set(name):
             sa, ss = coeff[k % len(coeff)]
             out.append(api.homogeneous_volume(box(lo, hi), sa, ss, phases[(k * 5 + 1) % len(phases)]))
         return out
+    if name == "four":
+        return [api.homogeneous_volume(box(BOX_LO, BOX_HI), 0.0005, 0.002, api.phase_isotropic()),
+                api.homogeneous_volume(box((-400, -400, -400), (1000, 1000, 1000)), (0.0002, 0.0004, 0.0001), (0.0006, 0.001, 0.0015), api.phase_hg(0.5)),
+                api.homogeneous_volume(box((0, 0, 0), (160, 160, 160)), 0.001, (0.004, 0.002, 0.001), api.phase_rayleigh()),
+                api.homogeneous_volume(box((396, 388.8, 0), (556, 548.8, 160)), 0.0005, 0.003, api.phase_kajiya_kay(0.4, 0.2, 4.0))]
     raise ValueError(name)
 
 
@@ -74,7 +84,7 @@ def _sampling_weight(v):
 
 
 def queries(set_name, volumes, what, n):
-    rs = np.random.RandomState(1000 + 17 * what + SETS.index(set_name))
+    rs = np.random.RandomState(1000 + 17 * what + GOLDEN_SETS.index(set_name))
     nv = len(volumes)
     o = rs.uniform(-300, 900, (n, 3)).astype(np.float32)
     inside = rs.rand(n) < 0.5
@@ -150,3 +160,48 @@ def same_rows(got, want):
     gn, wn = np.isnan(got), np.isnan(want)
     ok = (gn & wn) | (~gn & ~wn & (got.view(np.uint32) == want.view(np.uint32)))
     return [int(i) for i in np.nonzero(~ok.all(axis=1))[0]]
+
+
+# ---------------------------------------------------------------------------------------------------------------- the fixture recorded from the reference
+RULE_ONE = (api.VEVAL_SAMPLE_DISTANCE, api.VEVAL_SAMPLE_VOLUME, api.VEVAL_SAMPLE)   # the functions that go through sampleVolume
+SENT_CAP = 0.25   # at most this share of a function's rows on one set may be kept from the reference
+
+
+def golden_pairs():
+    """(function, set) pairs of tests/golden/volumes.npz: every function on every set, except the three functions that go through sampleVolume on `sixteen`, where the
+    mask-as-index reads past the table in most rows (the set `four` stands in for it there)"""
+    return [(what, name) for what in sorted(FUNCTIONS) for name in GOLDEN_SETS if not (name == "sixteen" and what in RULE_ONE)]
+
+
+def sent_mask(V, what, q):
+    """which query rows may be sent to the reference (1) — decided from the restatement V (volume_ref.Volumes) alone: a row in which sampleVolume forms an index past
+    the table (the reference reads past m_pVolumes there; the product answers 'no region') is not sent.  Also returns the set of region masks that occurred."""
+    sent = np.ones(len(q), np.uint8); masks = set()
+    if what in RULE_ONE:
+        for i, a in enumerate(np.asarray(q, np.float32).reshape(-1, 10)):
+            if what == api.VEVAL_SAMPLE:
+                raw = V.sample_volume_raw(a[0:3], a[3:6], f32(0), f32(3.402823466e+38), a[6])
+            else:
+                raw = V.sample_volume_raw(a[0:3], a[3:6], a[6], a[7], a[8])
+            sent[i] = raw[0] < V.n; masks.add(int(raw[3]))
+    return sent, masks
+
+
+def table_digest(volumes):
+    """sha256 over the ctl_volume array of a set, derived fields included"""
+    import ctypes
+    import hashlib
+    return hashlib.sha256(b"".join(ctypes.string_at(ctypes.addressof(v), ctypes.sizeof(v)) for v in volumes)).hexdigest()
+
+
+def with_normalization(volumes, values):
+    """copies of the regions with Kajiya-Kay's m_normalization replaced by the given values (one per region; ignored for the other phase functions): the reference
+    computes its own with glibc (tests/golden/volumes.npz records it), the product with the shared functions"""
+    import ctypes
+    out = []
+    for v, n in zip(volumes, values):
+        c = api.ctl_volume(); ctypes.memmove(ctypes.addressof(c), ctypes.addressof(v), ctypes.sizeof(c))
+        if c.phase.type == api.PHASE_KAJIYA_KAY:
+            c.phase.normalization = float(n)
+        out.append(c)
+    return out

@@ -8,8 +8,11 @@ Volumes(orc, list of ctl_volume) offers every function ctl_volume_eval offers; e
 path_trace(orc, desc, w, h, tables, ...) is pathKernel2 + PathTrace<DIRECT> (Integrators/PathTracer.cu:10-113, 182-194) with media, per pixel, from the oracle's exports
 (sampler draws, sensor rays, traversal of the product's flattened tree, fillDG, BSDF sample / eval, emitter sampling, light pdf / eval, environment), in the manner of
 prim_tracer_ref.shaded_modes.  Its scenes hold diffuse, dielectric and conductor materials with constant textures, so first-hit partials change nothing.
-Two things are the product's, not the reference's, and are stated where they stand: a path ends when its throughput is exactly zero (every kernel of the library makes
-that cut), and a medium record nothing has written yet reads as zeros (the reference reads uninitialised memory).
+Three things are the product's, not the reference's, and are stated where they stand: a path ends when its throughput is exactly zero (every kernel of the library makes
+that cut), and a medium record or a last_nor nothing has written yet reads as zeros (the reference reads uninitialised memory).
+With the glibc oracle (oracle.Oracle()) instead of the shared-math one, and path_trace's reference_rules, this file is held to the reference's OWN Volumes.cu,
+PhaseFunction.cu and PathTrace bit for bit (tests/test_oracle_volume.py over tests/golden/volumes.npz and pathtrace_media.npz); path_trace counts, per pixel, the places
+where the reference reads what nothing wrote, so that no such case is ever recorded from it.
 """
 import ctypes as C
 import struct
@@ -157,7 +160,7 @@ def _max3(s):
 
 
 def zero_rec():
-    return dict(t=f32(0), p=v3(0), transmittance=v3(0), sigmaA=v3(0), sigmaS=v3(0), pdfSuccess=f32(0), pdfSuccessRev=f32(0), pdfFailure=f32(0))
+    return dict(t=f32(0), p=v3(0), transmittance=v3(0), sigmaA=v3(0), sigmaS=v3(0), pdfSuccess=f32(0), pdfSuccessRev=f32(0), pdfFailure=f32(0), written=False)
 
 
 class Volumes:
@@ -171,6 +174,7 @@ class Volumes:
                                sig_a=np.array(list(V.sig_a), np.float32), sig_s=np.array(list(V.sig_s), np.float32), type=int(V.phase.type), g=f32(V.phase.g),
                                ks=f32(V.phase.ks), kd=f32(V.phase.kd), exponent=f32(V.phase.exponent), normalization=f32(V.phase.normalization)))
         self.n = len(self.v)
+        self.past_table = 0   # (bookkeeping) how often sample_volume formed an index >= n, where the reference reads past its table
         for V in self.v:
             V["bound"] = self.world_bound(V)   # a function of the region alone: made once
 
@@ -243,6 +247,7 @@ class Volumes:
             pdfFailure = _avg(tmp)
             pdfSuccess = _avg((sig_t * tmp).astype(np.float32))
             mRec["transmittance"] = m.exp3((sig_t * f32(-sampled)).astype(np.float32))
+            mRec["written"] = True   # (bookkeeping: the record's probabilities and transmittance hold values of some sampleDistance from here on)
             mRec["pdfSuccess"] = mRec["pdfSuccessRev"] = f32(pdfSuccess * weight)
             mRec["pdfFailure"] = f32(f32(weight * pdfFailure) + f32(f32(1) - weight))
             if _max3(mRec["transmittance"]) < f32(1e-8):
@@ -273,25 +278,34 @@ class Volumes:
     def sample_volume(self, o, d, minT, maxT, sample):
         """KernelAggregateVolume::sampleVolume -> (index or -1, sample, pdf).  As written: with several regions the 0-based slot of sampleReuse goes into the 1-based
         ffsn, and ffsn's mask is used as the index; an index past the table is 'none' here (the reference reads past its array)"""
+        i, sample, pdf, _ = self.sample_volume_raw(o, d, minT, maxT, sample)
+        if i >= self.n:
+            self.past_table += 1
+        return (i if 0 <= i < self.n else -1), sample, pdf
+
+    def sample_volume_raw(self, o, d, minT, maxT, sample):
+        """sampleVolume before the table's bound is applied -> (the index the reference forms, or -1 where it returns no region; sample; pdf; the mask of the regions
+        whose WorldBound() the segment meets, 0 with fewer than two regions).  An index >= n is where the reference reads past m_pVolumes: the fixtures of
+        tests/golden never send such a row to it (tests/golden/generate.py)"""
         sample = f32(sample); pdf = f32(0)
         if self.n == 0:
-            return -1, sample, pdf
+            return -1, sample, pdf, 0
         with np.errstate(**_ERR):
             if self.n == 1:
                 lo, hi = self.v[0]["bound"]
-                return (0 if aabb_intersect(lo, hi, o, d, f32(minT), f32(maxT))[0] else -1), sample, pdf
+                return (0 if aabb_intersect(lo, hi, o, d, f32(minT), f32(maxT))[0] else -1), sample, pdf, 0
             n = 0; flag = 0
             for i, V in enumerate(self.v):
                 lo, hi = V["bound"]
                 if aabb_intersect(lo, hi, o, d, f32(minT), f32(maxT))[0]:
                     n += 1; flag |= 1 << i
             if not n:
-                return -1, sample, pdf
+                return -1, sample, pdf, 0
             nth = int(f32(sample * f32(n)))
             sample = f32(f32(sample * f32(n)) - f32(nth))
             i = self.ffsn(flag, nth)
             pdf = f32(f32(1.0) / f32(n))
-        return (i if 0 <= i < self.n else -1), sample, pdf
+        return i, sample, pdf, flag
 
     def sample_distance(self, o, d, minT, maxT, sample, mRec):
         vi, sample, _ = self.sample_volume(o, d, minT, maxT, sample)
@@ -396,6 +410,15 @@ class Volumes:
             return self.m.exp3((-self.tau(p1, d, f32(0), l)).astype(np.float32))
 
 
+def kajiya_kay_normalization(m, exponent):
+    """KajiyaKayPhaseFunction::Update (PhaseFunction.cu:78-93): the 999-term Simpson sum in fp32; m: a Math"""
+    step = f32(PI / f32(1000)); mm = f32(4); theta = step; acc = f32(0)
+    for _ in range(1, 1000):
+        value = f32(m.pow(m.cos(f32(theta - f32(PI / f32(2)))), f32(exponent)) * m.sin(theta))
+        acc = f32(acc + f32(value * mm)); theta = f32(theta + step); mm = f32(f32(6) - mm)
+    return f32(f32(1) / f32(f32(f32(f32(acc * step) / f32(3)) * f32(2)) * PI))
+
+
 def _word(x):
     return struct.unpack("<I", struct.pack("<f", float(x)))[0]
 
@@ -489,10 +512,14 @@ class _Path:
         cdf = [f32(desc.light_cdf[i]) for i in range(desc.num_lights)]
         self.pdf_emitter = {int(desc.light_indices[i]): f32(cdf[i] - (cdf[i - 1] if i else f32(0))) for i in range(desc.num_lights)}
         self.rays = 0
+        self.half_host_quirk = False
+        self.unwritten_reads = 0; self.unwritten_normal_reads = 0; self.unset_directions = 0; self.zero_walks = 0; self.zero_rays = 0; self.zero_now = False
 
     def trace(self, o, d, tmax=FLT_MAX, any_hit=False):
         r = np.zeros((1, 8), np.float32); r[0, :3] = o; r[0, 3] = self.eps; r[0, 4:7] = d; r[0, 7] = tmax
         self.rays += 1
+        if self.zero_now:
+            self.zero_rays += 1
         return self.orc.intersect(self.desc, r, any_hit=any_hit, alpha_test=True, threads=1, flat=self.flat)[0]
 
     def surface(self, o, d, hd):
@@ -501,7 +528,7 @@ class _Path:
         tri, node = int(hd["tri_idx"]), int(hd["node_idx"])
         t, u, v = f32(hd["dist"]), f32(hd["u"]), f32(hd["v"])
         T = np.ascontiguousarray(self.tri_data[tri]); M = np.ascontiguousarray(self.xforms[node])
-        self.lib.orc_triangle_fill_dg(T.ctypes.data, M.ctypes.data, float(u), float(v), 0, dg.ctypes.data)
+        self.lib.orc_triangle_fill_dg(T.ctypes.data, M.ctypes.data, float(u), float(v), 1 if self.half_host_quirk else 0, dg.ctypes.data)
         P = np.array([f32(o[k] + f32(t * d[k])) for k in range(3)], np.float32)
         s_, t_, sn, gn = dg[0:3].copy(), dg[3:6].copy(), dg[6:9].copy(), dg[9:12].copy()
         md = (-np.asarray(d, np.float32)).astype(np.float32)
@@ -515,14 +542,25 @@ class _Path:
         return dict(t=t, n=gn, uv=dg[18:20].copy(), wi=wi, P=P, s=s_, tt=t_, sn=sn.astype(np.float32), mat=mat, node=node)
 
 
-def path_trace(orc, desc, volumes, w, h, tables, direct=True, max_path_length=6, rr_start=5, flat=None, debug_pixels=None, ray_count=None):
+def path_trace(orc, desc, volumes, w, h, tables, direct=True, max_path_length=6, rr_start=5, flat=None, debug_pixels=None, ray_count=None, reference_rules=False,
+               undefined=None, pixel_rays=None):
     """pathKernel2<DIRECT> over every pixel and every pass of `tables` -> pixel data (h, w, 7): rgb, splat (0), weightSum, as Image::AddSample accumulates them.
     volumes: the list of ctl_volume of the scene (empty: no media — then this is the oracle's render).  flat: the product's flattened tree (FlatBvh(...).desc), so that a
     ray grazing a shared edge resolves as on the device.  debug_pixels = [(x, y), ...]: instead PathTracer::DebugInternal for those pixels — Direct on, no jitter, the first
-    table set — returning their radiances (n, 3).  ray_count: a list that receives the number of rays traced."""
+    table set — returning their radiances (n, 3).  ray_count: a list that receives the number of rays traced.
+    reference_rules: the two places where this restatement follows the product and not the reference as compiled for the host are switched to the reference's: a path
+    whose throughput is exactly zero walks on (PathTrace has no such cut), and fillDG decodes the triangles' normals with the host branch of half::ToFloat
+    (half_host_quirk, as tests/test_oracle_pathtrace.py).  undefined: an int32 array (h, w, 6), added to — per pixel the places where the reference's PathTrace reads
+    what nothing has written (DESIGN.md, media): [..., 0] reads of a medium record that no sampleDistance had written; [..., 1] sampleVolume indices past the table;
+    [..., 2] emission MIS weights taken with a last_nor no surface had set (the path's only vertices so far were medium vertices); [..., 3] medium vertices at which
+    Sample found no region, so that the reference walks on — with a throughput of exactly zero — along a pRec.wo nothing has set; [..., 4] samples whose throughput
+    became exactly zero anywhere (after a failed BSDF sample the reference walks on along the record's previous wo); [..., 5] the rays traced after that point.
+    Channels 0 to 2 can change the radiance; 3 to 5 only the number of rays (whatever such a path meets is multiplied by zero).
+    pixel_rays: a uint32 array (h, w), added to: the rays each pixel traced."""
     from prim_tracer_ref import _dot
     lib = orc.lib
     ctx = _Path(orc, desc, volumes, flat)
+    ctx.half_host_quirk = reference_rules
     V = ctx.V
     img = np.zeros((h, w, 7), np.float32)
     o3 = np.zeros(3, np.float32); d3 = np.zeros(3, np.float32); dX = np.zeros(3, np.float32); dY = np.zeros(3, np.float32)
@@ -532,6 +570,7 @@ def path_trace(orc, desc, volumes, w, h, tables, direct=True, max_path_length=6,
     def one_path(t1, t2, x, y):
         idx = y * w + x
         k1 = [0]; k2 = [0]
+        ctx.zero_now = False
 
         def draw1():
             r = f32(lib.orc_sampler_float(t1.ctypes.data, t2.ctypes.data, idx, k1[0])); k1[0] += 1
@@ -548,7 +587,7 @@ def path_trace(orc, desc, volumes, w, h, tables, direct=True, max_path_length=6,
         ro, rd = o3.copy(), d3.copy()
         cl, cf = v3(0), v3(1)
         depth = 0; specular = False; had_hit = False
-        bsdf_pdf = f32(0); last_nor = v3(0)
+        bsdf_pdf = f32(0); last_nor = v3(0); nor_written = False; zero_seen = False   # (the reference's last_nor is uninitialised)
         mRec = zero_rec()   # (the reference's is uninitialised)
         is_direct = True if debug else direct
         while depth < max_path_length:
@@ -577,10 +616,14 @@ def path_trace(orc, desc, volumes, w, h, tables, direct=True, max_path_length=6,
                                     weight = _power_heuristic(dpdf, p)
                                     cl = _add(cl, _mul(_mul(_mul(cf, value), p), weight))
                     wgt, _, wo = V.sample(mRec["p"], (-rd).astype(np.float32), draw2())
+                    if wgt == 0 and not wo.any():
+                        ctx.unset_directions += 1   # no region found: the reference walks on along pRec.wo, which nothing has set
                     cf = _mul(cf, wgt)
                     rd = wo; ro = mRec["p"].copy()
             if not interaction and had_hit:
                 if in_medium:
+                    if not mRec["written"]:
+                        ctx.unwritten_reads += 1
                     cf = _mul(cf, _sdiv(mRec["transmittance"], mRec["pdfFailure"]))
                 rec = ctx.surface(ro, rd, hd)
                 mat = rec["mat"]
@@ -588,6 +631,8 @@ def path_trace(orc, desc, volumes, w, h, tables, direct=True, max_path_length=6,
                     light = int(ctx.nodes[rec["node"], 3 if mat.node_light_index == 0 else 4])
                     mis = f32(1)
                     if not (not is_direct or depth == 1 or specular):
+                        if not nor_written:
+                            ctx.unwritten_normal_reads += 1
                         a0 = np.ascontiguousarray(ro); a1 = np.ascontiguousarray(last_nor); a2 = np.ascontiguousarray(rd); a3 = np.ascontiguousarray(rec["n"])
                         dpdf = f32(lib.orc_light_pdf_direct(C.addressof(desc), light, a0.ctypes.data, a1.ctypes.data, a2.ctypes.data, float(rec["t"]), a3.ctypes.data))
                         mis = _power_heuristic(bsdf_pdf, f32(dpdf * ctx.pdf_emitter.get(light, f32(0))))
@@ -597,7 +642,7 @@ def path_trace(orc, desc, volumes, w, h, tables, direct=True, max_path_length=6,
                 so = np.zeros(9, np.float32); wi = np.ascontiguousarray(rec["wi"]); s2 = draw2()
                 lib.orc_bsdf_sample_uv(C.byref(mat), wi.ctypes.data, float(s2[0]), float(s2[1]), float(rec["uv"][0]), float(rec["uv"][1]), so.ctypes.data)
                 f, bsdf_pdf, wo_l, sampled = so[0:3].copy(), f32(so[3]), so[4:7].copy(), int(so[7])
-                last_nor = rec["sn"].copy()
+                last_nor = rec["sn"].copy(); nor_written = True
                 if is_direct and (mat.combined_type & E_SMOOTH):
                     est = v3(0)
                     if desc.num_lights:   # UniformSampleOneLight + EstimateDirect(attenuated = true)
@@ -632,7 +677,10 @@ def path_trace(orc, desc, volumes, w, h, tables, direct=True, max_path_length=6,
             if not interaction and not had_hit:
                 break
             if (cf == 0).all():   # the library's cut: a path whose throughput is exactly zero ends (the reference walks on and adds zeros)
-                break
+                if not reference_rules:
+                    break
+                if not zero_seen:
+                    ctx.zero_walks += 1; zero_seen = ctx.zero_now = True
             if depth > rr_start and not specular:
                 q = _max3(cf)
                 if draw1() >= q:
@@ -655,7 +703,14 @@ def path_trace(orc, desc, volumes, w, h, tables, direct=True, max_path_length=6,
         t1 = np.ascontiguousarray(t1, np.float32); t2 = np.ascontiguousarray(t2, np.float32)
         for y in range(h):
             for x in range(w):
+                before = (ctx.rays, ctx.unwritten_reads, V.past_table, ctx.unwritten_normal_reads, ctx.unset_directions, ctx.zero_walks, ctx.zero_rays)
                 px, py, L = one_path(t1, t2, x, y)
+                if pixel_rays is not None:
+                    pixel_rays[y, x] += ctx.rays - before[0]
+                if undefined is not None:
+                    undefined[y, x, 0] += ctx.unwritten_reads - before[1]; undefined[y, x, 1] += V.past_table - before[2]
+                    undefined[y, x, 2] += ctx.unwritten_normal_reads - before[3]; undefined[y, x, 3] += ctx.unset_directions - before[4]
+                    undefined[y, x, 4] += ctx.zero_walks - before[5]; undefined[y, x, 5] += ctx.zero_rays - before[6]
                 with np.errstate(**_ERR):
                     L = np.array([fmax(f32(0), L[0]), fmax(f32(0), L[1]), fmax(f32(0), L[2])], np.float32)   # clampNegative: (0 > s) ? 0 : s keeps a NaN
                 ix, iy = int(np.floor(px)), int(np.floor(py))
