@@ -90,7 +90,8 @@ class ctl_tracer_stats(C.Structure):
 
 
 PHASE_HG, PHASE_ISOTROPIC, PHASE_KAJIYA_KAY, PHASE_RAYLEIGH = 1, 2, 3, 4   # CTL_PHASE_*
-VOLUME_HOMOGENEOUS = 1
+VOLUME_HOMOGENEOUS, VOLUME_GRID = 1, 2
+MAX_GRID_CELLS = 1 << 22   # CTL_MAX_GRID_CELLS
 PARSE_EXTERIOR_MEDIA, PARSE_INTERIOR_MEDIA = 1, 2   # CTL_PARSE_*
 MAX_VOL_COUNT = 16
 
@@ -104,6 +105,12 @@ class ctl_volume(C.Structure):
                 ("sig_a", f32 * 3), ("sig_s", f32 * 3), ("le", f32 * 3)]
 
 
+class ctl_volume_grid(C.Structure):
+    _fields_ = [("volume", u32), ("single_grid", u32), ("dim", u32 * 3), ("dim_a", u32 * 3), ("dim_s", u32 * 3),
+                ("sig_a_min", f32 * 3), ("sig_a_max", f32 * 3), ("sig_s_min", f32 * 3), ("sig_s_max", f32 * 3), ("le_min", f32 * 3), ("le_max", f32 * 3),
+                ("data", C.POINTER(f32)), ("data_a", C.POINTER(f32)), ("data_s", C.POINTER(f32))]
+
+
 class ctl_scene_desc(C.Structure):
     _fields_ = [("tri_data", C.c_void_p), ("n_tri_data", u32), ("woop", C.c_void_p), ("n_woop", u32), ("woop_index", C.c_void_p),
                 ("bvh_nodes", C.c_void_p), ("n_bvh_nodes", u32), ("meshes", C.c_void_p), ("n_meshes", u32), ("nodes", C.c_void_p), ("n_nodes", u32),
@@ -113,7 +120,7 @@ class ctl_scene_desc(C.Structure):
                 ("box_min", f32 * 3), ("box_max", f32 * 3), ("camera", ctl_sensor), ("num_lights", u32),
                 ("light_indices", u32 * MAX_NUM_LIGHTS), ("light_cdf", f32 * MAX_NUM_LIGHTS), ("ray_trace_eps", f32),
                 ("images", C.POINTER(ctl_mipmap)), ("n_images", u32), ("rough_transmittance", C.POINTER(ctl_rough_transmittance)),
-                ("volumes", C.POINTER(ctl_volume)), ("n_volumes", u32)]
+                ("volumes", C.POINTER(ctl_volume)), ("n_volumes", u32), ("volume_grids", C.POINTER(ctl_volume_grid)), ("n_volume_grids", u32)]
 
     # numpy views of the reference-layout arrays (host memory owned by the builder)
     def view(self, name, dtype, count, width):
@@ -124,7 +131,7 @@ class ctl_scene_desc(C.Structure):
         return np.frombuffer(buf, dtype=dtype).reshape(count, width)
 
 
-assert C.sizeof(ctl_volume) == 192 and C.sizeof(ctl_phase_function) == 24
+assert C.sizeof(ctl_volume) == 192 and C.sizeof(ctl_phase_function) == 24 and C.sizeof(ctl_volume_grid) == 144
 assert C.sizeof(ctl_texture) == 48 and C.sizeof(ctl_material) == 384 and C.sizeof(ctl_pixel_data) == 28 and C.sizeof(ctl_hit) == 20
 
 lib.ctl_last_error.restype = C.c_char_p
@@ -163,6 +170,9 @@ lib.ctl_builder_set_camera_lookat.argtypes = [C.c_void_p, C.POINTER(f32), C.POIN
 lib.ctl_volume_update.argtypes = [C.POINTER(ctl_volume)]
 lib.ctl_builder_create_volume.argtypes = [C.c_void_p, C.POINTER(ctl_volume), C.POINTER(u32)]
 lib.ctl_builder_set_volume.argtypes = [C.c_void_p, u32, C.POINTER(ctl_volume)]
+lib.ctl_builder_create_volume_grid.argtypes = [C.c_void_p, C.POINTER(u32), u32, C.POINTER(ctl_float4x4), C.POINTER(ctl_phase_function), C.POINTER(u32)]
+lib.ctl_builder_set_volume_grid_data.argtypes = [C.c_void_p, u32, u32, C.c_void_p, u32]
+lib.ctl_builder_set_volume_grid_coefficients.argtypes = [C.c_void_p, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 lib.ctl_volume_eval.argtypes = [C.c_void_p, i32, C.c_void_p, u32, C.c_void_p, i32]
 
 
@@ -603,6 +613,44 @@ def homogeneous_volume(volume_to_world, sigma_a, sigma_s, phase=None, le=0.0):
     return volume_update(v)
 
 
+class GridVolume:
+    """a VolumeGrid region for a description: .volume (ctl_volume, type VOLUME_GRID, coefficients 0) and .grid (ctl_volume_grid without its volume index, which
+    volumes_desc sets); the float arrays the record points at are kept alive by this object"""
+
+    def __init__(self, volume, grid, arrays):
+        self.volume, self.grid, self._arrays = volume, grid, arrays
+
+
+def grid_volume(volume_to_world, density=None, density_a=None, density_s=None, sig_a=(0.0, 1.0), sig_s=(0.0, 1.0), phase=None):
+    """VolumeGrid(func, ToWorld, buffer, dim[, dimS, dimL]) with its data: `density` (an array of shape dim = (dim[0], dim[1], dim[2])) is the single-grid form,
+    density_a / density_s the three-grid form (gridL is not carried).  An array's shape is the grid's dim (x, y, z) and its flattened floats are the grid's floats in
+    the reference's linear order (DenseVolGrid::idx, include/ctl_amd.h).  sig_a / sig_s: (min, max), each a scalar or rgb; a coefficient at a point is
+    min + (max - min) * density.  Returns a GridVolume."""
+    v = ctl_volume(); v.type = VOLUME_GRID
+    v.phase = phase if phase is not None else phase_isotropic()
+    v.volume_to_world.m[:] = [float(x) for x in np.asarray(volume_to_world, np.float32).reshape(16)]
+    volume_update(v)
+    g = ctl_volume_grid(); arrays = []
+
+    def put(a, dim_field, ptr_field):
+        a = np.asarray(a, np.float32)
+        if a.ndim != 3:
+            raise ValueError("grid_volume: a density grid is a 3-D array")
+        flat = np.ascontiguousarray(a.reshape(-1)); arrays.append(flat)
+        getattr(g, dim_field)[:] = [int(x) for x in a.shape]
+        setattr(g, ptr_field, flat.ctypes.data_as(C.POINTER(f32)))
+    if density is not None:
+        if density_a is not None or density_s is not None:
+            raise ValueError("grid_volume: density, or density_a and density_s")
+        g.single_grid = 1; put(density, "dim", "data")
+    else:
+        if density_a is None or density_s is None:
+            raise ValueError("grid_volume: density, or density_a and density_s")
+        g.single_grid = 0; put(density_a, "dim_a", "data_a"); put(density_s, "dim_s", "data_s")
+    g.sig_a_min, g.sig_a_max, g.sig_s_min, g.sig_s_max = _rgb3(sig_a[0]), _rgb3(sig_a[1]), _rgb3(sig_s[0]), _rgb3(sig_s[1])
+    return GridVolume(v, g, arrays)
+
+
 def volume_update(v):
     """ctl_volume_update: world_to_volume and the Kajiya-Kay normalisation from the primary fields (host only); returns v"""
     _check(lib.ctl_volume_update(C.byref(v)))
@@ -621,16 +669,32 @@ def box_to_volume_matrix(box_min, box_max):
 
 VEVAL_QUERY_FLOATS, VEVAL_RESULT_FLOATS = 10, 17
 (VEVAL_REGION_INTERSECT, VEVAL_INTERSECT, VEVAL_REGION_TAU, VEVAL_TAU, VEVAL_REGION_SAMPLE_DISTANCE, VEVAL_SAMPLE_DISTANCE, VEVAL_SAMPLE_VOLUME, VEVAL_PHASE_EVAL,
- VEVAL_PHASE_SAMPLE, VEVAL_P, VEVAL_SAMPLE, VEVAL_TRANSMITTANCE, VEVAL_EVAL_TRANSMITTANCE) = range(13)   # CTL_VEVAL_*
+ VEVAL_PHASE_SAMPLE, VEVAL_P, VEVAL_SAMPLE, VEVAL_TRANSMITTANCE, VEVAL_EVAL_TRANSMITTANCE, VEVAL_GRID_VALUE, VEVAL_REGION_SIGMA, VEVAL_GRID_MARCH) = range(16)   # CTL_VEVAL_*
 
 
-def volumes_desc(volumes):
-    """a description that holds nothing but `volumes` (a list of ctl_volume): what volume_eval reads.  The array is kept alive by the returned object"""
-    d = ctl_scene_desc()
-    arr = (ctl_volume * max(1, len(volumes)))(*volumes)
-    d.volumes = C.cast(arr, C.POINTER(ctl_volume)); d.n_volumes = len(volumes)
-    d._keep = arr
+def set_desc_volumes(d, volumes, grids=None):
+    """point the description `d` at `volumes` — a list of ctl_volume and / or GridVolume (api.grid_volume), whose grid records follow in the volumes' order — and at
+    `grids`, further ctl_volume_grid records with their `volume` index set.  The arrays are kept alive by `d`; returns d"""
+    vols, recs, keep = [], [], []
+    for i, v in enumerate(volumes):
+        if isinstance(v, GridVolume):
+            g = ctl_volume_grid(); C.memmove(C.addressof(g), C.addressof(v.grid), C.sizeof(g)); g.volume = i
+            vols.append(v.volume); recs.append(g); keep.append(v)
+        else:
+            vols.append(v)
+    recs += list(grids or ())
+    arr = (ctl_volume * max(1, len(vols)))(*vols)
+    garr = (ctl_volume_grid * max(1, len(recs)))(*recs)
+    d.volumes = C.cast(arr, C.POINTER(ctl_volume)) if vols else None; d.n_volumes = len(vols)
+    d.volume_grids = C.cast(garr, C.POINTER(ctl_volume_grid)) if recs else None; d.n_volume_grids = len(recs)
+    d._keep = (arr, garr, keep, grids)
     return d
+
+
+def volumes_desc(volumes, grids=None):
+    """a description that holds nothing but `volumes` (a list of ctl_volume and / or GridVolume) and their grid records: what volume_eval reads (set_desc_volumes).
+    The arrays are kept alive by the returned object"""
+    return set_desc_volumes(ctl_scene_desc(), volumes, grids)
 
 
 def volume_eval(desc, what, queries, on_device=False):
@@ -774,12 +838,49 @@ class DynamicScene:
             m = ctl_float4x4(); m.m[:] = [float(x) for x in np.asarray(to_world, np.float32).reshape(16)]
         _check(lib.ctl_builder_set_environment_map(self._h, u32(image), (f32 * 3)(*scale), C.byref(m) if m is not None else None))
 
-    def CreateVolume(self, volume):
+    def CreateVolume(self, volume, *dims, volume_to_world=None, phase=None):
         """DynamicScene::CreateVolume(VolumeRegion) (DynamicScene.cpp:787-792): a ctl_volume (homogeneous_volume(...)), at most MAX_VOL_COUNT; returns its index.
-        UpdateScene() then hands the media out in desc.volumes; only the PathTracer plugin renders them."""
+        UpdateScene() then hands the media out in desc.volumes; only the PathTracer plugin renders them.
+        CreateVolume(w, h, d, volume_to_world=, phase=) and the nine-int form are DynamicScene::CreateVolume's grid overloads (:794-812, CreateVolumeGrid below);
+        CreateVolume(GridVolume) creates a grid with its data (CreateGridVolume)."""
+        if dims:
+            return self.CreateVolumeGrid(volume, *dims, volume_to_world=volume_to_world, phase=phase)
+        if isinstance(volume, GridVolume):
+            return self.CreateGridVolume(volume)
         idx = u32()
         _check(lib.ctl_builder_create_volume(self._h, C.byref(volume), C.byref(idx)))
         return idx.value
+
+    def CreateVolumeGrid(self, *dims, volume_to_world=None, phase=None):
+        """DynamicScene::CreateVolume(w, h, d, toWorld, phase) / (wA, hA, dA, wS, hS, dS, wL, hL, dL, toWorld, phase) (DynamicScene.cpp:794-812): a VolumeGrid whose
+        grids and coefficients are 0 until SetVolumeGridData / SetVolumeGridCoefficients; the L dims are accepted and ignored.  Returns the volume's index."""
+        if len(dims) not in (3, 9):
+            raise ValueError("CreateVolumeGrid: 3 or 9 dims")
+        m = ctl_float4x4(); m.m[:] = [float(x) for x in np.asarray(np.eye(4) if volume_to_world is None else volume_to_world, np.float32).reshape(16)]
+        p = phase if phase is not None else phase_isotropic()
+        idx = u32(0)
+        _check(lib.ctl_builder_create_volume_grid(self._h, (u32 * len(dims))(*[int(x) for x in dims]), u32(len(dims)), C.byref(m), C.byref(p), C.byref(idx)))
+        return idx.value
+
+    def SetVolumeGridData(self, index, data, which=0):
+        """copy `data` (dim[0] * dim[1] * dim[2] floats, the reference's linear order) into grid `which` of VolumeGrid `index`: 0 = grid / gridA, 1 = gridS"""
+        a = np.ascontiguousarray(np.asarray(data, np.float32).reshape(-1))
+        _check(lib.ctl_builder_set_volume_grid_data(self._h, u32(index), u32(which), a.ctypes.data, u32(len(a))))
+
+    def SetVolumeGridCoefficients(self, index, sig_a=(0.0, 1.0), sig_s=(0.0, 1.0)):
+        """sigAMin / sigAMax and sigSMin / sigSMax of VolumeGrid `index`: (min, max), each a scalar or rgb"""
+        a0, a1, s0, s1 = _rgb3(sig_a[0]), _rgb3(sig_a[1]), _rgb3(sig_s[0]), _rgb3(sig_s[1])
+        _check(lib.ctl_builder_set_volume_grid_coefficients(self._h, u32(index), a0, a1, s0, s1))
+
+    def CreateGridVolume(self, gv):
+        """a GridVolume (api.grid_volume) through CreateVolumeGrid and the two setters; returns the volume's index"""
+        g = gv.grid
+        dims = list(g.dim) if g.single_grid else list(g.dim_a) + list(g.dim_s) + [1, 1, 1]
+        i = self.CreateVolumeGrid(*dims, volume_to_world=np.array(list(gv.volume.volume_to_world.m), np.float32).reshape(4, 4), phase=gv.volume.phase)
+        for which, a in enumerate(gv._arrays):
+            self.SetVolumeGridData(i, a, which)
+        self.SetVolumeGridCoefficients(i, (np.array(list(g.sig_a_min)), np.array(list(g.sig_a_max))), (np.array(list(g.sig_s_min)), np.array(list(g.sig_s_max))))
+        return i
 
     def SetVolume(self, index, volume):
         """replace volume `index` (the host edits the region CreateVolume returned); Scene.update applies the next description in place (DIFF_VOLUMES)"""

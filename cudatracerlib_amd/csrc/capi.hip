@@ -132,6 +132,15 @@ int ctl_builder_finalize(ctl_builder* b, ctl_scene_desc* out) { CTL_REQUIRE(b &&
 int ctl_material_update(ctl_material* m) {   // (a weight from an IMAGE texture's average is final after ctl_builder_finalize, material_textures.h)
     CTL_REQUIRE(m, "null argument"); CTL_REQUIRE(material_update(*m), "unknown bsdf_type"); material_update_textures(*m, image_set()); return CTL_OK;
 }
+int ctl_builder_create_volume_grid(ctl_builder* b, const uint32_t* dims, uint32_t n_dims, const ctl_float4x4* volume_to_world, const ctl_phase_function* phase, uint32_t* index_out) {
+    CTL_REQUIRE(b && dims && volume_to_world && phase, "null argument");
+    CTL_TRY uint32_t i = b->b.create_volume_grid(dims, n_dims, *volume_to_world, *phase); if (index_out) *index_out = i; CTL_CATCH
+}
+int ctl_builder_set_volume_grid_data(ctl_builder* b, uint32_t index, uint32_t which, const float* data, uint32_t n) { CTL_REQUIRE(b && data, "null argument"); CTL_TRY b->b.set_volume_grid_data(index, which, data, n); CTL_CATCH }
+int ctl_builder_set_volume_grid_coefficients(ctl_builder* b, uint32_t index, const float* sig_a_min, const float* sig_a_max, const float* sig_s_min, const float* sig_s_max) {
+    CTL_REQUIRE(b && sig_a_min && sig_a_max && sig_s_min && sig_s_max, "null argument");
+    CTL_TRY b->b.set_volume_grid_coefficients(index, sig_a_min, sig_a_max, sig_s_min, sig_s_max); CTL_CATCH
+}
 int ctl_volume_update(ctl_volume* v) { CTL_REQUIRE(v, "null argument"); CTL_TRY volume_update(*v); CTL_CATCH }
 // ---- the participating-media functions (volume.h) one call per query, on the host or by a kernel (volume_eval.hip)
 int ctl_volume_eval(const ctl_scene_desc* desc, int32_t what, const float* queries, uint32_t n, float* out, int32_t on_device) {

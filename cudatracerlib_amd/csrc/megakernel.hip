@@ -21,13 +21,15 @@ namespace ctl {
 
 // pathKernel2<DIRECT> + PathTrace<DIRECT> (Integrators/PathTracer.cu:182-194, 10-113).  MEDIA = false: a scene without participating media (k_path_trace: the code it
 // always was); MEDIA = true: the medium half of PathTrace (:17-58) from the volume table V (volume.h) — the distance draw, the medium vertex's next-event estimation and
-// phase-function scattering, the surface NEE attenuated by Transmittance (k_path_trace_media, launched only for a scene that has volumes)
+// phase-function scattering, the surface NEE attenuated by Transmittance (k_path_trace_media, launched only for a scene that has volumes).  GRID = true (with MEDIA):
+// the regions' functions dispatch on the type and march the density grids of a VolumeGrid (volume_grid.h) — k_path_trace_media_grid, launched only for a scene whose
+// table holds such a region, so that the other two kernels keep the code they had
 #ifndef CTL_MEGA_WAVES
 #define CTL_MEGA_WAVES 2
 #endif
 template <bool MEDIA> struct media_state { vol::medium_rec rec = vol::zero_rec(); bool in_medium = false; };   // PathTrace's mRec lives across the bounces
 template <> struct media_state<false> {};
-template <bool MEDIA> __device__ __forceinline__ void path_trace(const dev_scene S, const pass_params P, const vol::table V, ctl_pixel_data* __restrict__ image, unsigned long long* __restrict__ ray_count) {
+template <bool MEDIA, bool GRID = false> __device__ __forceinline__ void path_trace(const dev_scene S, const pass_params P, const vol::table V, ctl_pixel_data* __restrict__ image, unsigned long long* __restrict__ ray_count) {
     const uint32_t tiles_x = (P.width + 63) / 64;
     const uint32_t n_total = P.n_local_pixels * P.batch;
     const uint32_t n1 = CTL_SAMPLER_NUM_SEQUENCES * CTL_SAMPLER_SEQUENCE_LENGTH;
@@ -58,7 +60,7 @@ template <bool MEDIA> __device__ __forceinline__ void path_trace(const dev_scene
                 float minT, maxT;
                 const bool isInMedium = ms.in_medium = vol::intersect(V, r_o, r_d, 0.0f, dist, minT, maxT);
                 // the distance draw is consumed whenever HasVolumes() && isInMedium, whatever the outcome
-                if (V.n > 0 && isInMedium && vol::sample_distance(V, r_o, r_d, 0.0f, dist, rng.next1(), mRec)) {
+                if (V.n > 0 && isInMedium && vol::sample_distance<GRID>(V, r_o, r_d, 0.0f, dist, rng.next1(), mRec)) {
                     cf = cf * sdiv(mRec.sigmaS * mRec.transmittance, mRec.pdfSuccess);
                     if (P.direct) {   // sampleAttenuatedEmitterDirect from DirectSamplingRecord(mRec.p, 0) (KernelDynamicScene.cu:98-123): ONE 2-D draw picks the emitter and, rescaled, samples it
                         direct_rec dr; dr.ref = mRec.p; dr.refN = f3(0.0f); dr.p = f3(0.0f); dr.pdf = 0.0f;
@@ -69,9 +71,9 @@ template <bool MEDIA> __device__ __forceinline__ void path_trace(const dev_scene
                             value = light_sample_direct(S, scene_lights(S)[li2], dr, sl);
                             if (dr.pdf != 0) { dr.pdf *= lpdf; value = sdiv(value, lpdf); } else value = f3(0.0f);
                         }
-                        value = value * vol::eval_transmittance(V, dr.ref, dr.p);
+                        value = value * vol::eval_transmittance<GRID>(V, dr.ref, dr.p);
                         if (!is_zero(value)) {
-                            const float p = vol::phase_p(V, mRec.p, -r_d, dr.d);
+                            const float p = vol::phase_p<GRID>(V, mRec.p, -r_d, dr.d);
                             if (p != 0) {
                                 float st, su, sv; int stri, snode;
                                 rays++;
@@ -132,7 +134,7 @@ template <bool MEDIA> __device__ __forceinline__ void path_trace(const dev_scene
                             if (!trace_single<true>(S, dr.ref, dr.d, S.eps, dr.dist - S.eps, st, su, sv, stri, snode)) {   // Occluded(r, 0, dist)
                                 float weight = 1.0f;
                                 if (dr.measure != kMeasureDiscrete) weight = power_heuristic((dr.measure == kMeasureArea ? dr.pdf * dr.dist / fabsf(dot(dr.n, dr.d)) : dr.pdf) * lpdf, bsdf_pdf_top(mat, b2));
-                                if constexpr (MEDIA) cl = cl + cf * sdiv((value * bsdfVal * weight) * vol::transmittance(V, dr.ref, dr.d, 0.0f, dr.dist), lpdf);   // EstimateDirect(..., attenuated = true) (TraceAlgorithms.cu:66-67)
+                                if constexpr (MEDIA) cl = cl + cf * sdiv((value * bsdfVal * weight) * vol::transmittance<GRID>(V, dr.ref, dr.d, 0.0f, dr.dist), lpdf);   // EstimateDirect(..., attenuated = true) (TraceAlgorithms.cu:66-67)
                                 else cl = cl + cf * sdiv(value * bsdfVal * weight, lpdf);
                             }
                         }
@@ -168,6 +170,11 @@ __global__ __launch_bounds__(256, CTL_MEGA_WAVES) void k_path_trace(dev_scene S,
 // the volume table is an argument of this kernel alone; its regions stay in global memory and are indexed wave-uniformly
 __global__ __launch_bounds__(256, CTL_MEGA_WAVES) void k_path_trace_media(dev_scene S, pass_params P, vol::table V, ctl_pixel_data* __restrict__ image, unsigned long long* __restrict__ ray_count) {
     path_trace<true>(S, P, V, image, ray_count);
+}
+// a scene with a VolumeGrid region: the table's grid records and cell buffer are read with ordinary (vector) loads.  No bar is set on this kernel's registers or
+// scratch; what its divergent march costs is unmeasured
+__global__ __launch_bounds__(256, CTL_MEGA_WAVES) void k_path_trace_media_grid(dev_scene S, pass_params P, vol::table V, ctl_pixel_data* __restrict__ image, unsigned long long* __restrict__ ray_count) {
+    path_trace<true, true>(S, P, V, image, ray_count);
 }
 
 // ---- PathTraceRegularization<DIRECT> (Integrators/PathTracer.cu:115-173): the plugin with Regularization = true
@@ -314,7 +321,8 @@ void PathTracer::DoRender(Image* I, const float* d_t1, const float* d_t2, unsign
         CTL_HIP(hipMemcpyAsync(mollifier_.p, m.data(), n_batch * sizeof(float), hipMemcpyHostToDevice, stream));
         CTL_HIP(hipStreamSynchronize(stream));   // `m` is pageable and leaves scope
         hipLaunchKernelGGL(k_path_trace_regularization, dim3(grid_blocks), dim3(256), 0, stream, m_pScene->S, P, (const float*)mollifier_.p, I->device(), count_.p);
-    } else if (V.n) hipLaunchKernelGGL(k_path_trace_media, dim3(grid_blocks), dim3(256), 0, stream, m_pScene->S, P, V, I->device(), count_.p);
+    } else if (V.n && V.g) hipLaunchKernelGGL(k_path_trace_media_grid, dim3(grid_blocks), dim3(256), 0, stream, m_pScene->S, P, V, I->device(), count_.p);
+    else if (V.n) hipLaunchKernelGGL(k_path_trace_media, dim3(grid_blocks), dim3(256), 0, stream, m_pScene->S, P, V, I->device(), count_.p);
     else hipLaunchKernelGGL(k_path_trace, dim3(grid_blocks), dim3(256), 0, stream, m_pScene->S, P, I->device(), count_.p);
     timer.end(stream);
     CTL_HIP(hipMemcpyAsync(&host_count_, count_.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
@@ -331,7 +339,8 @@ void PathTracer::DebugInternal(Image* I, unsigned int x, unsigned int y, const f
     P.debug_out = debug_.p; P.debug_x = x; P.debug_y = y;
     CTL_HIP(hipMemsetAsync(count_.p, 0, sizeof(unsigned long long), stream));
     const vol::table V = scene_volume_table(m_pScene);
-    if (V.n) hipLaunchKernelGGL(k_path_trace_media, dim3(1), dim3(256), 0, stream, m_pScene->S, P, V, I->device(), count_.p);
+    if (V.n && V.g) hipLaunchKernelGGL(k_path_trace_media_grid, dim3(1), dim3(256), 0, stream, m_pScene->S, P, V, I->device(), count_.p);
+    else if (V.n) hipLaunchKernelGGL(k_path_trace_media, dim3(1), dim3(256), 0, stream, m_pScene->S, P, V, I->device(), count_.p);
     else hipLaunchKernelGGL(k_path_trace, dim3(1), dim3(256), 0, stream, m_pScene->S, P, I->device(), count_.p);
     CTL_HIP(hipMemcpyAsync(rgb, debug_.p, 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
     CTL_HIP(hipStreamSynchronize(stream));

@@ -68,6 +68,9 @@ struct loader {
     std::map<uint32_t, uint32_t> node_mesh;
     uint32_t flags = 0;                              // CTL_PARSE_*: create_exterior_bssrdf / create_interior_bssrdf of ParseMitsubaScene
     std::map<std::string, ctl_volume> ref_medium;    // media with an id, as parsed
+    // the grids of a heterogeneous medium (MediumParser::heterogeneous): gridA and gridS, both of `dims`, in DenseVolGrid::idx's linear order; empty for a homogeneous one
+    struct medium_grids { uint32_t dims[3] = { 0, 0, 0 }; std::vector<float> a, s; bool present() const { return !a.empty(); } };
+    std::map<std::string, medium_grids> ref_medium_grids;
     std::vector<uint32_t> nodes_to_remove;           // ParserState::nodes_to_remove: the shapes that only carried a medium
     int film_w = 768, film_h = 576; bool have_film = false, have_sensor = false;
     mat4 id_matrix = identity();   // assume_rotated_coords = false (main.cpp passes false)
@@ -379,10 +382,127 @@ struct loader {
     }
     // MediumParser::parse / homogeneous (ObjectParser.h:173-227).  As written: a <ref> returns the medium AS IT WAS PARSED, with the transform of that parse — a top-level
     // <medium id> is parsed with the identity, so a shape that refers to it gets a volume over the unit cube, not over the scene box.  false: skipped (lenient mode)
-    bool parse_medium(const xml_node& n, const mat4& to_world, ctl_volume& out) {
-        if (is_ref(n)) { auto it = ref_medium.find(n.attr("id")); if (it == ref_medium.end()) bad("unknown reference : " + n.attr("id")); out = it->second; return true; }
+    // ---- a Mitsuba VOL3 file (the gridvolume of ObjectParser.cpp:279-325): "VOL", version 3, int32 data type (1 float32, 2 float16, 3 uint8), uint32 dims x y z,
+    // uint32 channels, six floats (the box), then dims.x * dims.y * dims.z * channels values, x fastest.  A file front-end like the others: every size is checked
+    // against the bytes that are there and against CTL_MAX_GRID_CELLS before anything is read or allocated; the channels are averaged (:303-325)
+    struct vol_data { bool is_constant = true; rgb const_value = rgb(0.0f); uint32_t dims[3] = { 1, 1, 1 }; std::vector<float> data; float box[6] = { 0, 0, 0, 0, 0, 0 }; };
+    static void read_vol3(const std::string& path, vol_data& dat) {
+        FILE* f = std::fopen(path.c_str(), "rb");
+        if (!f) bad("cannot open volume file " + path);
+        struct closer { FILE* f; ~closer() { std::fclose(f); } } guard{ f };
+        const size_t header = 4 + 4 + 12 + 4 + 24;
+        std::vector<uint8_t> bytes(header);
+        if (std::fread(bytes.data(), 1, header, f) != header) bad("volume file " + path + ": truncated (no VOL3 header)");
+        if (bytes[0] != 'V' || bytes[1] != 'O' || bytes[2] != 'L' || bytes[3] != 3) bad("volume file " + path + ": expected VOL3 header");
+        int32_t type; uint32_t channels;
+        std::memcpy(&type, &bytes[4], 4); std::memcpy(dat.dims, &bytes[8], 12); std::memcpy(&channels, &bytes[20], 4); std::memcpy(dat.box, &bytes[24], 24);
+        if (type < 1 || type > 3) bad("volume file " + path + ": unsopported volume data type : " + std::to_string(type));
+        if (channels == 0) bad("volume file " + path + ": zero channels");
+        if (!dat.dims[0] || !dat.dims[1] || !dat.dims[2]) bad("volume file " + path + ": a zero dimension");
+        if (dat.dims[0] > CTL_MAX_GRID_CELLS || dat.dims[1] > CTL_MAX_GRID_CELLS || dat.dims[2] > CTL_MAX_GRID_CELLS || (uint64_t)dat.dims[0] * dat.dims[1] > CTL_MAX_GRID_CELLS ||
+            (uint64_t)dat.dims[0] * dat.dims[1] * dat.dims[2] > CTL_MAX_GRID_CELLS)
+            bad("volume file " + path + ": more than " + std::to_string(CTL_MAX_GRID_CELLS) + " cells (CTL_MAX_GRID_CELLS)");
+        const uint64_t N = (uint64_t)dat.dims[0] * dat.dims[1] * dat.dims[2], val_size = type == 1 ? 4 : (type == 2 ? 2 : 1);
+        if (channels > 16) bad("volume file " + path + ": " + std::to_string(channels) + " channels (at most 16)");   // N * channels * val_size <= 2^22 * 16 * 4: no overflow
+        bytes.resize(header + N * channels * val_size);
+        const size_t got = std::fread(bytes.data() + header, 1, bytes.size() - header, f);
+        if (got != bytes.size() - header) bad("volume file " + path + ": truncated (" + std::to_string(got) + " bytes of data for " + std::to_string(N) + " cells of " + std::to_string(channels) + " channels)");
+        dat.data.resize(N);
+        for (uint64_t i = 0; i < N; i++) {
+            float sum = 0;
+            for (uint32_t c = 0; c < channels; c++) {
+                const uint8_t* ptr = &bytes[header + (i * channels + c) * val_size];
+                if (type == 1) { float v; std::memcpy(&v, ptr, 4); sum += v; }
+                else if (type == 2) {   // half::ToFloat, the HOST branch the reference's loader runs (Math/half.h:77-82): as written, zero decodes to 2^-15
+                    uint16_t h; std::memcpy(&h, ptr, 2);
+                    const uint32_t w = ((uint32_t)(h & 0x8000) << 16) | ((((uint32_t)(h & 0x7fff)) << 13) + 0x38000000u);
+                    float v; std::memcpy(&v, &w, 4); sum += v;
+                } else sum += (*ptr) / 255.0f;
+            }
+            dat.data[i] = sum / channels;
+        }
+        dat.is_constant = false;
+    }
+    // VolData::eval (ObjectParser.cpp:229-236): pos in [0,1]^3
+    static float vol_eval(const vol_data& v, float px, float py, float pz) {
+        if (v.is_constant) return v.const_value.r * 0.212671f + v.const_value.g * 0.715160f + v.const_value.b * 0.072169f;   // Spectrum::getLuminance (Spectrum.cu:174-177)
+        const int x = int(px * v.dims[0]), y = int(py * v.dims[1]), z = int(pz * v.dims[2]);
+        return v.data[((size_t)z * v.dims[1] + y) * v.dims[0] + x];
+    }
+    // MediumParser::heterogeneous (ObjectParser.cpp:206-376).  A medium whose density and albedo are both constant (no gridvolume child) stays refused: the reference
+    // makes a homogeneous region of it
+    bool parse_heterogeneous(const xml_node& n, const mat4& to_world, ctl_volume& out, medium_grids& G) {
+        bool any_grid = false;
+        for (const char* name : { "density", "albedo" }) if (const xml_node* v = n.property(name)) if (v->attr("type") == "gridvolume") any_grid = true;
+        if (!any_grid) { unsupported("heterogeneous medium (VolumeGrid)"); return false; }
+        ctl_volume V{}; V.type = CTL_VOLUME_GRID; V.phase.type = CTL_PHASE_ISOTROPIC;
+        if (const xml_node* ph = n.child("phase")) V.phase = parse_phase(*ph);
+        const float sc = prop_f(n, "scale", 1.0f);
+        bool have_matrix = false; mat4 volume_to_world = identity();
+        auto parse_volume = [&](const xml_node& v) {
+            vol_data dat; const std::string T = v.attr("type");
+            if (T == "constvolume") {
+                const xml_node* val = v.property("value"); if (!val) bad("no property of that name : value");
+                dat.const_value = parse_color(*val);
+                if (v.property("toWorld")) { if (have_matrix) bad("only one volume to world matrix allowed!"); volume_to_world = parse_matrix(*v.property("toWorld")); have_matrix = true; }
+            } else if (T == "gridvolume") {
+                const std::string path = asset(prop_s(v, "filename"));
+                bool have_box = false; f3 lo(0.0f), hi(0.0f);
+                if (v.property("toWorld") || v.property("min")) {
+                    if (have_matrix) bad("only one volume to world matrix allowed!");
+                    if (v.property("toWorld")) { volume_to_world = parse_matrix(*v.property("toWorld")); have_matrix = true; }
+                    if (v.property("min")) { if (!v.property("max")) bad("no property of that name : max"); lo = parse_vector(*v.property("min")); hi = parse_vector(*v.property("max")); have_box = true; }
+                }
+                read_vol3(path, dat);
+                if (have_box) { dat.box[0] = lo.x; dat.box[1] = lo.y; dat.box[2] = lo.z; dat.box[3] = hi.x; dat.box[4] = hi.y; dat.box[5] = hi.z; }
+                for (int k = 0; k < 6; k++) if (!std::isfinite(dat.box[k])) bad("volume file " + path + ": the box is not finite");
+                const mat4 vtow = have_matrix ? volume_to_world : identity();
+                const f3 bmin(dat.box[0], dat.box[1], dat.box[2]), bmax(dat.box[3], dat.box[4], dat.box[5]);
+                if (length(bmin - f3(0.0f)) > 1e-3f || length(bmax - f3(1.0f)) > 1e-3f) {   // :331-332
+                    volume_to_world = mul(mul(vtow, translate(bmin.x, bmin.y, bmin.z)), scale(bmax.x - bmin.x, bmax.y - bmin.y, bmax.z - bmin.z)); have_matrix = true;
+                }
+            } else bad("invalid volume type : " + T);
+            return dat;
+        };
+        vol_data density, albedo;
+        if (const xml_node* v = n.property("density")) density = parse_volume(*v);
+        if (const xml_node* v = n.property("albedo")) albedo = parse_volume(*v);
+        const mat4 m = mul(to_world, have_matrix ? volume_to_world : id_matrix);   // toWorld % vol_to_world (:346-347)
+        std::memcpy(V.volume_to_world.m, m.m, 64);
+        volume_update(V);
+        for (int c = 0; c < 3; c++) G.dims[c] = std::max(density.dims[c], albedo.dims[c]);   // max(density_data.dims(), albedo_data.dims()); each <= CTL_MAX_GRID_CELLS, the product is checked next
+        if ((uint64_t)G.dims[0] * G.dims[1] > CTL_MAX_GRID_CELLS || (uint64_t)G.dims[0] * G.dims[1] * G.dims[2] > CTL_MAX_GRID_CELLS) bad("heterogeneous medium: more than " + std::to_string(CTL_MAX_GRID_CELLS) + " cells (CTL_MAX_GRID_CELLS)");
+        const uint32_t dx = G.dims[0], dy = G.dims[1], dz = G.dims[2];
+        // the cells that DenseVolGrid::idx never addresses on a non-cubic grid stay 0 (the reference leaves them as its buffer had them)
+        G.a.assign((size_t)dx * dy * dz, 0.0f); G.s.assign((size_t)dx * dy * dz, 0.0f);
+        for (uint32_t x = 0; x < dx; x++) for (uint32_t y = 0; y < dy; y++) for (uint32_t z = 0; z < dz; z++) {   // :361-371
+            const float px = (float)x / (float)dx, py = (float)y / (float)dy, pz = (float)z / (float)dz;
+            const float d = vol_eval(density, px, py, pz) * sc, al = vol_eval(albedo, px, py, pz);
+            const size_t at = std::min(z, dx - 1) + (size_t)std::min(y, dy - 1) * dx + (size_t)std::min(x, dz - 1) * dx * dy;   // value(x, y, z): DenseVolGrid::idx, as written
+            G.s[at] = al * d;
+            G.a[at] = d * (1.0f - al);
+        }
+        if (n.has_attr("id")) { ref_medium[n.attr("id")] = V; ref_medium_grids[n.attr("id")] = G; }
+        out = V; return true;
+    }
+    // a parsed medium into the builder: a homogeneous region as it is, a heterogeneous one with its two grids and sigAMax = sigSMax = 1 (:359)
+    void create_medium(const ctl_volume& V, const medium_grids& G) {
+        if (!G.present()) { B.create_volume(V); return; }
+        const uint32_t dims[9] = { G.dims[0], G.dims[1], G.dims[2], G.dims[0], G.dims[1], G.dims[2], 1, 1, 1 };
+        const uint32_t i = B.create_volume_grid(dims, 9, V.volume_to_world, V.phase);
+        B.set_volume_grid_data(i, 0, G.a.data(), (uint32_t)G.a.size()); B.set_volume_grid_data(i, 1, G.s.data(), (uint32_t)G.s.size());
+        const float zero[3] = { 0, 0, 0 }, one[3] = { 1, 1, 1 };
+        B.set_volume_grid_coefficients(i, zero, one, zero, one);
+    }
+    bool parse_medium(const xml_node& n, const mat4& to_world, ctl_volume& out, medium_grids& grids) {
+        grids = medium_grids();
+        if (is_ref(n)) {
+            auto it = ref_medium.find(n.attr("id")); if (it == ref_medium.end()) bad("unknown reference : " + n.attr("id"));
+            out = it->second; auto g = ref_medium_grids.find(n.attr("id")); if (g != ref_medium_grids.end()) grids = g->second;
+            return true;
+        }
         const std::string T = n.attr("type");
-        if (T == "heterogeneous") { unsupported("heterogeneous medium (VolumeGrid)"); return false; }
+        if (T == "heterogeneous") return parse_heterogeneous(n, to_world, out, grids);
         if (T != "homogeneous") bad("invalid VolumeRegion type : " + T);
         ctl_volume V{}; V.type = CTL_VOLUME_HOMOGENEOUS; V.phase.type = CTL_PHASE_ISOTROPIC;
         if (const xml_node* ph = n.child("phase")) V.phase = parse_phase(*ph);
@@ -427,8 +547,8 @@ struct loader {
             const aabb box = B.scene_box();
             const mat4 obj_mat = mul(translate(box.lo[0], box.lo[1], box.lo[2]), scale(box.hi[0] - box.lo[0], box.hi[1] - box.lo[1], box.hi[2] - box.lo[2]));
             if (has_bsdf) { unsupported("a medium on a shape that has a BSDF (Material::bssrdf)"); return; }
-            ctl_volume V;
-            if (parse_medium(*m, obj_mat, V)) { B.create_volume(V); delete_node = true; }
+            ctl_volume V; medium_grids G;
+            if (parse_medium(*m, obj_mat, V, G)) { create_medium(V, G); delete_node = true; }
         };
         if (flags & CTL_PARSE_EXTERIOR_MEDIA) create_bssrdf("exterior");
         if (flags & CTL_PARSE_INTERIOR_MEDIA) create_bssrdf("interior");
@@ -663,7 +783,7 @@ void loader::parse_file(const std::string& file) {
         else if (t == "bsdf") parse_bsdf(n, 0);
         else if (t == "shape") parse_shape(n);
         else if (t == "texture") parse_texture(n);
-        else if (t == "medium") { if (!flags) unsupported("<medium>"); else { ctl_volume V; (void)parse_medium(n, identity(), V); } }   // MediumParser::parse(n, S): kept for a later <ref>
+        else if (t == "medium") { if (!flags) unsupported("<medium>"); else { ctl_volume V; medium_grids G; (void)parse_medium(n, identity(), V, G); } }   // MediumParser::parse(n, S): kept for a later <ref>
         // other elements (integrator, ...) are ignored, as in the reference
     }
 }

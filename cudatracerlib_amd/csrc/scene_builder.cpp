@@ -558,6 +558,36 @@ void scene_builder::set_volume(uint32_t index, const ctl_volume& v) {
     ctl_volume c = v; volume_update(c);
     volumes[index] = c;
 }
+uint32_t scene_builder::create_volume_grid(const uint32_t* dims, uint32_t n_dims, const ctl_float4x4& volume_to_world, const ctl_phase_function& phase) {
+    if (n_dims != 3 && n_dims != 9) throw std::runtime_error("ctl_builder_create_volume_grid: 3 dims (one grid) or 9 (gridA, gridS, gridL)");
+    grid_store g; g.rec.single_grid = n_dims == 3 ? 1u : 0u;
+    auto grid = [&](uint32_t* to, const uint32_t* from, std::vector<float>& data) {
+        if (!from[0] || !from[1] || !from[2] || from[0] > CTL_MAX_GRID_CELLS || from[1] > CTL_MAX_GRID_CELLS || from[2] > CTL_MAX_GRID_CELLS || (uint64_t)from[0] * from[1] > CTL_MAX_GRID_CELLS || (uint64_t)from[0] * from[1] * from[2] > CTL_MAX_GRID_CELLS)
+            throw std::runtime_error("ctl_builder_create_volume_grid: a grid has a zero dimension or more than " + std::to_string(CTL_MAX_GRID_CELLS) + " cells (CTL_MAX_GRID_CELLS)");
+        for (int c = 0; c < 3; c++) to[c] = from[c];
+        data.assign((size_t)from[0] * from[1] * from[2], 0.0f);
+    };
+    if (n_dims == 3) grid(g.rec.dim, dims, g.data[0]);
+    else { grid(g.rec.dim_a, dims, g.data[0]); grid(g.rec.dim_s, dims + 3, g.data[1]); }   // dims[6..8], gridL: not carried
+    ctl_volume v{}; v.type = CTL_VOLUME_GRID; v.phase = phase; v.volume_to_world = volume_to_world;
+    g.rec.volume = create_volume(v);
+    grid_stores.push_back(std::move(g));
+    return grid_stores.back().rec.volume;
+}
+static scene_builder::grid_store& grid_store_of(scene_builder& b, uint32_t index, const char* who) {
+    for (auto& g : b.grid_stores) if (g.rec.volume == index) return g;
+    throw std::runtime_error(std::string(who) + ": volume " + std::to_string(index) + " is no VolumeGrid of this builder");
+}
+void scene_builder::set_volume_grid_data(uint32_t index, uint32_t which, const float* data, uint32_t n) {
+    grid_store& g = grid_store_of(*this, index, "ctl_builder_set_volume_grid_data");
+    if (which > 1 || (which == 1 && g.rec.single_grid)) throw std::runtime_error("ctl_builder_set_volume_grid_data: which = 0 (grid / gridA) or, in the three-grid form, 1 (gridS)");
+    if (!data || n != g.data[which].size()) throw std::runtime_error("ctl_builder_set_volume_grid_data: " + std::to_string(n) + " floats for a grid of " + std::to_string(g.data[which].size()));
+    g.data[which].assign(data, data + n);
+}
+void scene_builder::set_volume_grid_coefficients(uint32_t index, const float* sig_a_min, const float* sig_a_max, const float* sig_s_min, const float* sig_s_max) {
+    grid_store& g = grid_store_of(*this, index, "ctl_builder_set_volume_grid_coefficients");
+    for (int c = 0; c < 3; c++) { g.rec.sig_a_min[c] = sig_a_min[c]; g.rec.sig_a_max[c] = sig_a_max[c]; g.rec.sig_s_min[c] = sig_s_min[c]; g.rec.sig_s_max[c] = sig_s_max[c]; }
+}
 
 void scene_builder::remove_node(uint32_t i) {
     if (i >= nodes.size()) throw std::runtime_error("remove_node: bad node index");
@@ -610,6 +640,13 @@ void scene_builder::finalize(ctl_scene_desc& out) {
     for (int i = 0; i < 3; i++) { rt[i].trans = rt_trans[i].empty() ? nullptr : rt_trans[i].data(); rt[i].diff_trans = rt_diff[i].empty() ? nullptr : rt_diff[i].data(); }
     out.rough_transmittance = have_rt ? rt : nullptr;
     out.volumes = volumes.empty() ? nullptr : volumes.data(); out.n_volumes = (uint32_t)volumes.size();
+    grid_records.clear();
+    for (auto& g : grid_stores) {
+        if (g.rec.volume >= volumes.size() || volumes[g.rec.volume].type != CTL_VOLUME_GRID) continue;   // ctl_builder_set_volume made the region a homogeneous one
+        ctl_volume_grid r = g.rec; r.data = r.single_grid ? g.data[0].data() : nullptr; r.data_a = r.single_grid ? nullptr : g.data[0].data(); r.data_s = r.single_grid ? nullptr : g.data[1].data();
+        grid_records.push_back(r);
+    }
+    out.volume_grids = grid_records.empty() ? nullptr : grid_records.data(); out.n_volume_grids = (uint32_t)grid_records.size();
     {   // the light that depends on the scene box: InfiniteLight::Update (SceneTypes/Light.h:318-325)
         f3 lo(scene.lo[0], scene.lo[1], scene.lo[2]), hi(scene.hi[0], scene.hi[1], scene.hi[2]);
         f3 center = (lo + hi) * 0.5f;   // AABB::Center (Math/AABB.h)

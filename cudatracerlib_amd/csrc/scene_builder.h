@@ -72,6 +72,13 @@ struct scene_builder {
     // DynamicScene::CreateVolume(VolumeRegion) (Engine/DynamicScene.cpp:787-792) / an edit of the region it returned; the derived fields are recomputed (ctl_volume_update)
     uint32_t create_volume(const ctl_volume& v);
     void set_volume(uint32_t index, const ctl_volume& v);
+    // DynamicScene::CreateVolume(w, h, d, ...) / (wA, ..., dL, ...) (Engine/DynamicScene.cpp:794-812): a VolumeGrid with zeroed grids and coefficients (VolumeGrid's
+    // constructors, Volumes.cu:99-111); n_dims = 3 or 9, the L dims are accepted and ignored.  The floats are the builder's own copies
+    struct grid_store { ctl_volume_grid rec{}; std::vector<float> data[2]; };   // data[0]: grid / gridA, data[1]: gridS
+    std::vector<grid_store> grid_stores; std::vector<ctl_volume_grid> grid_records;   // grid_records: what finalize hands out
+    uint32_t create_volume_grid(const uint32_t* dims, uint32_t n_dims, const ctl_float4x4& volume_to_world, const ctl_phase_function& phase);
+    void set_volume_grid_data(uint32_t index, uint32_t which, const float* data, uint32_t n);
+    void set_volume_grid_coefficients(uint32_t index, const float* sig_a_min, const float* sig_a_max, const float* sig_s_min, const float* sig_s_max);
     // DynamicScene::DeleteNode (Engine/DynamicScene.cpp:380-384) for a node without lights (the loader's medium-only shapes): the nodes behind it move up one index, the
     // area lights of those nodes follow; the node's material copies stay in the array, unreferenced
     void remove_node(uint32_t node_index);

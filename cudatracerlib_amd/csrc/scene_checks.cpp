@@ -87,11 +87,16 @@ void check_volumes(const ctl_scene_desc& d, const char* who) {
     if (d.n_volumes && !d.volumes) refuse(who, "n_volumes without a volumes array");
     for (uint32_t i = 0; i < d.n_volumes; i++) {
         const ctl_volume& V = d.volumes[i]; const std::string vi = "volume " + std::to_string(i) + ": ";
-        if (V.type != CTL_VOLUME_HOMOGENEOUS) refuse(who, vi + "volume type " + std::to_string(V.type) + " has no HIP implementation (homogeneous media only)");
+        if (V.type != CTL_VOLUME_HOMOGENEOUS && V.type != CTL_VOLUME_GRID) refuse(who, vi + "volume type " + std::to_string(V.type) + " has no HIP implementation (homogeneous media only)");
         for (int k = 0; k < 9; k++) {
             const float c = k < 3 ? V.sig_a[k] : (k < 6 ? V.sig_s[k - 3] : V.le[k - 6]);
             if (!std::isfinite(c) || c < 0.0f) refuse(who, vi + "sig_a, sig_s and le must be finite and non-negative");
+            if (V.type == CTL_VOLUME_GRID && c != 0.0f) refuse(who, vi + "a VolumeGrid's sig_a, sig_s and le must be 0 (its coefficients are its grid record's)");
         }
+        uint32_t records = 0;
+        for (uint32_t g = 0; g < d.n_volume_grids && d.volume_grids; g++) if (d.volume_grids[g].volume == i) records++;
+        if (V.type == CTL_VOLUME_GRID && records != 1) refuse(who, vi + "a VolumeGrid needs exactly one grid record, the description has " + std::to_string(records));
+        if (V.type != CTL_VOLUME_GRID && records != 0) refuse(who, vi + "a grid record names a volume that is no VolumeGrid");
         for (int k = 0; k < 16; k++) if (!std::isfinite(V.volume_to_world.m[k])) refuse(who, vi + "volume_to_world is not finite");
         for (int k = 0; k < 16; k++) if (!std::isfinite(V.world_to_volume.m[k])) refuse(who, vi + "volume_to_world is not invertible (world_to_volume is not finite; ctl_volume_update derives it)");
         const ctl_phase_function& F = V.phase;
@@ -99,6 +104,29 @@ void check_volumes(const ctl_scene_desc& d, const char* who) {
         if (F.type == CTL_PHASE_HG && !(std::fabs(F.g) < 1.0f)) refuse(who, vi + "the Henyey-Greenstein g must lie in (-1, 1)");
         if (F.type == CTL_PHASE_KAJIYA_KAY && !(std::isfinite(F.ks) && std::isfinite(F.kd) && std::isfinite(F.exponent) && std::isfinite(F.normalization)))
             refuse(who, vi + "the Kajiya-Kay ks, kd, exponent and normalization must be finite");
+    }
+    // the grid records (ctl_volume_grid): what csrc/volume_grid.h takes for granted
+    if (d.n_volume_grids && !d.volume_grids) refuse(who, "n_volume_grids without a volume_grids array");
+    if (d.n_volume_grids > CTL_MAX_VOL_COUNT) refuse(who, std::to_string(d.n_volume_grids) + " grid records; a table holds at most " + std::to_string(CTL_MAX_VOL_COUNT));
+    for (uint32_t g = 0; g < d.n_volume_grids; g++) {
+        const ctl_volume_grid& G = d.volume_grids[g]; const std::string gi = "volume grid " + std::to_string(g) + ": ";
+        if (G.volume >= d.n_volumes) refuse(who, gi + "names volume " + std::to_string(G.volume) + " of " + std::to_string(d.n_volumes));
+        auto grid = [&](const uint32_t* dim, const float* data, const char* name) {
+            if (!dim[0] || !dim[1] || !dim[2]) refuse(who, gi + name + " has a zero dimension");
+            // (each factor is checked first, so that the product cannot overflow 64 bits)
+            if (dim[0] > CTL_MAX_GRID_CELLS || dim[1] > CTL_MAX_GRID_CELLS || dim[2] > CTL_MAX_GRID_CELLS || (uint64_t)dim[0] * dim[1] > CTL_MAX_GRID_CELLS || (uint64_t)dim[0] * dim[1] * dim[2] > CTL_MAX_GRID_CELLS)
+                refuse(who, gi + name + " has more than " + std::to_string(CTL_MAX_GRID_CELLS) + " cells (CTL_MAX_GRID_CELLS)");
+            if (!data) refuse(who, gi + name + " has no data");
+            const size_t n = (size_t)dim[0] * dim[1] * dim[2];
+            for (size_t k = 0; k < n; k++) if (!std::isfinite(data[k]) || data[k] < 0.0f) refuse(who, gi + name + " values must be finite and non-negative");
+        };
+        if (G.single_grid) grid(G.dim, G.data, "grid");
+        else { grid(G.dim_a, G.data_a, "gridA"); grid(G.dim_s, G.data_s, "gridS"); }
+        const float* lo[3] = { G.sig_a_min, G.sig_s_min, G.le_min }; const float* hi[3] = { G.sig_a_max, G.sig_s_max, G.le_max };
+        for (int c = 0; c < 3; c++) for (int k = 0; k < 3; k++) {
+            if (!std::isfinite(lo[c][k]) || lo[c][k] < 0.0f || !std::isfinite(hi[c][k]) || hi[c][k] < 0.0f) refuse(who, gi + "sigAMin ... leMax must be finite and non-negative");
+            if (hi[c][k] < lo[c][k]) refuse(who, gi + "a maximum lies below its minimum (sigAMin ... leMax)");
+        }
     }
 }
 

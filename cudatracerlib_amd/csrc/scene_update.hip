@@ -16,6 +16,23 @@
 
 namespace ctl {
 
+// the grid records of two descriptions and the floats they point at (CTL_DIFF_VOLUMES): a record is compared field by field, its pointers by what they hold
+static bool volume_grids_same(const ctl_scene_desc& a, const ctl_scene_desc& b) {
+    if (a.n_volume_grids != b.n_volume_grids) return false;
+    if (a.n_volume_grids && (!a.volume_grids || !b.volume_grids)) return false;
+    auto cells_same = [](const uint32_t* da, const float* x, const uint32_t* db, const float* y) {
+        if (std::memcmp(da, db, 12) != 0) return false;
+        const size_t n = (size_t)da[0] * da[1] * da[2];
+        return n == 0 || (x && y && std::memcmp(x, y, n * 4) == 0);
+    };
+    for (uint32_t k = 0; k < a.n_volume_grids; k++) {
+        const ctl_volume_grid &x = a.volume_grids[k], &y = b.volume_grids[k];
+        if (x.volume != y.volume || (x.single_grid != 0) != (y.single_grid != 0) || std::memcmp(x.sig_a_min, y.sig_a_min, 18 * sizeof(float)) != 0) return false;
+        if (x.single_grid ? !cells_same(x.dim, x.data, y.dim, y.data) : !(cells_same(x.dim_a, x.data_a, y.dim_a, y.data_a) && cells_same(x.dim_s, x.data_s, y.dim_s, y.data_s))) return false;
+    }
+    return true;
+}
+
 uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const geometry_hashes* a_geometry, geometry_hashes* b_geometry, const std::vector<uint8_t>* ignore_values) {
     auto same = [](const void* x, const void* y, size_t bytes) { return bytes == 0 || (x && y && std::memcmp(x, y, bytes) == 0); };
     uint32_t mask = 0;
@@ -23,7 +40,7 @@ uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const
     if (a.n_tri_data != b.n_tri_data || a.n_woop != b.n_woop || a.n_bvh_nodes != b.n_bvh_nodes || a.n_meshes != b.n_meshes || a.n_nodes != b.n_nodes || a.n_materials != b.n_materials ||
         a.n_images != b.n_images || (a.rough_transmittance != nullptr) != (b.rough_transmittance != nullptr))
         return CTL_DIFF_TOPOLOGY | ((std::memcmp(&a.camera, &b.camera, sizeof(ctl_sensor)) != 0) ? CTL_DIFF_CAMERA : 0u) |
-               ((a.n_volumes != b.n_volumes || !same(a.volumes, b.volumes, (size_t)a.n_volumes * sizeof(ctl_volume))) ? (uint32_t)CTL_DIFF_VOLUMES : 0u);
+               ((a.n_volumes != b.n_volumes || !same(a.volumes, b.volumes, (size_t)a.n_volumes * sizeof(ctl_volume)) || !volume_grids_same(a, b)) ? (uint32_t)CTL_DIFF_VOLUMES : 0u);
     if (!same(a.meshes, b.meshes, (size_t)a.n_meshes * sizeof(ctl_kernel_mesh))) mask |= CTL_DIFF_TOPOLOGY;
     for (uint32_t k = 0; k < a.n_nodes; k++) {
         const ctl_node &x = a.nodes[k], &y = b.nodes[k];
@@ -54,29 +71,53 @@ uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const
     if (!same(a.node_transforms, b.node_transforms, (size_t)a.n_nodes * sizeof(ctl_float4x4)) || !same(a.node_inv_transforms, b.node_inv_transforms, (size_t)a.n_nodes * sizeof(ctl_float4x4)) ||
         a.scene_start_node != b.scene_start_node || a.n_scene_bvh_nodes != b.n_scene_bvh_nodes || !same(a.scene_bvh_nodes, b.scene_bvh_nodes, (size_t)a.n_scene_bvh_nodes * sizeof(ctl_bvh_node)) ||
         std::memcmp(a.box_min, b.box_min, 12) != 0 || std::memcmp(a.box_max, b.box_max, 12) != 0 || std::memcmp(&a.ray_trace_eps, &b.ray_trace_eps, 4) != 0) mask |= CTL_DIFF_TRANSFORMS;
-    if (a.n_volumes != b.n_volumes || !same(a.volumes, b.volumes, (size_t)a.n_volumes * sizeof(ctl_volume))) mask |= CTL_DIFF_VOLUMES;
+    if (a.n_volumes != b.n_volumes || !same(a.volumes, b.volumes, (size_t)a.n_volumes * sizeof(ctl_volume)) || !volume_grids_same(a, b)) mask |= CTL_DIFF_VOLUMES;
     return mask;
 }
 
 // ---- the scenes' volume tables (scene_volumes.h): device table, host copy (what the snapshot's `volumes` points at) and the kernel argument, per scene
 namespace {
-struct scene_volumes { dbuf<ctl_volume> dev; std::vector<ctl_volume> host; vol::table T{}; uint64_t id = 0; };
+// the grid records: `grids` is the host copy the snapshot points at, its data pointers into `pack.cells` (the floats as the device holds them); dev_grids has
+// CTL_MAX_VOL_COUNT slots like dev, dev_cells grows with the data and never shrinks
+struct scene_volumes {
+    dbuf<ctl_volume> dev; std::vector<ctl_volume> host; vol::table T{}; uint64_t id = 0;
+    dbuf<vol::grid_rec> dev_grids; dbuf<float> dev_cells; vol::grid_pack pack; std::vector<ctl_volume_grid> grids;
+};
 std::mutex g_volumes_mutex;
 // never destroyed: a scene that is still alive when the process ends must not free device memory during static destruction, after the runtime may have gone
 std::map<const Scene*, std::unique_ptr<scene_volumes>>& g_volumes = *new std::map<const Scene*, std::unique_ptr<scene_volumes>>();
 uint64_t g_next_volumes_id = 1;
-// the description's media into the scene's table, synchronously, when they differ from what it holds; returns the host copy (null without media)
-const ctl_volume* store_volumes(const Scene* s, const ctl_scene_desc& d) {
+// the description's media into the scene's table, synchronously, when they differ from what it holds; returns the host copy (null without media) and, in `grids_out`,
+// the host copy of the grid records
+const ctl_volume* store_volumes(const Scene* s, const ctl_scene_desc& d, const ctl_volume_grid** grids_out) {
     std::lock_guard<std::mutex> lock(g_volumes_mutex);
     std::unique_ptr<scene_volumes>& e = g_volumes[s];
     const bool fresh = !e;
-    if (fresh) { e.reset(new scene_volumes()); e->id = g_next_volumes_id++; e->dev.alloc(CTL_MAX_VOL_COUNT); CTL_HIP(hipMemset(e->dev.p, 0, CTL_MAX_VOL_COUNT * sizeof(ctl_volume))); }
+    if (fresh) {
+        e.reset(new scene_volumes()); e->id = g_next_volumes_id++; e->dev.alloc(CTL_MAX_VOL_COUNT); CTL_HIP(hipMemset(e->dev.p, 0, CTL_MAX_VOL_COUNT * sizeof(ctl_volume)));
+        e->dev_grids.alloc(CTL_MAX_VOL_COUNT); CTL_HIP(hipMemset(e->dev_grids.p, 0, CTL_MAX_VOL_COUNT * sizeof(vol::grid_rec)));
+    }
+    vol::grid_pack pack; vol::pack_grids(d, pack);
+    const bool grids_differ = fresh || !pack.same(e->pack);
+    if (grids_differ) {   // the records whole (16 slots), the floats into the buffer they had unless it must grow
+        CTL_HIP(hipMemcpy(e->dev_grids.p, pack.recs.data(), CTL_MAX_VOL_COUNT * sizeof(vol::grid_rec), hipMemcpyHostToDevice));
+        if (pack.cells.size() > e->dev_cells.n) e->dev_cells.alloc(pack.cells.size());
+        if (!pack.cells.empty()) CTL_HIP(hipMemcpy(e->dev_cells.p, pack.cells.data(), pack.cells.size() * 4, hipMemcpyHostToDevice));
+        e->pack = std::move(pack);
+    }
+    // the snapshot's records: the caller's, with the data pointers turned to the scene's own copy of the floats
+    e->grids.assign(d.volume_grids, d.volume_grids + d.n_volume_grids);
+    for (ctl_volume_grid& G : e->grids) {
+        const vol::grid_rec& R = e->pack.recs[G.volume];
+        G.data = G.single_grid ? e->pack.cells.data() + R.off : nullptr; G.data_a = G.single_grid ? nullptr : e->pack.cells.data() + R.off_a; G.data_s = G.single_grid ? nullptr : e->pack.cells.data() + R.off_s;
+    }
+    *grids_out = e->grids.empty() ? nullptr : e->grids.data();
     const size_t n = d.n_volumes;   // (<= CTL_MAX_VOL_COUNT: check_scene_desc)
     if (fresh || n != e->host.size() || (n && std::memcmp(e->host.data(), d.volumes, n * sizeof(ctl_volume)) != 0)) {
         e->host.assign(d.volumes, d.volumes + n);
         if (n) CTL_HIP(hipMemcpy(e->dev.p, e->host.data(), n * sizeof(ctl_volume), hipMemcpyHostToDevice));
-        e->T = vol::make_table(e->dev.p, (uint32_t)n);
     }
+    e->T = vol::make_table(e->dev.p, (uint32_t)n, e->pack.any ? e->dev_grids.p : nullptr, e->pack.any ? e->dev_cells.p : nullptr);
     return e->host.empty() ? nullptr : e->host.data();
 }
 }  // namespace
@@ -104,11 +145,13 @@ void Scene::snapshot(const ctl_scene_desc& d, const geometry_hashes* geom) {
     s->xf.assign(d.node_transforms, d.node_transforms + d.n_nodes); s->ixf.assign(d.node_inv_transforms, d.node_inv_transforms + d.n_nodes);
     s->images.assign(d.images, d.images + d.n_images); for (auto& m : s->images) m.texels = nullptr;
     // the media: creation and every update end here, after the device has been synchronised — the table is written in place (no re-creation, no refit)
-    s->d.volumes = store_volumes(this, d);
+    const ctl_volume_grid* grids = nullptr;
+    const ctl_volume* volumes = store_volumes(this, d, &grids);
     if (geom) s->geom = *geom;                    // after an update: the pass that found the difference made them
     else if (snap_) s->geom = snap_->geom;
     else hash_geometry(d, s->geom);
     s->d = d;
+    s->d.volumes = volumes; s->d.volume_grids = grids;
     s->d.tri_data = nullptr; s->d.woop = nullptr; s->d.woop_index = nullptr; s->d.bvh_nodes = nullptr;
     s->d.meshes = s->meshes.data(); s->d.nodes = s->nodes.data(); s->d.materials = s->materials.data(); s->d.lights = s->lights.data(); s->d.anim = s->anim.data();
     s->d.scene_bvh_nodes = s->top.data(); s->d.node_transforms = s->xf.data(); s->d.node_inv_transforms = s->ixf.data(); s->d.images = s->images.data();

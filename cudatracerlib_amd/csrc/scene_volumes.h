@@ -1,6 +1,8 @@
 // scene_volumes.h — KernelDynamicScene::m_sVolume of a Scene: the participating media in HBM, kept BESIDE the Scene object (scene_update.hip) so that dev_scene, the
 // Scene class and with them every other kernel's arguments stay as they are.  A fixed table of CTL_MAX_VOL_COUNT slots per scene, allocated when the scene is created and
-// written in place by ctl_scene_update (0 -> 1 volumes included); its only reader is the megakernel's MEDIA instantiation (megakernel.hip).
+// written in place by ctl_scene_update (0 -> 1 volumes included); its only readers are the megakernel's MEDIA instantiations (megakernel.hip).  Beside it, per scene, the grid
+// records of the VolumeGrid regions (CTL_MAX_VOL_COUNT slots) and ONE float buffer of their cells, re-uploaded by an update and re-allocated only when it grows; the table's
+// g / cells point at them when the scene has a grid region and are null otherwise.
 #pragma once
 #include "volume.h"
 

@@ -1,4 +1,4 @@
-// volume.h — participating media: the homogeneous regions, their aggregate and the four phase functions of the reference (SceneTypes/Volumes.{h,cu},
+// volume.h — participating media: the homogeneous regions, their aggregate (which dispatches to the VolumeGrid regions of volume_grid.h) and the four phase functions of the reference (SceneTypes/Volumes.{h,cu},
 // SceneTypes/PhaseFunction.{h,cu}, Kernel/TraceAlgorithms.cu:22-31, Engine/KernelDynamicScene.cu:90-96), single source for the megakernel's MEDIA instantiation
 // (megakernel.hip), the call-by-call kernel and the host yardstick (ctl_volume_eval, volume_eval.hip).  fp32 throughout, the operation order of the reference's source
 // (the library is built -ffp-contract=off), transcendental functions from ctl_fmath.h on the host AND on the device — never libm — so that the two agree bit for bit.
@@ -6,6 +6,8 @@
 #pragma once
 #include "../../include/ctl_amd.h"
 #include "ctl_math.h"
+#include <cstring>
+#include <vector>
 
 namespace ctl {
 namespace vol {
@@ -13,7 +15,11 @@ namespace vol {
 // KernelAggregateVolume as a kernel argument: the regions stay in global memory and are read with wave-uniform indices (scalar loads).  KernelAggregateVolume::box is
 // not carried: none of the reference's functions restated here reads it (IntersectP, tau and sampleVolume walk the regions), and a box test in front of them would be
 // arithmetic the reference does not do
-struct table { const ctl_volume* v; uint32_t n; };
+// A CTL_VOLUME_GRID region's record (ctl_volume_grid) as the kernels read it: slot i of `g` belongs to region i (CTL_MAX_VOL_COUNT slots, zeros for the other regions),
+// the grids' floats lie in ONE buffer `cells` at the record's offsets (pack_grids below).  g / cells are null in a table without grids; only the GRID = true
+// instantiations of the functions below read them
+struct grid_rec { uint32_t single; uint32_t dim[3], dim_a[3], dim_s[3]; uint32_t off, off_a, off_s; float sa_min[3], sa_max[3], ss_min[3], ss_max[3]; };
+struct table { const ctl_volume* v; uint32_t n; const grid_rec* g; const float* cells; };
 
 struct medium_rec {   // MediumSamplingRecord (Volumes.h:13-24) without the fields nothing reads
     float t; f3 p; f3 transmittance, sigmaA, sigmaS; float pdfSuccess, pdfSuccessRev, pdfFailure;
@@ -128,6 +134,27 @@ HD bool region_sample_distance(const ctl_volume& V, f3 o, f3 d, float minT, floa
     return success;
 }
 
+}  // namespace vol
+}  // namespace ctl
+#include "volume_grid.h"
+namespace ctl {
+namespace vol {
+
+// ---- VolumeRegion's dispatch on the type (CALLER(tau), CALLER(sampleDistance), CALLER(sigma_s), Volumes.h:289-337).  GRID = false is the code of a table without grid
+// regions — what it was before VolumeGrid was carried, so that the kernels of such scenes keep their code; GRID = true adds the type test
+template <bool GRID> HD f3 region_tau_d(const table& T, uint32_t i, f3 o, f3 d, float minT, float maxT) {
+    if constexpr (GRID) { if (T.v[i].type == CTL_VOLUME_GRID) return grid_tau(region_of(T, i), o, d, minT, maxT); }
+    return region_tau(T.v[i], o, d, minT, maxT);
+}
+template <bool GRID> HD bool region_sample_distance_d(const table& T, uint32_t i, f3 o, f3 d, float minT, float maxT, float rand, medium_rec& mRec) {
+    if constexpr (GRID) { if (T.v[i].type == CTL_VOLUME_GRID) return grid_sample_distance(region_of(T, i), o, d, minT, maxT, rand, mRec); }
+    return region_sample_distance(T.v[i], o, d, minT, maxT, rand, mRec);
+}
+template <bool GRID> HD f3 region_sigma_s_d(const table& T, uint32_t i, f3 p) {
+    if constexpr (GRID) { if (T.v[i].type == CTL_VOLUME_GRID) return grid_sigma_s(region_of(T, i), p); }
+    return inside_world(T.v[i], p) ? a3(T.v[i].sig_s) : f3(0.0f);
+}
+
 // ---- KernelAggregateVolume (Volumes.cu:219-336)
 HD bool intersect(const table& T, f3 o, f3 d, float minT, float maxT, float& t0, float& t1) {
     t0 = FLT_MAX; t1 = -FLT_MAX;
@@ -137,9 +164,9 @@ HD bool intersect(const table& T, f3 o, f3 d, float minT, float maxT, float& t0,
     }
     return t0 < t1;
 }
-HD f3 tau(const table& T, f3 o, f3 d, float minT, float maxT) {
+template <bool GRID = false> HD f3 tau(const table& T, f3 o, f3 d, float minT, float maxT) {
     f3 s(0.0f);
-    for (uint32_t i = 0; i < T.n; i++) s = s + region_tau(T.v[i], o, d, minT, maxT);
+    for (uint32_t i = 0; i < T.n; i++) s = s + region_tau_d<GRID>(T, i, o, d, minT, maxT);
     return s;
 }
 // ffsn (Volumes.cu:303-308): the n-th set bit as a MASK — which sampleVolume then uses as an index, as written
@@ -162,10 +189,10 @@ HD int sample_volume(const table& T, f3 o, f3 d, float minT, float maxT, float& 
     pdf = 1.0f / n;
     return (i >= 0 && (uint32_t)i < T.n) ? i : -1;
 }
-HD bool sample_distance(const table& T, f3 o, f3 d, float minT, float maxT, float sample, medium_rec& mRec) {
+template <bool GRID = false> HD bool sample_distance(const table& T, f3 o, f3 d, float minT, float maxT, float sample, medium_rec& mRec) {
     float vol_sample_pdf = 0;
     const int vi = sample_volume(T, o, d, minT, maxT, sample, vol_sample_pdf);
-    return vi >= 0 && region_sample_distance(T.v[vi], o, d, minT, maxT, sample, mRec);
+    return vi >= 0 && region_sample_distance_d<GRID>(T, (uint32_t)vi, o, d, minT, maxT, sample, mRec);
 }
 
 // ---- phase functions (PhaseFunction.cu)
@@ -235,12 +262,12 @@ HD float phase_sample(const ctl_phase_function& F, f3 wi, f3& wo, float& pdf, f2
     }
 }
 // KernelAggregateVolume::p (Volumes.cu:278-289): weighted by the regions' average sigma_s, over the regions whose WorldBound() holds the point — 0 outside all of them
-HD float phase_p(const table& T, f3 p, f3 wi, f3 wo) {
+template <bool GRID = false> HD float phase_p(const table& T, f3 p, f3 wi, f3 wo) {
     float ph = 0, sumWt = 0;
     for (uint32_t i = 0; i < T.n; i++) {
         f3 lo, hi; world_bound(T.v[i], lo, hi);
         if (aabb_contains(lo, hi, p)) {
-            const float wt = savg(inside_world(T.v[i], p) ? a3(T.v[i].sig_s) : f3(0.0f));
+            const float wt = savg(region_sigma_s_d<GRID>(T, i, p));
             sumWt += wt;
             ph += wt * phase_eval(T.v[i].phase, wi, wo);
         }
@@ -255,23 +282,42 @@ HD float phase_sample_aggregate(const table& T, f3 p, f3 wi, f3& wo, float& pdf,
     return 0.0f;
 }
 // Transmittance (Kernel/TraceAlgorithms.cu:22-31): the aggregate's (a, b) — FLT_MAX / -FLT_MAX on a miss — go into tau, which intersects again
-HD f3 transmittance(const table& T, f3 o, f3 d, float tmin, float tmax) {
+template <bool GRID = false> HD f3 transmittance(const table& T, f3 o, f3 d, float tmin, float tmax) {
     if (T.n > 0) {
         float a, b; intersect(T, o, d, tmin, tmax, a, b);
-        return sexp(-tau(T, o, d, a, b));
+        return sexp(-tau<GRID>(T, o, d, a, b));
     }
     return f3(1.0f);
 }
 // KernelDynamicScene::evalTransmittance (Engine/KernelDynamicScene.cu:90-96)
-HD f3 eval_transmittance(const table& T, f3 p1, f3 p2) {
+template <bool GRID = false> HD f3 eval_transmittance(const table& T, f3 p1, f3 p2) {
     f3 d = p2 - p1;
     const float l = length(d);
     d = d / l;
-    return sexp(-tau(T, p1, d, 0.0f, l));
+    return sexp(-tau<GRID>(T, p1, d, 0.0f, l));
 }
 
 // ---- host: the table of a description.  `where` = the array the kernels read (device memory, or the host array itself for the host yardstick)
-inline table make_table(const ctl_volume* where, uint32_t n) { table T{}; T.v = where; T.n = n; return T; }
+inline table make_table(const ctl_volume* where, uint32_t n, const grid_rec* g = nullptr, const float* cells = nullptr) { table T{}; T.v = where; T.n = n; T.g = g; T.cells = cells; return T; }
+// ---- host: the grid records of a (validated) description, one slot per region, and their floats in one buffer
+struct grid_pack {
+    std::vector<grid_rec> recs; std::vector<float> cells; bool any = false;
+    bool same(const grid_pack& o) const {
+        return any == o.any && cells.size() == o.cells.size() && (recs.empty() || std::memcmp(recs.data(), o.recs.data(), recs.size() * sizeof(grid_rec)) == 0) &&
+               (cells.empty() || std::memcmp(cells.data(), o.cells.data(), cells.size() * 4) == 0);
+    }
+};
+inline void pack_grids(const ctl_scene_desc& d, grid_pack& P) {
+    P.recs.assign(CTL_MAX_VOL_COUNT, grid_rec{}); P.cells.clear(); P.any = d.n_volume_grids != 0;
+    auto put = [&](const float* data, const uint32_t* dim) { const uint32_t off = (uint32_t)P.cells.size(); P.cells.insert(P.cells.end(), data, data + (size_t)dim[0] * dim[1] * dim[2]); return off; };
+    for (uint32_t k = 0; k < d.n_volume_grids; k++) {
+        const ctl_volume_grid& G = d.volume_grids[k]; grid_rec& R = P.recs[G.volume];
+        R.single = G.single_grid ? 1u : 0u;
+        for (int c = 0; c < 3; c++) { R.sa_min[c] = G.sig_a_min[c]; R.sa_max[c] = G.sig_a_max[c]; R.ss_min[c] = G.sig_s_min[c]; R.ss_max[c] = G.sig_s_max[c]; }
+        if (R.single) { for (int c = 0; c < 3; c++) R.dim[c] = G.dim[c]; R.off = put(G.data, G.dim); }
+        else { for (int c = 0; c < 3; c++) { R.dim_a[c] = G.dim_a[c]; R.dim_s[c] = G.dim_s[c]; } R.off_a = put(G.data_a, G.dim_a); R.off_s = put(G.data_s, G.dim_s); }
+    }
+}
 // ---- host: the derived fields
 // KajiyaKayPhaseFunction::Update (PhaseFunction.cu:64-77), with the shared fp32 functions
 inline float kajiya_kay_normalization(float exponent) {

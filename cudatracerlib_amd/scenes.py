@@ -172,6 +172,37 @@ def fog_box(width=256, height=256, sigma_a=0.0005, sigma_s=0.002, phase=None, fr
     return sc
 
 
+def smoke_density(dims, seed=7):
+    """a seeded, smooth, non-constant density in [0.05, 1] on a grid of shape `dims`: a few low-frequency cosines"""
+    rs = np.random.RandomState(seed)
+    x, y, z = np.meshgrid(*[(np.arange(n) + 0.5) / n for n in dims], indexing="ij")
+    f = np.zeros(dims, np.float64)
+    for _ in range(4):
+        k = rs.uniform(0.5, 2.5, 3); ph = rs.uniform(0, 2 * np.pi)
+        f += np.cos(2 * np.pi * (k[0] * x + k[1] * y + k[2] * z) + ph)
+    f = (f - f.min()) / max(f.max() - f.min(), 1e-30)
+    return (0.05 + 0.95 * f).astype(np.float32)
+
+
+def smoke_box(width=256, height=256, dims=(3, 4, 5), sigma_a=0.0005, sigma_s=0.002, phase=None, fraction=(1.0, 1.0, 1.0), seed=7, three_grid_dims=None):
+    """fog_box with a heterogeneous medium: ONE VolumeGrid over the scene box whose density (smoke_density(dims, seed)) is seeded, smooth and non-constant, on a
+    non-cubic grid by default.  sigma_a / sigma_s are the coefficients at density 1 (sigAMax / sigSMax; the minima are 0).  three_grid_dims = (dimsA, dimsS): the
+    three-grid form with two densities of those shapes instead.  Only the PathTracer plugin renders it.  The builder is returned after UpdateScene(); .volume is the
+    api.GridVolume, .volume_index its slot."""
+    sc = cornell_box(width, height)
+    lo = np.array(sc.desc.box_min, np.float32); hi = np.array(sc.desc.box_max, np.float32)
+    hi = (lo + (hi - lo) * np.asarray(fraction, np.float32)).astype(np.float32)
+    m = api.box_to_volume_matrix(lo, hi)
+    if three_grid_dims is None:
+        sc.volume = api.grid_volume(m, density=smoke_density(tuple(dims), seed), sig_a=(0.0, sigma_a), sig_s=(0.0, sigma_s), phase=phase)
+    else:
+        sc.volume = api.grid_volume(m, density_a=smoke_density(tuple(three_grid_dims[0]), seed), density_s=smoke_density(tuple(three_grid_dims[1]), seed + 1),
+                                    sig_a=(0.0, sigma_a), sig_s=(0.0, sigma_s), phase=phase)
+    sc.volume_index = sc.CreateGridVolume(sc.volume)
+    sc.UpdateScene()
+    return sc
+
+
 def _rotation(rs):
     q = rs.normal(size=4); q /= np.linalg.norm(q)
     w, x, y, z = q
@@ -205,8 +236,8 @@ def build_scene(desc, sensor=None):
     sc.setCamera(pos, target, up, fov, w, h)
     if sensor is not None:
         sc.setSensor(sensor)
-    for v in desc.get("volumes", ()):   # participating media: ctl_volume records (api.homogeneous_volume)
-        sc.CreateVolume(v)
+    for v in desc.get("volumes", ()):   # participating media: ctl_volume records (api.homogeneous_volume) or api.GridVolume (api.grid_volume)
+        sc.CreateGridVolume(v) if isinstance(v, api.GridVolume) else sc.CreateVolume(v)
     sc.UpdateScene()
     return sc
 

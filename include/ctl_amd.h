@@ -225,7 +225,8 @@ typedef struct {
     float ks, kd, exponent;    /* KajiyaKayPhaseFunction::m_ks, m_kd, m_exponent                                 */
     float normalization;       /* DERIVED: KajiyaKayPhaseFunction::m_normalization (ctl_volume_update)           */
 } ctl_phase_function;          /* 24 B */
-enum { CTL_VOLUME_HOMOGENEOUS = 1 };   /* HomogeneousVolumeDensity; VolumeGrid (2) is not carried */
+enum { CTL_VOLUME_HOMOGENEOUS = 1,     /* HomogeneousVolumeDensity */
+       CTL_VOLUME_GRID = 2 };          /* VolumeGrid: a ctl_volume of this type plus exactly one ctl_volume_grid record (below); its sig_a / sig_s / le are 0 */
 #define CTL_MAX_VOL_COUNT 16       /* KernelAggregateVolume::MAX_VOL_COUNT */
 /* A region is the unit cube [0,1]^3 under volume_to_world (BaseVolumeRegion); its coefficients hold inside and are 0 outside. */
 typedef struct {
@@ -235,6 +236,21 @@ typedef struct {
     ctl_float4x4 world_to_volume;      /* DERIVED: VolumeToWorld.inverse() (BaseVolumeRegion::Update; ctl_volume_update) */
     float sig_a[3], sig_s[3], le[3];   /* absorption, scattering, emission (the path tracer never reads le)      */
 } ctl_volume;                          /* 192 B */
+/* VolumeGrid (SceneTypes/Volumes.h:184-287): the density grids of one CTL_VOLUME_GRID region, a record in a side array of the description.  single_grid != 0: one grid
+ * (`dim`, `data`) serves absorption and scattering (VolumeGrid(func, ToWorld, buffer, dim)); otherwise gridA (`dim_a`, `data_a`) and gridS (`dim_s`, `data_s`) (the
+ * three-grid form; gridL is not carried: PathTrace never reads Lve, and m_stepSize is not carried: nothing reads it).  The floats lie in the reference's linear order,
+ * DenseVolGrid::idx (Volumes.h:139-142), dim[0] * dim[1] * dim[2] of them per grid, in HOST memory.  A coefficient at a point is min + (max - min) * density. */
+#define CTL_MAX_GRID_CELLS (1u << 22)  /* cells per grid: 16 MiB of floats, so that the 16 regions of a table, two grids each, stay within 512 MiB of device memory */
+typedef struct {
+    uint32_t volume;                   /* index of its ctl_volume, whose type is CTL_VOLUME_GRID                 */
+    uint32_t single_grid;              /* VolumeGrid::singleGrid                                                 */
+    uint32_t dim[3];                   /* grid.dim (single form)                                                 */
+    uint32_t dim_a[3], dim_s[3];       /* gridA.dim, gridS.dim (three-grid form)                                 */
+    float sig_a_min[3], sig_a_max[3], sig_s_min[3], sig_s_max[3], le_min[3], le_max[3];   /* sigAMin ... leMax (le*: carried, never read) */
+    const float* data;                 /* grid   (single form; otherwise NULL)                                   */
+    const float* data_a;               /* gridA  (three-grid form; otherwise NULL)                               */
+    const float* data_s;               /* gridS  (three-grid form; otherwise NULL)                               */
+} ctl_volume_grid;                     /* 144 B */
 
 /* Engine/KernelDynamicScene.h:28-109 restated with plain pointers (HOST memory). */
 typedef struct {
@@ -262,6 +278,7 @@ typedef struct {
     const ctl_mipmap* images;            uint32_t n_images;       /* m_sTexData (level 0) */
     const ctl_rough_transmittance* rough_transmittance;           /* [3] or NULL (needed by roughplastic only) */
     const ctl_volume* volumes;           uint32_t n_volumes;      /* m_sVolume (KernelAggregateVolume): at most CTL_MAX_VOL_COUNT regions; NULL / 0 = no participating media */
+    const ctl_volume_grid* volume_grids; uint32_t n_volume_grids; /* one record per CTL_VOLUME_GRID region of `volumes`; NULL / 0 = none (a zeroed description has none) */
 } ctl_scene_desc;
 
 /* BSDF::Update() (SceneTypes/BSDF_Simple.h:255-264 plastic, :298-304 roughplastic, :332-337 phong, :371-376 ward; BSDF_Complex.h:37-44 coating, :117-125
@@ -335,6 +352,14 @@ int ctl_builder_set_camera(ctl_builder* b, const ctl_sensor* sensor);
  * ctl_scene_update applies it in place (CTL_DIFF_VOLUMES).  Only the PathTracer plugin renders media; the other plugins refuse a scene that has any. */
 int ctl_builder_create_volume(ctl_builder* b, const ctl_volume* volume, uint32_t* index_out);
 int ctl_builder_set_volume(ctl_builder* b, uint32_t index, const ctl_volume* volume);
+/* DynamicScene::CreateVolume(w, h, d, toWorld, phase) and (wA, hA, dA, wS, hS, dS, wL, hL, dL, toWorld, phase) (Engine/DynamicScene.cpp:794-812): a VolumeGrid region with
+ * n_dims = 3 (one grid) or 9 dims (gridA, gridS, gridL; the L dims are accepted and ignored).  As the reference's constructors leave it: the grids' floats and
+ * sigAMin ... leMax are 0.  ctl_builder_set_volume_grid_data COPIES n = dim[0] * dim[1] * dim[2] floats, in DenseVolGrid::idx's linear order, into grid `which`
+ * (0: grid / gridA, 1: gridS); ctl_builder_set_volume_grid_coefficients sets sigAMin, sigAMax, sigSMin, sigSMax (3 floats each).  ctl_builder_set_volume edits the
+ * region (type, matrix, phase function) as before; made homogeneous there, the region loses its grids at the next finalize. */
+int ctl_builder_create_volume_grid(ctl_builder* b, const uint32_t* dims, uint32_t n_dims, const ctl_float4x4* volume_to_world, const ctl_phase_function* phase, uint32_t* index_out);
+int ctl_builder_set_volume_grid_data(ctl_builder* b, uint32_t index, uint32_t which, const float* data, uint32_t n);
+int ctl_builder_set_volume_grid_coefficients(ctl_builder* b, uint32_t index, const float* sig_a_min, const float* sig_a_max, const float* sig_s_min, const float* sig_s_max);
 /* DynamicScene::UpdateScene + getKernelSceneData (DynamicScene.cpp:480-589): builds the scene BVH and fills
  * `out` with pointers that stay valid until the builder is destroyed or finalized again. */
 int ctl_builder_finalize(ctl_builder* b, ctl_scene_desc* out);
@@ -385,7 +410,7 @@ enum { CTL_DIFF_CAMERA = 1,       /* ctl_scene_desc::camera                     
                                      images, rough-transmittance tables                                                                           */
        CTL_DIFF_GEOMETRY = 32,    /* only VALUES of the geometry arrays: the contents of tri_data and woop and the float boxes of bvh_nodes — a deformed mesh
                                      (ctl_builder_update_mesh) — with everything CTL_DIFF_TOPOLOGY names equal                                    */
-       CTL_DIFF_VOLUMES = 64 };   /* `volumes` / `n_volumes`: the participating media, and nothing else                                            */
+       CTL_DIFF_VOLUMES = 64 };   /* `volumes` / `n_volumes` and the grid records with their floats: the participating media, and nothing else                                            */
 int ctl_scene_desc_diff(const ctl_scene_desc* a, const ctl_scene_desc* b, uint32_t* mask_out);
 /* Everything ctl_scene_create and ctl_scene_update refuse a description for that can be judged from the description alone (host only, no device call): node transforms,
  * sensor, lights, textures, materials, the depth of the two-level BVH.  parts == 0: as ctl_scene_create checks; else the CTL_DIFF_* parts to check, as ctl_scene_update
@@ -770,7 +795,7 @@ int ctl_shading_eval(const ctl_scene* scene, int32_t build, int32_t what, const 
                      uint32_t n, const float* queries, uint32_t query_stride, float* out, uint32_t out_stride);
 
 /* TEST INFRASTRUCTURE: the participating-media functions (csrc/volume.h) one call per query, after ctl_shading_eval and ctl_shared_math_eval.  `desc` supplies volumes /
- * n_volumes (nothing else of it is read; the derived fields must be current: ctl_volume_update, or a description from the builder).  on_device = 0 runs the functions
+ * n_volumes and volume_grids / n_volume_grids (nothing else of it is read; the derived fields must be current: ctl_volume_update, or a description from the builder).  on_device = 0 runs the functions
  * on the host and needs no GPU — the yardstick; 1 runs one small kernel, one lane per query (CTL_ERR_NO_DEVICE without a device).  The two are bit-identical.
  * A query row is CTL_VEVAL_QUERY_FLOATS floats, a result row CTL_VEVAL_RESULT_FLOATS floats, unused ones 0; a [volume] index travels as the BITS of its float and is
  * checked against n_volumes before anything runs (CTL_ERR_INVALID, as for a description the validator refuses or an unknown `what`).  No reference counterpart. */
@@ -789,7 +814,11 @@ enum { CTL_VEVAL_REGION_INTERSECT = 0,        /* [volume] o(3) d(3) minT maxT   
        CTL_VEVAL_P = 9,                       /* p(3) wi(3) wo(3)                    -> value                                              (KernelAggregateVolume::p)                */
        CTL_VEVAL_SAMPLE = 10,                 /* p(3) wi(3) sample(2)                -> weight pdf wo(3), pdf and wo 0 where no region is found (KernelAggregateVolume::Sample)      */
        CTL_VEVAL_TRANSMITTANCE = 11,          /* o(3) d(3) tmin tmax                 -> T(3)                                               (Transmittance, TraceAlgorithms.cu:22-31) */
-       CTL_VEVAL_EVAL_TRANSMITTANCE = 12 };   /* p1(3) p2(3)                         -> T(3)                                               (KernelDynamicScene::evalTransmittance)   */
+       CTL_VEVAL_EVAL_TRANSMITTANCE = 12,     /* p1(3) p2(3)                         -> T(3)                                               (KernelDynamicScene::evalTransmittance)   */
+       /* the codes above dispatch on the region's type; the ones below need a CTL_VOLUME_GRID region (CTL_ERR_INVALID otherwise) */
+       CTL_VEVAL_GRID_VALUE = 13,             /* [volume] which(bits: 0 grid / gridA, 1 gridS) p(3) in voxel space -> value                (DenseVolGrid::sampleTrilinear)           */
+       CTL_VEVAL_REGION_SIGMA = 14,           /* [volume] p(3)                       -> sigma_a(3) sigma_s(3) sigma_t(3)                   (VolumeGrid::sigma_a / sigma_s / sigma_t) */
+       CTL_VEVAL_GRID_MARCH = 15 };           /* [volume] o(3) d(3) minT maxT        -> march steps, 1 if the step cap was reached         (VolumeGrid::tau's TraverseGridRay)       */
 int ctl_volume_eval(const ctl_scene_desc* desc, int32_t what, const float* queries, uint32_t n, float* out, int32_t on_device);
 
 /* device memory helpers so that Python callers need no HIP binding */
