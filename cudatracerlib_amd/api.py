@@ -282,6 +282,21 @@ class FlatBvh:
         _check(lib.ctl_flat_bvh_arrays(self._h, C.byref(self.desc)))
         return self
 
+    def rebuild(self, desc):
+        """ctl_flat_bvh_rebuild: the tree refitted to `desc` and then REBUILT over the same leaf entries (csrc/flat_rebuild.h: Morton codes, sort, Karras's hierarchy
+        collapsed 4-wide, breadth-first layout) on the host — the yardstick of Scene.update(desc) + Scene.rebuild_flat().  Q4 trees with implied links only.  Returns self."""
+        _check(lib.ctl_flat_bvh_rebuild(self._h, C.byref(desc)))
+        _check(lib.ctl_flat_bvh_arrays(self._h, C.byref(self.desc)))
+        return self
+
+    def levels(self):
+        """ctl_flat_bvh_levels: (level_start (n_levels + 1,), level_nodes (n_nodes,)) uint32 copies — the nodes by depth as a refit walks them"""
+        ls, ln = C.POINTER(u32)(), C.POINTER(u32)(); nl, nn = u32(), u64()
+        _check(lib.ctl_flat_bvh_levels(self._h, C.byref(ls), C.byref(nl), C.byref(ln), C.byref(nn)))
+        if nn.value == 0:
+            return np.zeros(0, np.uint32), np.zeros(0, np.uint32)
+        return np.ctypeslib.as_array(ls, shape=(nl.value + 1,)).copy(), np.ctypeslib.as_array(ln, shape=(nn.value,)).copy()
+
     def nodes(self):
         n = self.desc.n_nodes * self.desc.node_bytes // 4
         return np.ctypeslib.as_array(C.cast(self.desc.nodes, C.POINTER(C.c_uint32)), shape=(n,)).reshape(self.desc.n_nodes, -1)
@@ -945,6 +960,15 @@ class Scene:
         _check(lib.ctl_scene_get_update_stats(self._h, C.byref(st)))
         return {k: getattr(st, k) for k, _ in st._fields_}
 
+    def rebuild_flat(self):
+        """ctl_scene_rebuild_flat: a new flattened Q4 tree over the leaf entries the scene holds, made on the device in place (csrc/flat_rebuild.hip) — for a tree that
+        refits have degraded.  Returns the stats dict (n_nodes, n_entries, max_depth, levels, node_area_before / _after, sort_ms, topology_ms, refit_ms, total_ms).
+        CtlError(ERR_UNSUPPORTED) for a scene that is not a flattened Q4 scene with refit data and implied links, or when the new tree would be too deep (the scene keeps
+        its tree).  Start the next pass with new_trace."""
+        st = ctl_scene_rebuild_stats()
+        _check(lib.ctl_scene_rebuild_flat(self._h, C.addressof(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
     def bind_skin(self, mesh, rest_positions, indices, bone_indices, bone_weights, n_bones, rest_normals=None):
         """ctl_scene_bind_skin: binds `mesh` to a rest pose (arrays as DynamicScene.add_mesh takes them; indices None: a soup; rest_normals None: computed once) and to
         its bone bytes, uint8 (n_vert, 8) each.  The mesh is device-owned until unbind_skin."""
@@ -1005,6 +1029,18 @@ ERR_INVALID, ERR_NO_DEVICE, ERR_UNSUPPORTED = -1, -2, -5
 
 class ctl_scene_update_stats(C.Structure):
     _fields_ = [("node_area_before", C.c_double), ("node_area_after", C.c_double), ("refit_ms", f32), ("refit_levels", u32), ("mask", u32), ("restamped", u32)]
+
+
+class ctl_scene_rebuild_stats(C.Structure):
+    _fields_ = [("n_nodes", u32), ("n_entries", u32), ("max_depth", u32), ("levels", u32), ("node_area_before", C.c_double), ("node_area_after", C.c_double),
+                ("sort_ms", f32), ("topology_ms", f32), ("refit_ms", f32), ("total_ms", f32)]
+
+
+# (declared only where the library has them: tools/ab_bench.py loads the parent commit's library through $CTL_AMD_LIB for a same-box A/B of bench.py, which calls none
+# of them; calling one on such a library raises AttributeError)
+for _n, _a in (("ctl_scene_rebuild_flat", [C.c_void_p, C.c_void_p]), ("ctl_flat_bvh_rebuild", [C.c_void_p, C.c_void_p]), ("ctl_flat_bvh_levels", [C.c_void_p] * 5)):
+    if hasattr(lib, _n):
+        getattr(lib, _n).argtypes = _a
 
 
 def _ptr(a):

@@ -8,6 +8,7 @@
 #include "scene_checks.h"
 #include "mitsuba_loader.h"
 #include "flatten.h"
+#include "flat_rebuild.h"
 #include "mesh_skin.h"
 #include "material_factory.h"
 #include "material_textures.h"
@@ -391,6 +392,20 @@ int ctl_skin_mesh_host(const ctl_scene_desc* desc, uint32_t mesh_index, const fl
     CTL_TRY skin_mesh_host(*desc, mesh_index, rest_positions, rest_normals, n_vert, indices, n_tri, bone_indices, bone_weights, n_bones, bones0, bones1, lerp, positions_out, normals_out, tri_data_out, woop_out); CTL_CATCH
 }
 int ctl_flat_bvh_refit(ctl_flat_bvh* h, const ctl_scene_desc* new_desc) { CTL_REQUIRE(h && new_desc, "null argument"); CTL_TRY refit_flat_scene(h->f, *new_desc, nullptr); CTL_CATCH }
+// ---- rebuild of the flattened tree (flat_rebuild.hip, flat_rebuild.cpp)
+int ctl_scene_rebuild_flat(ctl_scene* scene, ctl_scene_rebuild_stats* stats_out) {
+    if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
+    CTL_REQUIRE(scene, "null scene");
+    CTL_TRY scene->s.rebuild_flat(stats_out); CTL_CATCH
+}
+int ctl_flat_bvh_rebuild(ctl_flat_bvh* h, const ctl_scene_desc* new_desc) { CTL_REQUIRE(h && new_desc, "null argument"); CTL_TRY rebuild_flat_scene(h->f, *new_desc, nullptr); CTL_CATCH }
+int ctl_flat_bvh_levels(const ctl_flat_bvh* h, const uint32_t** level_start, uint32_t* n_levels, const uint32_t** level_nodes, uint64_t* n_level_nodes) {
+    CTL_REQUIRE(h && level_start && n_levels && level_nodes && n_level_nodes, "null argument");
+    const auto& R = h->f.refit;
+    *level_start = R.level_start.data(); *n_levels = R.level_start.empty() ? 0u : (uint32_t)R.level_start.size() - 1u;
+    *level_nodes = R.level_nodes.data(); *n_level_nodes = R.level_nodes.size();
+    return CTL_OK;
+}
 int ctl_scene_read_flat_bvh(ctl_scene* scene, ctl_flat_bvh** out) {
     CTL_REQUIRE(scene && out, "null argument");
     CTL_TRY std::unique_ptr<ctl_flat_bvh> h(new ctl_flat_bvh()); scene->s.read_flat_bvh(h->f); *out = h.release(); CTL_CATCH

@@ -62,6 +62,9 @@ public:
     uint32_t update(const ctl_scene_desc& d, ctl_scene_update_stats* stats);
     uint32_t last_mask() const { return last_mask_; }   // the CTL_DIFF_* bits the last update() found, also when it refused
     const ctl_scene_update_stats& last_update() const { return last_update_; }
+    // ctl_scene_rebuild_flat (flat_rebuild.hip): a new flattened Q4 tree over the entries the scene holds, made on the device in place; refusals (unsupported_error) and failed
+    // allocations leave the scene as it was.  Synchronous.
+    void rebuild_flat(ctl_scene_rebuild_stats* stats);
     void read_flat_bvh(flat_scene& out);   // the device tree copied back, un-stamped: what flatten_scene handed to the upload, after any refit
     // skinned meshes (mesh_skin.hip; ctl_scene_bind_skin, ctl_scene_animate_mesh, ctl_scene_read_mesh_geometry, ctl_scene_unbind_skin).  A bound mesh is device-owned: update()
     // neither compares nor uploads its values
@@ -98,6 +101,7 @@ private:
     std::vector<int32_t> flat_child_links_;
     size_t flat_n_nodes_ = 0, flat_n_entries_ = 0, flat_slab_nodes_ = 0; int flat_max_depth_ = 0; bool flat_root_slab_ = false;
     dbuf<uint32_t> refit_part_index_, refit_level_nodes_; dbuf<refit_box> refit_part_boxes_, refit_ebox_, refit_nbox_; dbuf<double> refit_carry_, refit_area_;
+    dbuf<unsigned char> rebuild_temp_;   // rocPRIM's temporary storage (sort and scan), sized by its query calls, kept between rebuilds
     dbuf<float4> top_nodes_, bot_nodes_, leaf_tris_, inst_, inst_fwd_, flat_nodes_, flat_leaves_; dbuf<float2> normal_lut_;
     dbuf<uint4> tri_data_, node_info_;
     dbuf<ctl_material> mats_; dbuf<ctl_light> lights_; dbuf<unsigned char> anim_; dbuf<uint32_t> texels_; dbuf<ctl_mipmap> images_; dbuf<dev_mip_levels> mip_levels_; dbuf<float> mip_lut_; dbuf<float> rt_data_, rt_reduced_; dbuf<ctl_rough_transmittance> rt_;

@@ -435,8 +435,8 @@ int ctl_scene_desc_check(const ctl_scene_desc* desc, uint32_t parts, uint32_t st
  * The scene keeps its own host copy of the description (the geometry arrays as hashes: one of their structure, one per mesh of their values, which tell an update WHICH
  * meshes changed): new_desc's pointers are not kept. */
 int ctl_scene_update(ctl_scene* scene, const ctl_scene_desc* new_desc, uint32_t* mask_out);
-/* Report of the last ctl_scene_update: summed surface area of the flattened tree's node boxes before and after a refit (a SAH proxy: a host re-creates the scene when
- * the ratio says the tree has degraded — the library has no policy), both 0 when the update did not refit; HIP-event time of the refit kernels. */
+/* Report of the last ctl_scene_update: summed surface area of the flattened tree's node boxes before and after a refit (a SAH proxy: a host calls
+ * ctl_scene_rebuild_flat, below, or re-creates the scene when the ratio says the tree has degraded — the library has no policy), both 0 when the update did not refit; HIP-event time of the refit kernels. */
 typedef struct { double node_area_before, node_area_after; float refit_ms; uint32_t refit_levels; uint32_t mask; uint32_t restamped; } ctl_scene_update_stats;
 int ctl_scene_get_update_stats(ctl_scene* scene, ctl_scene_update_stats* out);
 /* ---- skinned meshes: the reference's AnimatedMesh::k_ComputeState with g_ComputeVertices / g_ComputeTriangles (Engine/AnimatedMesh.{h,cpp,cu}) — the host hands over bone
@@ -513,6 +513,29 @@ void ctl_flat_bvh_destroy(ctl_flat_bvh* h);
  * shows afterwards.  CTL_ERR_INVALID where ctl_scene_update would refuse the geometry (another structure, a degenerate triangle that is regular now).
  * Other formats: CTL_ERR_UNSUPPORTED. */
 int ctl_flat_bvh_refit(ctl_flat_bvh* h, const ctl_scene_desc* new_desc);
+/* ---- rebuild of the flattened tree (csrc/flat_rebuild.h, flat_rebuild.hip, flat_rebuild.cpp; INTEGRATION.md "Updating a scene").  A refit keeps the tree correct, not
+ * good: after large motions the node area grows and the rays/s fall (RESULTS.md "In-place scene updates").  ctl_scene_rebuild_flat makes a NEW tree on the device, in
+ * place, from what the scene holds — the leaf entries as they stand in HBM after any number of updates, deformations and poses, and the transforms of the last update:
+ * entry boxes, a 63-bit Morton code per entry, a radix sort, Karras's binary hierarchy over the sorted codes collapsed 4-wide level by level, the entries gathered into
+ * their new order, the boxes by the refit kernels.  The set of entries does not change (a triangle that was degenerate at creation still needs a new scene); split
+ * references keep their clip box; the rebuilt tree carries no oriented slabs.  Hits stay the reference's bit for bit: the tree only culls.  Synchronous like
+ * ctl_scene_update: call it between passes and start the next pass with new_trace; tracers follow the new arrays by themselves.  Everything that worked on the old tree
+ * works on the new one (ctl_scene_update, ctl_scene_animate_mesh, ctl_scene_read_flat_bvh, another rebuild).  The library has no policy: the host decides when to call
+ * (an LBVH without slabs or split decisions of its own may trace slower than a lightly refitted tree).
+ * Memory: during the call the entries exist twice (a second buffer of 128 B per entry — 1.1 GB more on an 8.6 M-entry scene) next to the sort's keys and a node buffer
+ * of 32 B per entry; the old node and entry buffers are freed after the swap.
+ * Refusals, all before anything is written: CTL_ERR_NO_DEVICE (checked first); CTL_ERR_UNSUPPORTED for a scene that is not flattened, a CTL_FLAT_Q8 scene, a tree
+ * without refit data or with explicit links, and a rebuilt tree whose depth does not fit the traversal stack (the new tree is made in buffers of its own; the old one
+ * stays in place).  A failed allocation leaves the scene as it was.
+ * stats_out (may be NULL): the node areas as ctl_scene_update_stats reports them (before = the tree as it stood, after = the rebuilt one); HIP-event times of the key +
+ * sort stage, the topology + gather stage, the box stages (entry boxes + node boxes) and the whole call.
+ * ctl_flat_bvh_rebuild does the same to a host handle for the pose of new_desc — a ctl_flat_bvh_refit to new_desc followed by the rebuild, with the same single-source
+ * arithmetic: the yardstick of the device, byte for byte (nodes, entries, part_index, levels).  Too deep a tree: CTL_ERR_UNSUPPORTED with the handle left refitted.
+ * ctl_flat_bvh_levels: the nodes by depth as the refit walks them (level l = level_nodes[level_start[l] .. level_start[l + 1])); after a rebuild level_nodes is 0, 1, 2 .. */
+typedef struct { uint32_t n_nodes, n_entries, max_depth, levels; double node_area_before, node_area_after; float sort_ms, topology_ms, refit_ms, total_ms; } ctl_scene_rebuild_stats;
+int ctl_scene_rebuild_flat(ctl_scene* scene, ctl_scene_rebuild_stats* stats_out);
+int ctl_flat_bvh_rebuild(ctl_flat_bvh* h, const ctl_scene_desc* new_desc);
+int ctl_flat_bvh_levels(const ctl_flat_bvh* h, const uint32_t** level_start, uint32_t* n_levels, const uint32_t** level_nodes, uint64_t* n_level_nodes);
 /* The flattened tree of a CTL_SCENE_FLATTEN scene copied back from HBM into a handle for ctl_flat_bvh_arrays, with the BSDF-model bits (28..31 of the index word)
  * and the alpha bit (31 of the node word) that ctl_scene_create_ex stamps into the device copy removed: the arrays the test oracle traverses. */
 int ctl_scene_read_flat_bvh(ctl_scene* scene, ctl_flat_bvh** out);

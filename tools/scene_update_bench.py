@@ -20,6 +20,10 @@ Per workload, on one GPU, in one process:
      (a) the host path: DynamicScene.UpdateMesh + ctl_builder_finalize + ctl_scene_update with the positions and normals skinned BEFOREHAND (ctl_skin_mesh_host, not timed);
      (b) ctl_scene_animate_mesh on the mesh bound with ctl_scene_bind_skin (the bind is timed once, apart): wall time and the HIP-event times of the three pose kernels
          and of the refit.  After (b) a camera update on the bound scene is timed too: the bound mesh is neither hashed nor compared.
+  6. (--only rebuild) ctl_scene_rebuild_flat after M3 (one node carried across a third of the scene) and after the deformation D1 of step 4, each on a scene of its
+     own: wall time around the (synchronous) call — the first call, which also loads the kernels and allocates rocPRIM's storage, and the median of 5 further calls —
+     with the stage times of ctl_scene_rebuild_stats; against the re-creation of the same pose measured in the same run (M3: warm cache; D1: as in step 4, the
+     flattened tree necessarily cold); and the Mrays/s of the refitted, the rebuilt and a fresh tree with the node-area ratios.
 One JSON line per workload is appended to --out; --results appends a section to that Markdown file.  bench.py is not involved.
 """
 import argparse
@@ -195,6 +199,75 @@ def skinning(workload, args, sc, scene, node, rec):
     rec["skin_faster_than_host_path"] = bool(rec["skin_animate_ms"] < rec["skin_host_path_ms"])
 
 
+def rebuild_block(scene, args):
+    """Mrays/s of the tree as it stands (refitted), then the rebuild: first call, median of 5 more, the last call's stats, Mrays/s of the rebuilt tree"""
+    r = mrays(scene, args)
+    t = time.perf_counter(); first = scene.rebuild_flat(); first_ms = (time.perf_counter() - t) * 1e3
+    stats = []
+    wall = timed(lambda k: stats.append(scene.rebuild_flat()), 5)
+    st = dict(stats[-1]); st.update(sort_ms=float(np.median([x["sort_ms"] for x in stats])), topology_ms=float(np.median([x["topology_ms"] for x in stats])),
+                                    refit_ms=float(np.median([x["refit_ms"] for x in stats])), total_ms=float(np.median([x["total_ms"] for x in stats])))
+    return dict(refit_mrays=r, rebuilt_mrays=mrays(scene, args), rebuild_first_ms=first_ms, rebuild_ms=wall, stats=st, node_area_refitted=first["node_area_before"], node_area_rebuilt=first["node_area_after"])
+
+
+def rebuilding(workload, args, sc, scene, node, X0, size, rec):
+    # after M3
+    sc.SetNodeTransform(node, motion(X0, size, "M3")); assert scene.update(sc.UpdateScene()) & api.DIFF_TRANSFORMS
+    b = rebuild_block(scene, args)
+    with tempfile.TemporaryDirectory() as cache:
+        api.set_cache_dir(cache)
+        s2 = ctl.Scene(sc.desc, flatten=True); del s2     # warms the cache for exactly this pose
+        t = time.perf_counter(); fresh = ctl.Scene(sc.UpdateScene(), flatten=True); b["recreate_warmcache_ms"] = (time.perf_counter() - t) * 1e3
+        api.set_cache_dir(None)
+    fb = fresh.flat_bvh(); b["fresh_nodes"] = int(fb.desc.n_nodes); del fb
+    b["fresh_mrays"] = mrays(fresh, args); del fresh
+    b["faster_than_recreate"] = bool(b["rebuild_ms"] < b["recreate_warmcache_ms"] and b["rebuild_first_ms"] < b["recreate_warmcache_ms"])
+    rec["rebuild_M3"] = b
+    del scene
+    # after D1, on a scene of its own (the tree as built, refitted to the deformed mesh)
+    sc.SetNodeTransform(node, X0.astype(np.float32))
+    scene = ctl.Scene(sc.UpdateScene(), flatten=True)
+    d = sc.desc
+    mesh = int(d.view("nodes", np.uint32, d.n_nodes, 6)[node, 0])
+    inp = sc.mesh_inputs.get(mesh)
+    P0, I, N, UV = (inp["positions"], inp["indices"], inp["normals"], inp["uvs"]) if inp else (mesh_soup(d, mesh), None, None, None)
+    P1 = ripple(P0, 100)
+    sc.UpdateMesh(mesh, P1, I, normals=N, uvs=UV); assert scene.update(sc.UpdateScene()) & api.DIFF_GEOMETRY
+    b = rebuild_block(scene, args)
+    del scene
+    with tempfile.TemporaryDirectory() as cache:   # the re-creation of step 4: every untouched mesh from the cache, the deformed one and the flattened tree cold
+        api.set_cache_dir(cache)
+        warm = build(workload, args); del warm
+        t = time.perf_counter()
+        again = build(workload, args)
+        cold = api.DynamicScene(); cold.add_mesh(P1, I, normals=N, uvs=UV)
+        builder_ms = (time.perf_counter() - t) * 1e3
+        again.UpdateMesh(mesh, P1, I, normals=N, uvs=UV); again.UpdateScene()
+        t = time.perf_counter(); fresh = ctl.Scene(again.desc, flatten=True); b["recreate_deformed_ms"] = builder_ms + (time.perf_counter() - t) * 1e3
+        api.set_cache_dir(None)
+    b["fresh_mrays"] = mrays(fresh, args); del fresh
+    b["faster_than_recreate"] = bool(b["rebuild_ms"] < b["recreate_deformed_ms"] and b["rebuild_first_ms"] < b["recreate_deformed_ms"])
+    rec["rebuild_D1"] = b
+
+
+def markdown_rebuild(recs):
+    out = ["", "## Rebuilding the flattened tree on the device (tools/scene_update_bench.py --only rebuild)", "",
+           "| workload | after | entries | nodes (fresh tree) | depth | ctl_scene_rebuild_flat: first call | median of 5 | key + sort | topology + gather | boxes | re-creation of the same pose |",
+           "|---|---|---|---|---|---|---|---|---|---|---|"]
+    for r in recs:
+        for what, key in (("M3", "recreate_warmcache_ms"), ("D1", "recreate_deformed_ms")):
+            b = r["rebuild_" + what]; st = b["stats"]
+            out.append("| %s | %s | %d | %d (%s) | %d | %.1f ms | %.1f ms | %.2f ms | %.2f ms | %.2f ms | %.0f ms (%s) |" % (r["workload"], what, st["n_entries"], st["n_nodes"], b.get("fresh_nodes", "-"), st["max_depth"],
+                       b["rebuild_first_ms"], b["rebuild_ms"], st["sort_ms"], st["topology_ms"], st["refit_ms"], b[key], "warm cache" if what == "M3" else "flattened tree cold"))
+    out += ["", "| workload | after | refitted tree | rebuilt tree | fresh tree | rebuilt / refitted | rebuilt / fresh | node area: rebuilt / refitted |", "|---|---|---|---|---|---|---|---|"]
+    for r in recs:
+        for what in ("M3", "D1"):
+            b = r["rebuild_" + what]
+            out.append("| %s | %s | %.0f Mrays/s | %.0f Mrays/s | %.0f Mrays/s | %.3f | %.3f | %.3f |" % (r["workload"], what, b["refit_mrays"], b["rebuilt_mrays"], b["fresh_mrays"], b["rebuilt_mrays"] / b["refit_mrays"],
+                       b["rebuilt_mrays"] / b["fresh_mrays"], b["node_area_rebuilt"] / b["node_area_refitted"]))
+    return "\n".join(out) + "\n"
+
+
 def markdown_skin(recs):
     out = ["", "## Skinned meshes: a pose from bone matrices (tools/scene_update_bench.py --only skin)", "",
            "| workload | skinned mesh (triangles x instances) | (a) UpdateMesh + finalize + ctl_scene_update, vertices skinned beforehand (refit kernels) | (b) ctl_scene_animate_mesh, wall | pose kernels | refit kernels | bind, once | camera update, mesh bound |",
@@ -233,6 +306,9 @@ def run(workload, args):
         return rec
     if args.only == "skin":
         skinning(workload, args, sc, scene, node, rec)
+        return rec
+    if args.only == "rebuild":
+        rebuilding(workload, args, sc, scene, node, X0, size, rec)
         return rec
 
     def material(k):
@@ -291,6 +367,8 @@ def markdown_deform(recs):
 def markdown(recs):
     if "skin_animate_ms" in recs[0]:
         return markdown_skin(recs)
+    if "rebuild_M3" in recs[0]:
+        return markdown_rebuild(recs)
     if "update_transform_ms" not in recs[0]:
         return markdown_deform(recs)
     out = ["", "## In-place scene updates (tools/scene_update_bench.py)", "",
@@ -313,7 +391,7 @@ def main():
     ap.add_argument("--depth", type=int, default=8); ap.add_argument("--passes", type=int, default=4)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scene_update.jsonl"))
     ap.add_argument("--results", default=None)
-    ap.add_argument("--only", default=None, choices=["deform", "skin"], help="deform: the camera update and the one-mesh deformation alone; skin: the camera update and the pose change of a bound mesh against the host path")
+    ap.add_argument("--only", default=None, choices=["deform", "skin", "rebuild"], help="rebuild: the camera update and ctl_scene_rebuild_flat after M3 and after D1 against the re-creation of the same pose; deform: the camera update and the one-mesh deformation alone; skin: the camera update and the pose change of a bound mesh against the host path")
     args = ap.parse_args()
     if ctl.device_count() < 1:
         raise SystemExit("scene_update_bench needs a HIP device")
