@@ -289,6 +289,15 @@ class FlatBvh:
         _check(lib.ctl_flat_bvh_arrays(self._h, C.byref(self.desc)))
         return self
 
+    def update_nodes(self, desc, old_of_new):
+        """ctl_flat_bvh_update_nodes: the tree after a change of the node set (old_of_new as Scene.update_nodes takes it), on the host with the device's single-source
+        functions (csrc/flat_nodes.h) — the yardstick of Scene.update_nodes.  A refusal leaves the handle as it was.  Returns self."""
+        M = np.ascontiguousarray(old_of_new, dtype=np.uint32)
+        _check(lib.ctl_flat_bvh_update_nodes(self._h, C.byref(desc), M.ctypes.data, u32(len(M))))
+        self._keepalive = desc
+        _check(lib.ctl_flat_bvh_arrays(self._h, C.byref(self.desc)))
+        return self
+
     def levels(self):
         """ctl_flat_bvh_levels: (level_start (n_levels + 1,), level_nodes (n_nodes,)) uint32 copies — the nodes by depth as a refit walks them"""
         ls, ln = C.POINTER(u32)(), C.POINTER(u32)(); nl, nn = u32(), u64()
@@ -740,6 +749,8 @@ class DynamicScene:
         _check(lib.ctl_builder_create(C.byref(self._h)))
         self.desc = None
         self.mesh_inputs = {}   # mesh index -> dict(positions, indices, normals, uvs) as add_mesh / UpdateMesh last took them: what a caller deforms
+        self._node_ids = []     # per node, in index order: its id — assigned at CreateNode, never reused, kept by DeleteNode's shift (node_ids, Scene.update_nodes)
+        self._next_node_id = 0
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -784,7 +795,26 @@ class DynamicScene:
             m = ctl_float4x4()
             m.m[:] = [float(x) for x in np.asarray(to_world, dtype=np.float32).reshape(16)]
         _check(lib.ctl_builder_add_node(self._h, u32(mesh_index), None if m is None else C.byref(m), C.byref(out)))
+        self._sync_node_ids(out.value)
+        self._node_ids.append(self._next_node_id); self._next_node_id += 1
         return out.value
+
+    def _sync_node_ids(self, n):
+        """nodes the builder made without CreateNode (ParseMitsubaScene) get their ids now"""
+        while len(self._node_ids) < n:
+            self._node_ids.append(self._next_node_id); self._next_node_id += 1
+
+    def DeleteNode(self, node):
+        """DynamicScene::DeleteNode (DynamicScene.cpp:380-384) — ctl_builder_remove_node: the nodes behind `node` move down by one index (their ids stay: node_ids());
+        the node's material copies stay in the table.  CtlError(ERR_UNSUPPORTED) for a node with area lights, CtlError(ERR_INVALID) for a bad index or the last node;
+        UpdateScene() then gives the new description, which Scene.update_nodes applies in place."""
+        _check(lib.ctl_builder_remove_node(self._h, u32(node)))
+        if node < len(self._node_ids):
+            del self._node_ids[node]
+
+    def node_ids(self):
+        """the stable id of every node, in index order (also on the description UpdateScene returns, as desc.node_ids)"""
+        return tuple(self._node_ids)
 
     def SetNodeTransform(self, node, to_world):
         """DynamicScene::SetNodeTransform (DynamicScene.cpp:338-346): the node's area lights follow; UpdateScene() then gives the moved description."""
@@ -920,6 +950,8 @@ class DynamicScene:
         """DynamicScene::UpdateScene + getKernelSceneData(false) (DynamicScene.cpp:480-589): host-side KernelDynamicScene."""
         self.desc = ctl_scene_desc()
         _check(lib.ctl_builder_finalize(self._h, C.byref(self.desc)))
+        self._sync_node_ids(self.desc.n_nodes)
+        self.desc.node_ids = self.node_ids()   # (a Python attribute next to the C fields) what Scene.update_nodes computes its map from
         return self.desc
 
     def getKernelSceneData(self):
@@ -941,6 +973,7 @@ class Scene:
         # (triangles, Woop rows) per mesh, taken while the description is certainly alive: the sizes read_mesh_geometry's buffers must have (an update keeps them)
         self._mesh_counts = mesh_counts(desc)
         self._skins = {}   # mesh -> dict(n_vert, n_bones) of the bound meshes
+        self._node_ids = getattr(desc, "node_ids", None)   # of the description the scene holds (DynamicScene.UpdateScene), or None
 
     def update(self, desc):
         """ctl_scene_update: applies what differs between the description the scene holds and `desc` — camera, materials, lights, node transforms, the vertex
@@ -952,7 +985,31 @@ class Scene:
         self.last_mask = mask.value
         _check(code)
         self._keepalive = desc
+        self._node_ids = getattr(desc, "node_ids", self._node_ids)
         return mask.value
+
+    def update_nodes(self, sc_or_desc, old_of_new=None):
+        """ctl_scene_update_nodes: another SET of nodes in place — after DynamicScene.DeleteNode and / or CreateNode of further instances of meshes the scene already
+        holds, and UpdateScene() — with everything else Scene.update applies.  On a flattened Q4 scene the entries of removed nodes are dropped, those of added nodes made
+        from the mesh arrays as they stand in HBM, and the tree rebuilt, all on the device (csrc/flat_nodes.hip).  sc_or_desc: the DynamicScene or its description.
+        old_of_new: per new node its index in the description the scene holds or 0xffffffff (added); None: computed from the stable node ids of the two descriptions.
+        Returns the stats dict (entries_before / _after / _dropped / _generated, degenerate_skipped, rebuilt, edit_ms, total_ms, rebuild = the rebuild_flat dict).
+        CtlError(ERR_INVALID / ERR_UNSUPPORTED) leaves the scene as it was.  Start the next pass with new_trace."""
+        desc = sc_or_desc.getKernelSceneData() if isinstance(sc_or_desc, DynamicScene) else sc_or_desc
+        if old_of_new is None:
+            new_ids = getattr(desc, "node_ids", None)
+            if new_ids is None or self._node_ids is None:
+                raise ValueError("update_nodes: no node ids on the descriptions (DynamicScene.UpdateScene sets them): pass old_of_new")
+            index = {i: k for k, i in enumerate(self._node_ids)}
+            old_of_new = [index.get(i, 0xffffffff) for i in new_ids]
+        M = np.ascontiguousarray(old_of_new, dtype=np.uint32)
+        st = ctl_scene_nodes_stats()
+        _check(lib.ctl_scene_update_nodes(self._h, C.byref(desc), M.ctypes.data, u32(len(M)), C.addressof(st)))
+        self._keepalive = desc
+        self._node_ids = getattr(desc, "node_ids", None)
+        out = {k: getattr(st, k) for k, _ in st._fields_ if k != "rebuild"}
+        out["rebuild"] = {k: getattr(st.rebuild, k) for k, _ in st.rebuild._fields_}
+        return out
 
     def update_stats(self):
         """ctl_scene_get_update_stats of the last update: dict(node_area_before, node_area_after, refit_ms, refit_levels, mask, restamped)"""
@@ -1036,9 +1093,16 @@ class ctl_scene_rebuild_stats(C.Structure):
                 ("sort_ms", f32), ("topology_ms", f32), ("refit_ms", f32), ("total_ms", f32)]
 
 
+class ctl_scene_nodes_stats(C.Structure):
+    _fields_ = [("entries_before", u32), ("entries_after", u32), ("entries_dropped", u32), ("entries_generated", u32), ("degenerate_skipped", u32), ("rebuilt", u32),
+                ("rebuild", ctl_scene_rebuild_stats), ("edit_ms", f32), ("total_ms", f32)]
+
+
 # (declared only where the library has them: tools/ab_bench.py loads the parent commit's library through $CTL_AMD_LIB for a same-box A/B of bench.py, which calls none
 # of them; calling one on such a library raises AttributeError)
-for _n, _a in (("ctl_scene_rebuild_flat", [C.c_void_p, C.c_void_p]), ("ctl_flat_bvh_rebuild", [C.c_void_p, C.c_void_p]), ("ctl_flat_bvh_levels", [C.c_void_p] * 5)):
+for _n, _a in (("ctl_scene_rebuild_flat", [C.c_void_p, C.c_void_p]), ("ctl_flat_bvh_rebuild", [C.c_void_p, C.c_void_p]), ("ctl_flat_bvh_levels", [C.c_void_p] * 5),
+               ("ctl_builder_remove_node", [C.c_void_p, u32]), ("ctl_scene_update_nodes", [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_void_p]),
+               ("ctl_flat_bvh_update_nodes", [C.c_void_p, C.c_void_p, C.c_void_p, u32])):
     if hasattr(lib, _n):
         getattr(lib, _n).argtypes = _a
 

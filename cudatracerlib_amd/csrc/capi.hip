@@ -9,6 +9,7 @@
 #include "mitsuba_loader.h"
 #include "flatten.h"
 #include "flat_rebuild.h"
+#include "flat_device.h"
 #include "mesh_skin.h"
 #include "material_factory.h"
 #include "material_textures.h"
@@ -28,9 +29,11 @@ using namespace ctl;
 struct ctl_builder { scene_builder b; };
 struct ctl_scene {
     Scene s; uint32_t n_materials, n_images;   // the sizes of the description's material and image arrays (ctl_shading_eval checks a query's indices against them)
-    ctl_scene(const ctl_scene_desc& d, bool flatten, int fmt = -1, bool reduced_rt = false) : s(d, flatten, fmt, reduced_rt), n_materials(d.n_materials), n_images(d.n_images) {}
+    node_set_basis basis;   // the small arrays of the description the scene holds, as ctl_scene_update_nodes checks a new node set against them (flat_nodes.h)
+    ctl_scene(const ctl_scene_desc& d, bool flatten, int fmt = -1, bool reduced_rt = false) : s(d, flatten, fmt, reduced_rt), n_materials(d.n_materials), n_images(d.n_images) { basis.fill(d); }
 };
-struct ctl_flat_bvh { flat_scene f; };
+// basis: of the description the tree stands for; extra_missing: triangles an added node got no entry for (flat_nodes.h), on top of what the entries themselves show
+struct ctl_flat_bvh { flat_scene f; node_set_basis basis; std::vector<uint32_t> extra_missing; };
 struct ctl_image { Image img; ctl_image(uint32_t w, uint32_t h) : img(w, h) {} };
 // wavefront / scene: the WavefrontPathTracer has no medium code and refuses a scene with participating media here, when the scene is handed over and when a pass starts
 // (scene_volumes.h; the PathTracer and the PrimTracer judge that themselves; WavefrontPathTracer is declared in tracer.h, whose text the committed counter profile's hash covers).
@@ -76,6 +79,13 @@ int ctl_builder_set_bvh_mode(ctl_builder* b, uint32_t mode) { CTL_REQUIRE(b && m
 int ctl_builder_add_node(ctl_builder* b, uint32_t mesh_index, const ctl_float4x4* to_world, uint32_t* node_index_out) {
     CTL_REQUIRE(b, "null builder");
     CTL_TRY uint32_t i = b->b.add_node(mesh_index, to_world); if (node_index_out) *node_index_out = i; CTL_CATCH
+}
+int ctl_builder_remove_node(ctl_builder* b, uint32_t node_index) {
+    CTL_REQUIRE(b, "null builder");
+    CTL_REQUIRE(node_index < b->b.nodes.size(), "ctl_builder_remove_node: bad node index");
+    CTL_REQUIRE(b->b.nodes.size() > 1, "ctl_builder_remove_node: the last node of the builder stays (a scene has at least one node)");
+    if (b->b.nodes[node_index].n_lights) return fail(CTL_ERR_UNSUPPORTED, "ctl_builder_remove_node: node " + std::to_string(node_index) + " carries area lights");
+    CTL_TRY b->b.remove_node(node_index); CTL_CATCH
 }
 int ctl_builder_add_area_light(ctl_builder* b, uint32_t node_index, uint32_t local_material, const float radiance[3]) {
     CTL_REQUIRE(b && radiance, "null argument");
@@ -357,7 +367,7 @@ int ctl_scene_update(ctl_scene* scene, const ctl_scene_desc* new_desc, uint32_t*
     CTL_REQUIRE(scene && new_desc, "null argument");
     const int rc = [&]() -> int { CTL_TRY scene->s.update(*new_desc, nullptr); CTL_CATCH }();
     if (mask_out) *mask_out = scene->s.last_mask();   // also when the update is refused: the caller sees why
-    if (rc == CTL_OK) { scene->n_materials = new_desc->n_materials; scene->n_images = new_desc->n_images; }
+    if (rc == CTL_OK) { scene->n_materials = new_desc->n_materials; scene->n_images = new_desc->n_images; scene->basis.fill(*new_desc); }
     return rc;
 }
 int ctl_scene_get_update_stats(ctl_scene* scene, ctl_scene_update_stats* out) { CTL_REQUIRE(scene && out, "null argument"); *out = scene->s.last_update(); return CTL_OK; }
@@ -391,14 +401,41 @@ int ctl_skin_mesh_host(const ctl_scene_desc* desc, uint32_t mesh_index, const fl
     CTL_REQUIRE(desc, "null description");
     CTL_TRY skin_mesh_host(*desc, mesh_index, rest_positions, rest_normals, n_vert, indices, n_tri, bone_indices, bone_weights, n_bones, bones0, bones1, lerp, positions_out, normals_out, tri_data_out, woop_out); CTL_CATCH
 }
-int ctl_flat_bvh_refit(ctl_flat_bvh* h, const ctl_scene_desc* new_desc) { CTL_REQUIRE(h && new_desc, "null argument"); CTL_TRY refit_flat_scene(h->f, *new_desc, nullptr); CTL_CATCH }
+// a triangle an added node got no entry for (ctl_flat_bvh_update_nodes) and that a changed mesh of `d` makes regular: refused as the device refuses it
+static void refuse_gained_triangles(const ctl_flat_bvh& h, const ctl_scene_desc& d, const char* who) {
+    if (h.extra_missing.empty() || h.f.refit.geom.empty()) return;
+    geometry_hashes g; hash_geometry(d, g);
+    if (!g.same_structure(h.f.refit.geom)) return;   // (the refit refuses it)
+    std::vector<uint8_t> changed(d.n_meshes, 0);
+    for (uint32_t m = 0; m < d.n_meshes; m++) changed[m] = g.same_values(h.f.refit.geom, m) ? 0 : 1;
+    std::vector<uint32_t> rows; triangle_woop_rows(d, rows);
+    const int m = mesh_gaining_a_triangle(d, h.extra_missing, rows, changed);
+    if (m >= 0) throw std::runtime_error(std::string(who) + ": mesh " + std::to_string(m) + " has a triangle that was degenerate when a node was added and no longer is: the tree has no leaf entry for it");
+}
+int ctl_flat_bvh_refit(ctl_flat_bvh* h, const ctl_scene_desc* new_desc) { CTL_REQUIRE(h && new_desc, "null argument"); CTL_TRY refuse_gained_triangles(*h, *new_desc, "refit"); refit_flat_scene(h->f, *new_desc, nullptr); h->basis.fill(*new_desc); CTL_CATCH }
 // ---- rebuild of the flattened tree (flat_rebuild.hip, flat_rebuild.cpp)
 int ctl_scene_rebuild_flat(ctl_scene* scene, ctl_scene_rebuild_stats* stats_out) {
     if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
     CTL_REQUIRE(scene, "null scene");
     CTL_TRY scene->s.rebuild_flat(stats_out); CTL_CATCH
 }
-int ctl_flat_bvh_rebuild(ctl_flat_bvh* h, const ctl_scene_desc* new_desc) { CTL_REQUIRE(h && new_desc, "null argument"); CTL_TRY rebuild_flat_scene(h->f, *new_desc, nullptr); CTL_CATCH }
+int ctl_flat_bvh_rebuild(ctl_flat_bvh* h, const ctl_scene_desc* new_desc) { CTL_REQUIRE(h && new_desc, "null argument"); CTL_TRY refuse_gained_triangles(*h, *new_desc, "rebuild"); rebuild_flat_scene(h->f, *new_desc, nullptr); h->basis.fill(*new_desc); CTL_CATCH }
+// ---- another set of nodes (flat_nodes.hip, flat_nodes.cpp)
+int ctl_scene_update_nodes(ctl_scene* scene, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes, ctl_scene_nodes_stats* stats_out) {
+    if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
+    CTL_REQUIRE(scene && new_desc, "null argument");
+    CTL_REQUIRE(old_of_new, "ctl_scene_update_nodes: null node map");
+    // the work needs the scene's own buffers: it enters through Scene::rebuild_flat, which takes the job posted for this thread (flat_device.h)
+    const node_set_job job{ new_desc, old_of_new, n_new_nodes, &scene->basis, stats_out };
+    struct posted { explicit posted(const node_set_job* j) { post_node_set_job(j); } ~posted() { post_node_set_job(nullptr); } } guard(&job);
+    const int rc = [&]() -> int { CTL_TRY scene->s.rebuild_flat(nullptr); CTL_CATCH }();
+    if (rc == CTL_OK) { scene->n_materials = new_desc->n_materials; scene->n_images = new_desc->n_images; scene->basis.fill(*new_desc); }
+    return rc;
+}
+int ctl_flat_bvh_update_nodes(ctl_flat_bvh* h, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes) {
+    CTL_REQUIRE(h && new_desc, "null argument");
+    CTL_TRY update_nodes_flat_scene(h->f, h->basis, *new_desc, old_of_new, n_new_nodes, h->extra_missing); h->basis.fill(*new_desc); CTL_CATCH
+}
 int ctl_flat_bvh_levels(const ctl_flat_bvh* h, const uint32_t** level_start, uint32_t* n_levels, const uint32_t** level_nodes, uint64_t* n_level_nodes) {
     CTL_REQUIRE(h && level_start && n_levels && level_nodes && n_level_nodes, "null argument");
     const auto& R = h->f.refit;
@@ -408,7 +445,7 @@ int ctl_flat_bvh_levels(const ctl_flat_bvh* h, const uint32_t** level_start, uin
 }
 int ctl_scene_read_flat_bvh(ctl_scene* scene, ctl_flat_bvh** out) {
     CTL_REQUIRE(scene && out, "null argument");
-    CTL_TRY std::unique_ptr<ctl_flat_bvh> h(new ctl_flat_bvh()); scene->s.read_flat_bvh(h->f); *out = h.release(); CTL_CATCH
+    CTL_TRY std::unique_ptr<ctl_flat_bvh> h(new ctl_flat_bvh()); scene->s.read_flat_bvh(h->f); h->basis = scene->basis; *out = h.release(); CTL_CATCH
 }
 int ctl_set_cache_dir(const char* dir) { CTL_TRY set_cache_dir(dir); CTL_CATCH }
 // the node formats 1 and 2 (F4 / F2) lost to Q4 and are retired; a format above CTL_FLAT_Q8 never existed
@@ -431,6 +468,7 @@ int ctl_flat_bvh_build(const ctl_scene_desc* desc, uint32_t format, ctl_flat_bvh
         std::unique_ptr<ctl_flat_bvh> h(new ctl_flat_bvh());
         if (!flatten_scene(*desc, h->f, (size_t)1 << 30, (int)format)) throw std::runtime_error("ctl_flat_bvh_build: nothing to flatten");
         if (h->f.format == kFlatQ4 && h->f.refit.ready()) hash_geometry(*desc, h->f.refit.geom);   // what ctl_flat_bvh_refit tells deformed meshes by
+        h->basis.fill(*desc);
         *out = h.release();
     CTL_CATCH
 }

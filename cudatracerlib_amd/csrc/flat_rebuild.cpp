@@ -34,6 +34,11 @@ void rebuild_flat_scene(flat_scene& F, const ctl_scene_desc& d, double* area_bef
     rebuild_refuse(F.format, F.refit.ready() && F.refit.part_index.size() == F.leaves.size(), F.compact_links, F.leaves.size(), "rebuild");
     double refit_area[2] = { 0, 0 };
     refit_flat_scene(F, d, refit_area);   // the pose (and the vertex values) of `d`: what ctl_scene_update does before ctl_scene_rebuild_flat; throws before it writes
+    rebuild_flat_entries(F, d);
+    if (area_before_after) { area_before_after[0] = refit_area[1]; area_before_after[1] = flat_scene_node_area(F); }
+}
+
+void rebuild_flat_entries(flat_scene& F, const ctl_scene_desc& d) {
     const uint32_t n = (uint32_t)F.leaves.size();
     // 1. entry boxes
     std::vector<double> P((size_t)d.n_nodes * 12);
@@ -117,7 +122,6 @@ void rebuild_flat_scene(flat_scene& F, const ctl_scene_desc& d, double* area_bef
             refit_node_boxes(w, exist, cb, nbox[i]);
             std::memcpy(&nd, w, 40);
         }
-    if (area_before_after) { area_before_after[0] = refit_area[1]; area_before_after[1] = flat_scene_node_area(F); }
 }
 
 }  // namespace ctl

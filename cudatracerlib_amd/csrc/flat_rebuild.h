@@ -147,5 +147,8 @@ CTL_REFIT_HD void rebuild_encode_node(const rebuild_slots& S, uint32_t first_chi
 struct flat_scene;
 void rebuild_refuse(int format, bool refit_ready, bool compact, size_t n_entries, const char* who);
 void rebuild_flat_scene(flat_scene& F, const ctl_scene_desc& d, double* area_before_after);
+// stages 1 - 9 alone, over the entries F holds (leaves, refit.part_index / part_boxes / xf0) for the transforms of `d`: what rebuild_flat_scene runs after its refit, and
+// update_nodes_flat_scene (flat_nodes.cpp) over another set of entries.  Too deep a tree: unsupported_error before F is written
+void rebuild_flat_entries(flat_scene& F, const ctl_scene_desc& d);
 
 }  // namespace ctl

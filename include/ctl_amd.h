@@ -315,6 +315,11 @@ enum { CTL_BVH_AUTO = 0, CTL_BVH_SBVH = 1, CTL_BVH_BINNED = 2 };
 int ctl_builder_set_bvh_mode(ctl_builder* b, uint32_t mode);
 /* DynamicScene::CreateNode + SetNodeTransform (DynamicScene.cpp:269-346): one instance of a mesh. */
 int ctl_builder_add_node(ctl_builder* b, uint32_t mesh_index, const ctl_float4x4* to_world, uint32_t* node_index_out);
+/* DynamicScene::DeleteNode (Engine/DynamicScene.cpp:380-384): the nodes behind node_index move down by one and the node_idx of their area lights follows; the node's
+ * material copies stay in the material table, unreferenced.  The next ctl_builder_finalize gives the new description (what ctl_scene_update_nodes takes).
+ * CTL_ERR_UNSUPPORTED for a node that carries area lights (their records and shape sets would have to leave the light tables), CTL_ERR_INVALID for an index that is no
+ * node's and for the last node of the builder; a refusal leaves the builder untouched. */
+int ctl_builder_remove_node(ctl_builder* b, uint32_t node_index);
 /* DynamicScene::CreateLight(node, matName, L) (DynamicScene.cpp:689-711): all triangles of the node whose local
  * material index is `local_material` become one DiffuseLight. */
 int ctl_builder_add_area_light(ctl_builder* b, uint32_t node_index, uint32_t local_material, const float radiance[3]);
@@ -536,6 +541,36 @@ typedef struct { uint32_t n_nodes, n_entries, max_depth, levels; double node_are
 int ctl_scene_rebuild_flat(ctl_scene* scene, ctl_scene_rebuild_stats* stats_out);
 int ctl_flat_bvh_rebuild(ctl_flat_bvh* h, const ctl_scene_desc* new_desc);
 int ctl_flat_bvh_levels(const ctl_flat_bvh* h, const uint32_t** level_start, uint32_t* n_levels, const uint32_t** level_nodes, uint64_t* n_level_nodes);
+/* ---- another SET OF NODES on a live scene (csrc/flat_nodes.h, flat_nodes.hip, flat_nodes.cpp; INTEGRATION.md "Updating a scene").  ctl_scene_update refuses a
+ * description with other nodes (CTL_DIFF_TOPOLOGY), and keeps doing so; ctl_scene_update_nodes takes one: new_desc is the scene's description after
+ * ctl_builder_remove_node and / or ctl_builder_add_node of further instances of meshes the scene already holds.
+ *   old_of_new[k]   the index new node k had in the description the scene holds, or UINT32_MAX for an added node; the kept indices strictly increasing (the builder
+ *                   never reorders: a removal shifts down, an addition appends); n_new_nodes == new_desc->n_nodes
+ * On a flattened CTL_FLAT_Q4 scene, on the device: the leaf entries of removed nodes are dropped and the kept ones renumbered (a flag per entry, a scan, a stable move);
+ * one entry per regular triangle of every added node is made from the mesh's Woop rows AS THEY STAND IN HBM (a deformed or posed mesh gives the new instance its current
+ * shape; a triangle whose Woop matrix is singular gets no entry, and a later geometry update that makes it regular is refused as for a triangle that was degenerate at
+ * creation); then the tree is rebuilt over the new set by the stages of ctl_scene_rebuild_flat.  Added instances get WHOLE-triangle entries (part_index UINT32_MAX, no
+ * early split clipping): they cull less well on long triangles, never wrongly.  On a two-level scene the call is host work: top level, instances, node info and the
+ * material table go into buffers of the new size.  Tracers follow the new arrays by themselves; start the next pass with new_trace.  Bound meshes stay bound.
+ * Accepted besides the node set: everything ctl_scene_update applies (camera, the contents of kept materials, lights — an added node may carry area lights —, the
+ * transforms of kept nodes, the scene BVH, box, ray_trace_eps, volumes), in the same call; n_materials may grow (the added nodes' copies), not shrink.  An identity map
+ * over the same count is valid: the call then is ctl_scene_update, without a rebuild.
+ * Refusals, all before anything is written and before a tracer is stalled, the scene as it was and ctl_last_error() naming the rule: CTL_ERR_NO_DEVICE (checked first);
+ * CTL_ERR_INVALID for a null, short, non-increasing or out-of-range map, a kept node with another mesh or material assignment, another mesh set, geometry structure,
+ * image set or transmittance tables, other geometry VALUES in a mesh that is not device-owned (ctl_scene_update first), a description ctl_scene_desc_check refuses, no
+ * node left; CTL_ERR_UNSUPPORTED for a CTL_FLAT_Q8 scene, a tree without refit data or with explicit links, and a rebuilt tree too deep for the traversal stack (it is
+ * made in buffers of its own; the old one stays).  A failed allocation leaves the scene as it was.  The library has no policy: whether this call or a new scene is the
+ * better answer (the result is an LBVH without slabs or split decisions) is the host's decision.
+ * stats_out (may be NULL): the entry counts, what ctl_scene_rebuild_stats reports (rebuild), HIP-event times of the drop + generate stage and of the whole call.
+ * ctl_flat_bvh_update_nodes does the same to a host handle (of ctl_flat_bvh_build or ctl_scene_read_flat_bvh) with the same single-source functions, reading the Woop
+ * rows from new_desc: the yardstick — after the device call ctl_scene_read_flat_bvh equals it byte for byte (nodes, entries, part_index, level lists, max_depth). */
+typedef struct {
+    uint32_t entries_before, entries_after, entries_dropped, entries_generated, degenerate_skipped, rebuilt;   /* rebuilt: 0 = an identity map (no rebuild) or a two-level scene */
+    ctl_scene_rebuild_stats rebuild;
+    float edit_ms, total_ms;   /* drop + generate; the whole device work of the call */
+} ctl_scene_nodes_stats;
+int ctl_scene_update_nodes(ctl_scene* scene, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes, ctl_scene_nodes_stats* stats_out);
+int ctl_flat_bvh_update_nodes(ctl_flat_bvh* h, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes);
 /* The flattened tree of a CTL_SCENE_FLATTEN scene copied back from HBM into a handle for ctl_flat_bvh_arrays, with the BSDF-model bits (28..31 of the index word)
  * and the alpha bit (31 of the node word) that ctl_scene_create_ex stamps into the device copy removed: the arrays the test oracle traverses. */
 int ctl_scene_read_flat_bvh(ctl_scene* scene, ctl_flat_bvh** out);

@@ -24,6 +24,9 @@ Per workload, on one GPU, in one process:
      own: wall time around the (synchronous) call — the first call, which also loads the kernels and allocates rocPRIM's storage, and the median of 5 further calls —
      with the stage times of ctl_scene_rebuild_stats; against the re-creation of the same pose measured in the same run (M3: warm cache; D1: as in step 4, the
      flattened tree necessarily cold); and the Mrays/s of the refitted, the rebuilt and a fresh tree with the node-area ratios.
+  7. (--only nodes) ctl_scene_update_nodes: one more instance of the moved node's mesh added (at the M3 place), then one node removed, each timed once — wall
+     time around the (synchronous) call with the stage times of ctl_scene_nodes_stats — against the warm-cache re-creation of the same description in the same run,
+     and the Mrays/s of the updated scene (an LBVH, the added instance with whole-triangle entries) against the freshly created one.
 One JSON line per workload is appended to --out; --results appends a section to that Markdown file.  bench.py is not involved.
 """
 import argparse
@@ -250,6 +253,38 @@ def rebuilding(workload, args, sc, scene, node, X0, size, rec):
     rec["rebuild_D1"] = b
 
 
+def node_set(workload, args, sc, scene, node, X0, size, rec):
+    d = sc.desc
+    mesh = int(d.view("nodes", np.uint32, d.n_nodes, 6)[node, 0])
+
+    def one(what, edit):
+        edit()
+        t = time.perf_counter(); st = scene.update_nodes(sc.UpdateScene()); wall = (time.perf_counter() - t) * 1e3
+        b = dict(wall_ms=wall, stats=st, updated_mrays=mrays(scene, args))
+        with tempfile.TemporaryDirectory() as cache:
+            api.set_cache_dir(cache)
+            s2 = ctl.Scene(sc.desc, flatten=True); del s2     # warms the cache for exactly this description
+            t = time.perf_counter(); fresh = ctl.Scene(sc.UpdateScene(), flatten=True); b["recreate_warmcache_ms"] = (time.perf_counter() - t) * 1e3
+            api.set_cache_dir(None)
+        b["fresh_mrays"] = mrays(fresh, args); del fresh
+        rec["nodes_" + what] = b
+    one("add", lambda: sc.CreateNode(mesh, motion(X0, size, "M3")))
+    one("remove", lambda: sc.DeleteNode(node))
+
+
+def markdown_nodes(recs):
+    out = ["", "## Adding and removing nodes in place (tools/scene_update_bench.py --only nodes)", "",
+           "| workload | edit | entries | dropped | generated | ctl_scene_update_nodes, wall | drop + generate | rebuild (key + sort / topology + gather / boxes) | device total | re-creation, warm cache | updated scene | fresh scene | ratio |",
+           "|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    for r in recs:
+        for what in ("add", "remove"):
+            b = r["nodes_" + what]; st = b["stats"]; rb = st["rebuild"]
+            out.append("| %s | %s one node | %d -> %d | %d | %d | %.1f ms | %.2f ms | %.2f ms (%.2f / %.2f / %.2f) | %.2f ms | %.0f ms | %.0f Mrays/s | %.0f Mrays/s | %.3f |" % (r["workload"], what, st["entries_before"], st["entries_after"],
+                       st["entries_dropped"], st["entries_generated"], b["wall_ms"], st["edit_ms"], rb["total_ms"], rb["sort_ms"], rb["topology_ms"], rb["refit_ms"], st["total_ms"], b["recreate_warmcache_ms"],
+                       b["updated_mrays"], b["fresh_mrays"], b["updated_mrays"] / b["fresh_mrays"]))
+    return "\n".join(out) + "\n"
+
+
 def markdown_rebuild(recs):
     out = ["", "## Rebuilding the flattened tree on the device (tools/scene_update_bench.py --only rebuild)", "",
            "| workload | after | entries | nodes (fresh tree) | depth | ctl_scene_rebuild_flat: first call | median of 5 | key + sort | topology + gather | boxes | re-creation of the same pose |",
@@ -310,6 +345,9 @@ def run(workload, args):
     if args.only == "rebuild":
         rebuilding(workload, args, sc, scene, node, X0, size, rec)
         return rec
+    if args.only == "nodes":
+        node_set(workload, args, sc, scene, node, X0, size, rec)
+        return rec
 
     def material(k):
         sc.desc.materials[0].tex[0].value[0] = 0.3 + 0.01 * k; assert scene.update(sc.desc) == api.DIFF_MATERIALS
@@ -369,6 +407,8 @@ def markdown(recs):
         return markdown_skin(recs)
     if "rebuild_M3" in recs[0]:
         return markdown_rebuild(recs)
+    if "nodes_add" in recs[0]:
+        return markdown_nodes(recs)
     if "update_transform_ms" not in recs[0]:
         return markdown_deform(recs)
     out = ["", "## In-place scene updates (tools/scene_update_bench.py)", "",
@@ -391,7 +431,7 @@ def main():
     ap.add_argument("--depth", type=int, default=8); ap.add_argument("--passes", type=int, default=4)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scene_update.jsonl"))
     ap.add_argument("--results", default=None)
-    ap.add_argument("--only", default=None, choices=["deform", "skin", "rebuild"], help="rebuild: the camera update and ctl_scene_rebuild_flat after M3 and after D1 against the re-creation of the same pose; deform: the camera update and the one-mesh deformation alone; skin: the camera update and the pose change of a bound mesh against the host path")
+    ap.add_argument("--only", default=None, choices=["deform", "skin", "rebuild", "nodes"], help="nodes: the camera update and ctl_scene_update_nodes adding and removing one node against the re-creation of the same description; rebuild: the camera update and ctl_scene_rebuild_flat after M3 and after D1 against the re-creation of the same pose; deform: the camera update and the one-mesh deformation alone; skin: the camera update and the pose change of a bound mesh against the host path")
     args = ap.parse_args()
     if ctl.device_count() < 1:
         raise SystemExit("scene_update_bench needs a HIP device")
