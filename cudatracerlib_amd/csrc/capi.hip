@@ -9,7 +9,7 @@
 #include "mitsuba_loader.h"
 #include "flatten.h"
 #include "flat_rebuild.h"
-#include "flat_device.h"
+#include "flat_nodes.h"
 #include "mesh_skin.h"
 #include "material_factory.h"
 #include "material_textures.h"
@@ -36,11 +36,10 @@ struct ctl_scene {
 struct ctl_flat_bvh { flat_scene f; node_set_basis basis; std::vector<uint32_t> extra_missing; };
 struct ctl_image { Image img; ctl_image(uint32_t w, uint32_t h) : img(w, h) {} };
 // wavefront / scene: the WavefrontPathTracer has no medium code and refuses a scene with participating media here, when the scene is handed over and when a pass starts
-// (scene_volumes.h; the PathTracer and the PrimTracer judge that themselves; WavefrontPathTracer is declared in tracer.h, whose text the committed counter profile's hash covers).
-// `scene` is only ever looked up, never dereferenced, and only while the registry still knows it under `scene_id`: a destroyed scene, or a new one at its address, is not judged
+// (Scene::refuse_volumes; the PathTracer and the PrimTracer judge that themselves).  `scene` is the pointer InitializeScene got, the one DoPass reads the scene through
 struct ctl_tracer {
-    std::unique_ptr<TracerBase> t; bool wavefront = false; const Scene* scene = nullptr; uint64_t scene_id = 0;
-    void refuse_media() const { if (wavefront && scene && scene_id && scene_volumes_id(scene) == scene_id) refuse_volumes(scene, "WavefrontPathTracer"); }
+    std::unique_ptr<TracerBase> t; bool wavefront = false; const Scene* scene = nullptr;
+    void refuse_media() const { if (wavefront && scene) scene->refuse_volumes("WavefrontPathTracer"); }
 };
 struct ctl_sequence_generator { sequence_generator g; };
 
@@ -425,10 +424,7 @@ int ctl_scene_update_nodes(ctl_scene* scene, const ctl_scene_desc* new_desc, con
     if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
     CTL_REQUIRE(scene && new_desc, "null argument");
     CTL_REQUIRE(old_of_new, "ctl_scene_update_nodes: null node map");
-    // the work needs the scene's own buffers: it enters through Scene::rebuild_flat, which takes the job posted for this thread (flat_device.h)
-    const node_set_job job{ new_desc, old_of_new, n_new_nodes, &scene->basis, stats_out };
-    struct posted { explicit posted(const node_set_job* j) { post_node_set_job(j); } ~posted() { post_node_set_job(nullptr); } } guard(&job);
-    const int rc = [&]() -> int { CTL_TRY scene->s.rebuild_flat(nullptr); CTL_CATCH }();
+    const int rc = [&]() -> int { CTL_TRY scene->s.update_nodes(*new_desc, old_of_new, n_new_nodes, scene->basis, stats_out); CTL_CATCH }();
     if (rc == CTL_OK) { scene->n_materials = new_desc->n_materials; scene->n_images = new_desc->n_images; scene->basis.fill(*new_desc); }
     return rc;
 }
@@ -624,7 +620,7 @@ int ctl_tracer_get_param_float(ctl_tracer* t, const char* key, float* value_out)
 int ctl_tracer_set_param_enum(ctl_tracer* t, const char* key, const char* value_name) { CTL_REQUIRE(t && key && value_name, "null argument"); CTL_TRY t->t->getParameters().setEnumByName(key, value_name); CTL_CATCH }
 int ctl_tracer_get_param_int(ctl_tracer* t, const char* key, int* value_out) { CTL_REQUIRE(t && key && value_out, "null argument"); CTL_TRY *value_out = t->t->getParameters().getValue(key); CTL_CATCH }
 int ctl_tracer_resize(ctl_tracer* t, uint32_t width, uint32_t height) { CTL_REQUIRE(t && width && height, "bad argument"); CTL_TRY t->t->Resize(width, height); CTL_CATCH }
-int ctl_tracer_initialize_scene(ctl_tracer* t, ctl_scene* s) { CTL_REQUIRE(t && s, "null argument"); CTL_TRY if (t->wavefront) refuse_volumes(&s->s, "WavefrontPathTracer"); t->t->InitializeScene(&s->s); t->scene = &s->s; t->scene_id = scene_volumes_id(&s->s); CTL_CATCH }
+int ctl_tracer_initialize_scene(ctl_tracer* t, ctl_scene* s) { CTL_REQUIRE(t && s, "null argument"); CTL_TRY if (t->wavefront) s->s.refuse_volumes("WavefrontPathTracer"); t->t->InitializeScene(&s->s); t->scene = &s->s; CTL_CATCH }
 int ctl_tracer_set_tile_shard(ctl_tracer* t, uint32_t rank, uint32_t world) { CTL_REQUIRE(t, "null tracer"); CTL_TRY t->t->setTileShard(rank, world); CTL_CATCH }
 int ctl_tracer_set_sampler_tables(ctl_tracer* t, const float* tables_1d, const float* tables_2d) { CTL_REQUIRE(t && tables_1d && tables_2d, "null argument"); CTL_TRY t->t->setSamplerTables(tables_1d, tables_2d); CTL_CATCH }
 int ctl_tracer_do_pass(ctl_tracer* t, ctl_image* img, int new_trace) { CTL_REQUIRE(t && img, "null argument"); CTL_TRY t->refuse_media(); t->t->DoPass(&img->img, new_trace != 0); CTL_CATCH }

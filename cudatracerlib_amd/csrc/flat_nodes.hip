@@ -88,61 +88,41 @@ struct event_set {
     ~event_set() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
 };
 
-thread_local const node_set_job* t_job = nullptr;
-
-// the instance records as Scene::upload_instances lays them out (tracer.hip)
-void pack_instances(const ctl_scene_desc& d, std::vector<float4>& inst, std::vector<float4>& fwd, std::vector<uint4>& ninfo) {
-    inst.resize((size_t)d.n_nodes * 4); fwd.resize((size_t)d.n_nodes * 3); ninfo.resize(d.n_nodes);
-    for (uint32_t k = 0; k < d.n_nodes; k++) {
-        const float* im = d.node_inv_transforms[k].m; const float* fm = d.node_transforms[k].m;
-        const ctl_node& N = d.nodes[k];
-        const ctl_kernel_mesh& km = d.meshes[N.mesh_index];
-        for (int r = 0; r < 3; r++) { inst[k * 4 + r] = make_float4(im[r * 4], im[r * 4 + 1], im[r * 4 + 2], im[r * 4 + 3]); fwd[k * 3 + r] = make_float4(fm[r * 4], fm[r * 4 + 1], fm[r * 4 + 2], fm[r * 4 + 3]); }
-        inst[k * 4 + 3] = make_float4(im[15], __builtin_bit_cast(float, km.bvh_node_offset), __builtin_bit_cast(float, km.bvh_tri_offset / 3), __builtin_bit_cast(float, km.tri_offset));
-        ninfo[k] = make_uint4(N.material_offset, N.lights[0], N.lights[1], N.n_lights);
-    }
-}
-
-void exclusive_scan_u32(flat_scene_state& A, uint32_t* in, uint32_t* out, size_t count, const char* who) {
+void exclusive_scan_u32(dbuf<unsigned char>& temp, uint32_t* in, uint32_t* out, size_t count, const char* who) {
     size_t need = 0;
     CTL_HIP(rocprim::exclusive_scan(nullptr, need, in, out, 0u, count, rocprim::plus<uint32_t>(), (hipStream_t) nullptr));
-    if (need > A.temp.n) throw std::runtime_error(std::string(who) + ": scan storage");
-    size_t bytes = A.temp.n;
-    CTL_HIP(rocprim::exclusive_scan(A.temp.p, bytes, in, out, 0u, count, rocprim::plus<uint32_t>(), (hipStream_t) nullptr));
+    if (need > temp.n) throw std::runtime_error(std::string(who) + ": scan storage");
+    size_t bytes = temp.n;
+    CTL_HIP(rocprim::exclusive_scan(temp.p, bytes, in, out, 0u, count, rocprim::plus<uint32_t>(), (hipStream_t) nullptr));
 }
 
 }  // namespace
 
-void post_node_set_job(const node_set_job* job) { t_job = job; }
-const node_set_job* take_node_set_job() { const node_set_job* j = t_job; t_job = nullptr; return j; }
-
-void update_nodes_device(flat_scene_state& A, const node_set_job& J) {
+void Scene::update_nodes(const ctl_scene_desc& d, const uint32_t* old_of_new, uint32_t n_new_nodes, const node_set_basis& basis, ctl_scene_nodes_stats* stats) {
     require_device();
     const char* who = "ctl_scene_update_nodes";
-    if (!A.snap) throw std::runtime_error(std::string(who) + ": the scene holds no description");
-    const ctl_scene_desc& d = *J.d;
-    const bool flat = A.scene.flattened();
-    if (flat) rebuild_refuse(A.S.flat_format, A.refit.level_start.size() >= 2 && A.part_index.p && A.part_index.n == A.n_entries, A.S.flat_compact != 0, A.n_entries, who);
-    std::vector<uint8_t> device_owned;   // the bound meshes (mesh_skin.hip): their values are the device's, whatever the description says
-    if (!A.skins.empty()) { device_owned.assign(A.snap->d.n_meshes, 0); for (const auto& kv : A.skins) if (kv.first < device_owned.size()) device_owned[kv.first] = 1; }
+    if (!snap_) throw std::runtime_error(std::string(who) + ": the scene holds no description");
+    const bool flat = flattened();
+    if (flat) rebuild_refuse(S.flat_format, refit_.level_start.size() >= 2 && refit_part_index_.p && refit_part_index_.n == flat_n_entries_, S.flat_compact != 0, flat_n_entries_, who);
+    const std::vector<uint8_t> device_owned = device_owned_meshes();
     node_set_plan plan;
-    plan_node_set(*J.basis, A.snap->geom, d, J.old_of_new, J.n_new_nodes, device_owned.empty() ? nullptr : &device_owned, plan, who);
-    const uint32_t n_old_nodes = A.snap->d.n_nodes;
-    if (J.basis->nodes.size() != n_old_nodes || (flat && A.refit.xf0.size() != n_old_nodes)) throw std::runtime_error(std::string(who) + ": the scene's description has another number of nodes than its tree");
-    ctl_scene_nodes_stats st{}; st.entries_before = st.entries_after = flat ? (uint32_t)A.n_entries : 0u;
+    plan_node_set(basis, snap_->geom, d, old_of_new, n_new_nodes, device_owned.empty() ? nullptr : &device_owned, plan, who);
+    const uint32_t n_old_nodes = snap_->d.n_nodes;
+    if (basis.nodes.size() != n_old_nodes || (flat && refit_.xf0.size() != n_old_nodes)) throw std::runtime_error(std::string(who) + ": the scene's description has another number of nodes than its tree");
+    ctl_scene_nodes_stats st{}; st.entries_before = st.entries_after = flat ? (uint32_t)flat_n_entries_ : 0u;
     if (plan.identity) {   // nothing of the node set changes: ctl_scene_update, no rebuild
-        A.scene.update(d, nullptr);
-        if (J.stats) *J.stats = st;
+        update(d, nullptr);
+        if (stats) *stats = st;
         return;
     }
     // host work before the device is touched: the instance records, the creation poses, the carry matrices
     const shading_state shade = derive_shading_state(d);
     std::vector<float4> inst, fwd; std::vector<uint4> ninfo;
     pack_instances(d, inst, fwd, ninfo);
-    std::vector<ctl_float4x4> xf0(d.n_nodes); std::vector<double> P((size_t)d.n_nodes * 12);
-    if (flat) for (uint32_t k = 0; k < d.n_nodes; k++) {
-        xf0[k] = J.old_of_new[k] == kNodesNone ? d.node_transforms[k] : A.refit.xf0[J.old_of_new[k]];
-        if (!refit_carry_matrix(d.node_transforms[k].m, xf0[k].m, &P[(size_t)k * 12])) throw std::runtime_error(std::string(who) + ": singular node transform");
+    std::vector<ctl_float4x4> xf0(d.n_nodes); std::vector<double> P;
+    if (flat) {
+        for (uint32_t k = 0; k < d.n_nodes; k++) xf0[k] = old_of_new[k] == kNodesNone ? d.node_transforms[k] : refit_.xf0[old_of_new[k]];
+        P = carry_matrices(d, xf0, who);
     }
     CTL_HIP(hipDeviceSynchronize());   // no trace reads the arrays any more
     dbuf<float4> inst_new, fwd_new; dbuf<uint4> ninfo_new;
@@ -152,7 +132,7 @@ void update_nodes_device(flat_scene_state& A, const node_set_job& J) {
     std::vector<uint32_t> skipped;
     flat_rebuilder B;
     if (flat) {
-        const uint32_t n_old = (uint32_t)A.n_entries, n_added = (uint32_t)plan.added.size(), G = plan.added_base.back();
+        const uint32_t n_old = (uint32_t)flat_n_entries_, n_added = (uint32_t)plan.added.size(), G = plan.added_base.back();
         // ---- scratch of this call; the scene's tri_row table and rocPRIM storage are caches without a meaning of their own
         dbuf<uint32_t> map_dev, flags, pos, base_dev, tri0_dev, added_dev, gflags, gpos, part_mid; dbuf<float4> leaves_mid; dbuf<ctl_material> mats_tmp; dbuf<unsigned char> temp;
         map_dev.alloc(n_old_nodes); flags.alloc((size_t)n_old + 1); pos.alloc((size_t)n_old + 1); gflags.alloc((size_t)G + 1); gpos.alloc((size_t)G + 1);
@@ -160,27 +140,27 @@ void update_nodes_device(flat_scene_state& A, const node_set_job& J) {
         CTL_HIP(hipMemcpy(map_dev.p, plan.new_of_old.data(), (size_t)n_old_nodes * 4, hipMemcpyHostToDevice));
         CTL_HIP(hipMemcpy(base_dev.p, plan.added_base.data(), plan.added_base.size() * 4, hipMemcpyHostToDevice));
         if (n_added) { CTL_HIP(hipMemcpy(tri0_dev.p, plan.added_tri0.data(), (size_t)n_added * 4, hipMemcpyHostToDevice)); CTL_HIP(hipMemcpy(added_dev.p, plan.added.data(), (size_t)n_added * 4, hipMemcpyHostToDevice)); }
-        if (!A.tri_row.p) {   // triangle -> row of the leaf stream; woop_index is structure (the hashes matched): the table holds for every later update
+        if (!refit_tri_row_.p) {   // triangle -> row of the leaf stream; woop_index is structure (the hashes matched): the table holds for every later update
             std::vector<uint32_t> rows; triangle_woop_rows(d, rows);
-            A.tri_row.upload(rows.data(), rows.size()); CTL_HIP(hipStreamSynchronize(nullptr));
+            refit_tri_row_.upload(rows.data(), rows.size()); CTL_HIP(hipStreamSynchronize(nullptr));
         }
         size_t scan_bytes = 0;
         CTL_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, flags.p, pos.p, 0u, (size_t)std::max(n_old, G) + 1, rocprim::plus<uint32_t>(), (hipStream_t) nullptr));
-        if (A.temp.n < std::max<size_t>(scan_bytes, 16)) { temp.alloc(std::max<size_t>(scan_bytes, 16)); swap_buffers(A.temp, temp); temp.free(); }
+        if (rebuild_temp_.n < std::max<size_t>(scan_bytes, 16)) { temp.alloc(std::max<size_t>(scan_bytes, 16)); swap_buffers(rebuild_temp_, temp); temp.free(); }
         event_set ev;
         CTL_HIP(hipEventRecord(ev.e[0], nullptr));
         // 1. which entries stay, 2. which triangles of the added nodes get an entry; the two scans
-        hipLaunchKernelGGL(k_nodes_flag, blocks_for((size_t)n_old + 1), dim3(256), 0, nullptr, A.flat_leaves.p, n_old, map_dev.p, n_old_nodes, flags.p);
-        const nodes_added D{ base_dev.p, tri0_dev.p, added_dev.p, n_added, G, A.tri_row.p, (uint32_t)A.tri_row.n, A.leaf_tris.p, (uint32_t)(A.leaf_tris.n / 4) };
+        hipLaunchKernelGGL(k_nodes_flag, blocks_for((size_t)n_old + 1), dim3(256), 0, nullptr, flat_leaves_.p, n_old, map_dev.p, n_old_nodes, flags.p);
+        const nodes_added D{ base_dev.p, tri0_dev.p, added_dev.p, n_added, G, refit_tri_row_.p, (uint32_t)refit_tri_row_.n, leaf_tris_.p, (uint32_t)(leaf_tris_.n / 4) };
         hipLaunchKernelGGL(k_nodes_candidates, blocks_for((size_t)G + 1), dim3(256), 0, nullptr, D, gflags.p);
         CTL_HIP(hipGetLastError());
-        exclusive_scan_u32(A, flags.p, pos.p, (size_t)n_old + 1, who);
-        exclusive_scan_u32(A, gflags.p, gpos.p, (size_t)G + 1, who);
+        exclusive_scan_u32(rebuild_temp_, flags.p, pos.p, (size_t)n_old + 1, who);
+        exclusive_scan_u32(rebuild_temp_, gflags.p, gpos.p, (size_t)G + 1, who);
         uint32_t n_kept = 0, n_gen = 0;
         CTL_HIP(hipMemcpy(&n_kept, pos.p + n_old, 4, hipMemcpyDeviceToHost)); CTL_HIP(hipMemcpy(&n_gen, gpos.p + G, 4, hipMemcpyDeviceToHost));
         if (n_kept > n_old || n_gen > G) throw std::runtime_error(std::string(who) + ": the positions handed out exceed the entry count");
         const uint64_t n_new64 = (uint64_t)n_kept + n_gen;
-        rebuild_refuse(A.S.flat_format, true, true, (size_t)n_new64, who);
+        rebuild_refuse(S.flat_format, true, true, (size_t)n_new64, who);
         const uint32_t n_new = (uint32_t)n_new64;
         if (n_gen < G) {   // the triangles without an entry join the scene's list (flat_missing_triangles)
             std::vector<uint32_t> f(G);
@@ -190,39 +170,39 @@ void update_nodes_device(flat_scene_state& A, const node_set_job& J) {
         // every allocation before the first entry is written
         leaves_mid.alloc(((size_t)n_new + 1) * 8); part_mid.alloc(n_new); mats_tmp.alloc(std::max<uint32_t>(1u, d.n_materials));
         B.who = who; B.n = n_new; B.src_leaves = leaves_mid.p; B.src_part = part_mid.p;
-        B.allocate(A, P);
+        B.allocate(*this, P);
         if (d.n_materials) CTL_HIP(hipMemcpy(mats_tmp.p, d.materials, (size_t)d.n_materials * sizeof(ctl_material), hipMemcpyHostToDevice));
-        const nodes_move M{ A.flat_leaves.p, A.part_index.p, flags.p, pos.p, map_dev.p, n_old_nodes, n_old, n_new, leaves_mid.p, part_mid.p };
+        const nodes_move M{ flat_leaves_.p, refit_part_index_.p, flags.p, pos.p, map_dev.p, n_old_nodes, n_old, n_new, leaves_mid.p, part_mid.p };
         hipLaunchKernelGGL(k_nodes_move, blocks_for((size_t)n_old * 8), dim3(256), 0, nullptr, M);
         if (G) hipLaunchKernelGGL(k_nodes_generate, blocks_for(G), dim3(256), 0, nullptr, D, gflags.p, gpos.p, inst_new.p, d.n_nodes, n_kept, n_new, leaves_mid.p, part_mid.p);
         CTL_HIP(hipGetLastError());
-        CTL_HIP(hipMemcpyAsync(leaves_mid.p + (size_t)n_new * 8, A.flat_leaves.p + (size_t)n_old * 8, 128, hipMemcpyDeviceToDevice, nullptr));   // the closing entry
+        CTL_HIP(hipMemcpyAsync(leaves_mid.p + (size_t)n_new * 8, flat_leaves_.p + (size_t)n_old * 8, 128, hipMemcpyDeviceToDevice, nullptr));   // the closing entry
         CTL_HIP(hipEventRecord(ev.e[1], nullptr));
         // the re-stamp, the entry boxes and 4. the rebuild, with the NEW instance records and materials (the scene still holds the old ones)
-        B.R.inst = inst_new.p; B.R.inst_fwd = fwd_new.p; B.R.restamp = (int)d.n_materials; B.R.leaf_keys = A.S.flat_leaf_keys; B.R.alpha_maps = (int)shade.alpha_maps;
-        B.R.tri_data = A.tri_data.p; B.R.node_info = ninfo_new.p; B.R.mats = mats_tmp.p;
-        B.run(A);   // (synchronises) a tree too deep is refused here: the scene as it was
+        B.R.inst = inst_new.p; B.R.inst_fwd = fwd_new.p; B.R.restamp = (int)d.n_materials; B.R.leaf_keys = S.flat_leaf_keys; B.R.alpha_maps = (int)shade.alpha_maps;
+        B.R.tri_data = tri_data_.p; B.R.node_info = ninfo_new.p; B.R.mats = mats_tmp.p;
+        B.run(*this);   // (synchronises) a tree too deep is refused here: the scene as it was
         CTL_HIP(hipEventRecord(ev.e[2], nullptr)); CTL_HIP(hipEventSynchronize(ev.e[2]));
         CTL_HIP(hipEventElapsedTime(&st.edit_ms, ev.e[0], ev.e[1])); CTL_HIP(hipEventElapsedTime(&st.total_ms, ev.e[0], ev.e[2]));
         st.entries_after = n_new; st.entries_dropped = n_old - n_kept; st.entries_generated = n_gen; st.degenerate_skipped = G - n_gen; st.rebuilt = 1u;
         B.report(st.rebuild);
         // ---- from here on the scene is written
-        B.commit(A);
-        A.refit.xf0 = xf0;
+        B.commit(*this);
+        refit_.xf0 = xf0;
         if (!skipped.empty()) {
-            A.missing_tris.insert(A.missing_tris.end(), skipped.begin(), skipped.end());
-            std::sort(A.missing_tris.begin(), A.missing_tris.end()); A.missing_tris.erase(std::unique(A.missing_tris.begin(), A.missing_tris.end()), A.missing_tris.end());
+            flat_missing_tris_.insert(flat_missing_tris_.end(), skipped.begin(), skipped.end());
+            std::sort(flat_missing_tris_.begin(), flat_missing_tris_.end()); flat_missing_tris_.erase(std::unique(flat_missing_tris_.begin(), flat_missing_tris_.end()), flat_missing_tris_.end());
         }
     }
     // the rest of the description, block by block as ctl_scene_update applies it; the instance records go in by a swap of buffers
-    swap_buffers(A.inst, inst_new); swap_buffers(A.inst_fwd, fwd_new); swap_buffers(A.node_info, ninfo_new);
-    A.set_shading_state(shade);
-    A.upload_materials(d); A.upload_lights(d); A.upload_top_level(d);
-    if (flat) A.S.inst_w_one = inverse_transforms_have_w_one(d);
+    swap_buffers(inst_, inst_new); swap_buffers(inst_fwd_, fwd_new); swap_buffers(node_info_, ninfo_new);
+    set_shading_state(shade);
+    upload_materials(d); upload_lights(d); upload_top_level(d);
+    if (flat) S.inst_w_one = inverse_transforms_have_w_one(d);
     CTL_HIP(hipDeviceSynchronize());
-    A.bind(d); A.set_camera(d);
-    A.snapshot(d, plan.geom.empty() ? nullptr : &plan.geom);
-    if (J.stats) *J.stats = st;
+    bind(d); n_nodes = d.n_nodes; set_camera(d);
+    snapshot(d, plan.geom.empty() ? nullptr : &plan.geom);
+    if (stats) *stats = st;
 }
 
 }  // namespace ctl

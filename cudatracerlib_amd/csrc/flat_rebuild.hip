@@ -100,42 +100,42 @@ __global__ void __launch_bounds__(256) k_rebuild_iota(uint32_t* __restrict__ out
 
 flat_rebuilder::~flat_rebuilder() { for (auto x : ev) if (x) (void)hipEventDestroy(x); }
 
-void flat_rebuilder::allocate(flat_scene_state& A, const std::vector<double>& P) {
+void flat_rebuilder::allocate(Scene& A, const std::vector<double>& P) {
     // a wide node that is not the root has more than kRebuildLeafMax entries under it, and one with an inner child has four slots: fewer than n / 3 + 1 nodes with leaves of up
     // to four entries (the per-level check in run() holds whatever the bound)
     cap = (kRebuildLeafMax >= 4u ? n / 2u : n) + 2u;
     // every allocation before the first write: a failed one leaves the scene as it was (the buffers free themselves)
     dbuf<refit_box> ebox_cur; dbuf<double> carry; dbuf<unsigned char> temp;
-    if (A.ebox.n < n) ebox_cur.alloc(n);
+    if (A.refit_ebox_.n < n) ebox_cur.alloc(n);
     ebox_new.alloc(n); nbox_new.alloc(cap); bounds.alloc(6); idx_in.alloc(n); idx_out.alloc(n); first.alloc(cap); last.alloc(cap); perm.alloc(n); part_new.alloc(n);
     keys_in.alloc(n); keys_out.alloc(n); counts.alloc(cap); incl.alloc(cap); nodes_new.alloc((size_t)cap * 4); leaves_new.alloc(((size_t)n + 1) * 8); carry.alloc(P.size()); area_dev.alloc(2);
     size_t sort_bytes = 0, scan_bytes = 0;
     CTL_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys_in.p, keys_out.p, idx_in.p, idx_out.p, (size_t)n, 0u, 64u, (hipStream_t) nullptr));
     CTL_HIP(rocprim::inclusive_scan(nullptr, scan_bytes, counts.p, incl.p, (size_t)cap, rocprim::plus<uint64_t>(), (hipStream_t) nullptr));
     const size_t temp_need = std::max<size_t>(std::max(sort_bytes, scan_bytes), 16);
-    if (A.temp.n < temp_need) { temp.alloc(temp_need); swap_buffers(A.temp, temp); temp.free(); }   // (scratch of no meaning between calls: kept)
+    if (A.rebuild_temp_.n < temp_need) { temp.alloc(temp_need); swap_buffers(A.rebuild_temp_, temp); temp.free(); }   // (scratch of no meaning between calls: kept)
     for (auto& x : ev) CTL_HIP(hipEventCreate(&x));
-    if (ebox_cur.p) swap_buffers(A.ebox, ebox_cur);
-    swap_buffers(A.carry, carry);
-    CTL_HIP(hipMemcpy(A.carry.p, P.data(), P.size() * sizeof(double), hipMemcpyHostToDevice));
-    R.nodes = A.flat_nodes.p; R.leaves = src_leaves; R.n_nodes = (uint32_t)A.n_nodes; R.n_entries = n; R.compact = 1;
-    R.part_index = src_part; R.part_boxes = A.part_boxes.p; R.carry = A.carry.p; R.ebox = A.ebox.p; R.nbox = A.nbox.p;
+    if (ebox_cur.p) swap_buffers(A.refit_ebox_, ebox_cur);
+    swap_buffers(A.refit_carry_, carry);
+    CTL_HIP(hipMemcpy(A.refit_carry_.p, P.data(), P.size() * sizeof(double), hipMemcpyHostToDevice));
+    R.nodes = A.flat_nodes_.p; R.leaves = src_leaves; R.n_nodes = (uint32_t)A.flat_n_nodes_; R.n_entries = n; R.compact = 1;
+    R.part_index = src_part; R.part_boxes = A.refit_part_boxes_.p; R.carry = A.refit_carry_.p; R.ebox = A.refit_ebox_.p; R.nbox = A.refit_nbox_.p;
 }
 
-void flat_rebuilder::run(flat_scene_state& A) {
+void flat_rebuilder::run(Scene& A) {
     CTL_HIP(hipMemsetAsync(area_dev.p, 0, 16, nullptr));
-    launch_refit_area(nullptr, A.flat_nodes.p, R.n_nodes, area_dev.p);
+    launch_refit_area(nullptr, A.flat_nodes_.p, R.n_nodes, area_dev.p);
     // 1. entry boxes
     CTL_HIP(hipEventRecord(ev[0], nullptr));
     launch_refit_entries(nullptr, R, true);
     CTL_HIP(hipEventRecord(ev[1], nullptr));
     // 2. - 4. bounds, keys, sort
     CTL_HIP(hipMemsetAsync(bounds.p, 0xff, 12, nullptr)); CTL_HIP(hipMemsetAsync(bounds.p + 3, 0, 12, nullptr));
-    hipLaunchKernelGGL(k_rebuild_bounds, dim3(std::min<unsigned>(blocks_for(n).x, 1024u)), dim3(256), 0, nullptr, A.ebox.p, n, bounds.p);
-    hipLaunchKernelGGL(k_rebuild_keys, blocks_for(n), dim3(256), 0, nullptr, A.ebox.p, n, bounds.p, keys_in.p, idx_in.p);
+    hipLaunchKernelGGL(k_rebuild_bounds, dim3(std::min<unsigned>(blocks_for(n).x, 1024u)), dim3(256), 0, nullptr, A.refit_ebox_.p, n, bounds.p);
+    hipLaunchKernelGGL(k_rebuild_keys, blocks_for(n), dim3(256), 0, nullptr, A.refit_ebox_.p, n, bounds.p, keys_in.p, idx_in.p);
     CTL_HIP(hipGetLastError());
-    size_t bytes = A.temp.n;
-    CTL_HIP(rocprim::radix_sort_pairs(A.temp.p, bytes, keys_in.p, keys_out.p, idx_in.p, idx_out.p, (size_t)n, 0u, 64u, (hipStream_t) nullptr));
+    size_t bytes = A.rebuild_temp_.n;
+    CTL_HIP(rocprim::radix_sort_pairs(A.rebuild_temp_.p, bytes, keys_in.p, keys_out.p, idx_in.p, idx_out.p, (size_t)n, 0u, 64u, (hipStream_t) nullptr));
     CTL_HIP(hipEventRecord(ev[2], nullptr));
     // 5. - 8. the wide nodes, level by level
     const uint32_t root_range[2] = { 0u, n - 1u };
@@ -151,9 +151,9 @@ void flat_rebuilder::run(flat_scene_state& A) {
         CTL_HIP(hipGetLastError());
         size_t need = 0;
         CTL_HIP(rocprim::inclusive_scan(nullptr, need, counts.p, incl.p, (size_t)count, rocprim::plus<uint64_t>(), (hipStream_t) nullptr));
-        if (need > A.temp.n) throw std::runtime_error(std::string(who) + ": scan storage");
-        bytes = A.temp.n;
-        CTL_HIP(rocprim::inclusive_scan(A.temp.p, bytes, counts.p, incl.p, (size_t)count, rocprim::plus<uint64_t>(), (hipStream_t) nullptr));
+        if (need > A.rebuild_temp_.n) throw std::runtime_error(std::string(who) + ": scan storage");
+        bytes = A.rebuild_temp_.n;
+        CTL_HIP(rocprim::inclusive_scan(A.rebuild_temp_.p, bytes, counts.p, incl.p, (size_t)count, rocprim::plus<uint64_t>(), (hipStream_t) nullptr));
         uint64_t total = 0;
         CTL_HIP(hipMemcpy(&total, incl.p + (count - 1u), 8, hipMemcpyDeviceToHost));
         const uint64_t n_inner = total >> 32, n_leaf_entries = total & 0xffffffffull;
@@ -168,7 +168,7 @@ void flat_rebuilder::run(flat_scene_state& A) {
     if (entry_base != n) throw std::runtime_error(std::string(who) + ": the entry positions handed out do not sum to the entry count");
     level_iota.alloc(n_nodes);
     // 9. the entries in their final order
-    const rebuild_gather G{ src_leaves, leaves_new.p, perm.p, n, src_part, part_new.p, A.ebox.p, ebox_new.p };
+    const rebuild_gather G{ src_leaves, leaves_new.p, perm.p, n, src_part, part_new.p, A.refit_ebox_.p, ebox_new.p };
     hipLaunchKernelGGL(k_rebuild_gather, blocks_for(((size_t)n + 1) * 8), dim3(256), 0, nullptr, G);
     hipLaunchKernelGGL(k_rebuild_iota, blocks_for(n_nodes), dim3(256), 0, nullptr, level_iota.p, n_nodes);
     CTL_HIP(hipGetLastError());
@@ -184,13 +184,13 @@ void flat_rebuilder::run(flat_scene_state& A) {
     for (int k = 0; k < 4; k++) CTL_HIP(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
 }
 
-void flat_rebuilder::commit(flat_scene_state& A) {
+void flat_rebuilder::commit(Scene& A) {
     // the swap: tracers read S at every launch
-    swap_buffers(A.flat_nodes, nodes_new); swap_buffers(A.flat_leaves, leaves_new); swap_buffers(A.part_index, part_new); swap_buffers(A.level_nodes, level_iota);
-    swap_buffers(A.ebox, ebox_new); swap_buffers(A.nbox, nbox_new);
-    A.S.flat_nodes = A.flat_nodes.p; A.S.flat_leaves = A.flat_leaves.p; A.S.flat_root = 0; A.S.flat_top_cached = (int)std::min<size_t>(n_nodes, (size_t)flat_top_cache_nodes());
-    A.n_nodes = n_nodes; A.n_entries = n; A.max_depth = max_depth; A.root_slab = false; A.slab_nodes = 0;
-    A.refit.level_start = level_start;
+    swap_buffers(A.flat_nodes_, nodes_new); swap_buffers(A.flat_leaves_, leaves_new); swap_buffers(A.refit_part_index_, part_new); swap_buffers(A.refit_level_nodes_, level_iota);
+    swap_buffers(A.refit_ebox_, ebox_new); swap_buffers(A.refit_nbox_, nbox_new);
+    A.S.flat_nodes = A.flat_nodes_.p; A.S.flat_leaves = A.flat_leaves_.p; A.S.flat_root = 0; A.S.flat_top_cached = (int)std::min<size_t>(n_nodes, (size_t)flat_top_cache_nodes());
+    A.flat_n_nodes_ = n_nodes; A.flat_n_entries_ = n; A.flat_max_depth_ = max_depth; A.flat_root_slab_ = false; A.flat_slab_nodes_ = 0;
+    A.refit_.level_start = level_start;
 }
 
 void flat_rebuilder::report(ctl_scene_rebuild_stats& st) const {
@@ -199,36 +199,22 @@ void flat_rebuilder::report(ctl_scene_rebuild_stats& st) const {
     st.sort_ms = ms[1]; st.topology_ms = ms[2]; st.refit_ms = ms[0] + ms[3]; st.total_ms = ms[0] + ms[1] + ms[2] + ms[3];
 }
 
-void rebuild_flat_device(flat_scene_state& A, ctl_scene_rebuild_stats* stats) {
+void Scene::rebuild_flat(ctl_scene_rebuild_stats* stats) {
     require_device();
     const char* who = "ctl_scene_rebuild_flat";
-    if (!A.scene.flattened()) throw unsupported_error(std::string(who) + ": the scene was not created with CTL_SCENE_FLATTEN");
-    rebuild_refuse(A.S.flat_format, A.refit.level_start.size() >= 2 && A.part_index.p && A.part_index.n == A.n_entries, A.S.flat_compact != 0, A.n_entries, who);
-    if (!A.snap) throw std::runtime_error(std::string(who) + ": the scene holds no description");
-    const ctl_scene_desc& d = A.snap->d;
-    if (d.n_nodes != A.refit.xf0.size()) throw std::runtime_error(std::string(who) + ": the description has another number of nodes than the tree was built from");
-    std::vector<double> P((size_t)d.n_nodes * 12);
-    for (uint32_t k = 0; k < d.n_nodes; k++)
-        if (!refit_carry_matrix(d.node_transforms[k].m, A.refit.xf0[k].m, &P[(size_t)k * 12])) throw std::runtime_error(std::string(who) + ": singular node transform");
+    if (!flattened()) throw unsupported_error(std::string(who) + ": the scene was not created with CTL_SCENE_FLATTEN");
+    rebuild_refuse(S.flat_format, refit_.level_start.size() >= 2 && refit_part_index_.p && refit_part_index_.n == flat_n_entries_, S.flat_compact != 0, flat_n_entries_, who);
+    if (!snap_) throw std::runtime_error(std::string(who) + ": the scene holds no description");
+    const ctl_scene_desc& d = snap_->d;
+    if (d.n_nodes != refit_.xf0.size()) throw std::runtime_error(std::string(who) + ": the description has another number of nodes than the tree was built from");
+    const std::vector<double> P = carry_matrices(d, refit_.xf0, who);
     CTL_HIP(hipDeviceSynchronize());   // no trace reads the arrays any more
-    flat_rebuilder B; B.who = who; B.n = (uint32_t)A.n_entries; B.src_leaves = A.flat_leaves.p; B.src_part = A.part_index.p;
-    B.R.inst = A.inst.p; B.R.inst_fwd = A.inst_fwd.p; B.R.restamp = 0; B.R.leaf_keys = A.S.flat_leaf_keys; B.R.alpha_maps = (int)A.S.alpha_maps; B.R.tri_data = A.tri_data.p; B.R.node_info = A.node_info.p; B.R.mats = A.mats.p;
-    B.allocate(A, P);
-    B.run(A);
-    B.commit(A);
+    flat_rebuilder B; B.who = who; B.n = (uint32_t)flat_n_entries_; B.src_leaves = flat_leaves_.p; B.src_part = refit_part_index_.p;
+    B.R.inst = inst_.p; B.R.inst_fwd = inst_fwd_.p; B.R.restamp = 0; B.R.leaf_keys = S.flat_leaf_keys; B.R.alpha_maps = (int)S.alpha_maps; B.R.tri_data = tri_data_.p; B.R.node_info = node_info_.p; B.R.mats = mats_.p;
+    B.allocate(*this, P);
+    B.run(*this);
+    B.commit(*this);
     if (stats) B.report(*stats);
-}
-
-// The one member through which the work on the flattened tree reaches the scene's private buffers (flat_device.h)
-void Scene::rebuild_flat(ctl_scene_rebuild_stats* stats) {
-    flat_scene_state A{ *this, S, snap_, refit_, flat_missing_tris_, skins_, flat_n_nodes_, flat_n_entries_, flat_slab_nodes_, flat_max_depth_, flat_root_slab_,
-                        refit_tri_row_, refit_part_index_, refit_level_nodes_, refit_part_boxes_, refit_ebox_, refit_nbox_, refit_carry_, rebuild_temp_,
-                        top_nodes_, leaf_tris_, inst_, inst_fwd_, flat_nodes_, flat_leaves_, tri_data_, node_info_, mats_,
-                        [this](const ctl_scene_desc& d) { upload_top_level(d); }, [this](const ctl_scene_desc& d) { upload_lights(d); }, [this](const ctl_scene_desc& d) { upload_materials(d); },
-                        [this](const ctl_scene_desc& d) { bind(d); n_nodes = d.n_nodes; }, [this](const ctl_scene_desc& d) { set_camera(d); },
-                        [this](const ctl_scene_desc& d, const geometry_hashes* g) { snapshot(d, g); }, [this](const shading_state& s) { set_shading_state(s); } };
-    if (const node_set_job* job = take_node_set_job()) update_nodes_device(A, *job);
-    else rebuild_flat_device(A, stats);
 }
 
 }  // namespace ctl

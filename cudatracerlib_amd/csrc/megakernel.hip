@@ -9,7 +9,7 @@
 #include "tracer.h"
 #include "single_ray.h"
 #include "mitsuba_loader.h"   // unsupported_error
-#include "scene_volumes.h"
+#include "volume.h"
 #include <climits>
 
 static_assert((int)ctl::kFmtQ4 == (int)ctl::kFlatQ4 && (int)ctl::kFmtQ8 == (int)ctl::kFlatQ8, "the kernels' format numbers (traverse_flat.h) are the flattener's (flatten.h)");
@@ -291,7 +291,7 @@ PathTracer::PathTracer() {
 }
 void PathTracer::InitializeScene(Scene* s) {
     if (!s->S.flat_nodes) throw unsupported_error("PathTracer (megakernel): the scene must be created with CTL_SCENE_FLATTEN");
-    if (m_sParameters.getValue("Regularization")) refuse_volumes(s, "PathTracer with Regularization = true (PathTraceRegularization)");
+    if (m_sParameters.getValue("Regularization")) s->refuse_volumes("PathTracer with Regularization = true (PathTraceRegularization)");
     Tracer<true>::InitializeScene(s);
 }
 void PathTracer::Resize(unsigned int _w, unsigned int _h) {
@@ -303,8 +303,8 @@ void PathTracer::Resize(unsigned int _w, unsigned int _h) {
 void PathTracer::DoRender(Image* I, const float* d_t1, const float* d_t2, unsigned int n_batch) {
     // the reference's megakernel renders a block once per mention by the sampler, i.e. the SAME sample twice; only the wavefront plugin honours block samplers here
     if (pass_block_counts_) throw unsupported_error("PathTracer (megakernel): block samplers other than Uniform are served by the WavefrontPathTracer plugin only");
-    if (m_sParameters.getValue("Regularization")) refuse_volumes(m_pScene, "PathTracer with Regularization = true (PathTraceRegularization)");
-    const vol::table V = scene_volume_table(m_pScene);   // read per pass: ctl_scene_update may have changed the media since InitializeScene
+    if (m_sParameters.getValue("Regularization")) m_pScene->refuse_volumes("PathTracer with Regularization = true (PathTraceRegularization)");
+    const vol::table V = m_pScene->volume_table();   // read per pass: ctl_scene_update may have changed the media since InitializeScene
     pass_params P{};
     P.t1 = d_t1; P.t2 = (const float2*)d_t2; P.batch = n_batch; P.width = w; P.height = h; P.tile_rank = shard_rank; P.tile_world = shard_world; P.n_local_pixels = n_local_pixels;
     P.direct = m_sParameters.getValue("Direct"); P.max_path_length = m_sParameters.getValue("MaxPathLength"); P.rr_start_depth = m_sParameters.getValue("RRStartDepth");
@@ -338,7 +338,7 @@ void PathTracer::DebugInternal(Image* I, unsigned int x, unsigned int y, const f
     P.direct = 1; P.max_path_length = m_sParameters.getValue("MaxPathLength"); P.rr_start_depth = m_sParameters.getValue("RRStartDepth");
     P.debug_out = debug_.p; P.debug_x = x; P.debug_y = y;
     CTL_HIP(hipMemsetAsync(count_.p, 0, sizeof(unsigned long long), stream));
-    const vol::table V = scene_volume_table(m_pScene);
+    const vol::table V = m_pScene->volume_table();
     if (V.n && V.g) hipLaunchKernelGGL(k_path_trace_media_grid, dim3(1), dim3(256), 0, stream, m_pScene->S, P, V, I->device(), count_.p);
     else if (V.n) hipLaunchKernelGGL(k_path_trace_media, dim3(1), dim3(256), 0, stream, m_pScene->S, P, V, I->device(), count_.p);
     else hipLaunchKernelGGL(k_path_trace, dim3(1), dim3(256), 0, stream, m_pScene->S, P, I->device(), count_.p);

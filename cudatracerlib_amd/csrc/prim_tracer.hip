@@ -10,7 +10,6 @@
 #include "compaction.h"
 #include "prim_tracer.h"
 #include "single_ray.h"
-#include "scene_volumes.h"
 #include "mitsuba_loader.h"   // unsupported_error
 #include <climits>
 
@@ -217,7 +216,7 @@ PrimTracer::PrimTracer() {
 }
 void PrimTracer::InitializeScene(Scene* s) {
     if (!s->S.flat_nodes) throw unsupported_error("PrimTracer: the scene must be created with CTL_SCENE_FLATTEN");
-    refuse_volumes(s, "PrimTracer");
+    s->refuse_volumes("PrimTracer");
     Tracer<false>::InitializeScene(s);
 }
 void PrimTracer::Resize(unsigned int _w, unsigned int _h) {
@@ -260,7 +259,7 @@ void PrimTracer::render(Image* I, const float* d_t1, const float* d_t2, float* d
 }
 void PrimTracer::DoRender(Image* I, const float* d_t1, const float* d_t2, unsigned int n_batch) {
     (void)n_batch;   // Tracer<false>: one pass per call of DoRender
-    refuse_volumes(m_pScene, "PrimTracer");
+    m_pScene->refuse_volumes("PrimTracer");
     render(I, d_t1, d_t2, nullptr, 0, 0);
     intersect_launches++;
     total_rays_ += host_count_;

@@ -11,8 +11,6 @@
 #include "mitsuba_loader.h"   // unsupported_error
 #include "scene_volumes.h"
 #include <cstring>
-#include <map>
-#include <mutex>
 
 namespace ctl {
 
@@ -75,68 +73,40 @@ uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const
     return mask;
 }
 
-// ---- the scenes' volume tables (scene_volumes.h): device table, host copy (what the snapshot's `volumes` points at) and the kernel argument, per scene
-namespace {
-// the grid records: `grids` is the host copy the snapshot points at, its data pointers into `pack.cells` (the floats as the device holds them); dev_grids has
-// CTL_MAX_VOL_COUNT slots like dev, dev_cells grows with the data and never shrinks
-struct scene_volumes {
-    dbuf<ctl_volume> dev; std::vector<ctl_volume> host; vol::table T{}; uint64_t id = 0;
-    dbuf<vol::grid_rec> dev_grids; dbuf<float> dev_cells; vol::grid_pack pack; std::vector<ctl_volume_grid> grids;
-};
-std::mutex g_volumes_mutex;
-// never destroyed: a scene that is still alive when the process ends must not free device memory during static destruction, after the runtime may have gone
-std::map<const Scene*, std::unique_ptr<scene_volumes>>& g_volumes = *new std::map<const Scene*, std::unique_ptr<scene_volumes>>();
-uint64_t g_next_volumes_id = 1;
-// the description's media into the scene's table, synchronously, when they differ from what it holds; returns the host copy (null without media) and, in `grids_out`,
-// the host copy of the grid records
-const ctl_volume* store_volumes(const Scene* s, const ctl_scene_desc& d, const ctl_volume_grid** grids_out) {
-    std::lock_guard<std::mutex> lock(g_volumes_mutex);
-    std::unique_ptr<scene_volumes>& e = g_volumes[s];
-    const bool fresh = !e;
-    if (fresh) {
-        e.reset(new scene_volumes()); e->id = g_next_volumes_id++; e->dev.alloc(CTL_MAX_VOL_COUNT); CTL_HIP(hipMemset(e->dev.p, 0, CTL_MAX_VOL_COUNT * sizeof(ctl_volume)));
-        e->dev_grids.alloc(CTL_MAX_VOL_COUNT); CTL_HIP(hipMemset(e->dev_grids.p, 0, CTL_MAX_VOL_COUNT * sizeof(vol::grid_rec)));
-    }
-    vol::grid_pack pack; vol::pack_grids(d, pack);
-    const bool grids_differ = fresh || !pack.same(e->pack);
-    if (grids_differ) {   // the records whole (16 slots), the floats into the buffer they had unless it must grow
-        CTL_HIP(hipMemcpy(e->dev_grids.p, pack.recs.data(), CTL_MAX_VOL_COUNT * sizeof(vol::grid_rec), hipMemcpyHostToDevice));
-        if (pack.cells.size() > e->dev_cells.n) e->dev_cells.alloc(pack.cells.size());
-        if (!pack.cells.empty()) CTL_HIP(hipMemcpy(e->dev_cells.p, pack.cells.data(), pack.cells.size() * 4, hipMemcpyHostToDevice));
-        e->pack = std::move(pack);
+// ---- the scene's volume tables (scene_volumes.h): device table, host copy (what the snapshot's `volumes` points at) and the kernel argument
+scene_volumes::scene_volumes() {
+    dev.alloc(CTL_MAX_VOL_COUNT); CTL_HIP(hipMemset(dev.p, 0, CTL_MAX_VOL_COUNT * sizeof(ctl_volume)));
+    dev_grids.alloc(CTL_MAX_VOL_COUNT); CTL_HIP(hipMemset(dev_grids.p, 0, CTL_MAX_VOL_COUNT * sizeof(vol::grid_rec)));
+    pack.recs.assign(CTL_MAX_VOL_COUNT, vol::grid_rec{});   // what dev_grids holds now
+}
+const ctl_volume* scene_volumes::store(const ctl_scene_desc& d, const ctl_volume_grid** grids_out) {
+    vol::grid_pack now; vol::pack_grids(d, now);
+    if (!now.same(pack)) {   // the records whole (16 slots), the floats into the buffer they had unless it must grow
+        CTL_HIP(hipMemcpy(dev_grids.p, now.recs.data(), CTL_MAX_VOL_COUNT * sizeof(vol::grid_rec), hipMemcpyHostToDevice));
+        if (now.cells.size() > dev_cells.n) dev_cells.alloc(now.cells.size());
+        if (!now.cells.empty()) CTL_HIP(hipMemcpy(dev_cells.p, now.cells.data(), now.cells.size() * 4, hipMemcpyHostToDevice));
+        pack = std::move(now);
     }
     // the snapshot's records: the caller's, with the data pointers turned to the scene's own copy of the floats
-    e->grids.assign(d.volume_grids, d.volume_grids + d.n_volume_grids);
-    for (ctl_volume_grid& G : e->grids) {
-        const vol::grid_rec& R = e->pack.recs[G.volume];
-        G.data = G.single_grid ? e->pack.cells.data() + R.off : nullptr; G.data_a = G.single_grid ? nullptr : e->pack.cells.data() + R.off_a; G.data_s = G.single_grid ? nullptr : e->pack.cells.data() + R.off_s;
+    grids.assign(d.volume_grids, d.volume_grids + d.n_volume_grids);
+    for (ctl_volume_grid& G : grids) {
+        const vol::grid_rec& R = pack.recs[G.volume];
+        G.data = G.single_grid ? pack.cells.data() + R.off : nullptr; G.data_a = G.single_grid ? nullptr : pack.cells.data() + R.off_a; G.data_s = G.single_grid ? nullptr : pack.cells.data() + R.off_s;
     }
-    *grids_out = e->grids.empty() ? nullptr : e->grids.data();
+    *grids_out = grids.empty() ? nullptr : grids.data();
     const size_t n = d.n_volumes;   // (<= CTL_MAX_VOL_COUNT: check_scene_desc)
-    if (fresh || n != e->host.size() || (n && std::memcmp(e->host.data(), d.volumes, n * sizeof(ctl_volume)) != 0)) {
-        e->host.assign(d.volumes, d.volumes + n);
-        if (n) CTL_HIP(hipMemcpy(e->dev.p, e->host.data(), n * sizeof(ctl_volume), hipMemcpyHostToDevice));
+    if (n != host.size() || (n && std::memcmp(host.data(), d.volumes, n * sizeof(ctl_volume)) != 0)) {
+        host.assign(d.volumes, d.volumes + n);
+        if (n) CTL_HIP(hipMemcpy(dev.p, host.data(), n * sizeof(ctl_volume), hipMemcpyHostToDevice));
     }
-    e->T = vol::make_table(e->dev.p, (uint32_t)n, e->pack.any ? e->dev_grids.p : nullptr, e->pack.any ? e->dev_cells.p : nullptr);
-    return e->host.empty() ? nullptr : e->host.data();
+    T = vol::make_table(dev.p, (uint32_t)n, pack.any ? dev_grids.p : nullptr, pack.any ? dev_cells.p : nullptr);
+    return host.empty() ? nullptr : host.data();
 }
-}  // namespace
-vol::table scene_volume_table(const Scene* s) {
-    std::lock_guard<std::mutex> lock(g_volumes_mutex);
-    auto it = g_volumes.find(s);
-    return it == g_volumes.end() ? vol::table{} : it->second->T;
-}
-uint64_t scene_volumes_id(const Scene* s) {
-    std::lock_guard<std::mutex> lock(g_volumes_mutex);
-    auto it = g_volumes.find(s);
-    return it == g_volumes.end() ? 0 : it->second->id;
-}
-void refuse_volumes(const Scene* s, const char* who) {
-    const uint32_t n = s ? scene_volume_table(s).n : 0;
+vol::table Scene::volume_table() const { return volumes_ ? volumes_->T : vol::table{}; }
+void Scene::refuse_volumes(const char* who) const {
+    const uint32_t n = volume_table().n;
     if (n) throw unsupported_error(std::string(who) + ": the scene has participating media (" + std::to_string(n) + " volumes), which only the PathTracer plugin with Regularization = false renders");
 }
-
-Scene::~Scene() { std::lock_guard<std::mutex> lock(g_volumes_mutex); g_volumes.erase(this); }
 
 void Scene::snapshot(const ctl_scene_desc& d, const geometry_hashes* geom) {
     std::unique_ptr<desc_snapshot> s(new desc_snapshot());
@@ -146,7 +116,8 @@ void Scene::snapshot(const ctl_scene_desc& d, const geometry_hashes* geom) {
     s->images.assign(d.images, d.images + d.n_images); for (auto& m : s->images) m.texels = nullptr;
     // the media: creation and every update end here, after the device has been synchronised — the table is written in place (no re-creation, no refit)
     const ctl_volume_grid* grids = nullptr;
-    const ctl_volume* volumes = store_volumes(this, d, &grids);
+    if (!volumes_) volumes_.reset(new scene_volumes());
+    const ctl_volume* volumes = volumes_->store(d, &grids);
     if (geom) s->geom = *geom;                    // after an update: the pass that found the difference made them
     else if (snap_) s->geom = snap_->geom;
     else hash_geometry(d, s->geom);
@@ -161,6 +132,18 @@ void Scene::snapshot(const ctl_scene_desc& d, const geometry_hashes* geom) {
     snap_ = std::move(s);
 }
 
+std::vector<double> Scene::carry_matrices(const ctl_scene_desc& d, const std::vector<ctl_float4x4>& xf0, const char* who) {
+    std::vector<double> P((size_t)d.n_nodes * 12);
+    for (uint32_t k = 0; k < d.n_nodes; k++)
+        if (!refit_carry_matrix(d.node_transforms[k].m, xf0[k].m, &P[(size_t)k * 12])) throw std::runtime_error(std::string(who) + ": singular node transform");
+    return P;
+}
+std::vector<uint8_t> Scene::device_owned_meshes() const {
+    std::vector<uint8_t> owned;
+    if (!skins_.empty()) { owned.assign(snap_->d.n_meshes, 0); for (const auto& kv : skins_) if (kv.first < owned.size()) owned[kv.first] = 1; }
+    return owned;
+}
+
 // The refit (and / or the re-stamp of the entries' material bits) of the device tree; the null stream, between two synchronisations: ordered after every trace that
 // was launched and before the next
 void Scene::refit_flat(const ctl_scene_desc& d, bool boxes, bool restamp, const std::vector<uint8_t>* mesh_changed, ctl_scene_update_stats* st) {
@@ -169,9 +152,7 @@ void Scene::refit_flat(const ctl_scene_desc& d, bool boxes, bool restamp, const 
     R.part_index = refit_part_index_.p; R.part_boxes = refit_part_boxes_.p; R.inst = inst_.p; R.inst_fwd = inst_fwd_.p;
     R.restamp = restamp ? (int)snap_->materials.size() : 0; R.leaf_keys = S.flat_leaf_keys; R.alpha_maps = (int)S.alpha_maps; R.tri_data = tri_data_.p; R.node_info = node_info_.p; R.mats = mats_.p;
     if (!boxes) { launch_refit_entries(nullptr, R, false); CTL_HIP(hipDeviceSynchronize()); return; }
-    std::vector<double> P((size_t)d.n_nodes * 12);
-    for (uint32_t k = 0; k < d.n_nodes; k++)
-        if (!refit_carry_matrix(d.node_transforms[k].m, refit_.xf0[k].m, &P[(size_t)k * 12])) throw std::runtime_error("ctl_scene_update: singular node transform");
+    const std::vector<double> P = carry_matrices(d, refit_.xf0, "ctl_scene_update");
     refit_carry_.upload(P.data(), P.size());
     if (refit_ebox_.n < flat_n_entries_) refit_ebox_.alloc(flat_n_entries_);
     if (refit_nbox_.n < flat_n_nodes_) refit_nbox_.alloc(flat_n_nodes_);
@@ -229,8 +210,7 @@ uint32_t Scene::update(const ctl_scene_desc& d, ctl_scene_update_stats* stats) {
     require_device();
     if (!snap_) throw std::runtime_error("ctl_scene_update: the scene holds no description");
     geometry_hashes geom;
-    std::vector<uint8_t> device_owned;   // the bound meshes (mesh_skin.hip): their values are the device's, whatever the description says
-    if (!skins_.empty()) { device_owned.assign(snap_->d.n_meshes, 0); for (const auto& kv : skins_) if (kv.first < device_owned.size()) device_owned[kv.first] = 1; }
+    const std::vector<uint8_t> device_owned = device_owned_meshes();
     const uint32_t mask = scene_desc_diff(snap_->d, d, &snap_->geom, &geom, device_owned.empty() ? nullptr : &device_owned);
     last_mask_ = mask;
     if (mask == 0) { last_update_ = ctl_scene_update_stats{}; if (stats) *stats = last_update_; return 0; }   // nothing differs: no synchronisation, no tracer is stalled

@@ -38,6 +38,10 @@ template <typename T> struct dbuf {   // tracked device allocation (Base/CudaMem
 // ignore_values (may be null): per mesh, non-zero = the VALUES of that mesh are not compared (a device-owned mesh, mesh_skin.hip): b's hash of it is a's
 uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const geometry_hashes* a_geometry = nullptr, geometry_hashes* b_geometry = nullptr, const std::vector<uint8_t>* ignore_values = nullptr);
 struct skin_binding;   // mesh_skin.hip
+struct scene_volumes;  // scene_volumes.h: a scene's participating media in HBM
+namespace vol { struct table; }   // volume.h
+struct node_set_basis;   // flat_nodes.h
+struct flat_rebuilder;   // flat_device.h
 // the host copy of a description that a scene keeps to diff an update against (scene_update.hip)
 struct desc_snapshot {
     ctl_scene_desc d{};   // pointers into the vectors below; the geometry arrays are null
@@ -65,6 +69,9 @@ public:
     // ctl_scene_rebuild_flat (flat_rebuild.hip): a new flattened Q4 tree over the entries the scene holds, made on the device in place; refusals (unsupported_error) and failed
     // allocations leave the scene as it was.  Synchronous.
     void rebuild_flat(ctl_scene_rebuild_stats* stats);
+    // ctl_scene_update_nodes (flat_nodes.hip): the description `d` with another set of nodes — old_of_new[k] = the node of the held description that node k was, or UINT32_MAX
+    // for an added one — applied in place; `basis`: the small arrays of the held description (flat_nodes.h).  Refusals and failed allocations leave the scene as it was.  Synchronous.
+    void update_nodes(const ctl_scene_desc& d, const uint32_t* old_of_new, uint32_t n_new_nodes, const node_set_basis& basis, ctl_scene_nodes_stats* stats);
     void read_flat_bvh(flat_scene& out);   // the device tree copied back, un-stamped: what flatten_scene handed to the upload, after any refit
     // skinned meshes (mesh_skin.hip; ctl_scene_bind_skin, ctl_scene_animate_mesh, ctl_scene_read_mesh_geometry, ctl_scene_unbind_skin).  A bound mesh is device-owned: update()
     // neither compares nor uploads its values
@@ -73,15 +80,21 @@ public:
     void animate_mesh(uint32_t mesh, const ctl_float4x4* bones0, const ctl_float4x4* bones1, float lerp, ctl_scene_update_stats* stats);
     void read_mesh_geometry(uint32_t mesh, float* positions_out, float* normals_out, ctl_triangle_data* tri_data_out, ctl_woop_tri* woop_out);
     float last_skin_ms() const { return last_skin_ms_; }   // HIP-event time of the three pose kernels of the last animate_mesh
+    // the participating media (scene_volumes.h): the kernel argument as the last creation / update left it (n == 0: no media), read by the PathTracer plugin at every pass;
+    // the plugins without medium code refuse a scene that has media instead of rendering it without them: unsupported_error naming `who` and the PathTracer plugin
+    vol::table volume_table() const;
+    void refuse_volumes(const char* who) const;
     dev_scene S{};
     uint32_t n_nodes = 0;
     float box_min[3] = { 0, 0, 0 }, box_max[3] = { 0, 0, 0 };   // KernelDynamicScene::m_sBox
     float near_depth = 0, far_depth = 0;                        // SensorBase::m_fNearFarDepths of the scene's camera (DeviceDepthImage::NormalizeDepthD3D)
 private:
+    friend struct flat_rebuilder;   // flat_device.h: builds a new tree beside the scene's and swaps it in
     // the upload, block by block: the constructor runs all of them, update() those whose part of the description changed.  None of them judges the description:
     // check_scene_desc (scene_checks.h) has, before the first of them runs
     void upload_top_level(const ctl_scene_desc& d);
     void upload_instances(const ctl_scene_desc& d);
+    static void pack_instances(const ctl_scene_desc& d, std::vector<float4>& inst, std::vector<float4>& fwd, std::vector<uint4>& node_info);   // the records upload_instances uploads
     void upload_lights(const ctl_scene_desc& d);
     void upload_materials(const ctl_scene_desc& d);
     void set_shading_state(const shading_state& s) { S.shade_features = s.features; S.shade_models = s.models; S.alpha_maps = s.alpha_maps; }   // derive_shading_state (device_scene.h)
@@ -90,11 +103,15 @@ private:
     void snapshot(const ctl_scene_desc& d, const geometry_hashes* geom = nullptr);   // host copy of the description an update diffs against (the geometry arrays as hashes; geom: already made)
     // mesh_changed (may be null): per mesh, whether its vertex values differ (CTL_DIFF_GEOMETRY): the entries of those meshes get their new Woop rows first
     void refit_flat(const ctl_scene_desc& d, bool boxes, bool restamp, const std::vector<uint8_t>* mesh_changed, ctl_scene_update_stats* stats);
+    // P = M_new * M_0^-1 per node of `d` (flat_refit.h, 12 doubles each), M_0 from xf0; throws "<who>: singular node transform"
+    static std::vector<double> carry_matrices(const ctl_scene_desc& d, const std::vector<ctl_float4x4>& xf0, const char* who);
+    std::vector<uint8_t> device_owned_meshes() const;   // per mesh, non-zero = bound to a skin (mesh_skin.hip): its values are the device's, whatever a description says; empty without bound meshes
     void upload_mesh_geometry(const ctl_scene_desc& d, const mesh_ranges& R, uint32_t mesh);   // the two-level arrays of one mesh, re-laid-out as the constructor does, into the same allocations
     bool reduced_rough_transmittance_ = false;
     std::map<uint32_t, std::shared_ptr<skin_binding>> skins_; float last_skin_ms_ = 0;   // the bound meshes
     ctl_scene_update_stats last_update_{}; uint32_t last_mask_ = 0;
     std::unique_ptr<desc_snapshot> snap_;
+    std::unique_ptr<scene_volumes> volumes_;   // made by the first snapshot(), written in place by every later one
     flat_scene::refit_side refit_;   // host part: xf0, level_start
     std::vector<uint32_t> flat_missing_tris_;   // triangles of instanced meshes without a leaf entry (flatten.h flat_missing_triangles): a geometry update cannot bring them back
     dbuf<uint32_t> refit_tri_row_, refit_node_changed_;   // made by the first geometry update: triangle -> row of leaf_tris_ (triangle_woop_rows); per node, whether its mesh changed

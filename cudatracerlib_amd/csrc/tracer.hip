@@ -4,6 +4,7 @@
 #include "tracer.h"
 #include "scene_builder.h"
 #include "scene_checks.h"
+#include "scene_volumes.h"
 #include "flatten.h"
 #include "image_io.h"
 #include "mitsuba_loader.h"   // unsupported_error
@@ -35,10 +36,9 @@ void Scene::upload_top_level(const ctl_scene_desc& d) {
     if (d.n_scene_bvh_nodes) std::memcpy(tmp.data(), d.scene_bvh_nodes, (size_t)d.n_scene_bvh_nodes * 64);
     top_nodes_.upload(tmp.data(), tmp.size());
 }
-void Scene::upload_instances(const ctl_scene_desc& d) {
+void Scene::pack_instances(const ctl_scene_desc& d, std::vector<float4>& inst, std::vector<float4>& fwd, std::vector<uint4>& ninfo) {
     // instances: inverse transform rows + the mesh offsets the reference fetches from Node / KernelMesh (TraceHelper.cu:530,557-560)
-    std::vector<float4> inst((size_t)d.n_nodes * 4), fwd((size_t)d.n_nodes * 3);
-    std::vector<uint4> ninfo(d.n_nodes);
+    inst.resize((size_t)d.n_nodes * 4); fwd.resize((size_t)d.n_nodes * 3); ninfo.resize(d.n_nodes);
     for (uint32_t k = 0; k < d.n_nodes; k++) {
         const float* im = d.node_inv_transforms[k].m; const float* fm = d.node_transforms[k].m;
         const ctl_node& N = d.nodes[k];   // (affine transforms, an existing mesh: check_scene_desc)
@@ -47,6 +47,10 @@ void Scene::upload_instances(const ctl_scene_desc& d) {
         inst[k * 4 + 3] = make_float4(im[15], __builtin_bit_cast(float, km.bvh_node_offset), __builtin_bit_cast(float, km.bvh_tri_offset / 3), __builtin_bit_cast(float, km.tri_offset));
         ninfo[k] = make_uint4(N.material_offset, N.lights[0], N.lights[1], N.n_lights);
     }
+}
+void Scene::upload_instances(const ctl_scene_desc& d) {
+    std::vector<float4> inst, fwd; std::vector<uint4> ninfo;
+    pack_instances(d, inst, fwd, ninfo);
     inst_.upload(inst.data(), inst.size()); inst_fwd_.upload(fwd.data(), fwd.size()); node_info_.upload(ninfo.data(), ninfo.size());
 }
 void Scene::upload_lights(const ctl_scene_desc& d) {
@@ -288,6 +292,7 @@ Scene::Scene(const ctl_scene_desc& d, bool flatten, int flat_format, bool reduce
     set_camera(d);
     snapshot(d);
 }
+Scene::~Scene() {}   // out of line: scene_volumes is complete here
 
 // ------------------------------------------------------------------------------------------------ Image
 Image::Image(uint32_t w, uint32_t h) : w_(w), h_(h) { require_device(); px_.alloc((size_t)w * h); Clear(); }

@@ -2,7 +2,6 @@
 #pragma once
 #include "../../include/ctl_amd.h"
 #include "volume.h"
-#include "scene_volumes.h"
 
 namespace ctl {
 

@@ -208,3 +208,22 @@ def test_refusals_leave_the_scene_as_it_was(gpu):
     # ... and after all that the scene takes the change
     s.update_nodes(new.desc, m)
     same_rebuilt_tree(validated(s), api.FlatBvh(old.desc).update_nodes(new.desc, m))
+
+
+def test_a_refused_update_nodes_leaves_nothing_behind(gpu):
+    """a refused update_nodes keeps no state for a later call: rebuild_flat() on the same thread right after it REBUILDS — rebuild stats over the entries the scene had,
+    the tree of the host rebuild of the same description — and the next update_nodes is still its yardstick's (N7: the case and the refused map of the test above)"""
+    old, new, m = pair("N7")
+    s = gpu.Scene(old.desc, flatten=True); host = api.FlatBvh(old.desc)
+    n_before = len(host.leaves())
+    other_mesh = m.copy(); other_mesh[3] = LONG          # a node of a mesh the scene does not hold at that place
+    with pytest.raises(api.CtlError) as e:
+        s.update_nodes(new.desc, other_mesh)
+    assert e.value.code == api.ERR_INVALID, str(e.value)
+    st = s.rebuild_flat(); host.rebuild(old.desc)
+    assert set(st) >= {"n_nodes", "n_entries", "max_depth", "levels", "sort_ms", "topology_ms"} and "entries_after" not in st
+    assert st["n_entries"] == n_before == len(host.leaves()) and st["n_nodes"] == len(host.nodes())
+    same_rebuilt_tree(validated(s), host)
+    st2 = s.update_nodes(new.desc, m); host.update_nodes(new.desc, m)
+    assert st2["rebuilt"] == 1 and st2["entries_before"] == n_before and st2["entries_after"] == len(host.leaves())
+    same_rebuilt_tree(validated(s), host)

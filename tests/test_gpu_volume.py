@@ -163,3 +163,57 @@ def test_plugins_that_refuse_volumes(gpu, orc):
     with pytest.raises(gpu.CtlError, match="PathTracer") as e:
         tr.DoPass(gpu.Image(W, H), new_trace=True)
     assert e.value.code == -5
+
+
+def test_two_scenes_two_media_tables(gpu, orc):
+    """every scene owns its volume table: two scenes with different homogeneous media (the sets `one` and `half` of volume_cases.py over the Cornell box, 16 x 16 pixels,
+    one PathTracer each, 2 passes with recorded tables) render, alive together and passes interleaved, the bytes each renders alone; B still does after A is destroyed;
+    the WavefrontPathTracer refuses either with ERR_UNSUPPORTED and today's message"""
+    import gc
+    import weakref
+    w = h = 16
+    tables = tables_of(orc)
+
+    def box_with(name):
+        sc = scenes.cornell_box(w, h)
+        for v in make_set(name):
+            sc.CreateVolume(v)
+        sc.UpdateScene()
+        return sc
+
+    def tracer_for(scene):
+        tr = gpu.PathTracer(); p = tr.getParameters(); p.setValue("MaxPathLength", MAX_LEN); p.setValue("RRStartDepth", RR)
+        tr.Resize(w, h); tr.InitializeScene(scene)
+        return tr
+
+    def one_pass(tr, img, k):
+        tr.setSamplerTables(*tables[k]); tr.DoPass(img, new_trace=(k == 0))
+
+    def alone(sc):
+        scene = gpu.Scene(sc.desc, flatten=True); tr = tracer_for(scene); img = gpu.Image(w, h)
+        for k in range(len(tables)):
+            one_pass(tr, img, k)
+        return img.getPixelData().copy()
+    sa, sb = box_with("one"), box_with("half")
+    assert sa.desc.n_volumes == sb.desc.n_volumes == 1
+    want_a = alone(sa); gc.collect()
+    want_b = alone(sb); gc.collect()
+    assert not np.array_equal(want_a, want_b) and want_a[..., :3].any() and want_b[..., :3].any()
+    A, B = gpu.Scene(sa.desc, flatten=True), gpu.Scene(sb.desc, flatten=True)
+    ta, tb = tracer_for(A), tracer_for(B)
+    ia, ib = gpu.Image(w, h), gpu.Image(w, h)
+    for k in range(len(tables)):
+        one_pass(ta, ia, k); one_pass(tb, ib, k)
+    assert np.array_equal(ia.getPixelData().view(np.uint32), want_a.view(np.uint32)), "scene A beside scene B"
+    assert np.array_equal(ib.getPixelData().view(np.uint32), want_b.view(np.uint32)), "scene B beside scene A"
+    for scene in (A, B):
+        wf = gpu.WavefrontPathTracer(); wf.Resize(w, h)
+        with pytest.raises(gpu.CtlError, match=r"WavefrontPathTracer: the scene has participating media \(1 volumes\), which only the PathTracer plugin with Regularization = false renders") as e:
+            wf.InitializeScene(scene)
+        assert e.value.code == api.ERR_UNSUPPORTED
+    gone = weakref.ref(A)
+    del ta, A, wf, scene, e; gc.collect()
+    assert gone() is None   # ctl_scene_destroy has run
+    for k in range(len(tables)):
+        one_pass(tb, ib, k)
+    assert np.array_equal(ib.getPixelData().view(np.uint32), want_b.view(np.uint32)), "scene B after scene A was destroyed"
