@@ -282,18 +282,30 @@ class FlatBvh:
         _check(lib.ctl_flat_bvh_arrays(self._h, C.byref(self.desc)))
         return self
 
-    def rebuild(self, desc):
-        """ctl_flat_bvh_rebuild: the tree refitted to `desc` and then REBUILT over the same leaf entries (csrc/flat_rebuild.h: Morton codes, sort, Karras's hierarchy
-        collapsed 4-wide, breadth-first layout) on the host — the yardstick of Scene.update(desc) + Scene.rebuild_flat().  Q4 trees with implied links only.  Returns self."""
-        _check(lib.ctl_flat_bvh_rebuild(self._h, C.byref(desc)))
+    def rebuild(self, desc, builder="lbvh"):
+        """ctl_flat_bvh_rebuild[_ex]: the tree refitted to `desc` and then REBUILT over the same leaf entries (csrc/flat_rebuild.h: Morton codes, sort, Karras's hierarchy
+        collapsed 4-wide, breadth-first layout) on the host — the yardstick of Scene.update(desc) + Scene.rebuild_flat().  builder: "lbvh" or "ploc" (csrc/flat_ploc.h:
+        the binary tree by locally-ordered clustering instead).  Q4 trees with implied links only.  Returns self."""
+        b = rebuild_builder(builder)
+        _check(lib.ctl_flat_bvh_rebuild(self._h, C.byref(desc)) if b == REBUILD_LBVH else lib.ctl_flat_bvh_rebuild_ex(self._h, C.byref(desc), b))
         _check(lib.ctl_flat_bvh_arrays(self._h, C.byref(self.desc)))
         return self
 
-    def update_nodes(self, desc, old_of_new):
-        """ctl_flat_bvh_update_nodes: the tree after a change of the node set (old_of_new as Scene.update_nodes takes it), on the host with the device's single-source
+    def rebuild_order(self, desc):
+        """ctl_flat_bvh_rebuild_order: what the rebuild's stages 1 - 4 hand to its builder for this tree (refitted to `desc`), nothing written:
+        (sorted_entry (n,) uint32, entry_boxes (n, 6) float32 by entry index, bounds (6,) float32)"""
+        n = len(self.leaves())
+        order, boxes, bounds = np.zeros(n, np.uint32), np.zeros((n, 6), np.float32), np.zeros(6, np.float32)
+        _check(lib.ctl_flat_bvh_rebuild_order(self._h, C.byref(desc), order.ctypes.data, boxes.ctypes.data, bounds.ctypes.data))
+        return order, boxes, bounds
+
+    def update_nodes(self, desc, old_of_new, builder="lbvh"):
+        """ctl_flat_bvh_update_nodes[_ex] (builder: "lbvh" or "ploc", as FlatBvh.rebuild takes it): the tree after a change of the node set (old_of_new as Scene.update_nodes takes it), on the host with the device's single-source
         functions (csrc/flat_nodes.h) — the yardstick of Scene.update_nodes.  A refusal leaves the handle as it was.  Returns self."""
         M = np.ascontiguousarray(old_of_new, dtype=np.uint32)
-        _check(lib.ctl_flat_bvh_update_nodes(self._h, C.byref(desc), M.ctypes.data, u32(len(M))))
+        b = rebuild_builder(builder)
+        _check(lib.ctl_flat_bvh_update_nodes(self._h, C.byref(desc), M.ctypes.data, u32(len(M))) if b == REBUILD_LBVH else
+               lib.ctl_flat_bvh_update_nodes_ex(self._h, C.byref(desc), M.ctypes.data, u32(len(M)), b))
         self._keepalive = desc
         _check(lib.ctl_flat_bvh_arrays(self._h, C.byref(self.desc)))
         return self
@@ -988,11 +1000,12 @@ class Scene:
         self._node_ids = getattr(desc, "node_ids", self._node_ids)
         return mask.value
 
-    def update_nodes(self, sc_or_desc, old_of_new=None):
+    def update_nodes(self, sc_or_desc, old_of_new=None, builder="lbvh"):
         """ctl_scene_update_nodes: another SET of nodes in place — after DynamicScene.DeleteNode and / or CreateNode of further instances of meshes the scene already
         holds, and UpdateScene() — with everything else Scene.update applies.  On a flattened Q4 scene the entries of removed nodes are dropped, those of added nodes made
         from the mesh arrays as they stand in HBM, and the tree rebuilt, all on the device (csrc/flat_nodes.hip).  sc_or_desc: the DynamicScene or its description.
         old_of_new: per new node its index in the description the scene holds or 0xffffffff (added); None: computed from the stable node ids of the two descriptions.
+        builder: "lbvh" or "ploc", the builder of the rebuild stage (Scene.rebuild_flat).
         Returns the stats dict (entries_before / _after / _dropped / _generated, degenerate_skipped, rebuilt, edit_ms, total_ms, rebuild = the rebuild_flat dict).
         CtlError(ERR_INVALID / ERR_UNSUPPORTED) leaves the scene as it was.  Start the next pass with new_trace."""
         desc = sc_or_desc.getKernelSceneData() if isinstance(sc_or_desc, DynamicScene) else sc_or_desc
@@ -1004,11 +1017,14 @@ class Scene:
             old_of_new = [index.get(i, 0xffffffff) for i in new_ids]
         M = np.ascontiguousarray(old_of_new, dtype=np.uint32)
         st = ctl_scene_nodes_stats()
-        _check(lib.ctl_scene_update_nodes(self._h, C.byref(desc), M.ctypes.data, u32(len(M)), C.addressof(st)))
+        b = rebuild_builder(builder)
+        _check(lib.ctl_scene_update_nodes(self._h, C.byref(desc), M.ctypes.data, u32(len(M)), C.addressof(st)) if b == REBUILD_LBVH else
+               lib.ctl_scene_update_nodes_ex(self._h, C.byref(desc), M.ctypes.data, u32(len(M)), b, C.addressof(st)))
         self._keepalive = desc
         self._node_ids = getattr(desc, "node_ids", None)
         out = {k: getattr(st, k) for k, _ in st._fields_ if k != "rebuild"}
         out["rebuild"] = {k: getattr(st.rebuild, k) for k, _ in st.rebuild._fields_}
+        out["rebuild"]["rounds"] = _last_rounds() if st.rebuilt else 0
         return out
 
     def update_stats(self):
@@ -1017,14 +1033,19 @@ class Scene:
         _check(lib.ctl_scene_get_update_stats(self._h, C.byref(st)))
         return {k: getattr(st, k) for k, _ in st._fields_}
 
-    def rebuild_flat(self):
-        """ctl_scene_rebuild_flat: a new flattened Q4 tree over the leaf entries the scene holds, made on the device in place (csrc/flat_rebuild.hip) — for a tree that
-        refits have degraded.  Returns the stats dict (n_nodes, n_entries, max_depth, levels, node_area_before / _after, sort_ms, topology_ms, refit_ms, total_ms).
+    def rebuild_flat(self, builder="lbvh"):
+        """ctl_scene_rebuild_flat[_ex]: a new flattened Q4 tree over the leaf entries the scene holds, made on the device in place (csrc/flat_rebuild.hip) — for a tree that
+        refits have degraded.  builder: "lbvh" (Karras's radix tree over the Morton codes) or "ploc" (csrc/flat_ploc.h: locally-ordered clustering from the same sorted
+        order — a smaller node area for more launches; INTEGRATION.md "Updating a scene" has the measured trade).
+        Returns the stats dict (n_nodes, n_entries, max_depth, levels, node_area_before / _after, sort_ms, topology_ms, refit_ms, total_ms, rounds = clustering rounds).
         CtlError(ERR_UNSUPPORTED) for a scene that is not a flattened Q4 scene with refit data and implied links, or when the new tree would be too deep (the scene keeps
         its tree).  Start the next pass with new_trace."""
         st = ctl_scene_rebuild_stats()
-        _check(lib.ctl_scene_rebuild_flat(self._h, C.addressof(st)))
-        return {k: getattr(st, k) for k, _ in st._fields_}
+        b = rebuild_builder(builder)
+        _check(lib.ctl_scene_rebuild_flat(self._h, C.addressof(st)) if b == REBUILD_LBVH else lib.ctl_scene_rebuild_flat_ex(self._h, b, C.addressof(st)))
+        out = {k: getattr(st, k) for k, _ in st._fields_}
+        out["rounds"] = _last_rounds()
+        return out
 
     def bind_skin(self, mesh, rest_positions, indices, bone_indices, bone_weights, n_bones, rest_normals=None):
         """ctl_scene_bind_skin: binds `mesh` to a rest pose (arrays as DynamicScene.add_mesh takes them; indices None: a soup; rest_normals None: computed once) and to
@@ -1081,7 +1102,7 @@ class Scene:
 
 
 DIFF_CAMERA, DIFF_MATERIALS, DIFF_LIGHTS, DIFF_TRANSFORMS, DIFF_TOPOLOGY, DIFF_GEOMETRY, DIFF_VOLUMES = 1, 2, 4, 8, 16, 32, 64   # CTL_DIFF_*
-ERR_INVALID, ERR_NO_DEVICE, ERR_UNSUPPORTED = -1, -2, -5
+ERR_INVALID, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_INTERNAL = -1, -2, -5, -7
 
 
 class ctl_scene_update_stats(C.Structure):
@@ -1102,9 +1123,31 @@ class ctl_scene_nodes_stats(C.Structure):
 # of them; calling one on such a library raises AttributeError)
 for _n, _a in (("ctl_scene_rebuild_flat", [C.c_void_p, C.c_void_p]), ("ctl_flat_bvh_rebuild", [C.c_void_p, C.c_void_p]), ("ctl_flat_bvh_levels", [C.c_void_p] * 5),
                ("ctl_builder_remove_node", [C.c_void_p, u32]), ("ctl_scene_update_nodes", [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_void_p]),
-               ("ctl_flat_bvh_update_nodes", [C.c_void_p, C.c_void_p, C.c_void_p, u32])):
+               ("ctl_flat_bvh_update_nodes", [C.c_void_p, C.c_void_p, C.c_void_p, u32]),
+               ("ctl_scene_rebuild_flat_ex", [C.c_void_p, C.c_int, C.c_void_p]), ("ctl_flat_bvh_rebuild_ex", [C.c_void_p, C.c_void_p, C.c_int]),
+               ("ctl_scene_update_nodes_ex", [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_int, C.c_void_p]),
+               ("ctl_flat_bvh_update_nodes_ex", [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_int]), ("ctl_rebuild_last_rounds", []),
+               ("ctl_flat_bvh_rebuild_order", [C.c_void_p] * 5)):
     if hasattr(lib, _n):
         getattr(lib, _n).argtypes = _a
+if hasattr(lib, "ctl_rebuild_last_rounds"):
+    lib.ctl_rebuild_last_rounds.restype = u32
+
+REBUILD_LBVH, REBUILD_PLOC = 0, 1   # CTL_REBUILD_LBVH, CTL_REBUILD_PLOC
+
+
+def rebuild_builder(builder):
+    """the builder constant of the _ex entry points: "lbvh" / "ploc"; an int goes through as it is (the library refuses an unknown one with ERR_INVALID)"""
+    if isinstance(builder, str):
+        try:
+            return {"lbvh": REBUILD_LBVH, "ploc": REBUILD_PLOC}[builder]
+        except KeyError:
+            raise ValueError("builder: 'lbvh' or 'ploc', not %r" % (builder,))
+    return int(builder)
+
+
+def _last_rounds():
+    return int(lib.ctl_rebuild_last_rounds()) if hasattr(lib, "ctl_rebuild_last_rounds") else 0
 
 
 def _ptr(a):

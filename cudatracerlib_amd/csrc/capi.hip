@@ -51,6 +51,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
     } catch (const hip_error& e) { return fail(device_count() > 0 ? CTL_ERR_HIP : CTL_ERR_NO_DEVICE, e.what()); } \
     catch (const io_error& e) { return fail(CTL_ERR_IO, e.what()); }             \
     catch (const unsupported_error& e) { return fail(CTL_ERR_UNSUPPORTED, e.what()); } \
+    catch (const internal_error& e) { return fail(CTL_ERR_INTERNAL, e.what()); } \
     catch (const std::bad_alloc&) { return fail(CTL_ERR_INVALID, "out of host memory"); } \
     catch (const std::exception& e) { return fail(CTL_ERR_INVALID, e.what()); }      \
     return CTL_OK;
@@ -413,24 +414,53 @@ static void refuse_gained_triangles(const ctl_flat_bvh& h, const ctl_scene_desc&
 }
 int ctl_flat_bvh_refit(ctl_flat_bvh* h, const ctl_scene_desc* new_desc) { CTL_REQUIRE(h && new_desc, "null argument"); CTL_TRY refuse_gained_triangles(*h, *new_desc, "refit"); refit_flat_scene(h->f, *new_desc, nullptr); h->basis.fill(*new_desc); CTL_CATCH }
 // ---- rebuild of the flattened tree (flat_rebuild.hip, flat_rebuild.cpp)
-int ctl_scene_rebuild_flat(ctl_scene* scene, ctl_scene_rebuild_stats* stats_out) {
+static bool known_builder(int b) { return b == CTL_REBUILD_LBVH || b == CTL_REBUILD_PLOC; }
+int ctl_scene_rebuild_flat_ex(ctl_scene* scene, int builder, ctl_scene_rebuild_stats* stats_out) {
     if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
     CTL_REQUIRE(scene, "null scene");
-    CTL_TRY scene->s.rebuild_flat(stats_out); CTL_CATCH
+    CTL_REQUIRE(known_builder(builder), "ctl_scene_rebuild_flat_ex: unknown builder");
+    CTL_TRY rebuild_builder_scope use(builder); scene->s.rebuild_flat(stats_out); CTL_CATCH
 }
-int ctl_flat_bvh_rebuild(ctl_flat_bvh* h, const ctl_scene_desc* new_desc) { CTL_REQUIRE(h && new_desc, "null argument"); CTL_TRY refuse_gained_triangles(*h, *new_desc, "rebuild"); rebuild_flat_scene(h->f, *new_desc, nullptr); h->basis.fill(*new_desc); CTL_CATCH }
+int ctl_scene_rebuild_flat(ctl_scene* scene, ctl_scene_rebuild_stats* stats_out) { return ctl_scene_rebuild_flat_ex(scene, CTL_REBUILD_LBVH, stats_out); }
+int ctl_flat_bvh_rebuild_ex(ctl_flat_bvh* h, const ctl_scene_desc* new_desc, int builder) {
+    CTL_REQUIRE(h && new_desc, "null argument");
+    CTL_REQUIRE(known_builder(builder), "ctl_flat_bvh_rebuild_ex: unknown builder");
+    CTL_TRY refuse_gained_triangles(*h, *new_desc, "rebuild"); rebuild_flat_scene(h->f, *new_desc, nullptr, builder); h->basis.fill(*new_desc); CTL_CATCH
+}
+int ctl_flat_bvh_rebuild(ctl_flat_bvh* h, const ctl_scene_desc* new_desc) { return ctl_flat_bvh_rebuild_ex(h, new_desc, CTL_REBUILD_LBVH); }
+uint32_t ctl_rebuild_last_rounds(void) { return rebuild_last_rounds(); }
+int ctl_flat_bvh_rebuild_order(const ctl_flat_bvh* h, const ctl_scene_desc* desc, uint32_t* sorted_entry, float* entry_boxes, float* bounds) {
+    CTL_REQUIRE(h && desc && sorted_entry && entry_boxes && bounds, "null argument");
+    CTL_TRY
+    refuse_gained_triangles(*h, *desc, "ctl_flat_bvh_rebuild_order");
+    rebuild_refuse(h->f.format, h->f.refit.ready() && h->f.refit.part_index.size() == h->f.leaves.size(), h->f.compact_links, h->f.leaves.size(), "ctl_flat_bvh_rebuild_order");
+    if (desc->n_nodes != h->f.refit.xf0.size() || !desc->node_transforms) throw std::runtime_error("ctl_flat_bvh_rebuild_order: the description has another number of nodes than the tree was built from");
+    std::vector<refit_box> ebox; refit_box B; std::vector<std::pair<uint64_t, uint32_t>> order;
+    rebuild_sorted_entries(h->f, *desc, ebox, B, order);
+    for (size_t i = 0; i < order.size(); i++) { sorted_entry[i] = order[i].second; std::memcpy(entry_boxes + 6 * i, &ebox[i], 24); }
+    std::memcpy(bounds, &B, 24);
+    CTL_CATCH
+}
 // ---- another set of nodes (flat_nodes.hip, flat_nodes.cpp)
-int ctl_scene_update_nodes(ctl_scene* scene, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes, ctl_scene_nodes_stats* stats_out) {
+int ctl_scene_update_nodes_ex(ctl_scene* scene, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes, int builder, ctl_scene_nodes_stats* stats_out) {
     if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
     CTL_REQUIRE(scene && new_desc, "null argument");
     CTL_REQUIRE(old_of_new, "ctl_scene_update_nodes: null node map");
-    const int rc = [&]() -> int { CTL_TRY scene->s.update_nodes(*new_desc, old_of_new, n_new_nodes, scene->basis, stats_out); CTL_CATCH }();
+    CTL_REQUIRE(known_builder(builder), "ctl_scene_update_nodes_ex: unknown builder");
+    const int rc = [&]() -> int { CTL_TRY rebuild_builder_scope use(builder); scene->s.update_nodes(*new_desc, old_of_new, n_new_nodes, scene->basis, stats_out); CTL_CATCH }();
     if (rc == CTL_OK) { scene->n_materials = new_desc->n_materials; scene->n_images = new_desc->n_images; scene->basis.fill(*new_desc); }
     return rc;
 }
-int ctl_flat_bvh_update_nodes(ctl_flat_bvh* h, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes) {
+int ctl_scene_update_nodes(ctl_scene* scene, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes, ctl_scene_nodes_stats* stats_out) {
+    return ctl_scene_update_nodes_ex(scene, new_desc, old_of_new, n_new_nodes, CTL_REBUILD_LBVH, stats_out);
+}
+int ctl_flat_bvh_update_nodes_ex(ctl_flat_bvh* h, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes, int builder) {
     CTL_REQUIRE(h && new_desc, "null argument");
-    CTL_TRY update_nodes_flat_scene(h->f, h->basis, *new_desc, old_of_new, n_new_nodes, h->extra_missing); h->basis.fill(*new_desc); CTL_CATCH
+    CTL_REQUIRE(known_builder(builder), "ctl_flat_bvh_update_nodes_ex: unknown builder");
+    CTL_TRY update_nodes_flat_scene(h->f, h->basis, *new_desc, old_of_new, n_new_nodes, h->extra_missing, builder); h->basis.fill(*new_desc); CTL_CATCH
+}
+int ctl_flat_bvh_update_nodes(ctl_flat_bvh* h, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes) {
+    return ctl_flat_bvh_update_nodes_ex(h, new_desc, old_of_new, n_new_nodes, CTL_REBUILD_LBVH);
 }
 int ctl_flat_bvh_levels(const ctl_flat_bvh* h, const uint32_t** level_start, uint32_t* n_levels, const uint32_t** level_nodes, uint64_t* n_level_nodes) {
     CTL_REQUIRE(h && level_start && n_levels && level_nodes && n_level_nodes, "null argument");

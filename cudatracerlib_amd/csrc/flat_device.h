@@ -4,6 +4,7 @@
 #pragma once
 #include "tracer.h"
 #include "flat_rebuild.h"
+#include "flat_ploc.h"
 #include "flat_nodes.h"
 #include <utility>
 
@@ -20,11 +21,13 @@ inline dim3 blocks_for(size_t n) { return dim3((unsigned)((n + 255u) / 256u)); }
 //   commit     the swap: tracers read S at every launch
 struct flat_rebuilder {
     const char* who = "";
+    int builder = CTL_REBUILD_LBVH;       // set where the rebuilder is made: Scene::rebuild_flat and Scene::update_nodes read rebuild_builder_choice() there
     uint32_t n = 0;                       // entries
     float4* src_leaves = nullptr; uint32_t* src_part = nullptr;   // what the tree is built over; src_leaves holds n + 1 entries
     refit_device R{};                     // the caller fills inst, inst_fwd, restamp, leaf_keys, alpha_maps, tri_data, node_info, mats; the rest is set by allocate()
     // results
     uint32_t n_nodes = 0; int max_depth = 0; std::vector<uint32_t> level_start; double area[2] = { 0, 0 }; float ms[4] = { 0, 0, 0, 0 };   // entry boxes, sort, topology, node boxes
+    uint32_t rounds = 0;                  // of the clustering (CTL_REBUILD_PLOC)
     void allocate(Scene& A, const std::vector<double>& carry_matrices);
     void run(Scene& A);
     void commit(Scene& A);
@@ -36,6 +39,10 @@ private:
     uint32_t cap = 0; hipEvent_t ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
     dbuf<refit_box> ebox_new, nbox_new; dbuf<uint32_t> bounds, idx_in, idx_out, first, last, perm, part_new, level_iota; dbuf<uint64_t> keys_in, keys_out, counts, incl;
     dbuf<float4> nodes_new, leaves_new; dbuf<double> area_dev;
+    // CTL_REBUILD_PLOC alone: the clusters' boxes and ids (read from one, written to the other), every cluster's pick, the round's flag words and their scan, the stored tree
+    dbuf<refit_box> cbox[2]; dbuf<uint32_t> cid[2], pick, tree_left, tree_right, tree_count; dbuf<uint64_t> round_flags, round_incl;
+    void cluster(Scene& A);
+    template <typename Tree> void wide_nodes(Scene& A, const Tree& T);
 };
 
 }  // namespace ctl

@@ -80,8 +80,9 @@ void plan_node_set(const node_set_basis& old, const geometry_hashes& old_geom, c
     }
 }
 
-void update_nodes_flat_scene(flat_scene& F, const node_set_basis& old, const ctl_scene_desc& nd, const uint32_t* old_of_new, uint32_t n_new_nodes, std::vector<uint32_t>& extra_missing) {
+void update_nodes_flat_scene(flat_scene& F, const node_set_basis& old, const ctl_scene_desc& nd, const uint32_t* old_of_new, uint32_t n_new_nodes, std::vector<uint32_t>& extra_missing, int builder) {
     const char* who = "ctl_flat_bvh_update_nodes";
+    rebuild_last_rounds() = 0u;
     rebuild_refuse(F.format, F.refit.ready() && F.refit.part_index.size() == F.leaves.size(), F.compact_links, F.leaves.size(), who);
     node_set_plan plan;
     plan_node_set(old, F.refit.geom, nd, old_of_new, n_new_nodes, nullptr, plan, who);
@@ -125,7 +126,7 @@ void update_nodes_flat_scene(flat_scene& F, const node_set_basis& old, const ctl
     for (uint32_t k = 0; k < n_new_nodes; k++) T.refit.xf0[k] = old_of_new[k] == kNodesNone ? nd.node_transforms[k] : F.refit.xf0[old_of_new[k]];
     // the inverse transforms of the new description into every entry (k_refit_entries does it on the device), then 4. the rebuild
     for (flat_leaf& L : T.leaves) { std::memcpy(L.inv, nd.node_inv_transforms[L.node].m, 48); L.w33 = nd.node_inv_transforms[L.node].m[15]; }
-    rebuild_flat_entries(T, nd);
+    rebuild_flat_entries(T, nd, builder);
     F = std::move(T);
     extra_missing.insert(extra_missing.end(), skipped.begin(), skipped.end());
     std::sort(extra_missing.begin(), extra_missing.end()); extra_missing.erase(std::unique(extra_missing.begin(), extra_missing.end()), extra_missing.end());

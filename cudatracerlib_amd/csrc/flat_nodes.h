@@ -76,6 +76,6 @@ void plan_node_set(const node_set_basis& old, const geometry_hashes& old_geom, c
 // the host yardstick (ctl_flat_bvh_update_nodes): steps 1 - 4 on a host handle, the Woop rows from `nd`.  extra_missing: the triangles step 2 skipped are merged in
 // (ascending, unique).  Refusals leave F as it was; an identity map is refit_flat_scene(F, nd) where a node has moved, else nothing.
 struct flat_scene;
-void update_nodes_flat_scene(flat_scene& F, const node_set_basis& old, const ctl_scene_desc& nd, const uint32_t* old_of_new, uint32_t n_new_nodes, std::vector<uint32_t>& extra_missing);
+void update_nodes_flat_scene(flat_scene& F, const node_set_basis& old, const ctl_scene_desc& nd, const uint32_t* old_of_new, uint32_t n_new_nodes, std::vector<uint32_t>& extra_missing, int builder = 0);   // builder: CTL_REBUILD_LBVH (0) or CTL_REBUILD_PLOC
 
 }  // namespace ctl

@@ -130,7 +130,8 @@ void Scene::update_nodes(const ctl_scene_desc& d, const uint32_t* old_of_new, ui
     CTL_HIP(hipMemcpy(inst_new.p, inst.data(), inst.size() * sizeof(float4), hipMemcpyHostToDevice)); CTL_HIP(hipMemcpy(fwd_new.p, fwd.data(), fwd.size() * sizeof(float4), hipMemcpyHostToDevice));
     CTL_HIP(hipMemcpy(ninfo_new.p, ninfo.data(), ninfo.size() * sizeof(uint4), hipMemcpyHostToDevice));
     std::vector<uint32_t> skipped;
-    flat_rebuilder B;
+    rebuild_last_rounds() = 0u;
+    flat_rebuilder B; B.builder = rebuild_builder_choice();   // what the C entry point asked for (rebuild_builder_scope, flat_rebuild.h)
     if (flat) {
         const uint32_t n_old = (uint32_t)flat_n_entries_, n_added = (uint32_t)plan.added.size(), G = plan.added_base.back();
         // ---- scratch of this call; the scene's tri_row table and rocPRIM storage are caches without a meaning of their own

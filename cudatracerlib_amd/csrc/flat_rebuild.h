@@ -21,10 +21,15 @@
 //   8. nodes           rebuild_encode_node: mask and link words as flat4_encode_links (flatten.h) and patch_empty_slots_q4 (flatten.cpp) make them; no node carries an
 //                      oriented slab: the last 16 B are zero, every slab flag is 0
 //   9. boxes           refit_node_boxes, deepest level first
+// Stage 5 is the LBVH builder (CTL_REBUILD_LBVH).  The PLOC builder (CTL_REBUILD_PLOC, flat_ploc.h) replaces it by a stored binary tree made bottom-up from the boxes in the
+// same sorted order; stages 6 and 7 are written over "a binary tree" (rebuild_lbvh_tree here, ploc_tree there) and do not know which one they walk.
 #pragma once
 #include "flat_refit.h"
 #include "../../include/ctl_amd.h"
 #include <cstddef>
+#include <stdexcept>
+#include <utility>
+#include <vector>
 
 namespace ctl {
 
@@ -94,29 +99,39 @@ CTL_REFIT_HD uint32_t rebuild_find_split(const uint64_t* keys, uint32_t first, u
     return split;
 }
 
-// the slots of the wide node over the sorted positions a .. b: ranges in key order; a range of at most four (kRebuildLeafMax) entries is a leaf slot, any other an inner child
+// the binary tree the collapse walks, as the LBVH supplies it: a binary node is its range first .. last of sorted positions, its split comes from rebuild_find_split, its
+// entries are the positions themselves.  (flat_ploc.h has the stored tree of the PLOC builder behind the same three functions.)
+struct rebuild_lbvh_tree {
+    const uint64_t* keys;
+    CTL_REFIT_HD void split(uint32_t first, uint32_t last, uint32_t& lf, uint32_t& ll, uint32_t& rf, uint32_t& rl) const { const uint32_t s = rebuild_find_split(keys, first, last); lf = first; ll = s; rf = s + 1u; rl = last; }
+    CTL_REFIT_HD uint32_t entry(uint32_t first, uint32_t last, uint32_t e) const { (void)last; return first + e; }   // the sorted position of the e-th entry under the node
+    CTL_REFIT_HD uint32_t root_first(uint32_t n) const { (void)n; return 0u; }
+};
+
+// the slots of a wide node: binary nodes in left-before-right order, each with its entry count (last - first + 1; what `first` names is the tree's business: a sorted
+// position for the LBVH, a node id for a stored tree); a binary node of at most four (kRebuildLeafMax) entries is a leaf slot, any other an inner child
 struct rebuild_slots {
     uint32_t n, first[4], last[4];
     CTL_REFIT_HD uint32_t count(uint32_t k) const { return last[k] - first[k] + 1u; }
     CTL_REFIT_HD bool leaf(uint32_t k) const { return count(k) <= kRebuildLeafMax; }
 };
-CTL_REFIT_HD void rebuild_split_slot(const uint64_t* keys, rebuild_slots& S, uint32_t k) {
+template <typename Tree> CTL_REFIT_HD void rebuild_split_slot(const Tree& T, rebuild_slots& S, uint32_t k) {
     for (uint32_t j = S.n; j > k + 1u; j--) { S.first[j] = S.first[j - 1u]; S.last[j] = S.last[j - 1u]; }
-    const uint32_t s = rebuild_find_split(keys, S.first[k], S.last[k]);
-    S.first[k + 1u] = s + 1u; S.last[k + 1u] = S.last[k]; S.last[k] = s; S.n++;
+    uint32_t lf, ll, rf, rl; T.split(S.first[k], S.last[k], lf, ll, rf, rl);
+    S.first[k + 1u] = rf; S.last[k + 1u] = rl; S.first[k] = lf; S.last[k] = ll; S.n++;
 }
-CTL_REFIT_HD void rebuild_node_slots(const uint64_t* keys, uint32_t a, uint32_t b, rebuild_slots& S) {
+template <typename Tree> CTL_REFIT_HD void rebuild_node_slots(const Tree& T, uint32_t a, uint32_t b, rebuild_slots& S) {
     S.n = 1u; S.first[0] = a; S.last[0] = b;
     for (int k = 1; k < 4; k++) { S.first[k] = 0u; S.last[k] = 0u; }
     if (S.leaf(0)) return;   // only the root of a tree of at most four entries: one leaf slot
-    rebuild_split_slot(keys, S, 0u);                      // the binary node's children ...
-    if (!S.leaf(1)) rebuild_split_slot(keys, S, 1u);      // ... and its grandchildren
-    if (!S.leaf(0)) rebuild_split_slot(keys, S, 0u);
+    rebuild_split_slot(T, S, 0u);                      // the binary node's children ...
+    if (!S.leaf(1)) rebuild_split_slot(T, S, 1u);      // ... and its grandchildren
+    if (!S.leaf(0)) rebuild_split_slot(T, S, 0u);
     while (S.n < 4u) {   // a free slot goes to the inner slot with the most entries, the lower one on a tie
         uint32_t best = 4u, most = kRebuildLeafMax;
         for (uint32_t k = 0; k < S.n; k++) if (S.count(k) > most) { most = S.count(k); best = k; }
         if (best == 4u) break;
-        rebuild_split_slot(keys, S, best);
+        rebuild_split_slot(T, S, best);
     }
 }
 // inner children and entries of leaf children of a node, packed for ONE scan per level: inner children << 32 | entries
@@ -143,12 +158,29 @@ CTL_REFIT_HD void rebuild_encode_node(const rebuild_slots& S, uint32_t first_chi
 }
 
 // flat_rebuild.cpp.  rebuild_refuse: what both sides refuse before anything is written (unsupported_error).  rebuild_flat_scene: refit_flat_scene to `d`, then the rebuild;
-// a rebuilt tree that is too deep for the traversal stack is refused with the tree left refitted.  area_before_after (may be null): the refitted and the rebuilt tree's
+// a rebuilt tree that is too deep for the traversal stack is refused with the tree left refitted.  area_before_after (may be null): the refitted and the rebuilt tree's.
+// builder: CTL_REBUILD_LBVH or CTL_REBUILD_PLOC (flat_ploc.h); the callers have refused any other value
 struct flat_scene;
 void rebuild_refuse(int format, bool refit_ready, bool compact, size_t n_entries, const char* who);
-void rebuild_flat_scene(flat_scene& F, const ctl_scene_desc& d, double* area_before_after);
+void rebuild_flat_scene(flat_scene& F, const ctl_scene_desc& d, double* area_before_after, int builder = CTL_REBUILD_LBVH);
 // stages 1 - 9 alone, over the entries F holds (leaves, refit.part_index / part_boxes / xf0) for the transforms of `d`: what rebuild_flat_scene runs after its refit, and
 // update_nodes_flat_scene (flat_nodes.cpp) over another set of entries.  Too deep a tree: unsupported_error before F is written
-void rebuild_flat_entries(flat_scene& F, const ctl_scene_desc& d);
+void rebuild_flat_entries(flat_scene& F, const ctl_scene_desc& d, int builder = CTL_REBUILD_LBVH);
+// stages 1 - 4 alone, nothing written: the entries' boxes for the transforms of `d`, their bounds, and (code, entry) in sorted order (ctl_flat_bvh_rebuild_order)
+void rebuild_sorted_entries(const flat_scene& F, const ctl_scene_desc& d, std::vector<refit_box>& ebox, refit_box& bounds, std::vector<std::pair<uint64_t, uint32_t>>& order);
+// a state of the rebuild that its own arithmetic rules out (a clustering round without a merge): CTL_ERR_INTERNAL
+struct internal_error : std::runtime_error { using std::runtime_error::runtime_error; };
+// The builder of the device calls, per thread: CTL_REBUILD_LBVH unless the C entry point holds a rebuild_builder_scope around the call.  It is read in exactly two
+// places, on the thread of the C call: where Scene::rebuild_flat and Scene::update_nodes make their flat_rebuilder (B.builder = rebuild_builder_choice()) — the members
+// keep their signatures, flat_rebuilder itself takes the builder as a plain field.  rebuild_last_rounds: the clustering rounds of this thread's last rebuild call, host
+// or device; every call sets it to 0 when it starts, so a refused call and the LBVH leave 0
+int& rebuild_builder_choice();
+uint32_t& rebuild_last_rounds();
+struct rebuild_builder_scope {
+    int prev;
+    explicit rebuild_builder_scope(int b) : prev(rebuild_builder_choice()) { rebuild_builder_choice() = b; }
+    ~rebuild_builder_scope() { rebuild_builder_choice() = prev; }
+    rebuild_builder_scope(const rebuild_builder_scope&) = delete; rebuild_builder_scope& operator=(const rebuild_builder_scope&) = delete;
+};
 
 }  // namespace ctl

@@ -95,6 +95,9 @@ struct sbvh {
     struct spa_split { float sah = FLT_MAX; int dim = 0; float pos = 0.0f; };
     struct bin_t { box3 box; int enter, exit; };
     bin_t bins[3][kSpatialBins];
+    // the bin of a scaled coordinate, clamped to 0 .. kSpatialBins - 1.  A flat node box has bin_size 0, so 0 * inf gives a coordinate that is no number: bin 0, decided
+    // here by a comparison (converting it to int is undefined; the conversion instruction happened to give INT_MIN, which the clamp turned into the same 0)
+    static int spatial_bin(float x) { return !(x >= 0.0f) ? 0 : (x >= (float)kSpatialBins ? kSpatialBins - 1 : (int)x); }
     spa_split find_spatial_split(const spec_t& s, float node_sah) {   // :427-513
         float origin[3], bin_size[3], inv_bin[3];
         for (int k = 0; k < 3; k++) { origin[k] = s.box.lo[k]; bin_size[k] = (s.box.hi[k] - origin[k]) * (1.0f / (float)kSpatialBins); inv_bin[k] = 1.0f / bin_size[k]; }
@@ -103,8 +106,8 @@ struct sbvh {
             const ref_t& rf = refs[ri];
             int fb[3], lb[3];
             for (int k = 0; k < 3; k++) {
-                fb[k] = std::min(std::max((int)((rf.box.lo[k] - origin[k]) * inv_bin[k]), 0), kSpatialBins - 1);
-                lb[k] = std::min(std::max((int)((rf.box.hi[k] - origin[k]) * inv_bin[k]), fb[k]), kSpatialBins - 1);
+                fb[k] = spatial_bin((rf.box.lo[k] - origin[k]) * inv_bin[k]);
+                lb[k] = std::max(spatial_bin((rf.box.hi[k] - origin[k]) * inv_bin[k]), fb[k]);
             }
             for (int d = 0; d < 3; d++) {
                 ref_t cur = rf;

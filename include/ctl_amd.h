@@ -36,7 +36,8 @@ typedef enum {
     CTL_ERR_HIP = -3,          /* hipError_t != hipSuccess, message in last_error */
     CTL_ERR_OVERFLOW = -4,     /* ray queue overflow (DoubleRayBuffer.h:86-89)    */
     CTL_ERR_UNSUPPORTED = -5,  /* e.g. participating media, unknown plugin name   */
-    CTL_ERR_IO = -6            /* scene loader: file / parse errors               */
+    CTL_ERR_IO = -6,           /* scene loader: file / parse errors               */
+    CTL_ERR_INTERNAL = -7      /* a state the library's own arithmetic rules out  */
 } ctl_status;
 
 const char* ctl_last_error(void);
@@ -541,6 +542,28 @@ typedef struct { uint32_t n_nodes, n_entries, max_depth, levels; double node_are
 int ctl_scene_rebuild_flat(ctl_scene* scene, ctl_scene_rebuild_stats* stats_out);
 int ctl_flat_bvh_rebuild(ctl_flat_bvh* h, const ctl_scene_desc* new_desc);
 int ctl_flat_bvh_levels(const ctl_flat_bvh* h, const uint32_t** level_start, uint32_t* n_levels, const uint32_t** level_nodes, uint64_t* n_level_nodes);
+/* ---- the builder of a rebuild (csrc/flat_ploc.h; DESIGN.md "PLOC", INTEGRATION.md "Updating a scene").  Every call that rebuilds the flattened tree has an _ex form
+ * that names the builder of the binary tree the wide nodes are collapsed from; the plain forms are the _ex forms with CTL_REBUILD_LBVH, byte for byte.
+ *   CTL_REBUILD_LBVH   Karras's radix tree over the sorted Morton codes: the cheapest call, the largest node area
+ *   CTL_REBUILD_PLOC   parallel locally-ordered clustering (Meister & Bittner): from the same sorted order, rounds in which every cluster picks, among the 8 clusters to
+ *                      either side, the one whose union box with its own is smallest (ties: the smaller XOR of the two positions), and clusters that picked each other merge; then the same collapse, layout and box
+ *                      stages.  A smaller node area (tests/test_flat_ploc_host.py) for some tens of rounds of launches more (RESULTS.md has the measured cost and rays/s)
+ * Entries, clip boxes, hits and everything a later call may do to the tree are as after the plain call; host handle and device agree byte for byte as they do there.
+ * Memory: CTL_REBUILD_PLOC takes 88 B per entry more during the call (the cluster boxes and ids twice — one read, one written per round —, every cluster's pick,
+ * the round's flag words and their scan, the binary tree's child and count arrays): 0.76 GB on an 8.6 M-entry scene, next to what the plain call takes, freed when it
+ * returns.  topology_ms includes the clustering.
+ * Refusals besides the plain calls', all before anything is written: CTL_ERR_INVALID for a builder that is none of the constants; CTL_ERR_UNSUPPORTED when the clustering
+ * has not finished after 8 ceil(log2 entries) + 16 rounds; CTL_ERR_INTERNAL for a round that merged nothing (the tie rule excludes it).  The tree that was there stays.
+ * ctl_rebuild_last_rounds: the clustering rounds of the calling thread's last rebuild of either kind (0 after CTL_REBUILD_LBVH). */
+enum { CTL_REBUILD_LBVH = 0, CTL_REBUILD_PLOC = 1 };
+int ctl_scene_rebuild_flat_ex(ctl_scene* scene, int builder, ctl_scene_rebuild_stats* stats_out);
+int ctl_flat_bvh_rebuild_ex(ctl_flat_bvh* h, const ctl_scene_desc* new_desc, int builder);
+uint32_t ctl_rebuild_last_rounds(void);
+/* TEST SUPPORT, not part of the product interface (no host needs it; it may change with the rebuild's internals): what stages 1 - 4 hand to either builder, for a host handle as it stands (refitted to desc) and the transforms of desc, nothing written: sorted_entry[s] = the entry at
+ * sorted position s (n_leaves elements), entry_boxes = lo xyz, hi xyz of every entry BY ENTRY INDEX (6 n_leaves floats; an entry without a box has lo > hi),
+ * bounds = lo xyz, hi xyz of the boxes that are not inverted.  tests/ploc_ref.py restates stages 5 - 7 from these.  Refuses what ctl_flat_bvh_rebuild refuses (a handle
+ * whose description has gained a triangle since a node was added included). */
+int ctl_flat_bvh_rebuild_order(const ctl_flat_bvh* h, const ctl_scene_desc* desc, uint32_t* sorted_entry, float* entry_boxes, float* bounds);
 /* ---- another SET OF NODES on a live scene (csrc/flat_nodes.h, flat_nodes.hip, flat_nodes.cpp; INTEGRATION.md "Updating a scene").  ctl_scene_update refuses a
  * description with other nodes (CTL_DIFF_TOPOLOGY), and keeps doing so; ctl_scene_update_nodes takes one: new_desc is the scene's description after
  * ctl_builder_remove_node and / or ctl_builder_add_node of further instances of meshes the scene already holds.
@@ -571,6 +594,10 @@ typedef struct {
 } ctl_scene_nodes_stats;
 int ctl_scene_update_nodes(ctl_scene* scene, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes, ctl_scene_nodes_stats* stats_out);
 int ctl_flat_bvh_update_nodes(ctl_flat_bvh* h, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes);
+/* the same with the builder of the rebuild stage named (CTL_REBUILD_LBVH: the plain calls; see "the builder of a rebuild" above).  After a node-set edit the host has no
+ * refitted tree to fall back on, so the builder is the whole choice: INTEGRATION.md says which to ask for. */
+int ctl_scene_update_nodes_ex(ctl_scene* scene, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes, int builder, ctl_scene_nodes_stats* stats_out);
+int ctl_flat_bvh_update_nodes_ex(ctl_flat_bvh* h, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes, int builder);
 /* The flattened tree of a CTL_SCENE_FLATTEN scene copied back from HBM into a handle for ctl_flat_bvh_arrays, with the BSDF-model bits (28..31 of the index word)
  * and the alpha bit (31 of the node word) that ctl_scene_create_ex stamps into the device copy removed: the arrays the test oracle traverses. */
 int ctl_scene_read_flat_bvh(ctl_scene* scene, ctl_flat_bvh** out);

@@ -205,9 +205,9 @@ def skinning(workload, args, sc, scene, node, rec):
 def rebuild_block(scene, args):
     """Mrays/s of the tree as it stands (refitted), then the rebuild: first call, median of 5 more, the last call's stats, Mrays/s of the rebuilt tree"""
     r = mrays(scene, args)
-    t = time.perf_counter(); first = scene.rebuild_flat(); first_ms = (time.perf_counter() - t) * 1e3
+    t = time.perf_counter(); first = scene.rebuild_flat(builder=args.builder); first_ms = (time.perf_counter() - t) * 1e3
     stats = []
-    wall = timed(lambda k: stats.append(scene.rebuild_flat()), 5)
+    wall = timed(lambda k: stats.append(scene.rebuild_flat(builder=args.builder)), 5)
     st = dict(stats[-1]); st.update(sort_ms=float(np.median([x["sort_ms"] for x in stats])), topology_ms=float(np.median([x["topology_ms"] for x in stats])),
                                     refit_ms=float(np.median([x["refit_ms"] for x in stats])), total_ms=float(np.median([x["total_ms"] for x in stats])))
     return dict(refit_mrays=r, rebuilt_mrays=mrays(scene, args), rebuild_first_ms=first_ms, rebuild_ms=wall, stats=st, node_area_refitted=first["node_area_before"], node_area_rebuilt=first["node_area_after"])
@@ -259,7 +259,7 @@ def node_set(workload, args, sc, scene, node, X0, size, rec):
 
     def one(what, edit):
         edit()
-        t = time.perf_counter(); st = scene.update_nodes(sc.UpdateScene()); wall = (time.perf_counter() - t) * 1e3
+        t = time.perf_counter(); st = scene.update_nodes(sc.UpdateScene(), builder=args.builder); wall = (time.perf_counter() - t) * 1e3
         b = dict(wall_ms=wall, stats=st, updated_mrays=mrays(scene, args))
         with tempfile.TemporaryDirectory() as cache:
             api.set_cache_dir(cache)
@@ -432,12 +432,18 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scene_update.jsonl"))
     ap.add_argument("--results", default=None)
     ap.add_argument("--only", default=None, choices=["deform", "skin", "rebuild", "nodes"], help="nodes: the camera update and ctl_scene_update_nodes adding and removing one node against the re-creation of the same description; rebuild: the camera update and ctl_scene_rebuild_flat after M3 and after D1 against the re-creation of the same pose; deform: the camera update and the one-mesh deformation alone; skin: the camera update and the pose change of a bound mesh against the host path")
+    ap.add_argument("--builder", default="lbvh", choices=["lbvh", "ploc"], help="the builder of --only rebuild and --only nodes (csrc/flat_ploc.h); the record carries it")
+    ap.add_argument("--tag", default=None, help="a word for the record: which library ran (an A/B against another commit's library through $CTL_AMD_LIB)")
     args = ap.parse_args()
     if ctl.device_count() < 1:
         raise SystemExit("scene_update_bench needs a HIP device")
     recs = []
     for w in args.workloads.split(","):
         rec = run(w, args)
+        if args.only in ("rebuild", "nodes"):
+            rec["builder"] = args.builder
+        if args.tag:
+            rec["tag"] = args.tag
         recs.append(rec)
         print(json.dumps(rec), flush=True)
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
