@@ -985,6 +985,7 @@ class Scene:
         # (triangles, Woop rows) per mesh, taken while the description is certainly alive: the sizes read_mesh_geometry's buffers must have (an update keeps them)
         self._mesh_counts = mesh_counts(desc)
         self._skins = {}   # mesh -> dict(n_vert, n_bones) of the bound meshes
+        self._light_counts = (int(desc.n_lights_buf), int(desc.n_anim_bytes))   # the sizes read_lights' buffers must have
         self._node_ids = getattr(desc, "node_ids", None)   # of the description the scene holds (DynamicScene.UpdateScene), or None
 
     def update(self, desc):
@@ -998,6 +999,7 @@ class Scene:
         _check(code)
         self._keepalive = desc
         self._node_ids = getattr(desc, "node_ids", self._node_ids)
+        self._light_counts = (int(desc.n_lights_buf), int(desc.n_anim_bytes))
         return mask.value
 
     def update_nodes(self, sc_or_desc, old_of_new=None, builder="lbvh"):
@@ -1022,6 +1024,7 @@ class Scene:
                lib.ctl_scene_update_nodes_ex(self._h, C.byref(desc), M.ctypes.data, u32(len(M)), b, C.addressof(st)))
         self._keepalive = desc
         self._node_ids = getattr(desc, "node_ids", None)
+        self._light_counts = (int(desc.n_lights_buf), int(desc.n_anim_bytes))
         out = {k: getattr(st, k) for k, _ in st._fields_ if k != "rebuild"}
         out["rebuild"] = {k: getattr(st.rebuild, k) for k, _ in st.rebuild._fields_}
         out["rebuild"]["rounds"] = _last_rounds() if st.rebuilt else 0
@@ -1047,16 +1050,23 @@ class Scene:
         out["rounds"] = _last_rounds()
         return out
 
-    def bind_skin(self, mesh, rest_positions, indices, bone_indices, bone_weights, n_bones, rest_normals=None):
+    def bind_skin(self, mesh, rest_positions, indices, bone_indices, bone_weights, n_bones, rest_normals=None, area_lights=False, flags=None):
         """ctl_scene_bind_skin: binds `mesh` to a rest pose (arrays as DynamicScene.add_mesh takes them; indices None: a soup; rest_normals None: computed once) and to
-        its bone bytes, uint8 (n_vert, 8) each.  The mesh is device-owned until unbind_skin."""
+        its bone bytes, uint8 (n_vert, 8) each.  The mesh is device-owned until unbind_skin.  area_lights=True (ctl_scene_bind_skin_ex with SKIN_AREA_LIGHTS): the mesh's
+        nodes may carry area lights; their shape sets are recomputed on the device after every pose and after every update that uploads the light tables or the
+        transforms, and are device-owned like the mesh.  flags: the CTL_SKIN_* word itself, through ctl_scene_bind_skin_ex (overrides area_lights)."""
         a = _skin_arrays(rest_positions, rest_normals, indices, bone_indices, bone_weights)
-        _check(lib.ctl_scene_bind_skin(self._h, u32(mesh), a["P"].ctypes.data, _ptr(a["N"]), u32(len(a["P"])), _ptr(a["I"]), u32(a["n_tri"]), a["BI"].ctypes.data, a["BW"].ctypes.data, u32(n_bones)))
+        args = (self._h, u32(mesh), a["P"].ctypes.data, _ptr(a["N"]), u32(len(a["P"])), _ptr(a["I"]), u32(a["n_tri"]), a["BI"].ctypes.data, a["BW"].ctypes.data, u32(n_bones))
+        if flags is None and not area_lights:
+            _check(lib.ctl_scene_bind_skin(*args))
+        else:
+            _check(lib.ctl_scene_bind_skin_ex(*(args + (u32(SKIN_AREA_LIGHTS if flags is None else flags),))))
         self._skins[mesh] = dict(n_vert=len(a["P"]), n_bones=n_bones)
 
     def animate_mesh(self, mesh, bones0, bones1=None, lerp=0.0):
         """ctl_scene_animate_mesh: poses a bound mesh from (n_bones, 4, 4) row-major bone matrices; bones1 None: bones0.  Returns the update-stats dict plus skin_ms, the
-        HIP-event time of the three pose kernels.  Start the next pass with new_trace."""
+        HIP-event time of the three pose kernels, and shape_set_ms, that of the shape-set kernels (0 unless the mesh was bound with area_lights=True).  Start the next
+        pass with new_trace."""
         B0 = np.ascontiguousarray(bones0, np.float32).reshape(-1, 16)
         B1 = None if bones1 is None else np.ascontiguousarray(bones1, np.float32).reshape(-1, 16)
         n = self._skins.get(mesh, {}).get("n_bones")
@@ -1066,7 +1076,22 @@ class Scene:
         _check(lib.ctl_scene_animate_mesh(self._h, u32(mesh), B0.ctypes.data, _ptr(B1), f32(lerp), C.addressof(st)))
         out = {k: getattr(st, k) for k, _ in st._fields_}
         ms = f32(); _check(lib.ctl_scene_get_skin_ms(self._h, C.byref(ms))); out["skin_ms"] = ms.value
+        out["shape_set_ms"] = self.shape_set_ms()
         return out
+
+    def shape_set_ms(self):
+        """ctl_scene_get_shape_set_ms: the HIP-event time of the shape-set kernels in the last call that ran them (animate_mesh, update, update_nodes)"""
+        if not hasattr(lib, "ctl_scene_get_shape_set_ms"):
+            return 0.0
+        ms = f32(); _check(lib.ctl_scene_get_shape_set_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def read_lights(self):
+        """ctl_scene_read_lights: dict(lights (n_lights_buf, sizeof(ctl_light) / 4) uint32, anim (n_anim_bytes,) uint8) as HBM holds them, for any scene"""
+        n_lights, n_anim = self._light_counts
+        L = np.zeros((n_lights, C.sizeof(ctl_light) // 4), np.uint32); A = np.zeros(n_anim, np.uint8)
+        _check(lib.ctl_scene_read_lights(self._h, L.ctypes.data, u32(n_lights), A.ctypes.data, C.c_size_t(n_anim)))
+        return dict(lights=L, anim=A)
 
     def read_mesh_geometry(self, mesh, vertices=False):
         """ctl_scene_read_mesh_geometry: dict(tri (n_tri, 8) uint32, woop (n_rows, 12) uint32) as HBM holds them — any mesh of any scene — and, with vertices=True
@@ -1127,13 +1152,17 @@ for _n, _a in (("ctl_scene_rebuild_flat", [C.c_void_p, C.c_void_p]), ("ctl_flat_
                ("ctl_scene_rebuild_flat_ex", [C.c_void_p, C.c_int, C.c_void_p]), ("ctl_flat_bvh_rebuild_ex", [C.c_void_p, C.c_void_p, C.c_int]),
                ("ctl_scene_update_nodes_ex", [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_int, C.c_void_p]),
                ("ctl_flat_bvh_update_nodes_ex", [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_int]), ("ctl_rebuild_last_rounds", []),
-               ("ctl_flat_bvh_rebuild_order", [C.c_void_p] * 5)):
+               ("ctl_flat_bvh_rebuild_order", [C.c_void_p] * 5),
+               ("ctl_scene_bind_skin_ex", [C.c_void_p, u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, u32, C.c_void_p, C.c_void_p, u32, u32]),
+               ("ctl_scene_get_shape_set_ms", [C.c_void_p, C.POINTER(f32)]), ("ctl_scene_read_lights", [C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_size_t]),
+               ("ctl_shape_sets_host", [C.c_void_p, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])):
     if hasattr(lib, _n):
         getattr(lib, _n).argtypes = _a
 if hasattr(lib, "ctl_rebuild_last_rounds"):
     lib.ctl_rebuild_last_rounds.restype = u32
 
 REBUILD_LBVH, REBUILD_PLOC = 0, 1   # CTL_REBUILD_LBVH, CTL_REBUILD_PLOC
+SKIN_AREA_LIGHTS = 1                # CTL_SKIN_AREA_LIGHTS
 
 
 def rebuild_builder(builder):
@@ -1178,6 +1207,17 @@ def skin_mesh_host(desc, mesh, rest_positions, indices, bone_indices, bone_weigh
     _check(lib.ctl_skin_mesh_host(C.addressof(desc), u32(mesh), a["P"].ctypes.data, _ptr(a["N"]), u32(len(a["P"])), _ptr(a["I"]), u32(a["n_tri"]), a["BI"].ctypes.data, a["BW"].ctypes.data,
                                   u32(n_bones), B0.ctypes.data, _ptr(B1), f32(lerp), P.ctypes.data, N.ctypes.data, tri.ctypes.data, woop.ctypes.data))
     return dict(positions=P, normals=N, tri=tri, woop=woop)
+
+
+def shape_sets_host(desc, mesh, tri, woop):
+    """ctl_shape_sets_host (host only): the yardstick of Scene.read_lights after a pose — desc's light table and anim blob with the shape sets of the lights on nodes that
+    instance `mesh` recalculated from tri (n_tri, 8) / woop (n_rows, 12) uint32, the mesh's posed ranges as skin_mesh_host returns them.  dict(lights, anim) as read_lights"""
+    T = np.ascontiguousarray(tri, np.uint32).reshape(-1, 8); Wp = np.ascontiguousarray(woop, np.uint32).reshape(-1, 12)
+    if 0 <= mesh < desc.n_meshes and (len(T), len(Wp)) != tuple(mesh_counts(desc)[mesh]):
+        raise ValueError("shape_sets_host: %d triangles and %d rows for a mesh of %s" % (len(T), len(Wp), mesh_counts(desc)[mesh]))
+    L = np.zeros((desc.n_lights_buf, C.sizeof(ctl_light) // 4), np.uint32); A = np.zeros(desc.n_anim_bytes, np.uint8)
+    _check(lib.ctl_shape_sets_host(C.addressof(desc), u32(mesh), T.ctypes.data, Wp.ctypes.data, L.ctypes.data, A.ctypes.data))
+    return dict(lights=L, anim=A)
 
 
 def mesh_counts(desc):

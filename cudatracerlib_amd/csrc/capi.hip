@@ -11,6 +11,7 @@
 #include "flat_rebuild.h"
 #include "flat_nodes.h"
 #include "mesh_skin.h"
+#include "shape_set.h"
 #include "material_factory.h"
 #include "material_textures.h"
 #include "image_io.h"
@@ -379,12 +380,29 @@ int ctl_scene_bind_skin(ctl_scene* scene, uint32_t mesh_index, const float* rest
     CTL_REQUIRE(scene, "null scene");
     CTL_TRY scene->s.bind_skin(mesh_index, rest_positions, rest_normals, n_vert, indices, n_tri, bone_indices, bone_weights, n_bones); CTL_CATCH
 }
+int ctl_scene_bind_skin_ex(ctl_scene* scene, uint32_t mesh_index, const float* rest_positions, const float* rest_normals, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri,
+                           const uint8_t* bone_indices, const uint8_t* bone_weights, uint32_t n_bones, uint32_t flags) {
+    if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
+    CTL_REQUIRE(scene, "null scene");
+    CTL_REQUIRE(!(flags & ~(uint32_t)CTL_SKIN_AREA_LIGHTS), "ctl_scene_bind_skin_ex: unknown CTL_SKIN_* bits");
+    CTL_TRY scene->s.bind_skin(mesh_index, rest_positions, rest_normals, n_vert, indices, n_tri, bone_indices, bone_weights, n_bones, flags); CTL_CATCH
+}
 int ctl_scene_animate_mesh(ctl_scene* scene, uint32_t mesh_index, const ctl_float4x4* bones0, const ctl_float4x4* bones1, float lerp, ctl_scene_update_stats* stats_out) {
     if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
     CTL_REQUIRE(scene && bones0, "null argument");
     CTL_TRY scene->s.animate_mesh(mesh_index, bones0, bones1, lerp, stats_out); CTL_CATCH
 }
 int ctl_scene_get_skin_ms(ctl_scene* scene, float* ms_out) { CTL_REQUIRE(scene && ms_out, "null argument"); *ms_out = scene->s.last_skin_ms(); return CTL_OK; }
+int ctl_scene_get_shape_set_ms(ctl_scene* scene, float* ms_out) { CTL_REQUIRE(scene && ms_out, "null argument"); *ms_out = scene->s.last_shape_set_ms(); return CTL_OK; }
+int ctl_scene_read_lights(ctl_scene* scene, ctl_light* lights_out, uint32_t n_lights, uint8_t* anim_out, size_t n_anim_bytes) {
+    if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
+    CTL_REQUIRE(scene, "null scene");
+    CTL_TRY scene->s.read_lights(lights_out, n_lights, anim_out, n_anim_bytes); CTL_CATCH
+}
+int ctl_shape_sets_host(const ctl_scene_desc* desc, uint32_t mesh_index, const ctl_triangle_data* tri_data, const ctl_woop_tri* woop, ctl_light* lights_out, uint8_t* anim_out) {
+    CTL_REQUIRE(desc, "null description");
+    CTL_TRY shape_sets_host(*desc, mesh_index, tri_data, woop, lights_out, anim_out); CTL_CATCH
+}
 int ctl_scene_read_mesh_geometry(ctl_scene* scene, uint32_t mesh_index, float* positions_out, float* normals_out, ctl_triangle_data* tri_data_out, ctl_woop_tri* woop_out) {
     if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
     CTL_REQUIRE(scene, "null scene");

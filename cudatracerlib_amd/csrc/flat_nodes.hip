@@ -199,6 +199,7 @@ void Scene::update_nodes(const ctl_scene_desc& d, const uint32_t* old_of_new, ui
     swap_buffers(inst_, inst_new); swap_buffers(inst_fwd_, fwd_new); swap_buffers(node_info_, ninfo_new);
     set_shading_state(shade);
     upload_materials(d); upload_lights(d); upload_top_level(d);
+    lights_stale_ = false; run_shape_sets(d);   // the lights of emissive skins: node indices by the new description, the pose stays (shape_set.hip)
     if (flat) S.inst_w_one = inverse_transforms_have_w_one(d);
     CTL_HIP(hipDeviceSynchronize());
     bind(d); n_nodes = d.n_nodes; set_camera(d);

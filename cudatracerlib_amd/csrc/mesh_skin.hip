@@ -155,9 +155,10 @@ void skin_mesh_host(const ctl_scene_desc& d, uint32_t mesh, const float* rest_po
 }
 
 void Scene::bind_skin(uint32_t mesh, const float* rest_positions, const float* rest_normals, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri,
-                      const uint8_t* bone_indices, const uint8_t* bone_weights, uint32_t n_bones) {
+                      const uint8_t* bone_indices, const uint8_t* bone_weights, uint32_t n_bones, uint32_t flags) {
     require_device();
     const char* who = "ctl_scene_bind_skin";
+    if (flags & ~(uint32_t)CTL_SKIN_AREA_LIGHTS) throw std::runtime_error("ctl_scene_bind_skin_ex: unknown CTL_SKIN_* bits");
     if (!snap_) throw std::runtime_error("ctl_scene_bind_skin: the scene holds no description");
     const ctl_scene_desc& d = snap_->d;
     if (mesh >= d.n_meshes) throw std::runtime_error("ctl_scene_bind_skin: bad mesh index");
@@ -166,7 +167,7 @@ void Scene::bind_skin(uint32_t mesh, const float* rest_positions, const float* r
     if (n_tri != tri1 - tri0) throw std::runtime_error("ctl_scene_bind_skin: mesh " + std::to_string(mesh) + " has " + std::to_string(tri1 - tri0) + " triangles; a skin keeps the triangle count");
     skin_check_arguments(who, rest_positions, n_vert, indices, n_tri, bone_indices, bone_weights, n_bones);
     if (!flattened() || S.flat_format != kFlatQ4 || refit_.level_start.size() < 2) throw unsupported_error("ctl_scene_bind_skin: needs a scene flattened in the CTL_FLAT_Q4 format with refit data (CTL_SCENE_FLATTEN)");
-    for (uint32_t k = 0; k < d.n_nodes; k++) if (d.nodes[k].mesh_index == mesh && d.nodes[k].n_lights)
+    if (!(flags & CTL_SKIN_AREA_LIGHTS)) for (uint32_t k = 0; k < d.n_nodes; k++) if (d.nodes[k].mesh_index == mesh && d.nodes[k].n_lights)
         throw unsupported_error("ctl_scene_bind_skin: node " + std::to_string(k) + " of mesh " + std::to_string(mesh) + " carries an area light, whose shape set is host work (ctl_builder_update_mesh)");
     for (uint32_t t : flat_missing_tris_) if (t >= tri0 && t < tri1)
         throw unsupported_error("ctl_scene_bind_skin: mesh " + std::to_string(mesh) + " has a triangle that was degenerate when the scene was flattened: the flattened tree has no leaf entry for it");
@@ -198,6 +199,8 @@ void Scene::bind_skin(uint32_t mesh, const float* rest_positions, const float* r
     if (indices) B->indices.upload(indices, (size_t)n_tri * 3);
     B->skinned_p.alloc(n_vert); B->skinned_n.alloc(n_vert); B->bones.alloc((size_t)n_bones * 8);
     CTL_HIP(hipStreamSynchronize(nullptr));   // the staging vectors are pageable: the copies have left them
+    if (flags & CTL_SKIN_AREA_LIGHTS) enable_skin_lights(mesh);   // its lights' shape sets follow every pose (shape_set.hip)
+    else if (skin_lights_.erase(mesh)) lights_stale_ = true;     // bound again without the flag: the tables go back to the description's with the next update
     skins_[mesh] = B;
 }
 
@@ -206,6 +209,7 @@ void Scene::unbind_skin(uint32_t mesh) {
     if (it == skins_.end()) throw std::runtime_error("ctl_scene_unbind_skin: mesh " + std::to_string(mesh) + " is not bound");
     CTL_HIP(hipDeviceSynchronize());
     skins_.erase(it);
+    if (skin_lights_.erase(mesh)) lights_stale_ = true;   // the shape sets in HBM are the last pose's: the next ctl_scene_update uploads the description's light tables
     // the values the device holds are no description's: the next ctl_scene_update must see the mesh as changed and restore its description's values
     if (snap_) snap_->geom.invalidate_values(mesh);
 }
@@ -232,13 +236,15 @@ void Scene::animate_mesh(uint32_t mesh, const ctl_float4x4* bones0, const ctl_fl
     if (B.n_rows) { hipLaunchKernelGGL(k_woop_rows, dim3((B.n_rows + 255u) / 256u), dim3(256), 0, nullptr, K); CTL_HIP(hipGetLastError()); }
     CTL_HIP(hipEventRecord(ev.b, nullptr));
     B.posed = true;
+    float shape_ms = 0;
+    if (skin_lights_.count(mesh)) { run_shape_sets(snap_->d); shape_ms = last_shape_set_ms_; }   // the lights on the mesh's nodes, from the rows just written; before the refit
     // the flat-tree half, as after a CTL_DIFF_GEOMETRY update of this mesh: its nodes' entries take the new rows and become whole, the refit, the re-stamp
     std::vector<uint8_t> mesh_changed(snap_->d.n_meshes, 0); mesh_changed[mesh] = 1;
     ctl_scene_update_stats st{}; st.mask = CTL_DIFF_GEOMETRY;
     refit_flat(snap_->d, true, true, &mesh_changed, &st);   // ends with a device synchronisation
     st.restamped = 1u;
     float ms = 0; CTL_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
-    last_skin_ms_ = ms; last_update_ = st; last_mask_ = st.mask;
+    last_skin_ms_ = ms; last_shape_set_ms_ = shape_ms; last_update_ = st; last_mask_ = st.mask;
     if (stats) *stats = st;
 }
 

@@ -9,6 +9,7 @@
 #include <string>
 #include "ctl_math.h"
 #include "mesh_skin.h"
+#include "shape_set.h"
 #include "volume_eval.h"
 #include <cstring>
 #include <algorithm>
@@ -30,14 +31,8 @@ void woop_set_data(ctl_woop_tri& w, f3 a, f3 b, f3 c) {
     float r[12]; woop_rows_from_vertices(r, a, b, c);
     std::memcpy(w.a, r, 16); std::memcpy(w.b, r + 4, 16); std::memcpy(w.c, r + 8, 16);
 }
-// and back (Engine/TriIntersectorData.cu:20-32) — area lights take their vertices from this round trip
-void woop_get_data(const ctl_woop_tri& w, f3& v0, f3& v1, f3& v2) {
-    float m[16] = { w.b[0], w.b[1], w.b[2], w.b[3], w.c[0], w.c[1], w.c[2], w.c[3], w.a[0], w.a[1], w.a[2], w.a[3] * -1.0f, 0, 0, 0, 1 }, inv[16];
-    mat_inverse(m, inv);
-    f3 e02(inv[0], inv[4], inv[8]), e12(inv[1], inv[5], inv[9]);
-    v2 = f3(inv[3], inv[7], inv[11]);
-    v0 = v2 + e02; v1 = v2 + e12;
-}
+// and back (Engine/TriIntersectorData.cu:20-32) — area lights take their vertices from this round trip (shape_set.h)
+void woop_get_data(const ctl_woop_tri& w, f3& v0, f3& v1, f3& v2) { woop_get_data(w.a, w.b, w.c, v0, v1, v2); }
 
 // TriangleData::setUvSetData + setData (Engine/TriangleData.cu:18-65)
 static void tri_data_pack(ctl_triangle_data& T, const f3 p[3], const f3 n[3], const f2 t[3], uint32_t mat_index) {
@@ -46,20 +41,6 @@ static void tri_data_pack(ctl_triangle_data& T, const f3 p[3], const f3 n[3], co
     tri_data_words<false>(words, p, n, uv, mat_index);   // mesh_skin.h; the normal codec over libm, as these arrays always were
     static_assert(sizeof(ctl_triangle_data) == sizeof(words), "TriangleData is eight words");
     std::memcpy(&T, words, sizeof(words));
-}
-
-// shading normal of a triangle at barycentrics (1/3,1/3) under `l2w` — the dg.sys.n of TriangleData::fillDG
-// (Engine/TriangleData.cu:75-103), used for ShapeSet::triData::n (Engine/ShapeSet.cu:11-23)
-static f3 tri_data_center_normal(const ctl_triangle_data& T, const m34& l2w) {
-    f3 na = uchar2_to_normal(T.nor_mat_extra[0] & 0xffff), nb = uchar2_to_normal(T.nor_mat_extra[0] >> 16), nc = uchar2_to_normal(T.nor_mat_extra[1] & 0xffff);
-    float u = 1.0f / 3.0f, v = 1.0f / 3.0f, w = 1.0f - u - v;
-    f3 n = normalize(u * na + v * nb + w * nc);
-    auto h = [](uint32_t bits) { return half_to_float((uint16_t)bits); };
-    f3 dpdu(h(T.dpdu_dpdv[0]), h(T.dpdu_dpdv[0] >> 16), h(T.dpdu_dpdv[1]));
-    f3 s = dpdu - n * dot(n, dpdu);
-    f3 t = cross(s, n);
-    s = xform_dir(l2w, s); t = xform_dir(l2w, t);
-    return normalize(cross(t, s));
 }
 
 // Mesh::ComputeVertexNormals (Engine/Mesh.cpp:151-190), "sphere inscribed polytope" weights
@@ -320,10 +301,10 @@ float scene_builder::recalculate_shape_set(uint32_t node_index, uint32_t cdf_off
     float sumArea = 0; cdf[0] = 0.0f;
     for (uint32_t i = 0; i < count; i++) {
         ctl_shape_tri& s = st[i];
-        f3 p[3]; woop_get_data(woop[s.i_dat], p[0], p[1], p[2]);
-        f3 n = tri_data_center_normal(tri[s.t_dat], l2w);
-        for (int k = 0; k < 3; k++) p[k] = xform_point(l2w, p[k]);
-        float area = 0.5f * length(cross(p[2] - p[0], p[1] - p[0]));
+        const ctl_woop_tri& w = woop[s.i_dat];
+        uint32_t T[8]; std::memcpy(T, &tri[s.t_dat], 32);
+        f3 p[3], n; float area;
+        shape_triangle(w.a, w.b, w.c, T, l2w, [](uint32_t code) { return uchar2_to_normal(code); }, p, n, area);   // shape_set.h: the device's kernels run the same function
         for (int k = 0; k < 3; k++) { s.p[k][0] = p[k].x; s.p[k][1] = p[k].y; s.p[k][2] = p[k].z; }
         s.n[0] = n.x; s.n[1] = n.y; s.n[2] = n.z; s.area = area;
         sumArea += area; cdf[i + 1] = cdf[i] + area;

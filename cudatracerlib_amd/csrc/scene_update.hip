@@ -211,7 +211,8 @@ uint32_t Scene::update(const ctl_scene_desc& d, ctl_scene_update_stats* stats) {
     if (!snap_) throw std::runtime_error("ctl_scene_update: the scene holds no description");
     geometry_hashes geom;
     const std::vector<uint8_t> device_owned = device_owned_meshes();
-    const uint32_t mask = scene_desc_diff(snap_->d, d, &snap_->geom, &geom, device_owned.empty() ? nullptr : &device_owned);
+    // lights_stale_: an emissive skin was unbound (shape_set.hip) and HBM holds its last pose's shape sets — the light tables are uploaded whatever the descriptions say
+    const uint32_t mask = scene_desc_diff(snap_->d, d, &snap_->geom, &geom, device_owned.empty() ? nullptr : &device_owned) | (lights_stale_ ? (uint32_t)CTL_DIFF_LIGHTS : 0u);
     last_mask_ = mask;
     if (mask == 0) { last_update_ = ctl_scene_update_stats{}; if (stats) *stats = last_update_; return 0; }   // nothing differs: no synchronisation, no tracer is stalled
     if (mask & CTL_DIFF_TOPOLOGY) throw std::runtime_error("ctl_scene_update: the topology of the scene differs (geometry arrays, counts, node -> mesh / material assignment, images or transmittance tables): re-create the scene");
@@ -252,7 +253,7 @@ uint32_t Scene::update(const ctl_scene_desc& d, ctl_scene_update_stats* stats) {
             if (had_alpha_maps != S.alpha_maps) restamp = true;
         }
     }
-    if (mask & CTL_DIFF_LIGHTS) { upload_lights(d); if (!(mask & CTL_DIFF_TRANSFORMS)) upload_instances(d); }   // node_info carries the nodes' light slots
+    if (mask & CTL_DIFF_LIGHTS) { upload_lights(d); lights_stale_ = false; if (!(mask & CTL_DIFF_TRANSFORMS)) upload_instances(d); }   // node_info carries the nodes' light slots
     if (mask & CTL_DIFF_TRANSFORMS) {
         upload_top_level(d); upload_instances(d);
         if (flattened()) S.inst_w_one = inverse_transforms_have_w_one(d);
@@ -261,6 +262,8 @@ uint32_t Scene::update(const ctl_scene_desc& d, ctl_scene_update_stats* stats) {
         for (uint32_t m = 0; m < d.n_meshes; m++) if (mesh_changed[m]) upload_mesh_geometry(d, ranges, m);
         if (flattened()) restamp = true;   // the entries' model / alpha bits come from tri_data: re-stamped from the new one
     }
+    // the shape sets of the lights on emissive skins are the device's: d's own were made from rest-pose rows (and have just been uploaded, or its transforms have moved the node)
+    if (mask & (CTL_DIFF_LIGHTS | CTL_DIFF_TRANSFORMS | CTL_DIFF_GEOMETRY)) run_shape_sets(d);
     CTL_HIP(hipDeviceSynchronize());
     bind(d);
     if (mask & CTL_DIFF_CAMERA) set_camera(d);

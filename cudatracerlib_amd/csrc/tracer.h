@@ -10,6 +10,7 @@
 #include "flatten.h"
 #include <hip/hip_runtime.h>
 #include <map>
+#include <set>
 #include <string>
 #include <vector>
 #include <memory>
@@ -75,11 +76,16 @@ public:
     void read_flat_bvh(flat_scene& out);   // the device tree copied back, un-stamped: what flatten_scene handed to the upload, after any refit
     // skinned meshes (mesh_skin.hip; ctl_scene_bind_skin, ctl_scene_animate_mesh, ctl_scene_read_mesh_geometry, ctl_scene_unbind_skin).  A bound mesh is device-owned: update()
     // neither compares nor uploads its values
-    void bind_skin(uint32_t mesh, const float* rest_positions, const float* rest_normals, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri, const uint8_t* bone_indices, const uint8_t* bone_weights, uint32_t n_bones);
+    // flags: CTL_SKIN_* (ctl_scene_bind_skin_ex); 0 = the plain call, which refuses a mesh whose nodes carry area lights
+    void bind_skin(uint32_t mesh, const float* rest_positions, const float* rest_normals, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri, const uint8_t* bone_indices, const uint8_t* bone_weights, uint32_t n_bones, uint32_t flags = 0);
     void unbind_skin(uint32_t mesh);
     void animate_mesh(uint32_t mesh, const ctl_float4x4* bones0, const ctl_float4x4* bones1, float lerp, ctl_scene_update_stats* stats);
     void read_mesh_geometry(uint32_t mesh, float* positions_out, float* normals_out, ctl_triangle_data* tri_data_out, ctl_woop_tri* woop_out);
     float last_skin_ms() const { return last_skin_ms_; }   // HIP-event time of the three pose kernels of the last animate_mesh
+    // the area lights of a mesh bound with CTL_SKIN_AREA_LIGHTS (shape_set.hip): their shape sets — ranges of anim_ and the sum_area of their records — are device-owned,
+    // recomputed after every pose and after every upload of the light tables or the instance transforms
+    float last_shape_set_ms() const { return last_shape_set_ms_; }   // HIP-event time of the shape-set kernels of the last call that ran them
+    void read_lights(ctl_light* lights_out, uint32_t n_lights, uint8_t* anim_out, size_t n_anim_bytes);   // ctl_scene_read_lights: the light table and the anim blob as HBM holds them
     // the participating media (scene_volumes.h): the kernel argument as the last creation / update left it (n == 0: no media), read by the PathTracer plugin at every pass;
     // the plugins without medium code refuse a scene that has media instead of rendering it without them: unsupported_error naming `who` and the PathTracer plugin
     vol::table volume_table() const;
@@ -109,6 +115,11 @@ private:
     void upload_mesh_geometry(const ctl_scene_desc& d, const mesh_ranges& R, uint32_t mesh);   // the two-level arrays of one mesh, re-laid-out as the constructor does, into the same allocations
     bool reduced_rough_transmittance_ = false;
     std::map<uint32_t, std::shared_ptr<skin_binding>> skins_; float last_skin_ms_ = 0;   // the bound meshes
+    void enable_skin_lights(uint32_t mesh);                // `mesh` joins skin_lights_; the first call uploads the normal-code table
+    bool launch_shape_sets(const ctl_scene_desc& d);       // the shape-set kernels of every light on a node of a mesh in skin_lights_, by d's lights and node transforms
+    void run_shape_sets(const ctl_scene_desc& d);          // the same between two events; waits for them and sets last_shape_set_ms_
+    std::set<uint32_t> skin_lights_; dbuf<float2> shape_lut_; float last_shape_set_ms_ = 0;   // meshes bound with CTL_SKIN_AREA_LIGHTS; shape_normal_lut (shape_set.h) in HBM
+    bool lights_stale_ = false;   // an emissive skin was unbound: lights_ / anim_ hold no description's values, the next update uploads them whatever the diff says
     ctl_scene_update_stats last_update_{}; uint32_t last_mask_ = 0;
     std::unique_ptr<desc_snapshot> snap_;
     std::unique_ptr<scene_volumes> volumes_;   // made by the first snapshot(), written in place by every later one

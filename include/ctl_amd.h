@@ -455,8 +455,9 @@ int ctl_scene_get_update_stats(ctl_scene* scene, ctl_scene_update_stats* out);
  *   CTL_ERR_NO_DEVICE    no device (checked first)
  *   CTL_ERR_INVALID      a bad mesh index, another triangle count than the mesh's, a vertex index out of range, n_bones of 0 or above 256, an index byte >= n_bones (under a
  *                        zero weight too: the matrix is still read)
- *   CTL_ERR_UNSUPPORTED  a scene that is not a flattened CTL_FLAT_Q4 scene with refit data; a mesh whose nodes carry an area light (their shape sets are host work:
- *                        ctl_builder_update_mesh); a mesh with a triangle that was degenerate when the scene was flattened (it has no leaf entry)
+ *   CTL_ERR_UNSUPPORTED  a scene that is not a flattened CTL_FLAT_Q4 scene with refit data; a mesh whose nodes carry an area light, unless it is bound through
+ *                        ctl_scene_bind_skin_ex with CTL_SKIN_AREA_LIGHTS (below; without the flag its shape sets are host work: ctl_builder_update_mesh); a mesh with a
+ *                        triangle that was degenerate when the scene was flattened (it has no leaf entry)
  * A bound mesh is DEVICE-OWNED: ctl_scene_update neither compares nor uploads its values, whatever new_desc holds for it, and never reports CTL_DIFF_GEOMETRY for it — a
  * camera, material or transform update during an animation keeps the pose and stays cheap.  Binding a bound mesh again replaces the binding.
  *
@@ -469,6 +470,20 @@ int ctl_scene_get_update_stats(ctl_scene* scene, ctl_scene_update_stats* out);
  * What a pose leaves alone: the scene box, ray_trace_eps and the box-dependent lights stay as created — a host whose character leaves the scene box re-creates the scene, or
  * runs a host update (ctl_builder_update_mesh) —, and so do the nodes of the mesh's two-level BVH, which a flattened scene never traverses.
  *
+ * ctl_scene_bind_skin_ex is ctl_scene_bind_skin with `flags`: 0 is the plain call, refusals included; an unknown bit is CTL_ERR_INVALID (after CTL_ERR_NO_DEVICE, before anything
+ * else).  CTL_SKIN_AREA_LIGHTS binds a mesh whose nodes carry area lights — a glowing character, a swinging lamp.  Next-event estimation samples a DiffuseLight's shape set
+ * (ctl_shape_tri records and the area CDF in the anim blob, sum_area in the light record), so every pose recomputes, ON THE DEVICE and after the three pose kernels, the shape
+ * sets of every CTL_LIGHT_DIFFUSE light with count > 0 whose node_idx names a node that instances the mesh (csrc/shape_set.h, shape_set.hip): one lane per triangle, then the CDF
+ * as ShapeSet's own serial fp32 sum in index order, so that the tables equal those of a host-updated description bit for bit.  ctl_scene_get_shape_set_ms: the HIP-event time
+ * of those kernels in the last call that ran them (ctl_scene_get_skin_ms stays the three pose kernels).  OWNERSHIP: while such a mesh is bound, those ranges of the anim blob
+ * and the sum_area of those lights are the device's.  Whenever the library uploads the light tables or the instance transforms of the scene — ctl_scene_update with
+ * CTL_DIFF_LIGHTS, CTL_DIFF_TRANSFORMS or CTL_DIFF_GEOMETRY, ctl_scene_update_nodes — it runs the kernels again afterwards, by the lights, nodes and node transforms of the new
+ * description: another radiance or a moved emissive node arrives, the pose stays, and the shape sets the host made for new_desc from its rest-pose rows are overwritten.
+ * ctl_scene_unbind_skin marks the light tables stale: the next ctl_scene_update uploads new_desc's lights and anim blob whole, whatever the diff says, and reports CTL_DIFF_LIGHTS.
+ *
+ * ctl_scene_read_lights copies back the first n_lights light records and the first n_anim_bytes of the anim blob as HBM holds them, for any scene (either count may be 0;
+ * more than the scene holds: CTL_ERR_INVALID).
+ *
  * ctl_scene_read_mesh_geometry copies back what HBM holds (any pointer may be NULL): positions_out / normals_out float[n_vert][3], the skinned vertices of the last pose
  * (CTL_ERR_INVALID unless the mesh is bound and posed); tri_data_out and woop_out, the mesh's ranges of tri_data and of the Woop rows, for any mesh of any scene.
  *
@@ -476,11 +491,21 @@ int ctl_scene_get_update_stats(ctl_scene* scene, ctl_scene_update_stats* out);
  * changed (CTL_DIFF_GEOMETRY) and restores the description's values.
  *
  * ctl_skin_mesh_host is the yardstick, host only: `desc` = the description the scene was made from, the bind arguments, the pose; returns the positions, the normals, the
- * mesh's TriangleData and its Woop rows through the same functions the kernels run (csrc/mesh_skin.h), bit for bit what ctl_scene_read_mesh_geometry reads back. */
+ * mesh's TriangleData and its Woop rows through the same functions the kernels run (csrc/mesh_skin.h), bit for bit what ctl_scene_read_mesh_geometry reads back.
+ *
+ * ctl_shape_sets_host is the yardstick of the shape sets, host only: desc's light table and anim blob copied into lights_out[desc->n_lights_buf] and
+ * anim_out[desc->n_anim_bytes], with the shape sets of the lights on nodes that instance `mesh_index` recalculated from tri_data / woop — the mesh's ranges, as
+ * ctl_skin_mesh_host returns them — and desc's node transforms, through the functions the kernels run (csrc/shape_set.h): what ctl_scene_read_lights reads back after the pose. */
+enum { CTL_SKIN_AREA_LIGHTS = 1 };
 int ctl_scene_bind_skin(ctl_scene* scene, uint32_t mesh_index, const float* rest_positions, const float* rest_normals, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri,
                         const uint8_t* bone_indices, const uint8_t* bone_weights, uint32_t n_bones);
+int ctl_scene_bind_skin_ex(ctl_scene* scene, uint32_t mesh_index, const float* rest_positions, const float* rest_normals, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri,
+                           const uint8_t* bone_indices, const uint8_t* bone_weights, uint32_t n_bones, uint32_t flags);
 int ctl_scene_animate_mesh(ctl_scene* scene, uint32_t mesh_index, const ctl_float4x4* bones0, const ctl_float4x4* bones1, float lerp, ctl_scene_update_stats* stats_out);
 int ctl_scene_get_skin_ms(ctl_scene* scene, float* ms_out);
+int ctl_scene_get_shape_set_ms(ctl_scene* scene, float* ms_out);
+int ctl_scene_read_lights(ctl_scene* scene, ctl_light* lights_out, uint32_t n_lights, uint8_t* anim_out, size_t n_anim_bytes);
+int ctl_shape_sets_host(const ctl_scene_desc* desc, uint32_t mesh_index, const ctl_triangle_data* tri_data, const ctl_woop_tri* woop, ctl_light* lights_out, uint8_t* anim_out);
 int ctl_scene_read_mesh_geometry(ctl_scene* scene, uint32_t mesh_index, float* positions_out, float* normals_out, ctl_triangle_data* tri_data_out, ctl_woop_tri* woop_out);
 int ctl_scene_unbind_skin(ctl_scene* scene, uint32_t mesh_index);
 int ctl_skin_mesh_host(const ctl_scene_desc* desc, uint32_t mesh_index, const float* rest_positions, const float* rest_normals, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri,
