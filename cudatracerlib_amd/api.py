@@ -1521,7 +1521,10 @@ class _Parameters:
 
 
 class WavefrontPathTracer:
-    """Integrators/PseudoRealtime/WavefrontPathTracer.h:24-67 behind Tracer<true> (Kernel/Tracer.h:193-294)."""
+    """Integrators/PseudoRealtime/WavefrontPathTracer.h:24-67 behind Tracer<true> (Kernel/Tracer.h:193-294).
+    Build-specific parameters, through getParameters().setValue like the reference's own: PassBatch, AlphaTest, ShadeByModelClass, FuseTraversal, PathSemantics,
+    U16Barycentrics, OrderedAccumulation(MaxMB), and ParticipatingMedia (bool, default False: a scene with participating media is refused; True: it is rendered under
+    PathTrace's rules, the volume table read at every pass — refused together with PathSemantics = "Wavefront")."""
 
     PLUGIN = b"WavefrontPathTracer"
 

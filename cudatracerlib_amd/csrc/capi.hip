@@ -36,11 +36,12 @@ struct ctl_scene {
 // basis: of the description the tree stands for; extra_missing: triangles an added node got no entry for (flat_nodes.h), on top of what the entries themselves show
 struct ctl_flat_bvh { flat_scene f; node_set_basis basis; std::vector<uint32_t> extra_missing; };
 struct ctl_image { Image img; ctl_image(uint32_t w, uint32_t h) : img(w, h) {} };
-// wavefront / scene: the WavefrontPathTracer has no medium code and refuses a scene with participating media here, when the scene is handed over and when a pass starts
-// (Scene::refuse_volumes; the PathTracer and the PrimTracer judge that themselves).  `scene` is the pointer InitializeScene got, the one DoPass reads the scene through
+// wavefront / scene: the WavefrontPathTracer judges what it refuses of participating media (WavefrontPathTracer::check_media: a scene that has media while its
+// ParticipatingMedia is off, PathSemantics = Wavefront while it is on) here, when the scene is handed over and — in front of every other complaint — when a pass starts;
+// the PathTracer and the PrimTracer judge theirs themselves.  `scene` is the pointer InitializeScene got, the one DoPass reads the scene through
 struct ctl_tracer {
     std::unique_ptr<TracerBase> t; bool wavefront = false; const Scene* scene = nullptr;
-    void refuse_media() const { if (wavefront && scene) scene->refuse_volumes("WavefrontPathTracer"); }
+    void refuse_media() const { if (wavefront && scene) static_cast<const WavefrontPathTracer*>(t.get())->check_media(scene); }
 };
 struct ctl_sequence_generator { sequence_generator g; };
 
@@ -668,7 +669,7 @@ int ctl_tracer_get_param_float(ctl_tracer* t, const char* key, float* value_out)
 int ctl_tracer_set_param_enum(ctl_tracer* t, const char* key, const char* value_name) { CTL_REQUIRE(t && key && value_name, "null argument"); CTL_TRY t->t->getParameters().setEnumByName(key, value_name); CTL_CATCH }
 int ctl_tracer_get_param_int(ctl_tracer* t, const char* key, int* value_out) { CTL_REQUIRE(t && key && value_out, "null argument"); CTL_TRY *value_out = t->t->getParameters().getValue(key); CTL_CATCH }
 int ctl_tracer_resize(ctl_tracer* t, uint32_t width, uint32_t height) { CTL_REQUIRE(t && width && height, "bad argument"); CTL_TRY t->t->Resize(width, height); CTL_CATCH }
-int ctl_tracer_initialize_scene(ctl_tracer* t, ctl_scene* s) { CTL_REQUIRE(t && s, "null argument"); CTL_TRY if (t->wavefront) s->s.refuse_volumes("WavefrontPathTracer"); t->t->InitializeScene(&s->s); t->scene = &s->s; CTL_CATCH }
+int ctl_tracer_initialize_scene(ctl_tracer* t, ctl_scene* s) { CTL_REQUIRE(t && s, "null argument"); CTL_TRY t->t->InitializeScene(&s->s); t->scene = &s->s; CTL_CATCH }
 int ctl_tracer_set_tile_shard(ctl_tracer* t, uint32_t rank, uint32_t world) { CTL_REQUIRE(t, "null tracer"); CTL_TRY t->t->setTileShard(rank, world); CTL_CATCH }
 int ctl_tracer_set_sampler_tables(ctl_tracer* t, const float* tables_1d, const float* tables_2d) { CTL_REQUIRE(t && tables_1d && tables_2d, "null argument"); CTL_TRY t->t->setSamplerTables(tables_1d, tables_2d); CTL_CATCH }
 int ctl_tracer_do_pass(ctl_tracer* t, ctl_image* img, int new_trace) { CTL_REQUIRE(t && img, "null argument"); CTL_TRY t->refuse_media(); t->t->DoPass(&img->img, new_trace != 0); CTL_CATCH }

@@ -6,6 +6,8 @@
 
 namespace ctl {
 
+namespace vol { struct table; }   // volume.h: a scene's participating media as a kernel argument
+
 // One path per slot, structure-of-arrays so that a wave's 64 lanes read/write 1 KiB contiguous per array.
 struct path_soa {
     float4* ray_o;    // origin.xyz, tmin                                  (traversalRay::a, Kernel/TraceHelper.h:55-59)
@@ -15,8 +17,10 @@ struct path_soa {
     float4* nor;      // normal of the previous vertex xyz, packed {d1:8, d2:8, pass-in-batch:8, flags:8}
     float4* pend;     // pending NEE contribution directF.rgb, shadow-ray index (bits)   (directF, dIdx)
     float2* px;       // film sample position pX
+    float4* mrec;     // participating media only (allocated while the tracer's ParticipatingMedia is on, else null): what PathTrace's mRec carries across bounces — transmittance.rgb, pdfFailure (medium_stage.hip)
 };
 enum { kFlagSpecular = 1 };
+constexpr int kHitConsumed = -2;   // wave_queues::hit[i].w of a slot whose path scattered in a medium before the hit: k_medium_stage has moved the path on, the shade stage skips the slot (-1 = miss)
 constexpr uint32_t kNoShadow = 0xffffffffu;
 
 struct final_soa {    // terminated paths that still wait for a shadow ray
@@ -89,7 +93,9 @@ void launch_intersect_pair(const launch_ctx& lc, const dev_scene& S, const float
                            const float4* sro, const float4* srd, const uint32_t* sn_ptr, uint32_t* swork, uint32_t* occ);
 void launch_intersect_count(const launch_ctx& lc, const dev_scene& S, const float4* ro, const float4* rd, const uint32_t* n_ptr, uint32_t* work, float4* hit, int* hit_node,
                             uint32_t* occ, int any_hit, unsigned long long* counts3);
-void launch_shade(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
+// media (a non-empty volume table; the tracer's ParticipatingMedia): the one media build of the full feature set (shade_full_media.hip, or shade_full_media_grid.hip for a table
+// with a VolumeGrid region) whatever the scene's feature set is — it skips the slots k_medium_stage consumed and attenuates the surface NEE by the media's transmittance
+void launch_shade(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image, const vol::table* media = nullptr);
 void read_stack_histogram(unsigned long long* h, bool reset);   // kernels.hip: rays of the counting traversals by deepest stack entry
 // The shade builds, X(name, keys): shade_<name>.hip defines launch_shade_<name> and shade_<name>_wf.hip launch_shade_<name>_wf (both from shade_kernel.inc).  keys: a model-class
 // build is launched for a scene that has one of these models (dev_scene::shade_models), 0 = whatever the scene has; the class builds in the order launch_shade runs them.
@@ -100,6 +106,10 @@ using shade_launch = void(const launch_ctx& lc, const dev_scene& S, const wave_q
 #define CTL_SHADE_DECLARE(name, keys) shade_launch launch_shade_##name, launch_shade_##name##_wf;
 CTL_SHADE_BUILDS(CTL_SHADE_DECLARE)
 #undef CTL_SHADE_DECLARE
+using shade_media_launch = void(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, const vol::table& V, int depth, ctl_pixel_data* image);
+shade_media_launch launch_shade_full_media, launch_shade_full_media_grid;   // shade_kernel.inc with CTL_SHADE_MEDIA 1 / 2
+// medium_stage.hip: the medium half of PathTrace (PathTracer.cu:17-58) for the paths of depth `depth`, between launch_finalize(depth - 1) and launch_shade(depth)
+void launch_medium_stage(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, const vol::table& V, int depth, ctl_pixel_data* image);
 void launch_class_partition(const launch_ctx& lc, const wave_queues& Q, int depth);
 void launch_finalize(const launch_ctx& lc, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image);
 // frame += the staged samples of a batch, pass by pass; clears the stage.  variance + stray_stage (both or neither; whole frames only): per pass the samples that strayed into the pixel

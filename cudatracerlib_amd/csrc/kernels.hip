@@ -11,6 +11,7 @@
 #include <type_traits>
 #include "shading.h"
 #include "compaction.h"
+#include "volume.h"
 #include <cstdlib>
 
 namespace ctl {
@@ -354,7 +355,9 @@ void launch_class_partition(const launch_ctx& lc, const wave_queues& Q, int dept
 
 // the shade kernel exists in feature-specialised builds (kernels.h CTL_SHADE_BUILDS): a scene that uses only the basic
 // material / light / texture set runs the variant whose code does not carry the registers of the rest (dev_scene::shade_features)
-void launch_shade(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image) {
+void launch_shade(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image, const vol::table* media) {
+    // participating media: the one media build, with the march of the density grids only for a table that holds a VolumeGrid region (the full build is a superset of every other)
+    if (media) { (media->g ? launch_shade_full_media_grid : launch_shade_full_media)(lc, S, Q, P, *media, depth, image); return; }
 #define CTL_SHADE_INDEX(name, keys) build_##name,
 #define CTL_SHADE_ROW(name, keys) { keys, { launch_shade_##name, launch_shade_##name##_wf } },
     enum { CTL_SHADE_BUILDS(CTL_SHADE_INDEX) n_builds };

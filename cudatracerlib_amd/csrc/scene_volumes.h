@@ -1,6 +1,6 @@
 // scene_volumes.h — KernelDynamicScene::m_sVolume of a Scene: the participating media in HBM, a member of the Scene (Scene::volumes_, tracer.h; dev_scene and with it every
 // other kernel's arguments stay as they are).  A fixed table of CTL_MAX_VOL_COUNT slots, allocated when the scene is created and written in place by every later
-// Scene::snapshot (ctl_scene_update, 0 -> 1 volumes included); its only readers are the megakernel's MEDIA instantiations (megakernel.hip, through Scene::volume_table).
+// Scene::snapshot (ctl_scene_update, 0 -> 1 volumes included); its readers, through Scene::volume_table, are the megakernel's MEDIA instantiations (megakernel.hip) and the wavefront's medium path (medium_stage.hip, shade_full_media*.hip).
 // Beside it the grid records of the VolumeGrid regions (CTL_MAX_VOL_COUNT slots) and ONE float buffer of their cells, re-uploaded by an update and re-allocated only when it
 // grows; the table's g / cells point at them when the scene has a grid region and are null otherwise.
 #pragma once

@@ -54,9 +54,27 @@
 #if CTL_SHADE_PARK && CTL_SHADE_WAVEFRONT_RULES
 #error "CTL_SHADE_PARK is written for the default path rules"
 #endif
+// CTL_SHADE_MEDIA (shade_full_media.hip: 1, shade_full_media_grid.hip: 2 = the table may hold VolumeGrid regions): the build the WavefrontPathTracer launches behind
+// k_medium_stage (medium_stage.hip) for a scene with participating media.  It takes the volume table as a further kernel argument, leaves the slots that stage consumed
+// (Q.hit[i].w == kHitConsumed) alone, attenuates the surface NEE by the media's transmittance where EstimateDirect does, and hands path_soa::mrec on to the next depth.
+// Undefined or 0: none of that is compiled — the builds without media keep their code.
+#ifndef CTL_SHADE_MEDIA
+#define CTL_SHADE_MEDIA 0
+#endif
+#if CTL_SHADE_MEDIA && (CTL_SHADE_WAVEFRONT_RULES || CTL_SHADE_PARK || CTL_SHADE_CLASSED)
+#error "CTL_SHADE_MEDIA is written for the default path rules of the unclassed, unparked build"
+#endif
 #include "kernels.h"
 #include "shading.h"
 #include "compaction.h"
+#if CTL_SHADE_MEDIA
+#include "volume.h"
+#define CTL_SHADE_MEDIA_PARAM vol::table V,
+#define CTL_SHADE_MEDIA_ARG V,
+#else
+#define CTL_SHADE_MEDIA_PARAM
+#define CTL_SHADE_MEDIA_ARG
+#endif
 
 namespace ctl {
 
@@ -72,7 +90,7 @@ __device__ __forceinline__ uint32_t park_lane() { uint32_t t = threadIdx.x; asm 
 #endif
 enum { kParkCl = 0, kParkCf = 3, kParkNewD = 6, kParkPx = 9, kParkPass = 11, kParkWords = 12 };
 // One lane = one queued path vertex.  `depth` is the megakernel's 1-based depth of this vertex.
-__global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERNEL(dev_scene S, wave_queues Q, pass_params P, int depth, ctl_pixel_data* __restrict__ image) {
+__global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERNEL(dev_scene S, wave_queues Q, pass_params P, CTL_SHADE_MEDIA_PARAM int depth, ctl_pixel_data* __restrict__ image) {
     __shared__ uint32_t s_cnt[3][kWideBlock / 64]; __shared__ uint32_t s_base[3];
 #if CTL_SHADE_PARK
     __shared__ float s_park[kParkWords][CTL_SHADE_BLOCK];
@@ -136,6 +154,9 @@ __global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERN
             active = j2 < n;
             i = j2;
         }
+#endif
+#if CTL_SHADE_MEDIA
+        if (active && __float_as_int(Q.hit[i].w) == kHitConsumed) active = false;   // the path scattered in a medium before this hit and k_medium_stage has moved it on: the slot is empty, like one beyond n
 #endif
         bool alive = false, want_shadow = false, terminated = false;
         f3 cl(0.0f), cf(0.0f), directF(0.0f), new_o(0.0f), new_d(0.0f), last_nor(0.0f), sh_org(0.0f), sh_dir(0.0f);
@@ -275,7 +296,11 @@ __global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERN
                                         weight = power_heuristic(directPdf, bp);
                                     }
                                     CTL_UNPARK3(kParkCf, cf);
+#if CTL_SHADE_MEDIA
+                                    directF = cf * sdiv((value * bsdfVal * weight) * vol::transmittance<(CTL_SHADE_MEDIA == 2)>(V, dr.ref, dr.d, 0.0f, dr.dist), lpdf);   // EstimateDirect(..., attenuated = true) (TraceAlgorithms.cu:65-67), the megakernel's order
+#else
                                     directF = cf * sdiv(value * bsdfVal * weight, lpdf);
+#endif
                                     want_shadow = true;
                                     sh_org = dr.ref; sh_dir = dr.d; sh_tmax = dr.dist - S.eps;   // Occluded(r, 0, dist) (KernelDynamicScene.cu:70-80)
                                 }
@@ -334,6 +359,9 @@ __global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERN
             B.nor[nslot] = make_float4(last_nor.x, last_nor.y, last_nor.z, __uint_as_float((d1 % CTL_SAMPLER_SEQUENCE_LENGTH) | ((d2 % CTL_SAMPLER_SEQUENCE_LENGTH) << 8) | (pass_b << 16)   /* only d mod 30 matters (Sampler_device.h:98,104) */ | ((specular ? kFlagSpecular : 0u) << 24)));
             B.pend[nslot] = make_float4(directF.x, directF.y, directF.z, __uint_as_float(want_shadow ? sslot : kNoShadow));
             B.px[nslot] = px;
+#if CTL_SHADE_MEDIA
+            B.mrec[nslot] = A.mrec[i];   // PathTrace's mRec lives across the bounces: what k_medium_stage left in it travels on
+#endif
         } else if (want_shadow) {
             Q.fin.rad[fslot] = make_float4(cl.x, cl.y, cl.z, __uint_as_float(sslot));
             Q.fin.dir[fslot] = make_float4(directF.x, directF.y, directF.z, 0.0f);
@@ -344,11 +372,15 @@ __global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERN
     }
 }
 
+#if CTL_SHADE_MEDIA
+void CTL_SHADE_LAUNCH(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, const vol::table& V, int depth, ctl_pixel_data* image) {
+#else
 void CTL_SHADE_LAUNCH(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image) {
+#endif
 #ifndef CTL_SHADE_GRID_WAVES
 #define CTL_SHADE_GRID_WAVES 4   // waves per SIMD the grid is sized for (the kernels are grid-stride loops over the queue)
 #endif
-    hipLaunchKernelGGL(CTL_SHADE_KERNEL, dim3(lc.grid_blocks / 8 * (kWideBlock / CTL_SHADE_BLOCK) * CTL_SHADE_GRID_WAVES / 4), dim3(CTL_SHADE_BLOCK), 0, lc.stream, S, Q, P, depth, image);   // 16 waves per CU by default
+    hipLaunchKernelGGL(CTL_SHADE_KERNEL, dim3(lc.grid_blocks / 8 * (kWideBlock / CTL_SHADE_BLOCK) * CTL_SHADE_GRID_WAVES / 4), dim3(CTL_SHADE_BLOCK), 0, lc.stream, S, Q, P, CTL_SHADE_MEDIA_ARG depth, image);   // 16 waves per CU by default
 }
 
 } // namespace ctl

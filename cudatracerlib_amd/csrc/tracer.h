@@ -86,8 +86,8 @@ public:
     // recomputed after every pose and after every upload of the light tables or the instance transforms
     float last_shape_set_ms() const { return last_shape_set_ms_; }   // HIP-event time of the shape-set kernels of the last call that ran them
     void read_lights(ctl_light* lights_out, uint32_t n_lights, uint8_t* anim_out, size_t n_anim_bytes);   // ctl_scene_read_lights: the light table and the anim blob as HBM holds them
-    // the participating media (scene_volumes.h): the kernel argument as the last creation / update left it (n == 0: no media), read by the PathTracer plugin at every pass;
-    // the plugins without medium code refuse a scene that has media instead of rendering it without them: unsupported_error naming `who` and the PathTracer plugin
+    // the participating media (scene_volumes.h): the kernel argument as the last creation / update left it (n == 0: no media), read at every pass by the PathTracer plugin
+    // and by the WavefrontPathTracer with ParticipatingMedia = true; whoever runs no medium code refuses a scene that has media instead of rendering it without them: unsupported_error naming `who` and the PathTracer plugin
     vol::table volume_table() const;
     void refuse_volumes(const char* who) const;
     dev_scene S{};
@@ -338,6 +338,10 @@ class WavefrontPathTracer : public Tracer<true> {
 public:
     WavefrontPathTracer();
     void Resize(unsigned int w, unsigned int h) override;
+    void InitializeScene(Scene* s) override { check_media(s); Tracer<true>::InitializeScene(s); }
+    // what the plugin refuses (unsupported_error), judged when a scene is handed over and when a pass starts.  ParticipatingMedia = false: a scene with participating media
+    // (Scene::refuse_volumes — the plugin then runs no medium code and would render the scene without them); true: PathSemantics = Wavefront (pathIterateKernel has no medium rules)
+    void check_media(const Scene* s) const;
     void setDepthBuffer(float* device_data, unsigned int dw, unsigned int dh) override { depth_buffer_ = device_data; depth_w_ = dw; depth_h_ = dh; }   // WavefrontPathTracer : IDepthTracer (WavefrontPathTracer.h:24)
     void reservePasses(unsigned int n) override { const unsigned int b = std::min(passBatch(), std::max(1u, n)); growBatch(b, "reservePasses"); ensureTableRing(b); if (w != 0xffffffffu) (void)ensureStage(b); }
 protected:
@@ -351,7 +355,7 @@ private:
     wave_queues Q{};
     uint32_t capacity = 0, n_local_pixels = 0, alloc_batch_ = 1;
     float* depth_buffer_ = nullptr; unsigned int depth_w_ = 0, depth_h_ = 0;
-    std::vector<std::unique_ptr<dbuf<float4>>> f4_; dbuf<float2> px_[2]; dbuf<float4> stage_, stray_stage_; dbuf<int> hit_node_; dbuf<uint32_t> occ_[2], counts_, work_, class_order_, class_counts_; dbuf<unsigned char> mat_key_; dbuf<unsigned long long> stats_;
+    std::vector<std::unique_ptr<dbuf<float4>>> f4_; dbuf<float2> px_[2]; dbuf<float4> stage_, stray_stage_, mrec_[2]; dbuf<int> hit_node_; dbuf<uint32_t> occ_[2], counts_, work_, class_order_, class_counts_; dbuf<unsigned char> mat_key_; dbuf<unsigned long long> stats_;
     int grid_blocks = 0;
     float4* new_f4(size_t n);
 };

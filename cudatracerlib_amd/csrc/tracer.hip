@@ -560,8 +560,18 @@ WavefrontPathTracer::WavefrontPathTracer() {
     // build-specific: hit barycentrics through the 16-bit pair of the reference's traversal result (Kernel/TraceHelper.cu:722-731); off = full floats (single-ray traceRay)
     m_sParameters.addBool("U16Barycentrics", false);
     m_sParameters.addInterval("OrderedAccumulationMaxMB", 4096, 0, 1 << 20);   // build-specific: largest stage of the ordered accumulation (MB of HBM); a batch that needs more accumulates with atomics
+    // build-specific: render participating media.  false (default): the plugin has no medium code in its launches and refuses a scene that has media; true: k_medium_stage
+    // (medium_stage.hip) runs the medium half of PathTrace (PathTracer.cu:17-58) in front of every depth's shade launch and the media build of the shade kernel
+    // (shade_full_media*.hip) attenuates the surface NEE — for a scene whose volume table is empty the pass launches exactly the kernels it launches with false.
+    // PathTrace rules only: refused together with PathSemantics = Wavefront
+    m_sParameters.addBool("ParticipatingMedia", false);
     m_sParameters.addBool("OrderedAccumulation", true);   // build-specific: finished paths are staged per (pass, pixel) and added to the frame in pass order (kernels.h pass_params::stage); false = four float atomics per path as Image::AddSample does
     grid_blocks = persistent_grid_blocks();
+}
+void WavefrontPathTracer::check_media(const Scene* s) const {
+    if (m_sParameters.getValue("ParticipatingMedia") == 0) { if (s) s->refuse_volumes("WavefrontPathTracer"); return; }
+    if (m_sParameters.getValue("PathSemantics") == 1)
+        throw unsupported_error("WavefrontPathTracer: ParticipatingMedia = true with PathSemantics = Wavefront is not supported: pathIterateKernel has no medium rules; participating media are rendered under PathSemantics = PathTrace");
 }
 float4* WavefrontPathTracer::new_f4(size_t n) { f4_.emplace_back(new dbuf<float4>()); f4_.back()->alloc(n); return f4_.back()->p; }
 
@@ -623,6 +633,7 @@ void WavefrontPathTracer::Resize(unsigned int _w, unsigned int _h) {
     class_order_.free(); for (int c = 0; c < 5; c++) Q.class_order[c] = nullptr;   // the model-class lists (20 B per slot) are allocated by the first render that shades by class
     mat_key_.alloc(capacity); Q.mat_key = mat_key_.p;
     counts_.free(); work_.free(); class_counts_.free(); stage_.free(); stray_stage_.free();
+    for (int b = 0; b < 2; b++) { mrec_[b].free(); Q.path[b].mrec = nullptr; }   // allocated by the first render with participating media (DoRender)
 }
 
 // stats: [0] path rays, [1] shadow rays, [2..6] closest-hit traversal counts, [7..11] any-hit traversal counts
@@ -653,7 +664,16 @@ unsigned int WavefrontPathTracer::passBatch() const {
 }
 
 void WavefrontPathTracer::DoRender(Image* I, const float* d_t1p, const float* d_t2p, unsigned int n_batch) {
+    check_media(m_pScene);
     growBatch(n_batch, "DoRender");   // the queues grow to the largest batch asked for
+    // participating media: the table is read per pass — ctl_scene_update may have changed the media since InitializeScene.  An empty table: the launches of a scene without media
+    const bool media_on = m_sParameters.getValue("ParticipatingMedia") != 0;
+    const vol::table V = media_on ? m_pScene->volume_table() : vol::table{};
+    const bool media = V.n != 0;
+    for (int b = 0; b < 2; b++) {   // path_soa::mrec exists only while the parameter is on; never cleared: k_medium_stage starts every camera path from the zero record
+        if (!media_on) mrec_[b].free(); else if (media && mrec_[b].n < capacity) mrec_[b].alloc(capacity);
+        Q.path[b].mrec = mrec_[b].p;
+    }
     const int maxPathLength = m_sParameters.getValue("MaxPathLength"), rrStart = m_sParameters.getValue("RRStartDepth");
     const bool direct = m_sParameters.getValue("Direct") != 0;
     const size_t n_counts = (size_t)(maxPathLength + 2) * 4, n_work = (size_t)2 * (maxPathLength + 2);
@@ -692,8 +712,9 @@ void WavefrontPathTracer::DoRender(Image* I, const float* d_t1p, const float* d_
     const bool fuse = !counting && direct && m_sParameters.getValue("FuseTraversal") != 0;
     // closest-hit traversals of a flattened scene leave the BSDF model of every hit in Q.mat_key (device_scene.h hit_key_out) for the shade kernel's regrouping and the model-class lists;
     // the counting kernels do without
-    P.model_classes = (S.shade_features != 0 && m_sParameters.getValue("ShadeByModelClass") != 0) ? 1 : 0;
-    dev_scene Sk = S; Sk.hit_key_out = (S.flat_leaf_keys && (S.shade_features == 0 || P.model_classes) && !counting) ? Q.mat_key : nullptr;   // (k_shade_full keys its regrouping by model AND material index)
+    // (with media the one media build of the full kernel shades every vertex: no model classes, and its regrouping keys itself)
+    P.model_classes = (!media && S.shade_features != 0 && m_sParameters.getValue("ShadeByModelClass") != 0) ? 1 : 0;
+    dev_scene Sk = S; Sk.hit_key_out = (!media && S.flat_leaf_keys && (S.shade_features == 0 || P.model_classes) && !counting) ? Q.mat_key : nullptr;   // (k_shade_full keys its regrouping by model AND material index)
     P.key_from_traversal = Sk.hit_key_out ? 1 : 0;
     if (!P.key_from_traversal) P.model_classes = 0;
     if (P.model_classes && !class_order_.p) { class_order_.alloc((size_t)capacity * 5); for (int c = 0; c < 5; c++) Q.class_order[c] = class_order_.p + (size_t)c * capacity; }
@@ -708,7 +729,8 @@ void WavefrontPathTracer::DoRender(Image* I, const float* d_t1p, const float* d_
             fused_launches++;
             timer.begin(stream, 2);
             launch_finalize(lc, Q, P, depth - 1, I->device());
-            launch_shade(lc, S, Q, P, depth, I->device());
+            if (media) launch_medium_stage(lc, S, Q, P, V, depth, I->device());
+            launch_shade(lc, S, Q, P, depth, I->device(), media ? &V : nullptr);
             timer.end(stream);
             continue;
         }
@@ -720,7 +742,8 @@ void WavefrontPathTracer::DoRender(Image* I, const float* d_t1p, const float* d_
         if (depth > 1 && direct) shadow_pass(depth - 1);
         timer.begin(stream, 2);
         if (depth > 1 && direct) launch_finalize(lc, Q, P, depth - 1, I->device());
-        launch_shade(lc, S, Q, P, depth, I->device());
+        if (media) launch_medium_stage(lc, S, Q, P, V, depth, I->device());   // the medium half of PathTrace for this depth's vertices: Q.hit is written, the previous depth's shadow rays are resolved
+        launch_shade(lc, S, Q, P, depth, I->device(), media ? &V : nullptr);
         timer.end(stream);
     }
     if (direct) {

@@ -737,7 +737,9 @@ typedef struct ctl_tracer ctl_tracer;
 int ctl_tracer_create(const char* plugin, ctl_tracer** out);
 void ctl_tracer_destroy(ctl_tracer* t);
 /* TracerParameterCollection (Kernel/TracerSettings.h:221-350): keys Direct(bool), MaxPathLength(int>=1),
- * RRStartDepth(int>=1) (WavefrontPathTracer.h:29-39). Out-of-interval values -> CTL_ERR_INVALID. */
+ * RRStartDepth(int>=1) (WavefrontPathTracer.h:29-39). Out-of-interval values -> CTL_ERR_INVALID.
+ * Build-specific, WavefrontPathTracer: ParticipatingMedia(bool, default 0) — 1: the plugin renders scenes with participating media (PathTrace's rules; refused together
+ * with PathSemantics = Wavefront); 0: it answers CTL_ERR_UNSUPPORTED for such a scene, at ctl_tracer_initialize_scene and when a pass starts. */
 int ctl_tracer_set_param_bool(ctl_tracer* t, const char* key, int value);
 int ctl_tracer_set_param_int(ctl_tracer* t, const char* key, int value);
 int ctl_tracer_get_param_int(ctl_tracer* t, const char* key, int* value_out);   /* bool, int and enum (its index) parameters */
