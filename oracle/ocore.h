@@ -1440,7 +1440,10 @@ inline void getBsdfSample(const Scene& S, const Hit& h, V3 rayO, V3 rayD, BRec& 
 }
 
 // --------------------------------------------------------------------------- direct lighting (Kernel/TraceAlgorithms.cu:44-101)
-inline Spec estimateDirect(const Scene& S, BRec bRec, const ctl_material& mat, const ctl_light* light, float light_pdf, unsigned flags, Sampler& rng, uint64_t* rays) {
+// EstimateDirect's `attenuated` factor (TraceAlgorithms.cu:22-31, 66-67) as a hook: the oracle has no media, a caller that has (tests/volume_ref.py) supplies Transmittance(Ray(p, d), tmin, tmax)
+typedef void (*TransmittanceHook)(const float p[3], const float d[3], float tmin, float tmax, float out[3], void* user);
+inline Spec estimateDirect(const Scene& S, BRec bRec, const ctl_material& mat, const ctl_light* light, float light_pdf, unsigned flags, Sampler& rng, uint64_t* rays,
+                           TransmittanceHook transmittance = nullptr, void* user = nullptr) {
     DirectRec dRec(bRec.dg.P, bRec.dg.sys.n);
     Spec value = lightSampleDirect(S, *light, dRec, rng.randomFloat2());
     Spec retVal(0.0f);
@@ -1458,18 +1461,23 @@ inline Spec estimateDirect(const Scene& S, BRec bRec, const ctl_material& mat, c
                     weight = powerHeuristic(1, directPdf, 1, bsdfPdf_);
                 }
                 retVal = value * bsdfVal * weight;
+                if (transmittance) {   // retVal *= Transmittance(Ray(dRec.ref, dRec.d), 0, dRec.dist), before the caller's division by the light's pdf
+                    const float p[3] = { dRec.ref.x, dRec.ref.y, dRec.ref.z }, d[3] = { dRec.d.x, dRec.d.y, dRec.d.z }; float T[3] = { 1.0f, 1.0f, 1.0f };
+                    transmittance(p, d, 0.0f, dRec.dist, T, user);
+                    retVal = retVal * Spec(T[0], T[1], T[2]);
+                }
             }
         }
     }
     return retVal;
 }
-inline Spec uniformSampleOneLight(const Scene& S, const BRec& bRec, const ctl_material& mat, Sampler& rng, uint64_t* rays) {
+inline Spec uniformSampleOneLight(const Scene& S, const BRec& bRec, const ctl_material& mat, Sampler& rng, uint64_t* rays, TransmittanceHook transmittance = nullptr, void* user = nullptr) {
     if (!S.d.num_lights) return Spec(0.0f);
     V2 sample = rng.randomFloat2();
     float pdf;
     const ctl_light* light = sampleEmitter(S, pdf, sample);
     if (light == nullptr) return Spec(0.0f);
-    return sdiv(estimateDirect(S, bRec, mat, light, pdf, EAll & ~EDelta, rng, rays), pdf);
+    return sdiv(estimateDirect(S, bRec, mat, light, pdf, EAll & ~EDelta, rng, rays, transmittance, user), pdf);
 }
 
 // --------------------------------------------------------------------------- PathTrace<DIRECT> (Integrators/PathTracer.cu:10-113), no volumes
@@ -1512,70 +1520,87 @@ inline std::vector<float>*& pathLog() { static thread_local std::vector<float>* 
 // (orc_set_zero_stop_image), so that a test can hold the kernels' frame to `oracle frame + side image` pixel by pixel instead of masking the pixels whose weights differ.
 struct ZeroStop { bool have = false; bool pending = false; Spec cl; };
 inline ZeroStop& zeroStop() { static thread_local ZeroStop z; return z; }
-inline Spec pathTrace(const Scene& S, bool DIRECT, V3 ro, V3 rd, Sampler& rnd, int maxPathLength, int rrStartDepth, uint64_t* rays, const RayDiff* diff = nullptr, bool omitLastNEE = false) {
-    Spec cl(0.0f), cf(1.0f);
-    int depth = 0; bool specularBounce = false;
-    BRec bRec; Hit r2; r2.init();
-    float brdf_scattering_pdf = 0; V3 last_nor;
-    zeroStop() = ZeroStop();
-    while (depth++ < maxPathLength) {
-        r2 = traceRayClosest(S, ro, rd);
-        if (rays) (*rays)++;
-        const V3 log_o = ro, log_d = rd;
-        if (r2.hasHit()) {
-            getBsdfSample(S, r2, ro, rd, bRec);
-            if (depth == 1 && diff && S.pyramids) { bRec.dg.pyramids = S.pyramids; computePartials(bRec.dg, diff->ox, diff->dx, diff->oy, diff->dy); }
-            const ctl_material& mat = hitMat(S, r2);
-            uint32_t li = hitLightIndex(S, r2);
-            if (li != UINT32_MAX) {
-                float misWeight = 1.0f;
-                if (!DIRECT || depth == 1 || specularBounce) misWeight = 1.0f;
-                else {
-                    DirectRec dRec(ro, last_nor);   // DirectSamplingRecFromRay (TraceAlgorithms.cu:33-42)
-                    dRec.p = bRec.dg.P; dRec.n = bRec.dg.n; dRec.d = rd; dRec.dist = r2.dist; dRec.measure = ESolidAngle;
-                    const ctl_light* light = S.d.lights + li;
-                    float direct_pdf = lightPdfDirect(S, *light, dRec) * pdfEmitter(S, light);
-                    misWeight = powerHeuristic(1, brdf_scattering_pdf, 1, direct_pdf);
-                }
-                cl = cl + misWeight * cf * lightEval(S, S.d.lights[li], bRec.dg.P, bRec.dg.sys, -rd);
-            }
-            Spec f = bsdfSample(mat, bRec, brdf_scattering_pdf, rnd.randomFloat2());
-            last_nor = bRec.dg.sys.n;
-            // omitLastNEE (a test's what-if, not the reference): PathTrace without the next-event estimation of its last vertex — the term pathIterateKernel never takes
-            if (DIRECT && bsdfHasComponent(mat, ESmooth) && !(omitLastNEE && depth == maxPathLength)) cl = cl + cf * uniformSampleOneLight(S, bRec, mat, rnd, rays);
-            specularBounce = (bRec.sampledType & EDelta) != 0;
-            cf = cf * f;
-            if (!zeroStop().have && isZero(cf)) { zeroStop().have = true; zeroStop().cl = cl; }   // where the kernels end the path (next-event estimation of this vertex included, as theirs is)
-            ro = bRec.dg.P; rd = bRec.dg.sys.toWorld(bRec.wo);   // BSDFSamplingRecord::getOutgoing (Samples.cu)
-            if (pathLog()) {
-                const float rec[26] = { (float)depth, (float)r2.tri, (float)r2.node, (float)(&mat - S.d.materials), (float)mat.bsdf_type, li == UINT32_MAX ? -1.0f : (float)li, f.x, f.y, f.z,
-                                        brdf_scattering_pdf, (float)bRec.sampledType, cf.x, cf.y, cf.z, cl.x, cl.y, cl.z, r2.dist, r2.u, r2.v, log_o.x, log_o.y, log_o.z, log_d.x, log_d.y, log_d.z };
-                pathLog()->insert(pathLog()->end(), rec, rec + 26);
-            }
+// What PathTrace keeps from one vertex to the next: the radiance and throughput, the ray, the last surface's sampling pdf, shading normal and delta flag, and the BSDF record
+// (declared outside the loop, PathTracer.cu:16: a failed sample leaves the previous wo in it).  info: what the last pathVertex call met — the hit's light or -1, and whether
+// its emission took an MIS weight (the one place that reads last_nor)
+struct PathState {
+    Spec cl = Spec(0.0f), cf = Spec(1.0f); V3 ro, rd; float brdf_scattering_pdf = 0; V3 last_nor; bool specularBounce = false; BRec bRec;
+    int light_index = -1; bool mis_taken = false;
+};
+// One surface vertex of PathTrace<DIRECT> (PathTracer.cu:57-85 without the medium's rescale of :58): the body of `else if (r2.hasHit())`.  transmittance: EstimateDirect's
+// attenuation (null: none).  nee = false: a test's what-if, the vertex without its next-event estimation
+inline void pathVertex(const Scene& S, bool DIRECT, PathState& st, const Hit& r2, int depth, Sampler& rnd, uint64_t* rays, const RayDiff* diff = nullptr, bool nee = true,
+                       TransmittanceHook transmittance = nullptr, void* user = nullptr) {
+    BRec& bRec = st.bRec;
+    const V3 ro = st.ro, rd = st.rd;
+    getBsdfSample(S, r2, ro, rd, bRec);
+    if (depth == 1 && diff && S.pyramids) { bRec.dg.pyramids = S.pyramids; computePartials(bRec.dg, diff->ox, diff->dx, diff->oy, diff->dy); }
+    const ctl_material& mat = hitMat(S, r2);
+    uint32_t li = hitLightIndex(S, r2);
+    st.light_index = li == UINT32_MAX ? -1 : (int)li; st.mis_taken = false;
+    if (li != UINT32_MAX) {
+        float misWeight = 1.0f;
+        if (!DIRECT || depth == 1 || st.specularBounce) misWeight = 1.0f;
+        else {
+            DirectRec dRec(ro, st.last_nor);   // DirectSamplingRecFromRay (TraceAlgorithms.cu:33-42)
+            dRec.p = bRec.dg.P; dRec.n = bRec.dg.n; dRec.d = rd; dRec.dist = r2.dist; dRec.measure = ESolidAngle;
+            const ctl_light* light = S.d.lights + li;
+            float direct_pdf = lightPdfDirect(S, *light, dRec) * pdfEmitter(S, light);
+            misWeight = powerHeuristic(1, st.brdf_scattering_pdf, 1, direct_pdf);
+            st.mis_taken = true;
         }
-        if (!r2.hasHit()) break;
-        if (depth > rrStartDepth && !specularBounce) {
-            if (rnd.randomFloat() >= vmax(cf)) break;
-            cf = sdiv(cf, vmax(cf));
-        }
+        st.cl = st.cl + misWeight * st.cf * lightEval(S, S.d.lights[li], bRec.dg.P, bRec.dg.sys, -rd);
     }
-    if (!r2.hasHit() && S.d.env_map_index != 0xffffffffu) {   // PathTracer.cu:99-111; EvalEnvironment == 0 without an environment map
+    Spec f = bsdfSample(mat, bRec, st.brdf_scattering_pdf, rnd.randomFloat2());
+    st.last_nor = bRec.dg.sys.n;
+    if (DIRECT && bsdfHasComponent(mat, ESmooth) && nee) st.cl = st.cl + st.cf * uniformSampleOneLight(S, bRec, mat, rnd, rays, transmittance, user);
+    st.specularBounce = (bRec.sampledType & EDelta) != 0;
+    st.cf = st.cf * f;
+    if (!zeroStop().have && isZero(st.cf)) { zeroStop().have = true; zeroStop().cl = st.cl; }   // where the kernels end the path (next-event estimation of this vertex included, as theirs is)
+    st.ro = bRec.dg.P; st.rd = bRec.dg.sys.toWorld(bRec.wo);   // BSDFSamplingRecord::getOutgoing (Samples.cu)
+    if (pathLog()) {
+        const float rec[26] = { (float)depth, (float)r2.tri, (float)r2.node, (float)(&mat - S.d.materials), (float)mat.bsdf_type, li == UINT32_MAX ? -1.0f : (float)li, f.x, f.y, f.z,
+                                st.brdf_scattering_pdf, (float)bRec.sampledType, st.cf.x, st.cf.y, st.cf.z, st.cl.x, st.cl.y, st.cl.z, r2.dist, r2.u, r2.v, ro.x, ro.y, ro.z, rd.x, rd.y, rd.z };
+        pathLog()->insert(pathLog()->end(), rec, rec + 26);
+    }
+}
+// The term after the loop for a path whose last ray met nothing (PathTracer.cu:98-111).  depth: PathTrace's counter as the loop left it; dist: the last ray's m_fDist (FLT_MAX)
+inline void pathEscape(const Scene& S, bool DIRECT, PathState& st, int depth, float dist) {
+    if (S.d.env_map_index != 0xffffffffu) {   // PathTracer.cu:99-111; EvalEnvironment == 0 without an environment map
         const ctl_light* light = S.d.lights + S.d.env_map_index;
         float misWeight = 1.0f;
-        if (!DIRECT || depth == 1 || specularBounce) misWeight = 1.0f;
+        if (!DIRECT || depth == 1 || st.specularBounce) misWeight = 1.0f;
         else {
-            DirectRec dRec(ro, last_nor);   // DirectSamplingRecFromRay(r, dist, last_nor, Vec3f(), NormalizedT<Vec3f>()), measure ESolidAngle
-            dRec.p = V3(0.0f); dRec.n = V3(0.0f); dRec.d = rd; dRec.dist = r2.dist; dRec.measure = ESolidAngle;
+            DirectRec dRec(st.ro, st.last_nor);   // DirectSamplingRecFromRay(r, dist, last_nor, Vec3f(), NormalizedT<Vec3f>()), measure ESolidAngle
+            dRec.p = V3(0.0f); dRec.n = V3(0.0f); dRec.d = st.rd; dRec.dist = dist; dRec.measure = ESolidAngle;
             float direct_pdf = lightPdfDirect(S, *light, dRec) * pdfEmitter(S, light);
-            misWeight = powerHeuristic(1, brdf_scattering_pdf, 1, direct_pdf);
+            misWeight = powerHeuristic(1, st.brdf_scattering_pdf, 1, direct_pdf);
         }
-        cl = cl + misWeight * cf * envEval(S, *light, rd);
-    } else if (!r2.hasHit()) {
+        st.cl = st.cl + misWeight * st.cf * envEval(S, *light, st.rd);
+    } else {
         // without an environment map the line is still executed: cl += 1 * cf * Spectrum(0) (EvalEnvironment, KernelDynamicScene.cu:54-60) — nothing for a finite throughput, a NaN
         // for a NaN / infinite one: the escaped path of a BSDF evaluated outside its domain poisons its sample, and Image::AddSample drops it (found reading for the round-5 fuzz)
-        cl = cl + 1.0f * cf * Spec(0.0f);
+        st.cl = st.cl + 1.0f * st.cf * Spec(0.0f);
     }
-    return cl;
+}
+inline Spec pathTrace(const Scene& S, bool DIRECT, V3 ro, V3 rd, Sampler& rnd, int maxPathLength, int rrStartDepth, uint64_t* rays, const RayDiff* diff = nullptr, bool omitLastNEE = false) {
+    PathState st; st.ro = ro; st.rd = rd;
+    int depth = 0;
+    Hit r2; r2.init();
+    zeroStop() = ZeroStop();
+    while (depth++ < maxPathLength) {
+        r2 = traceRayClosest(S, st.ro, st.rd);
+        if (rays) (*rays)++;
+        // omitLastNEE (a test's what-if, not the reference): PathTrace without the next-event estimation of its last vertex — the term pathIterateKernel never takes
+        if (r2.hasHit()) pathVertex(S, DIRECT, st, r2, depth, rnd, rays, diff, !(omitLastNEE && depth == maxPathLength));
+        if (!r2.hasHit()) break;
+        if (depth > rrStartDepth && !st.specularBounce) {
+            if (rnd.randomFloat() >= vmax(st.cf)) break;
+            st.cf = sdiv(st.cf, vmax(st.cf));
+        }
+    }
+    if (!r2.hasHit()) pathEscape(S, DIRECT, st, depth, r2.dist);
+    return st.cl;
 }
 
 // KernelDynamicScene::sampleEmitterDirect (Engine/KernelDynamicScene.cu:98-117): the emitter choice re-uses (and re-scales) the sample's first coordinate.

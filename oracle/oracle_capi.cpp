@@ -633,4 +633,65 @@ void orc_env_eval_differential_n(const ctl_scene_desc* desc, uint32_t n, const f
     }
 }
 
+// ---- PathTrace<DIRECT> vertex by vertex (ocore.h pathVertex / pathEscape, the two functions pathTrace itself is made of): the surface half of tests/volume_ref.path_trace,
+// whose medium half — Volumes.cu, which this oracle does not have — stays in Python.  One thread: the transmittance hook runs on the calling thread.
+// The state a path carries from one vertex to the next.  The named fields are read and written by the caller (ctypes mirror: tests/volume_ref.PathState); the BSDF record behind
+// them is PathTrace's bRec, which lives across bounces (a failed sample leaves the previous wo) and is opaque to the caller: allocate orc_path_state_size() bytes.
+struct orc_path_state {
+    float cl[3], cf[3], ro[3], rd[3], brdf_scattering_pdf, last_nor[3];
+    int32_t specular_bounce;
+    uint32_t d1, d2;                  // the sampler's two dimension counters (Sampler::d1 / d2)
+    int32_t light_index, mis_taken;   // out, of the last orc_path_vertex: the hit's light or -1; whether its emission took an MIS weight (the read of last_nor)
+    BRec bRec;
+};
+struct PathCtx { Scene S; std::vector<MipPyramid> pyramids; };
+uint32_t orc_path_state_size() { return (uint32_t)sizeof(orc_path_state); }
+// a fresh path: cl = 0, cf = 1, no specular bounce, pdf 0, last_nor 0 (the reference leaves it uninitialised), counters 0, an empty record; ro / rd are the caller's
+void orc_path_state_init(orc_path_state* st) {
+    new (st) orc_path_state();
+    std::memset(st->cl, 0, sizeof(float) * 16); st->cf[0] = st->cf[1] = st->cf[2] = 1.0f;
+    st->specular_bounce = 0; st->d1 = st->d2 = 0; st->light_index = -1; st->mis_taken = 0;
+    st->bRec.eta = 1.0f; st->bRec.typeMask = EAll; st->bRec.sampledType = 0;
+    zeroStop() = ZeroStop();
+}
+// flags: orc_render's bits 0 (half::ToFloat's host branch), 1 (alpha test) and 2 (first-hit ray differentials: the image pyramids are built here, once); flat: as orc_set_flat_bvh,
+// for the shadow rays the vertex traces.  The description and the tree must outlive the context.
+void* orc_path_ctx_create(const ctl_scene_desc* desc, int flags, const ctl_flat_bvh_desc* flat) {
+    PathCtx* c = new PathCtx();
+    c->S.d = *desc; c->S.half_host_quirk = (flags & 1) != 0; c->S.alpha_test = (flags & 2) != 0 && sceneHasAlphaMaps(*desc); c->S.flat = flat;
+    if (flags & 4) { c->pyramids.resize(desc->n_images); for (uint32_t i = 0; i < desc->n_images; i++) c->pyramids[i].build(desc->images[i]); c->S.pyramids = c->pyramids.data(); }
+    return c;
+}
+void orc_path_ctx_destroy(void* ctx) { delete (PathCtx*)ctx; }
+static inline PathState loadState(const orc_path_state& s) {
+    PathState st; st.cl = Spec(s.cl[0], s.cl[1], s.cl[2]); st.cf = Spec(s.cf[0], s.cf[1], s.cf[2]); st.ro = V3(s.ro[0], s.ro[1], s.ro[2]); st.rd = V3(s.rd[0], s.rd[1], s.rd[2]);
+    st.brdf_scattering_pdf = s.brdf_scattering_pdf; st.last_nor = V3(s.last_nor[0], s.last_nor[1], s.last_nor[2]); st.specularBounce = s.specular_bounce != 0; st.bRec = s.bRec;
+    return st;
+}
+static inline void storeState(orc_path_state& s, const PathState& st) {
+    put3(s.cl, st.cl); put3(s.cf, st.cf); put3(s.ro, st.ro); put3(s.rd, st.rd); s.brdf_scattering_pdf = st.brdf_scattering_pdf; put3(s.last_nor, st.last_nor);
+    s.specular_bounce = st.specularBounce ? 1 : 0; s.light_index = st.light_index; s.mis_taken = st.mis_taken ? 1 : 0; s.bRec = st.bRec;
+}
+// the surface vertex at `hit` of the ray (st.ro, st.rd), found by the caller: everything PathTrace does between `r2.hasHit()` and the roulette.  t1 / t2 / idx: the sampler
+// (its counters are the state's); diff12: the sensor's x and y differential rays (origin, direction, origin, direction) for depth 1, or NULL; transmittance / user: EstimateDirect's
+// attenuation, or NULL; rays: added to for every shadow ray traced
+void orc_path_vertex(void* ctx, const float* t1, const float* t2, uint32_t idx, orc_path_state* s, const ctl_hit* hit, int depth, int direct, const float* diff12,
+                     TransmittanceHook transmittance, void* user, uint64_t* rays) {
+    const PathCtx& c = *(const PathCtx*)ctx;
+    Sampler rnd(t1, t2, idx); rnd.d1 = s->d1; rnd.d2 = s->d2;
+    Hit h; h.dist = hit->dist; h.u = hit->u; h.v = hit->v; h.tri = (uint32_t)hit->tri_idx; h.node = (uint32_t)hit->node_idx;
+    RayDiff diff;
+    if (diff12) { diff.ox = V3(diff12[0], diff12[1], diff12[2]); diff.dx = V3(diff12[3], diff12[4], diff12[5]); diff.oy = V3(diff12[6], diff12[7], diff12[8]); diff.dy = V3(diff12[9], diff12[10], diff12[11]); }
+    PathState st = loadState(*s);
+    pathVertex(c.S, direct != 0, st, h, depth, rnd, rays, diff12 ? &diff : nullptr, true, transmittance, user);
+    storeState(*s, st); s->d1 = rnd.d1; s->d2 = rnd.d2;
+}
+// the term after PathTrace's loop when its last ray met nothing: the environment map's radiance with its MIS weight, or cf * 0.  depth: the loop's counter as it was left
+void orc_path_escape(void* ctx, orc_path_state* s, int depth, int direct, float dist) {
+    const PathCtx& c = *(const PathCtx*)ctx;
+    PathState st = loadState(*s);
+    pathEscape(c.S, direct != 0, st, depth, dist);
+    storeState(*s, st);
+}
+
 } // extern "C"

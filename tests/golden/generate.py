@@ -1016,14 +1016,18 @@ MEDIA_PASSES, MEDIA_MAX_PATH_LENGTH, MEDIA_RR_START = 2, 6, 3
 # A case's passes use the table sets first, first + 1 of a fresh SequenceGenerator.  `first` is 0 unless some pixel of the case then takes an emission MIS weight with
 # PathTrace's uninitialised last_nor (a path that reaches the emitter, Direct on, after medium vertices only: Integrators/PathTracer.cu:21,71); then it is the first
 # window in which no pixel does — found with the restatement's counter (volume_ref.path_trace, undefined[..., 2]) and asserted again whenever the fixture is recorded.
-MEDIA_FIRST_PASS = {"half_box_direct": 1, "isotropic_direct": 2, "two_regions_direct": 1, "isotropic_50x33": 2}
+MEDIA_FIRST_PASS = {"half_box_direct": 1, "isotropic_direct": 2, "two_regions_direct": 1, "isotropic_50x33": 2,
+                    # the Direct-on *_pair_* cases: the first window that media_pair_windows() below finds among first = 0 .. 7.  fog_glass_pair_direct has none:
+                    # 3, 2, 2, 2, 2, 3, 3, 1 pixels take an emission MIS weight with the unwritten last_nor for first = 0 .. 7 (MEDIA_PAIR_LEFT_OUT)
+                    "cornell_materials_pair_direct": 0, "env_pair_direct": 0, "env_lights_pair_direct": 0}
 
 
 def pathtrace_media_cases():
     """the media fixture's cases: (key, scene builder, width, height, DIRECT, first table set).  2 passes, MaxPathLength 6, RRStartDepth 3 (roulette runs after a medium vertex, with the
     stale specularBounce).  The four media of tests/test_gpu_volume.py at 48 x 32 with Direct on and off; `two_regions`: the whole box isotropic plus its lower half
     HG -0.5, built with CreateVolume on cornell_box — the masks 1 and 3 occur (both index region 1, as written) and p weights two phase functions; one 50 x 33 frame,
-    neither dimension a multiple of the wave or tile size; `clear_*`: the same scene without media, what the sanity test holds the media frames against."""
+    neither dimension a multiple of the wave or tile size; `*_pair_*`: the scenes of MEDIA_PAIR_SCENES under that region pair (media_pair_scene), Direct off always
+    and Direct on where a table window qualifies; `clear_*`: the same scene without media, what the sanity test holds the media frames against."""
     sys.path.insert(0, os.path.dirname(HERE))
     from cudatracerlib_amd import api, scenes
     from test_gpu_volume import MEDIA
@@ -1041,14 +1045,53 @@ def pathtrace_media_cases():
         return sc
     cases = [("%s_%s" % (name, "direct" if direct else "nodirect"), fog(name, 48, 32), 48, 32, direct) for name in sorted(MEDIA) for direct in (True, False)]
     cases += [("two_regions_direct", two_regions, 48, 32, True), ("isotropic_50x33", fog("isotropic", 50, 33), 50, 33, True)]
+    cases += [("%s_pair_%s" % (name, "direct" if direct else "nodirect"), (lambda name=name: media_pair_scene(name, True)), 48, 32, direct)
+              for name in sorted(MEDIA_PAIR_SCENES) for direct in (False, True) if ("%s_pair_%s" % (name, "direct" if direct else "nodirect")) not in MEDIA_PAIR_LEFT_OUT]
     cases = [c + (MEDIA_FIRST_PASS.get(c[0], 0),) for c in cases]
-    clear = sorted({(clear_case_of(c), c[2], c[3], c[4], c[5]) for c in cases})
-    return cases + [(key, (lambda w=w, h=h: scenes.cornell_box(w, h)), w, h, direct, first) for key, w, h, direct, first in clear]
+    box = [c for c in cases if not c[0].split("_pair_")[0] in MEDIA_PAIR_SCENES]
+    clear = sorted({(clear_case_of(c), c[2], c[3], c[4], c[5]) for c in box})
+    out = cases + [(key, (lambda w=w, h=h: scenes.cornell_box(w, h)), w, h, direct, first) for key, w, h, direct, first in clear]
+    pair_clear = sorted({(clear_case_of(c), c[0].split("_pair_")[0], c[4], c[5]) for c in cases if c not in box})
+    return out + [(key, (lambda name=name: media_pair_scene(name, False)), 48, 32, direct, first) for key, name, direct, first in pair_clear]
+
+
+# The surface features the Cornell box does not have, each under the region pair of `two_regions` (the scene box isotropic, its lower half HG -0.5), Direct off and on:
+# an environment map seen by a camera that stands outside part of the medium; point, spot and distant lights; the extra BSDF models; a glass sphere.
+MEDIA_PAIR_SCENES = ("cornell_materials", "env", "env_lights", "fog_glass")
+# The variants that cannot be recorded, because the reference's own frame of them depends on memory nothing has written (media_pair_windows() prints the counts):
+#  * fog_glass_pair_direct: in every table window first = 0 .. 7, 1 to 3 pixels take an emission MIS weight with PathTrace's uninitialised last_nor.
+#  * env_pair_nodirect, env_lights_pair_nodirect: the camera stands outside the medium, and in 466 of the 1536 pixels of the first pass KernelAggregateVolume::Sample
+#    finds no region at a medium vertex, so that PathTrace walks on, with a throughput of exactly zero, along a pRec.wo nothing has set (PathTracer.cu:50-53).  In the
+#    Cornell box whatever that ray meets is finite and multiplied by zero; here the ray escapes, EvalEnvironment of a garbage direction is NaN, 0 * NaN is NaN, and
+#    Image::AddSample drops the sample: the reference's build of this recipe drops 320 of the 3072 samples (all of them in such pixels), the product — which ends a
+#    zero-throughput path — none.  With Direct on the same reads happen, but in the recorded build what the slot holds is finite (presumably the light sample's direction of
+#    a few lines before, :39): the frame equals the restatement's in every pixel, and the Direct-on variants are recorded.  That is a property of this build, which the
+#    fixture fixes; it is not defined behaviour.
+MEDIA_PAIR_LEFT_OUT = ("fog_glass_pair_direct", "env_pair_nodirect", "env_lights_pair_nodirect")
+
+
+def media_pair_scene(name, media):
+    """one scene of MEDIA_PAIR_SCENES at 48 x 32, with (media) or without the region pair.  The pair's coefficients are two_regions' per unit of a 550-unit box, scaled
+    to this scene's box: the same optical depths across it."""
+    from cudatracerlib_amd import api, scenes
+    sc = {"env": lambda: scenes.env_scene(48, 32), "env_lights": lambda: scenes.env_scene(48, 32, extra_lights=True),
+          "cornell_materials": lambda: scenes.cornell_box(48, 32, extra_materials=True),
+          "fog_glass": lambda: scenes.fog_box(48, 32, glass_sphere=True) if media else scenes.cornell_box(48, 32, glass_sphere=True)}[name]()   # (fog_box's own region stays: three regions)
+    if media:
+        lo = np.array(sc.desc.box_min, np.float32); hi = np.array(sc.desc.box_max, np.float32)
+        k = 550.0 / float((hi - lo).max())
+        sc.CreateVolume(api.homogeneous_volume(api.box_to_volume_matrix(lo, hi), 0.0005 * k, 0.002 * k, api.phase_isotropic()))
+        sc.CreateVolume(api.homogeneous_volume(api.box_to_volume_matrix(lo, (lo + (hi - lo) * np.array([1, 0.5, 1], np.float32)).astype(np.float32)), 0.0004 * k,
+                                               (0.003 * k, 0.002 * k, 0.0012 * k), api.phase_hg(-0.5)))
+        sc.UpdateScene()
+    return sc
 
 
 def clear_case_of(case):
-    """the key of the case without media that a media case is held against: the same frame size, Direct setting and tables"""
-    return "clear_%dx%d_%s_%d" % (case[2], case[3], "direct" if case[4] else "nodirect", case[5])
+    """the key of the case without media that a media case is held against: the same scene, frame size, Direct setting and tables"""
+    name = case[0].split("_pair_")[0]
+    scene = name + "_" if name in MEDIA_PAIR_SCENES and "_pair_" in case[0] else ""
+    return "clear_%s%dx%d_%s_%d" % (scene, case[2], case[3], "direct" if case[4] else "nodirect", case[5])
 
 
 def pathtrace_media_tables(first):
@@ -1073,7 +1116,11 @@ def gen_pathtrace_media(r):
     cases of pathtrace_media_cases(): rgb sums, weightSum, rays per pixel, input digest.  Before a case goes to the reference the restatement
     (volume_ref.path_trace, glibc oracle, the reference's rules) renders it and counts, per pixel, the places where the reference's behaviour is undefined — a read
     of a medium record nothing has written, a sampleVolume index past the table, an emission MIS weight taken with PathTrace's uninitialised last_nor; a case is recorded only when all three counts are zero in EVERY pixel.  (A path whose throughput is exactly zero walks on in the
-    reference along a direction nothing has set: that changes no radiance, only the recorded ray counts of such pixels — tests/test_oracle_volume.py says how they are held.)"""
+    reference along a direction nothing has set: that changes no radiance, only the recorded ray counts of such pixels — tests/test_oracle_volume.py says how they are held.)
+    The escaped path's environment term takes an MIS weight too, after medium vertices only as well, but it does NOT read last_nor: InfiniteLight::pdfDirect
+    (SceneTypes/Light.cu:367-377) looks at dRec.d, and at dRec.n / dRec.dist for the area measure only, never at dRec.refN — unlike DiffuseLight::pdfDirect (:136-152),
+    whose first test is dot(dRec.d, dRec.refN).  So the third count covers the emission term of a surface hit alone, and brdf_scattering_pdf, the weight's other input, is
+    initialised (PathTracer.cu:20)."""
     sys.path.insert(0, os.path.dirname(HERE))
     import volume_ref
     r.ref_pathtrace_render.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
@@ -1089,6 +1136,8 @@ def gen_pathtrace_media(r):
             volume_ref.path_trace(orc, d, media_volumes(d), w, h, tables, direct=direct, max_path_length=MEDIA_MAX_PATH_LENGTH, rr_start=MEDIA_RR_START, reference_rules=True, undefined=undefined)
             assert not undefined[..., :3].any(), "%s: %d pixels reach undefined behaviour of the reference (unwritten record reads %d, indices past the table %d, unwritten last_nor reads %d): choose another case or window" % (
                 key, undefined[..., :3].any(axis=2).sum(), undefined[..., 0].sum(), undefined[..., 1].sum(), undefined[..., 2].sum())
+            # under an environment map the fourth count changes the radiance too (0 * EvalEnvironment(garbage) = NaN, MEDIA_PAIR_LEFT_OUT): no such case with Direct off
+            assert direct or d.env_map_index == 0xffffffff or not undefined[..., 3].any(), "%s: %d medium vertices without a region under an environment map" % (key, undefined[..., 3].sum())
         px = np.zeros((h, w, 7), np.float32); rays = np.zeros((h, w), np.uint32)
         assert r.ref_pathtrace_render(C.addressof(d), w, h, MEDIA_PASSES, t1.ctypes.data, t2.ctypes.data, int(direct), 0, MEDIA_MAX_PATH_LENGTH, MEDIA_RR_START, 0, px.ctypes.data, rays.ctypes.data) == 0, key
         assert (px[..., 3:6] == 0).all() and rays.max() < 65536 and px[..., 6].sum() > 0.9 * w * h * MEDIA_PASSES and px[..., :3].mean() > 1e-3, key
@@ -1098,8 +1147,31 @@ def gen_pathtrace_media(r):
     assert os.path.getsize(os.path.join(HERE, "pathtrace_media.npz")) < os.path.getsize(os.path.join(HERE, "pathtrace.npz"))
 
 
+def media_pair_windows():
+    """how MEDIA_FIRST_PASS's entries for the *_pair_* cases were found: for every scene of MEDIA_PAIR_SCENES, Direct off at window 0 and Direct on at the windows
+    first = 0 .. 7, the restatement's counts of pixels / places where the reference's PathTrace reads what nothing wrote (volume_ref.path_trace, undefined[..., :3]).
+    A Direct-on variant is recorded with its first window whose three counts are zero; one that has none is left out and named in DESIGN.md §11."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import volume_ref
+    orc = oracle.Oracle()
+    for name in sorted(MEDIA_PAIR_SCENES):
+        sc = media_pair_scene(name, True); d = sc.desc
+        for direct, windows in ((False, (0,)), (True, range(8))):
+            for first in windows:
+                undefined = np.zeros((32, 48, 6), np.int32)
+                volume_ref.path_trace(orc, d, media_volumes(d), 48, 32, pathtrace_media_tables(first), direct=direct, max_path_length=MEDIA_MAX_PATH_LENGTH, rr_start=MEDIA_RR_START,
+                                      reference_rules=True, undefined=undefined)
+                print("%s_pair_%s first %d: pixels %d; unwritten record reads %d, indices past the table %d, unwritten last_nor reads %d; medium vertices without a region %d in %d pixels" % (
+                    name, "direct" if direct else "nodirect", first, undefined[..., :3].any(axis=2).sum(), undefined[..., 0].sum(), undefined[..., 1].sum(), undefined[..., 2].sum(),
+                    undefined[..., 3].sum(), (undefined[..., 3] > 0).sum()), flush=True)
+                if direct and not undefined[..., :3].any():
+                    break
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["volumes"]:         # only this fixture
+    if sys.argv[1:] == ["pathtrace_media_windows"]:   # prints; records nothing
+        media_pair_windows()
+    elif sys.argv[1:] == ["volumes"]:         # only this fixture
         gen_volumes(oracle.load_ref())
     elif sys.argv[1:] == ["pathtrace_media"]:   # only this fixture
         gen_pathtrace_media(oracle.load_ref())

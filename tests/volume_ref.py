@@ -5,9 +5,11 @@ exp / log / sin / cos / pow come from the shared-math oracle (orc_math_eval), sq
 library's to the bit.
 
 Volumes(orc, list of ctl_volume) offers every function ctl_volume_eval offers; eval_rows(V, what, queries) lays the results out as ctl_volume_eval does.
-path_trace(orc, desc, w, h, tables, ...) is pathKernel2 + PathTrace<DIRECT> (Integrators/PathTracer.cu:10-113, 182-194) with media, per pixel, from the oracle's exports
-(sampler draws, sensor rays, traversal of the product's flattened tree, fillDG, BSDF sample / eval, emitter sampling, light pdf / eval, environment), in the manner of
-prim_tracer_ref.shaded_modes.  Its scenes hold diffuse, dielectric and conductor materials with constant textures, so first-hit partials change nothing.
+path_trace(orc, desc, w, h, tables, ...) is pathKernel2 + PathTrace<DIRECT> (Integrators/PathTracer.cu:10-113, 182-194) with media, per pixel.  The loop, the medium vertex
+and the roulette are restated here from the oracle's exports (sampler draws, sensor rays, traversal of the product's flattened tree, emitter sampling); the surface
+vertex and the escaped path's environment term are the oracle's own pathVertex / pathEscape (oracle/ocore.h: the two functions its pathTrace is made of, exported as
+orc_path_vertex / orc_path_escape), with this file's Transmittance hooked into EstimateDirect — so any scene the oracle renders can carry media here, with first-hit
+partials where asked.  tests/test_media_fuzz_host.py pins the join: without volumes path_trace is the oracle's render, bit for bit.
 Three things are the product's, not the reference's, and are stated where they stand: a path ends when its throughput is exactly zero (every kernel of the library makes
 that cut), and a medium record or a last_nor nothing has written yet reads as zeros (the reference reads uninitialised memory).
 With the glibc oracle (oracle.Oracle()) instead of the shared-math one, and path_trace's reference_rules, this file is held to the reference's OWN Volumes.cu,
@@ -477,6 +479,18 @@ def _bind(lib):
     lib.orc_light_pdf_direct.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]; lib.orc_light_pdf_direct.restype = C.c_float
     lib.orc_light_eval.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.orc_env_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.orc_sensor_sample_rays.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+    lib.orc_path_state_size.restype = C.c_uint32; lib.orc_path_state_size.argtypes = []
+    lib.orc_path_state_init.argtypes = [C.c_void_p]; lib.orc_path_state_init.restype = None
+    lib.orc_path_ctx_create.argtypes = [C.c_void_p, C.c_int, C.c_void_p]; lib.orc_path_ctx_create.restype = C.c_void_p
+    lib.orc_path_ctx_destroy.argtypes = [C.c_void_p]; lib.orc_path_ctx_destroy.restype = None
+    lib.orc_path_vertex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, TRANSMITTANCE_HOOK, C.c_void_p, C.c_void_p]
+    lib.orc_path_vertex.restype = None
+    lib.orc_path_escape.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float]; lib.orc_path_escape.restype = None
+
+
+# EstimateDirect's attenuation as the oracle's vertex calls it (oracle/ocore.h TransmittanceHook): (p, d, tmin, tmax, out, user)
+TRANSMITTANCE_HOOK = C.CFUNCTYPE(None, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float, C.POINTER(C.c_float), C.c_void_p)
 
 
 def _power_heuristic(f, g):   # MonteCarlo::PowerHeuristic(1, f, 1, g)
@@ -501,76 +515,102 @@ def _add(a, b):
 
 
 class _Path:
-    def __init__(self, orc, desc, volumes, flat):
+    """one path_trace call's scene: the media (Python), the closest-hit and occlusion rays of the loop and of the medium vertex, and the oracle's own surface vertex and
+    escape term (oracle_capi.cpp orc_path_vertex / orc_path_escape — the two functions the oracle's pathTrace is made of) behind one state buffer"""
+    handle = None
+
+    def __init__(self, orc, desc, volumes, flat, half_host_quirk=False, partials=False):
         self.orc, self.lib, self.desc, self.flat = orc, orc.lib, desc, flat
         _bind(self.lib)
         self.V = Volumes(orc, volumes)
-        self.tri_data = np.frombuffer(C.string_at(desc.tri_data, desc.n_tri_data * 32), np.uint32).reshape(-1, 8)
-        self.xforms = np.frombuffer(C.string_at(desc.node_transforms, desc.n_nodes * 64), np.float32).reshape(-1, 16)
-        self.nodes = np.frombuffer(C.string_at(desc.nodes, desc.n_nodes * 24), np.uint32).reshape(-1, 6)
         self.eps = f32(desc.ray_trace_eps)
-        cdf = [f32(desc.light_cdf[i]) for i in range(desc.num_lights)]
-        self.pdf_emitter = {int(desc.light_indices[i]): f32(cdf[i] - (cdf[i - 1] if i else f32(0))) for i in range(desc.num_lights)}
         self.rays = 0
-        self.half_host_quirk = False
+        self.half_host_quirk = half_host_quirk
         self.unwritten_reads = 0; self.unwritten_normal_reads = 0; self.unset_directions = 0; self.zero_walks = 0; self.zero_rays = 0; self.zero_now = False
+        # orc_render's bits: 1 half::ToFloat's host branch, 2 the alpha test (as trace() below), 4 first-hit ray differentials
+        self.handle = self.lib.orc_path_ctx_create(C.addressof(desc), (1 if half_host_quirk else 0) | 2 | (4 if partials else 0), C.addressof(flat) if flat is not None else None)
+        self.buf = C.create_string_buffer(int(self.lib.orc_path_state_size()))
+        # the named fields of orc_path_state: cl, cf, ro, rd, brdf_scattering_pdf, last_nor | specular_bounce, d1, d2, light_index, mis_taken
+        self.sf = np.frombuffer(self.buf, np.float32, 16); self.si = np.frombuffer(self.buf, np.int32, 5, offset=64)
+        self.hits = None; self.shadow = C.c_uint64(0); self.hook_error = None
+        self.hook = TRANSMITTANCE_HOOK(self._transmittance) if self.V.n else C.cast(None, TRANSMITTANCE_HOOK)   # a null hook: the oracle's own EstimateDirect
+
+    def close(self):
+        if self.handle:
+            self.lib.orc_path_ctx_destroy(self.handle); self.handle = None
+
+    __del__ = close   # (a path_trace call that raises)
+
+    def _transmittance(self, p, d, tmin, tmax, out, user):   # Transmittance(Ray(dRec.ref, dRec.d), 0, dRec.dist) for EstimateDirect(attenuated = true)
+        try:
+            T = self.V.transmittance(np.array([p[0], p[1], p[2]], np.float32), np.array([d[0], d[1], d[2]], np.float32), f32(tmin), f32(tmax))
+            out[0], out[1], out[2] = float(T[0]), float(T[1]), float(T[2])
+        except BaseException as e:   # (an exception cannot cross the C frames: it is raised again when the vertex call returns)
+            self.hook_error = e
 
     def trace(self, o, d, tmax=FLT_MAX, any_hit=False):
         r = np.zeros((1, 8), np.float32); r[0, :3] = o; r[0, 3] = self.eps; r[0, 4:7] = d; r[0, 7] = tmax
         self.rays += 1
         if self.zero_now:
             self.zero_rays += 1
-        return self.orc.intersect(self.desc, r, any_hit=any_hit, alpha_test=True, threads=1, flat=self.flat)[0]
+        self.hits = self.orc.intersect(self.desc, r, any_hit=any_hit, alpha_test=True, threads=1, flat=self.flat, half_host_quirk=self.half_host_quirk)
+        return self.hits[0]
 
-    def surface(self, o, d, hd):
-        """TraceResult::getBsdfSample: fillDG, wi, the two-sided flip (no normal maps in these scenes)"""
-        dg = np.zeros(21, np.float32)
-        tri, node = int(hd["tri_idx"]), int(hd["node_idx"])
-        t, u, v = f32(hd["dist"]), f32(hd["u"]), f32(hd["v"])
-        T = np.ascontiguousarray(self.tri_data[tri]); M = np.ascontiguousarray(self.xforms[node])
-        self.lib.orc_triangle_fill_dg(T.ctypes.data, M.ctypes.data, float(u), float(v), 1 if self.half_host_quirk else 0, dg.ctypes.data)
-        P = np.array([f32(o[k] + f32(t * d[k])) for k in range(3)], np.float32)
-        s_, t_, sn, gn = dg[0:3].copy(), dg[3:6].copy(), dg[6:9].copy(), dg[9:12].copy()
-        md = (-np.asarray(d, np.float32)).astype(np.float32)
-        from prim_tracer_ref import _dot   # ctl_math.h's dot, as the device's to_local
-        wi = np.array([_dot(md, s_), _dot(md, t_), _dot(md, sn)], np.float32)
-        mi = int(self.nodes[node, 1]) + int((T[1] >> 16) & 0xff)
-        mat = self.desc.materials[mi]
-        assert mat.map_kind == 0 and all(mat.tex[k].type != 4 for k in range(4)), "path_trace: constant textures, no surface maps"
-        if mat.two_sided and wi[2] < 0:
-            gn = -gn; sn = -sn; wi[2] = -wi[2]
-        return dict(t=t, n=gn, uv=dg[18:20].copy(), wi=wi, P=P, s=s_, tt=t_, sn=sn.astype(np.float32), mat=mat, node=node)
+    def vertex(self, t1, t2, idx, depth, direct, diff):
+        """PathTrace's surface vertex at the hit trace() returned last, on the state buffer; the shadow rays it traced are counted like trace()'s"""
+        self.shadow.value = 0
+        self.lib.orc_path_vertex(self.handle, t1.ctypes.data, t2.ctypes.data, idx, self.buf, self.hits.ctypes.data, depth, 1 if direct else 0,
+                                 diff.ctypes.data if diff is not None else None, self.hook, None, C.byref(self.shadow))
+        if self.hook_error is not None:
+            e, self.hook_error = self.hook_error, None
+            raise e
+        self.rays += self.shadow.value
+        if self.zero_now:
+            self.zero_rays += self.shadow.value
 
 
 def path_trace(orc, desc, volumes, w, h, tables, direct=True, max_path_length=6, rr_start=5, flat=None, debug_pixels=None, ray_count=None, reference_rules=False,
-               undefined=None, pixel_rays=None):
+               undefined=None, pixel_rays=None, partials=False, walk_on_zero=None, vertex_counts=None):
     """pathKernel2<DIRECT> over every pixel and every pass of `tables` -> pixel data (h, w, 7): rgb, splat (0), weightSum, as Image::AddSample accumulates them.
+    The loop, the medium vertex and the roulette are restated here; the surface vertex (getBsdfSample, first-hit partials, emission MIS, BSDF sample, UniformSampleOneLight
+    with the transmittance of this file's media hooked into EstimateDirect) and the escaped path's environment term are the oracle's own pathVertex / pathEscape, the
+    functions its pathTrace is made of — every BSDF model, texture, surface map and emitter the oracle has.
     volumes: the list of ctl_volume of the scene (empty: no media — then this is the oracle's render).  flat: the product's flattened tree (FlatBvh(...).desc), so that a
     ray grazing a shared edge resolves as on the device.  debug_pixels = [(x, y), ...]: instead PathTracer::DebugInternal for those pixels — Direct on, no jitter, the first
     table set — returning their radiances (n, 3).  ray_count: a list that receives the number of rays traced.
+    partials: as Oracle.render(partials=True) — the sensor's ray differentials, the image pyramids, filtered lookups at the first hit (what the PathTracer plugin and its
+    Debug do).
     reference_rules: the two places where this restatement follows the product and not the reference as compiled for the host are switched to the reference's: a path
-    whose throughput is exactly zero walks on (PathTrace has no such cut), and fillDG decodes the triangles' normals with the host branch of half::ToFloat
-    (half_host_quirk, as tests/test_oracle_pathtrace.py).  undefined: an int32 array (h, w, 6), added to — per pixel the places where the reference's PathTrace reads
+    whose throughput is exactly zero walks on (PathTrace has no such cut; walk_on_zero switches this one alone), and fillDG decodes the triangles' normals with the host
+    branch of half::ToFloat (half_host_quirk, as tests/test_oracle_pathtrace.py).
+    vertex_counts: an int array (h, w, 3), added to — per pixel the medium vertices, the surface vertices, and the paths whose escape term was evaluated, with an
+    environment map in the scene, for a ray that left a MEDIUM vertex.
+    undefined: an int32 array (h, w, 6), added to — per pixel the places where the reference's PathTrace reads
     what nothing has written (DESIGN.md, media): [..., 0] reads of a medium record that no sampleDistance had written; [..., 1] sampleVolume indices past the table;
     [..., 2] emission MIS weights taken with a last_nor no surface had set (the path's only vertices so far were medium vertices); [..., 3] medium vertices at which
     Sample found no region, so that the reference walks on — with a throughput of exactly zero — along a pRec.wo nothing has set; [..., 4] samples whose throughput
     became exactly zero anywhere (after a failed BSDF sample the reference walks on along the record's previous wo); [..., 5] the rays traced after that point.
-    Channels 0 to 2 can change the radiance; 3 to 5 only the number of rays (whatever such a path meets is multiplied by zero).
+    Channels 0 to 2 can change the radiance; 3 to 5 only the number of rays (whatever such a path meets is multiplied by zero) — unless the scene has an environment
+    map: a ray along the unset direction of channel 3 that escapes makes 0 * EvalEnvironment(garbage) = NaN in the reference, which drops the sample
+    (tests/golden/generate.py MEDIA_PAIR_LEFT_OUT).
     pixel_rays: a uint32 array (h, w), added to: the rays each pixel traced."""
-    from prim_tracer_ref import _dot
     lib = orc.lib
-    ctx = _Path(orc, desc, volumes, flat)
-    ctx.half_host_quirk = reference_rules
+    ctx = _Path(orc, desc, volumes, flat, half_host_quirk=reference_rules, partials=partials)
+    walk = reference_rules if walk_on_zero is None else walk_on_zero
     V = ctx.V
+    sf, si = ctx.sf, ctx.si
     img = np.zeros((h, w, 7), np.float32)
     o3 = np.zeros(3, np.float32); d3 = np.zeros(3, np.float32); dX = np.zeros(3, np.float32); dY = np.zeros(3, np.float32)
+    rays18 = np.zeros(18, np.float32); ray6 = np.zeros(6, np.float32)
     debug = debug_pixels is not None
     debug_out = []
+    counts = np.zeros(3, np.int64)   # of the current path: medium vertices, surface vertices, escape terms with a map after a medium vertex
 
     def one_path(t1, t2, x, y):
         idx = y * w + x
         k1 = [0]; k2 = [0]
         ctx.zero_now = False
+        counts[:] = 0
 
         def draw1():
             r = f32(lib.orc_sampler_float(t1.ctypes.data, t2.ctypes.data, idx, k1[0])); k1[0] += 1
@@ -582,14 +622,22 @@ def path_trace(orc, desc, volumes, w, h, tables, direct=True, max_path_length=6,
             return out
         j = np.zeros(2, np.float32) if debug else draw2()
         px, py = f32(f32(x) + j[0]), f32(f32(y) + j[1])
-        draw2()   # the aperture sample (a perspective sensor ignores it)
-        lib.orc_sensor_sample_ray_differential(C.addressof(desc.camera), float(px), float(py), o3.ctypes.data, d3.ctypes.data, dX.ctypes.data, dY.ctypes.data)
-        ro, rd = o3.copy(), d3.copy()
+        ap = draw2()   # the aperture sample (a perspective sensor ignores it)
+        diff = None
+        if partials:   # sampleRayDifferential: its own ray, then the x and the y ray (origin, direction each), as orc_render with partials hands them to pathTrace
+            lib.orc_sensor_sample_rays(C.addressof(desc.camera), float(px), float(py), float(ap[0]), float(ap[1]), rays18.ctypes.data, ray6.ctypes.data)
+            ro, rd = ray6[0:3].copy(), ray6[3:6].copy()
+            diff = np.ascontiguousarray(rays18[6:18])
+        else:
+            lib.orc_sensor_sample_ray_differential(C.addressof(desc.camera), float(px), float(py), o3.ctypes.data, d3.ctypes.data, dX.ctypes.data, dY.ctypes.data)
+            ro, rd = o3.copy(), d3.copy()
         cl, cf = v3(0), v3(1)
-        depth = 0; specular = False; had_hit = False
-        bsdf_pdf = f32(0); last_nor = v3(0); nor_written = False; zero_seen = False   # (the reference's last_nor is uninitialised)
+        depth = 0; specular = False; had_hit = False; after_medium = False
+        nor_written = False; zero_seen = False
+        lib.orc_path_state_init(ctx.buf)   # brdf_scattering_pdf = 0, last_nor = 0 (the reference's last_nor is uninitialised), an empty BSDF record
         mRec = zero_rec()   # (the reference's is uninitialised)
         is_direct = True if debug else direct
+        exhausted = False
         while depth < max_path_length:
             depth += 1
             hd = ctx.trace(ro, rd)
@@ -600,6 +648,7 @@ def path_trace(orc, desc, volumes, w, h, tables, direct=True, max_path_length=6,
                 in_medium = V.intersect(ro, rd, f32(0), dist)[0]
                 if in_medium and V.sample_distance(ro, rd, f32(0), dist, draw1(), mRec):   # the WHOLE segment, and the draw whenever in the medium
                     interaction = True
+                    counts[0] += 1; after_medium = True
                     cf = _mul(cf, _sdiv(_mul(mRec["sigmaS"], mRec["transmittance"]), mRec["pdfSuccess"]))
                     if is_direct:
                         out = np.zeros(15, np.float32); ref = np.ascontiguousarray(mRec["p"]); refN = v3(0)
@@ -625,59 +674,20 @@ def path_trace(orc, desc, volumes, w, h, tables, direct=True, max_path_length=6,
                     if not mRec["written"]:
                         ctx.unwritten_reads += 1
                     cf = _mul(cf, _sdiv(mRec["transmittance"], mRec["pdfFailure"]))
-                rec = ctx.surface(ro, rd, hd)
-                mat = rec["mat"]
-                if mat.node_light_index != 0xffffffff:
-                    light = int(ctx.nodes[rec["node"], 3 if mat.node_light_index == 0 else 4])
-                    mis = f32(1)
-                    if not (not is_direct or depth == 1 or specular):
-                        if not nor_written:
-                            ctx.unwritten_normal_reads += 1
-                        a0 = np.ascontiguousarray(ro); a1 = np.ascontiguousarray(last_nor); a2 = np.ascontiguousarray(rd); a3 = np.ascontiguousarray(rec["n"])
-                        dpdf = f32(lib.orc_light_pdf_direct(C.addressof(desc), light, a0.ctypes.data, a1.ctypes.data, a2.ctypes.data, float(rec["t"]), a3.ctypes.data))
-                        mis = _power_heuristic(bsdf_pdf, f32(dpdf * ctx.pdf_emitter.get(light, f32(0))))
-                    le = np.zeros(3, np.float32); P = np.ascontiguousarray(rec["P"]); sn = np.ascontiguousarray(rec["sn"]); md = np.ascontiguousarray((-rd).astype(np.float32))
-                    lib.orc_light_eval(C.addressof(desc), light, P.ctypes.data, sn.ctypes.data, md.ctypes.data, le.ctypes.data)
-                    cl = _add(cl, _mul(_mul(mis, cf), le))
-                so = np.zeros(9, np.float32); wi = np.ascontiguousarray(rec["wi"]); s2 = draw2()
-                lib.orc_bsdf_sample_uv(C.byref(mat), wi.ctypes.data, float(s2[0]), float(s2[1]), float(rec["uv"][0]), float(rec["uv"][1]), so.ctypes.data)
-                f, bsdf_pdf, wo_l, sampled = so[0:3].copy(), f32(so[3]), so[4:7].copy(), int(so[7])
-                last_nor = rec["sn"].copy(); nor_written = True
-                if is_direct and (mat.combined_type & E_SMOOTH):
-                    est = v3(0)
-                    if desc.num_lights:   # UniformSampleOneLight + EstimateDirect(attenuated = true)
-                        sl = draw2()
-                        slot = np.zeros(1, np.int32); lpdf = np.zeros(1, np.float32); rs = np.zeros(1, np.float32); pe = np.zeros(1, np.float32)
-                        lib.orc_emitter_select(C.addressof(desc), 0, 1, sl.ctypes.data, slot.ctypes.data, lpdf.ctypes.data, rs.ctypes.data, pe.ctypes.data)
-                        if slot[0] >= 0:
-                            s3 = draw2()
-                            lo = np.zeros(14, np.float32); P = np.ascontiguousarray(rec["P"]); sn = np.ascontiguousarray(rec["sn"])
-                            lib.orc_light_sample_direct(C.addressof(desc), int(slot[0]), P.ctypes.data, sn.ctypes.data, float(s3[0]), float(s3[1]), lo.ctypes.data)
-                            value, pdf, dd, ddist, dn = lo[0:3].copy(), f32(lo[3]), lo[4:7].copy(), f32(lo[7]), lo[11:14].copy()
-                            r = v3(0)
-                            if not (value == 0).all():
-                                wo2 = np.array([_dot(dd, rec["s"]), _dot(dd, rec["tt"]), _dot(dd, rec["sn"])], np.float32)
-                                eo = np.zeros(4, np.float32)
-                                lib.orc_bsdf_eval_uv(C.byref(mat), wi.ctypes.data, wo2.ctypes.data, E_ALL & ~E_DELTA, 1, float(rec["uv"][0]), float(rec["uv"][1]), eo.ctypes.data)
-                                bf, bpdf = eo[0:3].copy(), f32(eo[3])
-                                if not (bf == 0).all() and ctx.trace(P, dd, f32(ddist - ctx.eps), any_hit=True)["tri_idx"] < 0:
-                                    L = desc.lights[int(slot[0])]
-                                    discrete = L.type in (CTL_LIGHT_POINT, CTL_LIGHT_SPOT, CTL_LIGHT_DISTANT) or (L.type == CTL_LIGHT_DIFFUSE and L.orthogonal)
-                                    weight = f32(1)
-                                    if not discrete:   # these scenes' emitters sample in solid angle: directPdf = dRec.pdf * light_pdf
-                                        weight = _power_heuristic(f32(pdf * lpdf[0]), bpdf)
-                                    r = _mul(_mul(value, bf), weight)
-                                    if V.n:
-                                        r = _mul(r, V.transmittance(P, dd, f32(0), ddist))
-                            est = _sdiv(r, lpdf[0])
-                    cl = _add(cl, _mul(cf, est))
-                specular = (sampled & E_DELTA) != 0
-                cf = _mul(cf, f)
-                ro = rec["P"].copy(); rd = frame_to_world(rec["s"], rec["tt"], rec["sn"], wo_l)
+                # the oracle's own vertex (ocore.h pathVertex): getBsdfSample, first-hit partials, emission with its MIS weight, the BSDF sample, UniformSampleOneLight +
+                # EstimateDirect(attenuated = true) through the transmittance hook, specularBounce / cf / the next ray.  The state buffer carries what lives across vertices
+                sf[0:3] = cl; sf[3:6] = cf; sf[6:9] = ro; sf[9:12] = rd; si[1] = k1[0]; si[2] = k2[0]
+                ctx.vertex(t1, t2, idx, depth, is_direct, diff)
+                if si[4] and not nor_written:   # the emission's MIS weight read last_nor (DirectSamplingRecFromRay) and no surface vertex had set it
+                    ctx.unwritten_normal_reads += 1
+                nor_written = True
+                cl, cf, ro, rd = sf[0:3].copy(), sf[3:6].copy(), sf[6:9].copy(), sf[9:12].copy(); k1[0] = int(si[1]); k2[0] = int(si[2])
+                specular = bool(si[0])
+                counts[1] += 1; after_medium = False
             if not interaction and not had_hit:
                 break
             if (cf == 0).all():   # the library's cut: a path whose throughput is exactly zero ends (the reference walks on and adds zeros)
-                if not reference_rules:
+                if not walk:
                     break
                 if not zero_seen:
                     ctx.zero_walks += 1; zero_seen = ctx.zero_now = True
@@ -686,10 +696,14 @@ def path_trace(orc, desc, volumes, w, h, tables, direct=True, max_path_length=6,
                 if draw1() >= q:
                     break
                 cf = _sdiv(cf, q)
-        if not had_hit:
-            if desc.env_map_index != 0xffffffff:
-                raise NotImplementedError("path_trace: scenes without an environment map")
-            cl = _add(cl, _mul(cf, v3(0)))
+        else:
+            exhausted = True
+        if not had_hit:   # PathTracer.cu:98-111, the oracle's pathEscape: the environment map with its MIS weight (InfiniteLight::pdfDirect reads d alone, not refN), or cf * 0
+            sf[0:3] = cl; sf[3:6] = cf; sf[6:9] = ro; sf[9:12] = rd
+            lib.orc_path_escape(ctx.handle, ctx.buf, depth + 1 if exhausted else depth, 1 if is_direct else 0, float(FLT_MAX))   # `while (depth++ < maxPathLength)` leaves depth + 1 behind when it runs out
+            cl = sf[0:3].copy()
+            if after_medium and desc.env_map_index != 0xffffffff:
+                counts[2] += 1
         return px, py, cl
 
     if debug:
@@ -698,6 +712,7 @@ def path_trace(orc, desc, volumes, w, h, tables, direct=True, max_path_length=6,
             debug_out.append(one_path(t1, t2, x, y)[2])
         if ray_count is not None:
             ray_count.append(ctx.rays)
+        ctx.close()
         return np.array(debug_out, np.float32)
     for t1, t2 in tables:
         t1 = np.ascontiguousarray(t1, np.float32); t2 = np.ascontiguousarray(t2, np.float32)
@@ -705,6 +720,8 @@ def path_trace(orc, desc, volumes, w, h, tables, direct=True, max_path_length=6,
             for x in range(w):
                 before = (ctx.rays, ctx.unwritten_reads, V.past_table, ctx.unwritten_normal_reads, ctx.unset_directions, ctx.zero_walks, ctx.zero_rays)
                 px, py, L = one_path(t1, t2, x, y)
+                if vertex_counts is not None:
+                    vertex_counts[y, x] += counts
                 if pixel_rays is not None:
                     pixel_rays[y, x] += ctx.rays - before[0]
                 if undefined is not None:
@@ -720,4 +737,5 @@ def path_trace(orc, desc, volumes, w, h, tables, direct=True, max_path_length=6,
                 img[iy, ix, 6] = f32(img[iy, ix, 6] + f32(1))
     if ray_count is not None:
         ray_count.append(ctx.rays)
+    ctx.close()
     return img
