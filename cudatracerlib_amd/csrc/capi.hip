@@ -41,7 +41,11 @@ struct ctl_image { Image img; ctl_image(uint32_t w, uint32_t h) : img(w, h) {} }
 // the PathTracer and the PrimTracer judge theirs themselves.  `scene` is the pointer InitializeScene got, the one DoPass reads the scene through
 struct ctl_tracer {
     std::unique_ptr<TracerBase> t; bool wavefront = false; const Scene* scene = nullptr;
-    void refuse_media() const { if (wavefront && scene) static_cast<const WavefrontPathTracer*>(t.get())->check_media(scene); }
+    void refuse_media() const {   // (and, at the same two places, what it refuses of TextureFiltering: check_texture_filtering)
+        if (!wavefront || !scene) return;
+        const WavefrontPathTracer* w = static_cast<const WavefrontPathTracer*>(t.get());
+        w->check_media(scene); w->check_texture_filtering();
+    }
 };
 struct ctl_sequence_generator { sequence_generator g; };
 

@@ -75,6 +75,7 @@ struct pass_params {
     // that pass, so it cannot take the landing pixel's stage slot, and added to the frame at once it would count for the batch's first pass.  It is added (atomics) to
     // stray_stage[pass-in-batch][landing pixel] instead (same layout as `stage`), and the resolve adds it when it reaches its pass.  nullptr: such a sample goes to the frame at once.
     float4* stray_stage;
+    int tex_partials;                    // TextureFiltering on a scene with image textures: the vertices of depth 1 are shaded by k_shade_full_partials (ray differentials, filtered image lookups) instead of the scene's usual build
 };
 
 struct launch_ctx { hipStream_t stream; int grid_blocks; bool alpha_test = false; };   // alpha_test: intersect kernels run Material::AlphaTest on candidate hits
@@ -95,6 +96,7 @@ void launch_intersect_count(const launch_ctx& lc, const dev_scene& S, const floa
                             uint32_t* occ, int any_hit, unsigned long long* counts3);
 // media (a non-empty volume table; the tracer's ParticipatingMedia): the one media build of the full feature set (shade_full_media.hip, or shade_full_media_grid.hip for a table
 // with a VolumeGrid region) whatever the scene's feature set is — it skips the slots k_medium_stage consumed and attenuates the surface NEE by the media's transmittance
+// first-hit texture filtering (pass_params::tex_partials): depth 1 goes to the one partials build of the full feature set, unclassed — no k_class_partition, no class launches at that depth
 void launch_shade(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image, const vol::table* media = nullptr);
 void read_stack_histogram(unsigned long long* h, bool reset);   // kernels.hip: rays of the counting traversals by deepest stack entry
 // The shade builds, X(name, keys): shade_<name>.hip defines launch_shade_<name> and shade_<name>_wf.hip launch_shade_<name>_wf (both from shade_kernel.inc).  keys: a model-class
@@ -108,6 +110,7 @@ CTL_SHADE_BUILDS(CTL_SHADE_DECLARE)
 #undef CTL_SHADE_DECLARE
 using shade_media_launch = void(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, const vol::table& V, int depth, ctl_pixel_data* image);
 shade_media_launch launch_shade_full_media, launch_shade_full_media_grid;   // shade_kernel.inc with CTL_SHADE_MEDIA 1 / 2
+shade_launch launch_shade_full_partials;   // shade_kernel.inc with CTL_TEX_PARTIALS (shade_full_partials.hip): depth 1 under pass_params::tex_partials, PathTrace rules only
 // medium_stage.hip: the medium half of PathTrace (PathTracer.cu:17-58) for the paths of depth `depth`, between launch_finalize(depth - 1) and launch_shade(depth)
 void launch_medium_stage(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, const vol::table& V, int depth, ctl_pixel_data* image);
 void launch_class_partition(const launch_ctx& lc, const wave_queues& Q, int depth);

@@ -358,6 +358,8 @@ void launch_class_partition(const launch_ctx& lc, const wave_queues& Q, int dept
 void launch_shade(const launch_ctx& lc, const dev_scene& S, const wave_queues& Q, const pass_params& P, int depth, ctl_pixel_data* image, const vol::table* media) {
     // participating media: the one media build, with the march of the density grids only for a table that holds a VolumeGrid region (the full build is a superset of every other)
     if (media) { (media->g ? launch_shade_full_media_grid : launch_shade_full_media)(lc, S, Q, P, *media, depth, image); return; }
+    // first-hit texture filtering: the vertices of depth 1 go to the partials build (unclassed: it reads the depth's queue and keys its regrouping itself); every other depth as usual
+    if (P.tex_partials && depth == 1) { launch_shade_full_partials(lc, S, Q, P, depth, image); return; }
 #define CTL_SHADE_INDEX(name, keys) build_##name,
 #define CTL_SHADE_ROW(name, keys) { keys, { launch_shade_##name, launch_shade_##name##_wf } },
     enum { CTL_SHADE_BUILDS(CTL_SHADE_INDEX) n_builds };

@@ -64,6 +64,13 @@
 #if CTL_SHADE_MEDIA && (CTL_SHADE_WAVEFRONT_RULES || CTL_SHADE_PARK || CTL_SHADE_CLASSED)
 #error "CTL_SHADE_MEDIA is written for the default path rules of the unclassed, unparked build"
 #endif
+// CTL_TEX_PARTIALS (shade_full_partials.hip): the build the WavefrontPathTracer launches for the vertices of depth 1 with TextureFiltering = true.  It re-derives the pixel's
+// differential rays from the film position the path carries (path_soa::px) and the pixel's aperture draw, runs DifferentialGeometry::computePartials where PathTrace does
+// (PathTracer.cu:60-61) and so hands every texture lookup of the vertex — the NEE's bsdf.f included — uv partials (shading.h tex_eval -> mipmap.h mip_eval).
+// Undefined: none of that is compiled.
+#if defined(CTL_TEX_PARTIALS) && (CTL_SHADE_WAVEFRONT_RULES || CTL_SHADE_PARK || CTL_SHADE_CLASSED || CTL_SHADE_MEDIA)
+#error "CTL_TEX_PARTIALS is written for the default path rules of the unclassed, unparked build without media"
+#endif
 #include "kernels.h"
 #include "shading.h"
 #include "compaction.h"
@@ -213,6 +220,17 @@ __global__ __launch_bounds__(CTL_SHADE_BLOCK) CTL_SHADE_ATTR void CTL_SHADE_KERN
                 if (mat.map_kind != CTL_MAP_NONE) sample_normal_map(mat, b.dg);   // after wi, as TraceResult.cu:30-34
 #endif
                 if (mat.two_sided && b.wi.z < 0) { b.dg.n = -b.dg.n; b.dg.sys.n = -b.dg.sys.n; b.wi.z *= -1.0f; }
+#ifdef CTL_TEX_PARTIALS
+                if (depth == 1) {   // PathTracer.cu:60-61: r2.getBsdfSample(r, bRec, ...) then bRec.dg.computePartials(r, rX, rY) — the differential rays of pathKernel2's sampleSensorRay (:186-190)
+                    // the aperture sample is the second 2-D draw of this sample of the pixel (k_raygen); the path's sampler stands one draw behind it and has drawn nothing since.
+                    // Only the thin-lens and the telecentric sensor read it (wave-uniform)
+                    f2 ap{ 0.0f, 0.0f };
+                    if (S.cam.type == CTL_SENSOR_THINLENS || S.cam.type == CTL_SENSOR_TELECENTRIC) { sampler aps = rng; aps.d2 = rng.d2 - 1u; ap = aps.next2(); }
+                    f3 m_o, m_d, r_ox, r_dx, r_oy, r_dy;   // the main ray again (unused: the path carries it), then its x / y neighbours
+                    sensor_sample_ray_differential(S.cam, f2{ px.x, px.y }, ap, m_o, m_d, r_ox, r_dx, r_oy, r_dy);
+                    compute_partials(b.dg, r_ox, r_dx, r_oy, r_dy);
+                }
+#endif
                 // emission, MIS-weighted against NEE of the previous vertex (PathTracer.cu:64-77)
                 const uint32_t nli = mat.node_light_index;
                 if (nli != 0xffffffffu) {

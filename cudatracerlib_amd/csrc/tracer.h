@@ -338,10 +338,13 @@ class WavefrontPathTracer : public Tracer<true> {
 public:
     WavefrontPathTracer();
     void Resize(unsigned int w, unsigned int h) override;
-    void InitializeScene(Scene* s) override { check_media(s); Tracer<true>::InitializeScene(s); }
+    void InitializeScene(Scene* s) override { check_media(s); check_texture_filtering(); Tracer<true>::InitializeScene(s); }
     // what the plugin refuses (unsupported_error), judged when a scene is handed over and when a pass starts.  ParticipatingMedia = false: a scene with participating media
     // (Scene::refuse_volumes — the plugin then runs no medium code and would render the scene without them); true: PathSemantics = Wavefront (pathIterateKernel has no medium rules)
     void check_media(const Scene* s) const;
+    // TextureFiltering = true is refused (unsupported_error) at the same two places with PathSemantics = Wavefront (pathIterateKernel has no ray differentials) and with
+    // ParticipatingMedia = true (the media build of the shade kernel has none either)
+    void check_texture_filtering() const;
     void setDepthBuffer(float* device_data, unsigned int dw, unsigned int dh) override { depth_buffer_ = device_data; depth_w_ = dw; depth_h_ = dh; }   // WavefrontPathTracer : IDepthTracer (WavefrontPathTracer.h:24)
     void reservePasses(unsigned int n) override { const unsigned int b = std::min(passBatch(), std::max(1u, n)); growBatch(b, "reservePasses"); ensureTableRing(b); if (w != 0xffffffffu) (void)ensureStage(b); }
 protected:

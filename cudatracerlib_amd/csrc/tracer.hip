@@ -565,13 +565,25 @@ WavefrontPathTracer::WavefrontPathTracer() {
     // (shade_full_media*.hip) attenuates the surface NEE — for a scene whose volume table is empty the pass launches exactly the kernels it launches with false.
     // PathTrace rules only: refused together with PathSemantics = Wavefront
     m_sParameters.addBool("ParticipatingMedia", false);
-    m_sParameters.addBool("OrderedAccumulation", true);   // build-specific: finished paths are staged per (pass, pixel) and added to the frame in pass order (kernels.h pass_params::stage); false = four float atomics per path as Image::AddSample does
+    // build-specific: ray differentials at the first hit and filtered image textures there, as PathTrace has them (PathTracer.cu:60-61, Texture.cu:15-29, MIPMap.cu:193-278).
+    // false (default): every lookup reads level 0 and the pass launches what it always launched; true: the vertices of depth 1 are shaded by k_shade_full_partials
+    // (shade_full_partials.hip) — for a scene without image textures the pass launches exactly the kernels it launches with false.
+    // PathTrace rules only: refused together with PathSemantics = Wavefront, and together with ParticipatingMedia
+    m_sParameters.addBool("TextureFiltering", false);
+    m_sParameters.addBool("OrderedAccumulation", true);  // build-specific: finished paths are staged per (pass, pixel) and added to the frame in pass order (kernels.h pass_params::stage); false = four float atomics per path as Image::AddSample does
     grid_blocks = persistent_grid_blocks();
 }
 void WavefrontPathTracer::check_media(const Scene* s) const {
     if (m_sParameters.getValue("ParticipatingMedia") == 0) { if (s) s->refuse_volumes("WavefrontPathTracer"); return; }
     if (m_sParameters.getValue("PathSemantics") == 1)
         throw unsupported_error("WavefrontPathTracer: ParticipatingMedia = true with PathSemantics = Wavefront is not supported: pathIterateKernel has no medium rules; participating media are rendered under PathSemantics = PathTrace");
+}
+void WavefrontPathTracer::check_texture_filtering() const {
+    if (m_sParameters.getValue("TextureFiltering") == 0) return;
+    if (m_sParameters.getValue("PathSemantics") == 1)
+        throw unsupported_error("WavefrontPathTracer: TextureFiltering = true with PathSemantics = Wavefront is not supported: pathIterateKernel has no ray differentials; first-hit texture filtering is rendered under PathSemantics = PathTrace");
+    if (m_sParameters.getValue("ParticipatingMedia") != 0)
+        throw unsupported_error("WavefrontPathTracer: TextureFiltering = true with ParticipatingMedia = true is not supported: the media build of the shade kernel has no ray differentials; the PathTracer plugin renders participating media with filtered textures");
 }
 float4* WavefrontPathTracer::new_f4(size_t n) { f4_.emplace_back(new dbuf<float4>()); f4_.back()->alloc(n); return f4_.back()->p; }
 
@@ -664,7 +676,7 @@ unsigned int WavefrontPathTracer::passBatch() const {
 }
 
 void WavefrontPathTracer::DoRender(Image* I, const float* d_t1p, const float* d_t2p, unsigned int n_batch) {
-    check_media(m_pScene);
+    check_media(m_pScene); check_texture_filtering();
     growBatch(n_batch, "DoRender");   // the queues grow to the largest batch asked for
     // participating media: the table is read per pass — ctl_scene_update may have changed the media since InitializeScene.  An empty table: the launches of a scene without media
     const bool media_on = m_sParameters.getValue("ParticipatingMedia") != 0;
@@ -689,6 +701,9 @@ void WavefrontPathTracer::DoRender(Image* I, const float* d_t1p, const float* d_
     P.direct = direct ? 1 : 0; P.max_path_length = maxPathLength; P.rr_start_depth = rrStart;
     P.block_counts = pass_block_counts_; P.max_block_count = pass_max_block_count_;
     P.wavefront_rules = m_sParameters.getValue("PathSemantics") == 1 ? 1 : 0; P.u16_bary = m_sParameters.getValue("U16Barycentrics") != 0 ? 1 : 0;
+    // first-hit texture filtering: only an image texture can see the partials (material textures, normal maps, textured area lights: all behind kShadeImageTextures), so a scene
+    // without one keeps its usual depth-1 launches — the frame is the default one by construction
+    P.tex_partials = (m_sParameters.getValue("TextureFiltering") != 0 && (S.shade_features & kShadeImageTextures)) ? 1 : 0;
     P.depth_buffer = depth_buffer_; P.depth_w = depth_w_; P.depth_h = depth_h_; P.depth_near = m_pScene->near_depth; P.depth_far = m_pScene->far_depth;
     // ordered accumulation (kernels.h pass_params::stage): one staged sample per (pass of the batch, pixel), added to the frame in pass order after the last bounce
     // The stage covers THIS RANK'S tiles only (n_local_pixels slots per pass of the batch, 16 B each: 663 MB for 20 passes of a whole 1080p frame, an eighth of that on a rank

@@ -739,7 +739,11 @@ void ctl_tracer_destroy(ctl_tracer* t);
 /* TracerParameterCollection (Kernel/TracerSettings.h:221-350): keys Direct(bool), MaxPathLength(int>=1),
  * RRStartDepth(int>=1) (WavefrontPathTracer.h:29-39). Out-of-interval values -> CTL_ERR_INVALID.
  * Build-specific, WavefrontPathTracer: ParticipatingMedia(bool, default 0) — 1: the plugin renders scenes with participating media (PathTrace's rules; refused together
- * with PathSemantics = Wavefront); 0: it answers CTL_ERR_UNSUPPORTED for such a scene, at ctl_tracer_initialize_scene and when a pass starts. */
+ * with PathSemantics = Wavefront); 0: it answers CTL_ERR_UNSUPPORTED for such a scene, at ctl_tracer_initialize_scene and when a pass starts.
+ * TextureFiltering(bool, default 0) — 1: the first hit of every path is shaded with ray differentials and its image textures are filtered through the mip pyramid
+ * (trilinear / EWA, the image's filter mode), as the PathTracer plugin does; deeper vertices read level 0.  0: every lookup reads level 0.  Refused with
+ * CTL_ERR_UNSUPPORTED, at the same two places, together with PathSemantics = Wavefront and together with ParticipatingMedia = 1 (the PathTracer plugin renders both).
+ * The PathTracer and PrimTracer plugins do not have the key. */
 int ctl_tracer_set_param_bool(ctl_tracer* t, const char* key, int value);
 int ctl_tracer_set_param_int(ctl_tracer* t, const char* key, int value);
 int ctl_tracer_get_param_int(ctl_tracer* t, const char* key, int* value_out);   /* bool, int and enum (its index) parameters */
