@@ -11,7 +11,7 @@ from .api import (  # noqa: F401
     ctl_tracer_stats, ctl_traversal_counts, ctl_float4x4,
     diffuse, dielectric, conductor, roughconductor, device_count, intersect, intersect_count, intersect_ex, intersect_pair,
     traversal_stack_histogram, traversal_lds_rows,
-    FlatBvh, scene_desc_diff, DIFF_CAMERA, DIFF_MATERIALS, DIFF_LIGHTS, DIFF_TRANSFORMS, DIFF_TOPOLOGY, DIFF_GEOMETRY, skin_mesh_host, shape_sets_host, SKIN_AREA_LIGHTS,
+    FlatBvh, scene_desc_diff, DIFF_CAMERA, DIFF_MATERIALS, DIFF_LIGHTS, DIFF_TRANSFORMS, DIFF_TOPOLOGY, DIFF_GEOMETRY, skin_mesh_host, shape_sets_host, SKIN_AREA_LIGHTS, mip_pyramid_host, IMAGE_TEXELS_DEVICE,
     DIFF_VOLUMES, ctl_volume, ctl_phase_function, homogeneous_volume, volume_update, volume_eval, volumes_desc,
     VOLUME_HOMOGENEOUS, VOLUME_GRID, ctl_volume_grid, GridVolume, grid_volume, set_desc_volumes,
     phase_isotropic, phase_hg, phase_rayleigh, phase_kajiya_kay,

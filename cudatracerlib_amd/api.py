@@ -865,6 +865,16 @@ class DynamicScene:
         _check(lib.ctl_builder_add_image(self._h, t.ctypes.data_as(C.c_void_p), u32(t.shape[1]), u32(t.shape[0]), u32(texel_type), u32(wrap), u32(filter), C.byref(idx)))
         return idx.value
 
+    def update_image(self, image, texels):
+        """ctl_builder_update_image — DynamicScene::ReloadTextures for a caller that supplies the bitmap: new level-0 texels (h, w) uint32 for a registered image, same size.
+        The environment light's CDFs and normalization follow if the image is its map; UpdateScene() then makes the sampling weights of the materials that read the
+        image's average.  The host yardstick of Scene.update_image, and what a host that keeps its builder calls beside it.  CtlError(ERR_INVALID) for a bad index or another
+        size: the builder is untouched."""
+        t = np.ascontiguousarray(texels, dtype=np.uint32)
+        if t.ndim != 2:
+            raise ValueError("update_image: texels (h, w) uint32")
+        _check(lib.ctl_builder_update_image(self._h, u32(image), t.ctypes.data_as(C.c_void_p), u32(t.shape[1]), u32(t.shape[0])))
+
     def set_bvh_mode(self, mode):
         """mesh BVH builder for the following add_mesh calls: "auto" (default), "sbvh" (the reference's SplitBVHBuilder restated) or "binned"."""
         _check(lib.ctl_builder_set_bvh_mode(self._h, u32({"auto": 0, "sbvh": 1, "binned": 2}[mode])))
@@ -987,6 +997,7 @@ class Scene:
         self._skins = {}   # mesh -> dict(n_vert, n_bones) of the bound meshes
         self._light_counts = (int(desc.n_lights_buf), int(desc.n_anim_bytes))   # the sizes read_lights' buffers must have
         self._node_ids = getattr(desc, "node_ids", None)   # of the description the scene holds (DynamicScene.UpdateScene), or None
+        self._image_dims = [(int(desc.images[i].width), int(desc.images[i].height)) for i in range(desc.n_images)]   # an update keeps them (read_image)
 
     def update(self, desc):
         """ctl_scene_update: applies what differs between the description the scene holds and `desc` — camera, materials, lights, node transforms, the vertex
@@ -1093,6 +1104,42 @@ class Scene:
         _check(lib.ctl_scene_read_lights(self._h, L.ctypes.data, u32(n_lights), A.ctypes.data, C.c_size_t(n_anim)))
         return dict(lights=L, anim=A)
 
+    def update_image(self, image, texels, width=None, height=None, device=False):
+        """ctl_scene_update_image: new level-0 texels for image `image` of the live scene, same size, and everything derived from texels rebuilt on the device in place — the
+        pyramid, the sampling weights of the materials that read the image's average, the environment light's CDFs and normalization (csrc/scene_images.hip).  texels: an
+        (h, w) uint32 array; or, with device=True, the address of width x height uint32 texels in device memory (ctl_device_malloc, tensor.data_ptr()) — or a torch tensor,
+        whose data_ptr() and shape are taken.  Returns the stats dict (levels, texels_written, materials_patched, env_tables, upload_ms, pyramid_ms, env_ms, hash_ms,
+        total_ms).  CtlError(ERR_INVALID) leaves the scene as it was.  Start the next pass with new_trace; a host that keeps its DynamicScene calls its update_image too."""
+        st = ctl_scene_image_stats()
+        if device or hasattr(texels, "data_ptr"):
+            if hasattr(texels, "data_ptr"):
+                if width is None:
+                    height, width = int(texels.shape[0]), int(texels.shape[1])
+                keep, ptr = texels, int(texels.data_ptr())
+            else:
+                keep, ptr = None, int(texels)
+            if width is None or height is None:
+                raise ValueError("update_image: a device pointer needs width and height")
+            _check(lib.ctl_scene_update_image(self._h, u32(image), C.c_void_p(ptr), u32(width), u32(height), u32(IMAGE_TEXELS_DEVICE), C.addressof(st)))
+            del keep
+        else:
+            t = np.ascontiguousarray(texels, dtype=np.uint32)
+            if t.ndim != 2:
+                raise ValueError("update_image: texels (h, w) uint32")
+            _check(lib.ctl_scene_update_image(self._h, u32(image), t.ctypes.data_as(C.c_void_p), u32(t.shape[1]), u32(t.shape[0]), u32(0), C.addressof(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def read_image(self, image):
+        """ctl_scene_read_image: dict(texels (n,) uint32 — level 0 and the pyramid behind it as the pool holds them —, levels, offsets (15,) uint32: offsets[l - 1] = the
+        texel offset of level l >= 1), the layout of mip_pyramid_host"""
+        levels = u32(); off = (u32 * 15)()
+        _check(lib.ctl_scene_read_image(self._h, u32(image), None, C.c_size_t(0), C.byref(levels), off))
+        w, h = self._image_dims[image]   # (the call above refused a bad index)
+        n = _pyramid_texels(w, h, levels.value, off)
+        T = np.zeros(n, np.uint32)
+        _check(lib.ctl_scene_read_image(self._h, u32(image), T.ctypes.data, C.c_size_t(n), C.byref(levels), off))
+        return dict(texels=T, levels=levels.value, offsets=np.array(off[:], np.uint32))
+
     def read_mesh_geometry(self, mesh, vertices=False):
         """ctl_scene_read_mesh_geometry: dict(tri (n_tri, 8) uint32, woop (n_rows, 12) uint32) as HBM holds them — any mesh of any scene — and, with vertices=True
         (a bound, posed mesh), positions and normals (n_vert, 3) float32 of the last pose"""
@@ -1134,6 +1181,11 @@ class ctl_scene_update_stats(C.Structure):
     _fields_ = [("node_area_before", C.c_double), ("node_area_after", C.c_double), ("refit_ms", f32), ("refit_levels", u32), ("mask", u32), ("restamped", u32)]
 
 
+class ctl_scene_image_stats(C.Structure):
+    _fields_ = [("levels", u32), ("texels_written", u32), ("materials_patched", u32), ("env_tables", u32),
+                ("upload_ms", f32), ("pyramid_ms", f32), ("env_ms", f32), ("hash_ms", f32), ("total_ms", f32)]
+
+
 class ctl_scene_rebuild_stats(C.Structure):
     _fields_ = [("n_nodes", u32), ("n_entries", u32), ("max_depth", u32), ("levels", u32), ("node_area_before", C.c_double), ("node_area_after", C.c_double),
                 ("sort_ms", f32), ("topology_ms", f32), ("refit_ms", f32), ("total_ms", f32)]
@@ -1155,7 +1207,10 @@ for _n, _a in (("ctl_scene_rebuild_flat", [C.c_void_p, C.c_void_p]), ("ctl_flat_
                ("ctl_flat_bvh_rebuild_order", [C.c_void_p] * 5),
                ("ctl_scene_bind_skin_ex", [C.c_void_p, u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, u32, C.c_void_p, C.c_void_p, u32, u32]),
                ("ctl_scene_get_shape_set_ms", [C.c_void_p, C.POINTER(f32)]), ("ctl_scene_read_lights", [C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_size_t]),
-               ("ctl_shape_sets_host", [C.c_void_p, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])):
+               ("ctl_shape_sets_host", [C.c_void_p, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+               ("ctl_builder_update_image", [C.c_void_p, u32, C.c_void_p, u32, u32]), ("ctl_mip_pyramid_host", [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+               ("ctl_scene_update_image", [C.c_void_p, u32, C.c_void_p, u32, u32, u32, C.c_void_p]),
+               ("ctl_scene_read_image", [C.c_void_p, u32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p])):
     if hasattr(lib, _n):
         getattr(lib, _n).argtypes = _a
 if hasattr(lib, "ctl_rebuild_last_rounds"):
@@ -1163,6 +1218,7 @@ if hasattr(lib, "ctl_rebuild_last_rounds"):
 
 REBUILD_LBVH, REBUILD_PLOC = 0, 1   # CTL_REBUILD_LBVH, CTL_REBUILD_PLOC
 SKIN_AREA_LIGHTS = 1                # CTL_SKIN_AREA_LIGHTS
+IMAGE_TEXELS_DEVICE = 1             # CTL_IMAGE_TEXELS_DEVICE
 
 
 def rebuild_builder(builder):
@@ -1218,6 +1274,27 @@ def shape_sets_host(desc, mesh, tri, woop):
     L = np.zeros((desc.n_lights_buf, C.sizeof(ctl_light) // 4), np.uint32); A = np.zeros(desc.n_anim_bytes, np.uint8)
     _check(lib.ctl_shape_sets_host(C.addressof(desc), u32(mesh), T.ctypes.data, Wp.ctypes.data, L.ctypes.data, A.ctypes.data))
     return dict(lights=L, anim=A)
+
+
+def _pyramid_texels(width, height, levels, offsets):
+    """the texel count of a pyramid from its level table: the last level's offset plus its size"""
+    last = levels - 1
+    return (int(offsets[last - 1]) if last else 0) + (width >> last) * (height >> last)
+
+
+def mip_pyramid_host(texels, texel_type=TEXEL_RGBCOL):
+    """ctl_mip_pyramid_host (host only): the pyramid a scene keeps of an (h, w) uint32 image — dict(texels (n,) uint32: level 0, then levels 1 .., levels, offsets (15,)
+    uint32: offsets[l - 1] = the texel offset of level l >= 1; level l is (w >> l) x (h >> l)).  What Scene.read_image reads back."""
+    t = np.ascontiguousarray(texels, dtype=np.uint32)
+    if t.ndim != 2:
+        raise ValueError("mip_pyramid_host: texels (h, w) uint32")
+    m = ctl_mipmap(); m.texels = t.ctypes.data; m.width, m.height, m.texel_type = t.shape[1], t.shape[0], texel_type
+    levels = u32(); off = (u32 * 15)()
+    _check(lib.ctl_mip_pyramid_host(C.addressof(m), None, C.c_size_t(0), C.byref(levels), off))
+    n = _pyramid_texels(m.width, m.height, levels.value, off)
+    T = np.zeros(n, np.uint32)
+    _check(lib.ctl_mip_pyramid_host(C.addressof(m), T.ctypes.data, C.c_size_t(n), C.byref(levels), off))
+    return dict(texels=T, levels=levels.value, offsets=np.array(off[:], np.uint32))
 
 
 def mesh_counts(desc):

@@ -81,6 +81,24 @@ int ctl_builder_update_mesh(ctl_builder* b, uint32_t mesh_index, const float* po
     CTL_REQUIRE(b, "null builder");
     CTL_TRY b->b.update_mesh(mesh_index, positions, n_vert, indices, n_tri, normals, uvs); CTL_CATCH
 }
+int ctl_builder_update_image(ctl_builder* b, uint32_t image_index, const uint32_t* texels, uint32_t width, uint32_t height) {
+    CTL_REQUIRE(b, "null builder");
+    CTL_TRY b->b.update_image(image_index, texels, width, height); CTL_CATCH
+}
+int ctl_mip_pyramid_host(const ctl_mipmap* image, uint32_t* texels_out, size_t capacity, uint32_t* levels_out, uint32_t level_offsets_out[15]) {
+    CTL_REQUIRE(image && image->texels && image->width && image->height, "ctl_mip_pyramid_host: null or empty image");
+    CTL_REQUIRE(image->texel_type <= CTL_TEXEL_RGBCOL, "ctl_mip_pyramid_host: unknown texel type");
+    CTL_TRY
+        std::vector<uint32_t> pool; mip_level_table L;
+        mip_pyramid_append(*image, pool, L);
+        if (levels_out) *levels_out = L.levels;
+        if (level_offsets_out) for (int k = 0; k < 15; k++) level_offsets_out[k] = L.offsets[k];
+        if (texels_out) {
+            if (capacity < pool.size()) throw std::runtime_error("ctl_mip_pyramid_host: the pyramid holds " + std::to_string(pool.size()) + " texels in " + std::to_string(L.levels) + " levels");
+            std::memcpy(texels_out, pool.data(), pool.size() * 4);
+        }
+    CTL_CATCH
+}
 int ctl_builder_set_bvh_mode(ctl_builder* b, uint32_t mode) { CTL_REQUIRE(b && mode <= CTL_BVH_BINNED, "null builder or unknown mode"); b->b.bvh_mode = mode; return CTL_OK; }
 int ctl_builder_add_node(ctl_builder* b, uint32_t mesh_index, const ctl_float4x4* to_world, uint32_t* node_index_out) {
     CTL_REQUIRE(b, "null builder");
@@ -403,6 +421,17 @@ int ctl_scene_read_lights(ctl_scene* scene, ctl_light* lights_out, uint32_t n_li
     if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
     CTL_REQUIRE(scene, "null scene");
     CTL_TRY scene->s.read_lights(lights_out, n_lights, anim_out, n_anim_bytes); CTL_CATCH
+}
+// ---- images in place (scene_images.hip)
+int ctl_scene_update_image(ctl_scene* scene, uint32_t image_index, const uint32_t* texels, uint32_t width, uint32_t height, uint32_t flags, ctl_scene_image_stats* stats_out) {
+    if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
+    CTL_REQUIRE(scene, "null scene");
+    CTL_TRY scene->s.update_image(image_index, texels, width, height, flags, stats_out); CTL_CATCH
+}
+int ctl_scene_read_image(ctl_scene* scene, uint32_t image_index, uint32_t* texels_out, size_t capacity, uint32_t* levels_out, uint32_t level_offsets_out[15]) {
+    if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
+    CTL_REQUIRE(scene, "null scene");
+    CTL_TRY scene->s.read_image(image_index, texels_out, capacity, levels_out, level_offsets_out); CTL_CATCH
 }
 int ctl_shape_sets_host(const ctl_scene_desc* desc, uint32_t mesh_index, const ctl_triangle_data* tri_data, const ctl_woop_tri* woop, ctl_light* lights_out, uint8_t* anim_out) {
     CTL_REQUIRE(desc, "null description");

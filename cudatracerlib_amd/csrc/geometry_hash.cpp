@@ -27,6 +27,12 @@ mesh_ranges::mesh_ranges(const ctl_scene_desc& d) {
     ranges_of(s, d.n_bvh_nodes, node0, node1);
 }
 
+void hash_image(uint32_t width, uint32_t height, const uint32_t* texels, uint64_t out[2]) {
+    content_hash H; H.add_value(width); H.add_value(height);
+    if (texels) H.add(texels, (size_t)width * height * 4);
+    H.digest(out);
+}
+
 void hash_geometry(const ctl_scene_desc& d, geometry_hashes& out, const std::vector<uint8_t>* skip_values) {
     const mesh_ranges R(d);
     content_hash S; std::vector<content_hash> V(d.n_meshes);
@@ -46,7 +52,8 @@ void hash_geometry(const ctl_scene_desc& d, geometry_hashes& out, const std::vec
         if (R.woop1[m] > R.woop0[m]) H.add(d.woop + R.woop0[m], (size_t)(R.woop1[m] - R.woop0[m]) * sizeof(ctl_woop_tri));
         for (uint32_t i = R.node0[m]; i < R.node1[m]; i++) { H.add(&d.bvh_nodes[i], 48); S.add(&d.bvh_nodes[i].child0, 16); }
     }
-    for (uint32_t i = 0; i < d.n_images; i++) if (d.images[i].texels) S.add(d.images[i].texels, (size_t)d.images[i].width * d.images[i].height * 4);
+    out.images.resize((size_t)d.n_images * 2);
+    for (uint32_t i = 0; i < d.n_images; i++) hash_image(d.images[i].width, d.images[i].height, d.images[i].texels, &out.images[(size_t)i * 2]);
     const int have_rt = d.rough_transmittance ? 1 : 0; S.add_value(have_rt);
     if (d.rough_transmittance) for (int i = 0; i < 3; i++) {
         const ctl_rough_transmittance& t = d.rough_transmittance[i];

@@ -10,6 +10,7 @@
 #include "ctl_math.h"
 #include "mesh_skin.h"
 #include "shape_set.h"
+#include "env_tables.h"
 #include "volume_eval.h"
 #include <cstring>
 #include <algorithm>
@@ -404,59 +405,62 @@ uint32_t scene_builder::add_image(const uint32_t* texels, uint32_t w, uint32_t h
     return (uint32_t)images.size() - 1;
 }
 
-static f3 texel_decode(uint32_t v, uint32_t type) {   // SpectrumConverter::RGBEToFloat3 / COLORREFToFloat3 (Math/Spectrum.h:528-565)
-    unsigned x = v & 0xff, y = (v >> 8) & 0xff, z = (v >> 16) & 0xff, w = v >> 24;
-    if (type == CTL_TEXEL_RGBE) {
-        if (!w) return f3(0.0f);
-        float e = ldexpf(1.0f, int(w) - (128 + 8));
-        return f3(x * e, y * e, z * e);
+// the level-0 texels of a registered image replaced (ctl_builder_update_image): size, texel type, wrap and filter mode stay.  What the builder derives from texels follows:
+// the environment light's column / row CDFs and its normalization, rewritten where they stand if the image is the environment map's; the sampling weights of the materials
+// that read the image's average are made by the next finalize, as they always are (material_update_textures).  A refused call leaves the builder as it was
+void scene_builder::update_image(uint32_t image, const uint32_t* texels, uint32_t w, uint32_t h) {
+    if (image >= images.size()) throw std::runtime_error("ctl_builder_update_image: bad image index " + std::to_string(image) + " of " + std::to_string(images.size()));
+    if (!texels) throw std::runtime_error("ctl_builder_update_image: null texels");
+    if (w != images[image].width || h != images[image].height)
+        throw std::runtime_error("ctl_builder_update_image: image " + std::to_string(image) + " is " + std::to_string(images[image].width) + " x " + std::to_string(images[image].height) + "; an update keeps the size");
+    image_texels[image].assign(texels, texels + (size_t)w * h);
+    if (env_light < lights.size() && lights[env_light].type == CTL_LIGHT_INFINITE && lights[env_light].env_image == image) environment_tables(lights[env_light]);
+}
+
+// InfiniteLight::InfiniteLight (SceneTypes/Light.cpp:10-61), the part that reads texels: cdfCols and cdfRows at the light's offsets in the anim blob and its normalization,
+// from the image's texels and the rowWeights already there.  The arithmetic is env_tables.h's, which the device runs too (scene_images.hip)
+void scene_builder::environment_tables(ctl_light& L) {
+    const ctl_mipmap& M = images[L.env_image]; const uint32_t* tx = image_texels[L.env_image].data();
+    const uint32_t W = M.width, H = M.height, type = M.texel_type;
+    std::vector<float> cdfCols((size_t)(W + 1) * H), cdfRows(H + 1), colSums(H), rowWeights(H);
+    std::memcpy(rowWeights.data(), anim.data() + L.row_weights_index, rowWeights.size() * sizeof(float));
+    for (uint32_t y = 0; y < H; ++y) {
+        float* row = &cdfCols[(size_t)y * (W + 1)]; const uint32_t* t = tx + (size_t)y * W;
+        row[0] = 0;
+        const float colSum = env_running_sum([&](uint32_t x) { return env_texel_luminance(t[x], type); }, W, 0.0f, row + 1);
+        const float normalization = 1.0f / colSum;
+        for (uint32_t x = 0; x <= W; ++x) row[x] = env_normalized_entry(row[x], x, W, normalization);
+        colSums[y] = colSum;
     }
-    return f3(float(x) / 255.0f, float(y) / 255.0f, float(z) / 255.0f);
+    cdfRows[0] = 0;
+    const float rowSum = env_running_sum([&](uint32_t y) { return colSums[y] * rowWeights[y]; }, H, 0.0f, cdfRows.data() + 1);
+    const float normalization = 1.0f / rowSum;
+    for (uint32_t y = 0; y <= H; ++y) cdfRows[y] = env_normalized_entry(cdfRows[y], y, H, normalization);
+    std::memcpy(anim.data() + L.cdf_cols_index, cdfCols.data(), cdfCols.size() * sizeof(float));
+    std::memcpy(anim.data() + L.cdf_rows_index, cdfRows.data(), cdfRows.size() * sizeof(float));
+    L.normalization = env_normalization(rowSum, W, H);
 }
 
 // DynamicScene::setEnvironementMap (Engine/DynamicScene.cpp:846-859) + InfiniteLight::InfiniteLight (SceneTypes/Light.cpp:10-61)
 uint32_t scene_builder::set_environment_map(uint32_t image, const float scale[3], const ctl_float4x4* to_world) {
     if (env_light != 0xffffffffu) throw std::runtime_error("Can't set environment map when it is already set!");
     if (image >= images.size()) throw std::runtime_error("ctl_builder_set_environment_map: bad image index");
-    const ctl_mipmap& M = images[image]; const std::vector<uint32_t>& tx = image_texels[image];
+    const ctl_mipmap& M = images[image];
     const uint32_t W = M.width, H = M.height;
     auto align_to = [&](size_t a) { while (anim.size() % a) anim.push_back(0); };
     align_to(16); uint32_t cols_off = (uint32_t)anim.size(); anim.resize(anim.size() + (size_t)(W + 1) * H * sizeof(float));
     align_to(16); uint32_t rows_off = (uint32_t)anim.size(); anim.resize(anim.size() + (size_t)(H + 1) * sizeof(float));
     align_to(16); uint32_t wts_off = (uint32_t)anim.size(); anim.resize(anim.size() + (size_t)H * sizeof(float));
-    std::vector<float> cdfCols((size_t)(W + 1) * H), cdfRows(H + 1), rowWeights(H);
-    const float sizeX = (float)W, sizeY = (float)H;
-    size_t colPos = 0, rowPos = 0;
-    float rowSum = 0.0f;
-    cdfRows[rowPos++] = 0;
-    for (uint32_t y = 0; y < H; ++y) {
-        float colSum = 0;
-        cdfCols[colPos++] = 0;
-        for (uint32_t x = 0; x < W; ++x) {
-            f3 v = texel_decode(tx[(size_t)y * W + x], M.texel_type);
-            colSum += v.x * 0.212671f + v.y * 0.715160f + v.z * 0.072169f;   // Spectrum::getLuminance
-            cdfCols[colPos++] = colSum;
-        }
-        float normalization = 1.0f / colSum;
-        for (uint32_t x = 1; x < W; ++x) cdfCols[colPos - x - 1] *= normalization;
-        cdfCols[colPos - 1] = 1.0f;
-        float weight = sinf((y + 0.5f) * kPi / sizeY);
-        rowWeights[y] = weight;
-        rowSum += colSum * weight;
-        cdfRows[rowPos++] = rowSum;
-    }
-    float normalization = 1.0f / rowSum;
-    for (uint32_t y = 1; y < H; ++y) cdfRows[rowPos - y - 1] *= normalization;
-    cdfRows[rowPos - 1] = 1.0f;
-    std::memcpy(anim.data() + cols_off, cdfCols.data(), cdfCols.size() * sizeof(float));
-    std::memcpy(anim.data() + rows_off, cdfRows.data(), cdfRows.size() * sizeof(float));
+    std::vector<float> rowWeights(H);
+    const float sizeY = (float)H;
+    for (uint32_t y = 0; y < H; ++y) rowWeights[y] = sinf((y + 0.5f) * kPi / sizeY);
     std::memcpy(anim.data() + wts_off, rowWeights.data(), rowWeights.size() * sizeof(float));
     ctl_light L{};
     L.type = CTL_LIGHT_INFINITE;
     L.env_image = image;
     for (int i = 0; i < 3; i++) L.env_scale[i] = scale[i];
     L.cdf_cols_index = cols_off; L.cdf_rows_index = rows_off; L.row_weights_index = wts_off;
-    L.normalization = 1.0f / (rowSum * (2 * kPi / sizeX) * (kPi / sizeY));
+    environment_tables(L);
     static const float ident[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
     std::memcpy(L.to_world, to_world ? to_world->m : ident, 64);
     lights.push_back(L);

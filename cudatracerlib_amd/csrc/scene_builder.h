@@ -65,6 +65,9 @@ struct scene_builder {
     uint32_t add_distant_light(const float direction[3], const float irradiance[3], float scene_radius);
     uint32_t add_image(const uint32_t* texels, uint32_t w, uint32_t h, uint32_t texel_type, uint32_t wrap, uint32_t filter);
     uint32_t set_environment_map(uint32_t image, const float scale[3], const ctl_float4x4* to_world);
+    // new level-0 texels for a registered image, same size (ctl_builder_update_image): the environment light's CDFs and normalization follow if the image is its map
+    void update_image(uint32_t image, const uint32_t* texels, uint32_t w, uint32_t h);
+    void environment_tables(ctl_light& L);   // cdfCols, cdfRows and normalization of an infinite light from its image's texels, at the light's offsets in the anim blob (env_tables.h)
     void set_rough_transmittance(uint32_t slot, const ctl_rough_transmittance& t);
     void load_rough_transmittance(uint32_t slot, const char* path);
     void set_camera_lookat(const float pos[3], const float target[3], const float up[3], float fov_degrees, uint32_t w, uint32_t h);

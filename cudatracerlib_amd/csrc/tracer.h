@@ -85,6 +85,12 @@ public:
     // the area lights of a mesh bound with CTL_SKIN_AREA_LIGHTS (shape_set.hip): their shape sets — ranges of anim_ and the sum_area of their records — are device-owned,
     // recomputed after every pose and after every upload of the light tables or the instance transforms
     float last_shape_set_ms() const { return last_shape_set_ms_; }   // HIP-event time of the shape-set kernels of the last call that ran them
+    // ctl_scene_update_image (scene_images.hip): new level-0 texels for image `image` of the scene, same size — host memory, or device memory with CTL_IMAGE_TEXELS_DEVICE —
+    // and everything the library derives from texels rebuilt in place: the pyramid in the texel pool, the sampling weights of the materials that read the image's average,
+    // the environment light's CDFs and normalization.  Refusals (std::runtime_error, before the device is touched) leave the scene as it was.  Synchronous.
+    void update_image(uint32_t image, const uint32_t* texels, uint32_t width, uint32_t height, uint32_t flags, ctl_scene_image_stats* stats);
+    // ctl_scene_read_image: level 0 and the pyramid of one image as the pool holds them; texels_out may be null (the level table alone)
+    void read_image(uint32_t image, uint32_t* texels_out, size_t capacity, uint32_t* levels_out, uint32_t* level_offsets_out);
     void read_lights(ctl_light* lights_out, uint32_t n_lights, uint8_t* anim_out, size_t n_anim_bytes);   // ctl_scene_read_lights: the light table and the anim blob as HBM holds them
     // the participating media (scene_volumes.h): the kernel argument as the last creation / update left it (n == 0: no media), read at every pass by the PathTracer plugin
     // and by the WavefrontPathTracer with ParticipatingMedia = true; whoever runs no medium code refuses a scene that has media instead of rendering it without them: unsupported_error naming `who` and the PathTracer plugin
@@ -119,6 +125,9 @@ private:
     bool launch_shape_sets(const ctl_scene_desc& d);       // the shape-set kernels of every light on a node of a mesh in skin_lights_, by d's lights and node transforms
     void run_shape_sets(const ctl_scene_desc& d);          // the same between two events; waits for them and sets last_shape_set_ms_
     std::set<uint32_t> skin_lights_; dbuf<float2> shape_lut_; float last_shape_set_ms_ = 0;   // meshes bound with CTL_SKIN_AREA_LIGHTS; shape_normal_lut (shape_set.h) in HBM
+    // the texel pool on the host side: per image the offset of its level 0 in texels_, its level table and {r, g, b, 1} of ImageTexture::Average() (mip_image_average) — what
+    // update_image re-runs material_update_textures with; env_scratch_: one colSum per row of the environment map and rowSum
+    std::vector<size_t> image_off_; std::vector<dev_mip_levels> image_levels_; std::vector<float> image_avg_; dbuf<float> env_scratch_;
     bool lights_stale_ = false;   // an emissive skin was unbound: lights_ / anim_ hold no description's values, the next update uploads them whatever the diff says
     ctl_scene_update_stats last_update_{}; uint32_t last_mask_ = 0;
     std::unique_ptr<desc_snapshot> snap_;

@@ -206,6 +206,11 @@ Scene::Scene(const ctl_scene_desc& d, bool flatten, int flat_format, bool reduce
             std::memcpy(&lv[i], &L, sizeof(L));
         }
         if (!pool.empty()) texels_.upload(pool.data(), pool.size()); else texels_.alloc(4);
+        image_off_ = off; image_levels_.assign(lv.begin(), lv.begin() + d.n_images); image_avg_.assign((size_t)d.n_images * 4, 0.0f);   // what ctl_scene_update_image starts from (scene_images.hip)
+        for (uint32_t i = 0; i < d.n_images; i++) {
+            mip_level_table L; std::memcpy(&L, &lv[i], sizeof(L));
+            mip_texel_decode(pool[off[i] + mip_average_texel_offset(d.images[i], L)], d.images[i].texel_type, &image_avg_[(size_t)i * 4]); image_avg_[(size_t)i * 4 + 3] = 1.0f;
+        }
         std::vector<ctl_mipmap> tab(d.n_images);
         for (uint32_t i = 0; i < d.n_images; i++) { tab[i] = d.images[i]; tab[i].texels = texels_.p + off[i]; }
         if (d.n_images) images_.upload(tab.data(), tab.size()); else images_.alloc(1);

@@ -383,6 +383,17 @@ int ctl_builder_set_node_transform(ctl_builder* b, uint32_t node_index, const ct
  * CTL_ERR_INVALID (a bad mesh index, another triangle count, an index out of range) leaves the builder untouched. */
 int ctl_builder_update_mesh(ctl_builder* b, uint32_t mesh_index, const float* positions, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri,
                             const float* normals, const float* uvs);
+/* DynamicScene::ReloadTextures (Engine/DynamicScene.cpp:457-) for a host that supplies the bitmap: new level-0 texels for the registered image `image_index`.  width and
+ * height must be the image's; texel type, wrap and filter mode stay.  If the image is the environment map's, the light's column and row CDFs are rewritten where they stand
+ * in the anim blob and its `normalization` in its record (rowWeights depends on the height only and stays).  The sampling weights of the materials that read the image's
+ * average (plastic, roughplastic, phong, ward, coating, roughcoating) are made by the next ctl_builder_finalize, as always.  This is the host yardstick of
+ * ctl_scene_update_image (below), and what a host that keeps its builder calls beside it, so that the next ctl_scene_update finds no difference.
+ * CTL_ERR_INVALID (a null builder or texels, a bad index, another width or height) leaves the builder untouched. */
+int ctl_builder_update_image(ctl_builder* b, uint32_t image_index, const uint32_t* texels, uint32_t width, uint32_t height);
+/* The pyramid a scene keeps of an image (MIPMap::CompileToBinary, Engine/MIPMap.cpp:41-95), host only: level 0 followed by levels 1 .. into texels_out[capacity]
+ * (may be NULL: the level table alone), *levels_out = 1 + floor(log2(min(width, height))), level_offsets_out[l - 1] = the texel offset of level l >= 1; level l is
+ * (width >> l) x (height >> l).  CTL_ERR_INVALID: a null or empty image, an unknown texel type, a capacity below the pyramid's texel count. */
+int ctl_mip_pyramid_host(const ctl_mipmap* image, uint32_t* texels_out, size_t capacity, uint32_t* levels_out, uint32_t level_offsets_out[15]);
 
 /* ------------------------------------------------------------------- scenes */
 typedef struct ctl_scene ctl_scene;
@@ -511,6 +522,31 @@ int ctl_scene_unbind_skin(ctl_scene* scene, uint32_t mesh_index);
 int ctl_skin_mesh_host(const ctl_scene_desc* desc, uint32_t mesh_index, const float* rest_positions, const float* rest_normals, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri,
                        const uint8_t* bone_indices, const uint8_t* bone_weights, uint32_t n_bones, const ctl_float4x4* bones0, const ctl_float4x4* bones1, float lerp,
                        float* positions_out, float* normals_out, ctl_triangle_data* tri_data_out, ctl_woop_tri* woop_out);
+/* ---- images in place: DynamicScene::ReloadTextures + UpdateMaterialsPhase2 (Engine/DynamicScene.cpp:457-, :84-89) on a live scene (csrc/scene_images.hip; INTEGRATION.md
+ * "Updating an image").  ctl_scene_update_image replaces the level-0 texels of image `image_index` — width and height must be the image's; texel type, wrap and filter mode
+ * stay — and rebuilds, in place, in the scene's own texel pool, anim blob, light table and material table, everything the library derives from texels:
+ *   1. level 0 into the image's slot of the pool: a host -> device copy, or device -> device with CTL_IMAGE_TEXELS_DEVICE (`texels` is then a device pointer:
+ *      ctl_device_malloc, a torch tensor);
+ *   2. the pyramid, one kernel launch per level (csrc/mip_texel.h: decode, ((a + b) + c) + e, times 0.25, encode — the host builder's own functions);
+ *   3. the sampling weights of the materials whose BSDF::Update() reads the image's average (ImageTexture::Average(): one texel of the coarsest level, read back), made on
+ *      the host and patched into the device records that changed;
+ *   4. if the image is an environment light's: cdfCols, cdfRows (csrc/env_tables.h; the running sums stay serial, one lane per row, in the reference's order) and the
+ *      record's `normalization`.  A row of the map without luminance gives the reference's 1 / 0 and 0 * inf: the NaN entries of such a row may differ from a host-built
+ *      description's in their payload bits;
+ *   5. the scene's host copy of the description: materials, the light record, the table ranges of the anim blob (read back) and the image's digest (from `texels`, or from a
+ *      read-back under CTL_IMAGE_TEXELS_DEVICE).
+ * Afterwards the scene equals, bit for bit, one created from the description of a builder that went through ctl_builder_update_image + ctl_builder_finalize, and
+ * ctl_scene_desc_diff / ctl_scene_update against that description find nothing.  It takes no description and works on any scene, two-level or flattened, for every plugin.
+ * Synchronous, like ctl_scene_update: call it between passes and start the next pass with new_trace.  ctl_scene_desc_diff and ctl_scene_update still call another texel in a
+ * description CTL_DIFF_TOPOLOGY.  stats_out (may be NULL): wall-clock times of the steps, each ended by a device synchronisation (env_ms includes the read-back of the tables).
+ *   CTL_ERR_NO_DEVICE    no device (checked first)
+ *   CTL_ERR_INVALID      a null scene or texels, a bad image index, another width or height, an unknown flag bit: before the device is touched, the scene stays as it was
+ * ctl_scene_read_image copies back level 0 and the pyramid of an image as the pool holds them, with the arguments and the layout of ctl_mip_pyramid_host. */
+enum { CTL_IMAGE_TEXELS_DEVICE = 1 };   /* `texels` is a device pointer */
+typedef struct { uint32_t levels, texels_written, materials_patched, env_tables;
+                 float upload_ms, pyramid_ms, env_ms, hash_ms, total_ms; } ctl_scene_image_stats;
+int ctl_scene_update_image(ctl_scene* scene, uint32_t image_index, const uint32_t* texels, uint32_t width, uint32_t height, uint32_t flags, ctl_scene_image_stats* stats_out);
+int ctl_scene_read_image(ctl_scene* scene, uint32_t image_index, uint32_t* texels_out, size_t capacity, uint32_t* levels_out, uint32_t level_offsets_out[15]);
 /* On-disk cache of compiled geometry — the role of the reference's .xmsh files (Engine/Mesh.cpp:46-98,199-290; DynamicScene::CreateNode
  * compiles a mesh only when its .xmsh is missing).  With a directory set, ctl_builder_add_mesh stores / reloads a compiled mesh
  * (TriangleData, BVH nodes, Woop rows) and CTL_SCENE_FLATTEN stores / reloads the flattened BVH, both keyed by a hash of their
