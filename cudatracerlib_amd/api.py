@@ -310,6 +310,17 @@ class FlatBvh:
         _check(lib.ctl_flat_bvh_arrays(self._h, C.byref(self.desc)))
         return self
 
+    def update_meshes(self, desc, old_of_new, builder="lbvh"):
+        """ctl_flat_bvh_update_meshes[_ex]: as update_nodes, for a description that also APPENDS meshes (csrc/flat_meshes.h) — the yardstick of Scene.update_meshes.
+        A refusal leaves the handle as it was.  Returns self."""
+        M = np.ascontiguousarray(old_of_new, dtype=np.uint32)
+        b = rebuild_builder(builder)
+        _check(lib.ctl_flat_bvh_update_meshes(self._h, C.byref(desc), M.ctypes.data, u32(len(M))) if b == REBUILD_LBVH else
+               lib.ctl_flat_bvh_update_meshes_ex(self._h, C.byref(desc), M.ctypes.data, u32(len(M)), b))
+        self._keepalive = desc
+        _check(lib.ctl_flat_bvh_arrays(self._h, C.byref(self.desc)))
+        return self
+
     def levels(self):
         """ctl_flat_bvh_levels: (level_start (n_levels + 1,), level_nodes (n_nodes,)) uint32 copies — the nodes by depth as a refit walks them"""
         ls, ln = C.POINTER(u32)(), C.POINTER(u32)(); nl, nn = u32(), u64()
@@ -770,7 +781,8 @@ class DynamicScene:
             self._h = None
 
     def add_mesh(self, positions, indices=None, normals=None, uvs=None, tri_material=None, materials=None):
-        """Mesh::CompileMesh (Engine/Mesh.cpp:199-290) -> mesh index."""
+        """Mesh::CompileMesh (Engine/Mesh.cpp:199-290) -> mesh index.  After a first UpdateScene() the call appends to the builder's arrays: the next UpdateScene()
+        gives the description that Scene.update_meshes applies to a scene made from the earlier one."""
         P = _f32(positions, (-1, 3))
         I = None if indices is None else np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1, 3)
         n_tri = len(P) // 3 if I is None else len(I)
@@ -1041,6 +1053,44 @@ class Scene:
         out["rebuild"]["rounds"] = _last_rounds() if st.rebuilt else 0
         return out
 
+    def triangle_rows(self):
+        """ctl_scene_read_triangle_rows (test hook): the triangle -> row table as HBM holds it, uint32 per triangle, or None while the scene has none"""
+        n = C.c_size_t(0)
+        _check(lib.ctl_scene_read_triangle_rows(self._h, None, 0, C.byref(n)))
+        if not n.value:
+            return None
+        rows = np.zeros(n.value, np.uint32)
+        _check(lib.ctl_scene_read_triangle_rows(self._h, rows.ctypes.data, n.value, C.byref(n)))
+        return rows
+
+    def update_meshes(self, sc_or_desc, old_of_new=None, builder="lbvh"):
+        """ctl_scene_update_meshes: NEW meshes in place — after DynamicScene.add_mesh on a builder whose description the scene holds, any CreateNode / DeleteNode, and
+        UpdateScene().  The geometry arrays grow on the device (csrc/flat_meshes.hip: the old contents are copied there, so deformed and posed meshes keep their shape),
+        then the stages of update_nodes run; with nothing appended the call is update_nodes.  Arguments as update_nodes takes them.
+        Returns the stats dict: meshes_added, triangles_added, rows_added, bvh_nodes_added, append_ms, hash_ms, nodes = the update_nodes dict.
+        CtlError(ERR_INVALID / ERR_UNSUPPORTED) leaves the scene as it was.  Start the next pass with new_trace."""
+        desc = sc_or_desc.getKernelSceneData() if isinstance(sc_or_desc, DynamicScene) else sc_or_desc
+        if old_of_new is None:
+            new_ids = getattr(desc, "node_ids", None)
+            if new_ids is None or self._node_ids is None:
+                raise ValueError("update_meshes: no node ids on the descriptions (DynamicScene.UpdateScene sets them): pass old_of_new")
+            index = {i: k for k, i in enumerate(self._node_ids)}
+            old_of_new = [index.get(i, 0xffffffff) for i in new_ids]
+        M = np.ascontiguousarray(old_of_new, dtype=np.uint32)
+        st = ctl_scene_meshes_stats()
+        b = rebuild_builder(builder)
+        _check(lib.ctl_scene_update_meshes(self._h, C.byref(desc), M.ctypes.data, u32(len(M)), C.addressof(st)) if b == REBUILD_LBVH else
+               lib.ctl_scene_update_meshes_ex(self._h, C.byref(desc), M.ctypes.data, u32(len(M)), b, C.addressof(st)))
+        self._keepalive = desc
+        self._node_ids = getattr(desc, "node_ids", None)
+        self._light_counts = (int(desc.n_lights_buf), int(desc.n_anim_bytes))
+        self._mesh_counts = mesh_counts(desc)
+        out = {k: getattr(st, k) for k, _ in st._fields_ if k != "nodes"}
+        out["nodes"] = {k: getattr(st.nodes, k) for k, _ in st.nodes._fields_ if k != "rebuild"}
+        out["nodes"]["rebuild"] = {k: getattr(st.nodes.rebuild, k) for k, _ in st.nodes.rebuild._fields_}
+        out["nodes"]["rebuild"]["rounds"] = _last_rounds() if st.nodes.rebuilt else 0
+        return out
+
     def update_stats(self):
         """ctl_scene_get_update_stats of the last update: dict(node_area_before, node_area_after, refit_ms, refit_levels, mask, restamped)"""
         st = ctl_scene_update_stats()
@@ -1196,6 +1246,10 @@ class ctl_scene_nodes_stats(C.Structure):
                 ("rebuild", ctl_scene_rebuild_stats), ("edit_ms", f32), ("total_ms", f32)]
 
 
+class ctl_scene_meshes_stats(C.Structure):
+    _fields_ = [("meshes_added", u32), ("triangles_added", u32), ("rows_added", u32), ("bvh_nodes_added", u32), ("append_ms", f32), ("hash_ms", f32), ("nodes", ctl_scene_nodes_stats)]
+
+
 # (declared only where the library has them: tools/ab_bench.py loads the parent commit's library through $CTL_AMD_LIB for a same-box A/B of bench.py, which calls none
 # of them; calling one on such a library raises AttributeError)
 for _n, _a in (("ctl_scene_rebuild_flat", [C.c_void_p, C.c_void_p]), ("ctl_flat_bvh_rebuild", [C.c_void_p, C.c_void_p]), ("ctl_flat_bvh_levels", [C.c_void_p] * 5),
@@ -1210,7 +1264,10 @@ for _n, _a in (("ctl_scene_rebuild_flat", [C.c_void_p, C.c_void_p]), ("ctl_flat_
                ("ctl_shape_sets_host", [C.c_void_p, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
                ("ctl_builder_update_image", [C.c_void_p, u32, C.c_void_p, u32, u32]), ("ctl_mip_pyramid_host", [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
                ("ctl_scene_update_image", [C.c_void_p, u32, C.c_void_p, u32, u32, u32, C.c_void_p]),
-               ("ctl_scene_read_image", [C.c_void_p, u32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p])):
+               ("ctl_scene_read_image", [C.c_void_p, u32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+               ("ctl_scene_update_meshes", [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_void_p]), ("ctl_scene_update_meshes_ex", [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_int, C.c_void_p]),
+               ("ctl_flat_bvh_update_meshes", [C.c_void_p, C.c_void_p, C.c_void_p, u32]), ("ctl_flat_bvh_update_meshes_ex", [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_int]),
+               ("ctl_triangle_woop_rows", [C.c_void_p, C.c_void_p]), ("ctl_scene_read_triangle_rows", [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]), ("ctl_append_leaf_rows_host", [C.c_void_p, u32, u32, u32, u32, C.c_void_p, C.c_void_p])):
     if hasattr(lib, _n):
         getattr(lib, _n).argtypes = _a
 if hasattr(lib, "ctl_rebuild_last_rounds"):
@@ -1295,6 +1352,22 @@ def mip_pyramid_host(texels, texel_type=TEXEL_RGBCOL):
     T = np.zeros(n, np.uint32)
     _check(lib.ctl_mip_pyramid_host(C.addressof(m), T.ctypes.data, C.c_size_t(n), C.byref(levels), off))
     return dict(texels=T, levels=levels.value, offsets=np.array(off[:], np.uint32))
+
+
+def triangle_woop_rows(desc):
+    """ctl_triangle_woop_rows: per triangle the first row of the two-level leaf stream that names it (0xffffffff: none)"""
+    rows = np.zeros(desc.n_tri_data, np.uint32)
+    _check(lib.ctl_triangle_woop_rows(C.byref(desc), rows.ctypes.data))
+    return rows
+
+
+def append_leaf_rows_host(new_desc, old_desc, old_rows):
+    """ctl_append_leaf_rows_host: the arithmetic of k_append_leaf_rows (csrc/flat_meshes.h) on the host for what new_desc appends to old_desc; old_rows: the table of
+    old_desc.  Returns (the table of new_desc.n_tri_data words, the appended 64-B leaf-stream rows as (rows, 16) uint32)"""
+    table = np.zeros(new_desc.n_tri_data, np.uint32); table[:old_desc.n_tri_data] = old_rows
+    leaf = np.zeros((new_desc.n_woop - old_desc.n_woop, 16), np.uint32)
+    _check(lib.ctl_append_leaf_rows_host(C.byref(new_desc), u32(old_desc.n_meshes), u32(old_desc.n_tri_data), u32(old_desc.n_woop), u32(old_desc.n_bvh_nodes), table.ctypes.data, leaf.ctypes.data))
+    return table, leaf
 
 
 def mesh_counts(desc):

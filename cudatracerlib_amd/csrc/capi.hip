@@ -10,6 +10,8 @@
 #include "flatten.h"
 #include "flat_rebuild.h"
 #include "flat_nodes.h"
+#include "flat_meshes.h"
+#include "flat_device.h"
 #include "mesh_skin.h"
 #include "shape_set.h"
 #include "material_factory.h"
@@ -513,6 +515,40 @@ int ctl_flat_bvh_update_nodes_ex(ctl_flat_bvh* h, const ctl_scene_desc* new_desc
 }
 int ctl_flat_bvh_update_nodes(ctl_flat_bvh* h, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes) {
     return ctl_flat_bvh_update_nodes_ex(h, new_desc, old_of_new, n_new_nodes, CTL_REBUILD_LBVH);
+}
+// ---- new meshes (flat_meshes.hip, flat_meshes.cpp)
+int ctl_scene_update_meshes_ex(ctl_scene* scene, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes, int builder, ctl_scene_meshes_stats* stats_out) {
+    if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
+    CTL_REQUIRE(scene && new_desc, "null argument");
+    CTL_REQUIRE(old_of_new, "ctl_scene_update_meshes: null node map");
+    CTL_REQUIRE(known_builder(builder), "ctl_scene_update_meshes_ex: unknown builder");
+    const int rc = [&]() -> int { CTL_TRY rebuild_builder_scope use(builder); flat_rebuilder::update_meshes(scene->s, *new_desc, old_of_new, n_new_nodes, scene->basis, stats_out); CTL_CATCH }();
+    if (rc == CTL_OK) { scene->n_materials = new_desc->n_materials; scene->n_images = new_desc->n_images; scene->basis.fill(*new_desc); }
+    return rc;
+}
+int ctl_scene_update_meshes(ctl_scene* scene, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes, ctl_scene_meshes_stats* stats_out) {
+    return ctl_scene_update_meshes_ex(scene, new_desc, old_of_new, n_new_nodes, CTL_REBUILD_LBVH, stats_out);
+}
+int ctl_flat_bvh_update_meshes_ex(ctl_flat_bvh* h, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes, int builder) {
+    CTL_REQUIRE(h && new_desc, "null argument");
+    CTL_REQUIRE(known_builder(builder), "ctl_flat_bvh_update_meshes_ex: unknown builder");
+    CTL_TRY update_meshes_flat_scene(h->f, h->basis, *new_desc, old_of_new, n_new_nodes, h->extra_missing, builder); h->basis.fill(*new_desc); CTL_CATCH
+}
+int ctl_flat_bvh_update_meshes(ctl_flat_bvh* h, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes) {
+    return ctl_flat_bvh_update_meshes_ex(h, new_desc, old_of_new, n_new_nodes, CTL_REBUILD_LBVH);
+}
+int ctl_scene_read_triangle_rows(ctl_scene* scene, uint32_t* rows_out, size_t capacity, size_t* count_out) {
+    if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
+    CTL_REQUIRE(scene && count_out, "null argument");
+    CTL_TRY *count_out = flat_rebuilder::read_tri_rows(scene->s, rows_out, capacity); CTL_CATCH
+}
+int ctl_triangle_woop_rows(const ctl_scene_desc* desc, uint32_t* rows_out) {
+    CTL_REQUIRE(desc && rows_out, "null argument");
+    CTL_TRY std::vector<uint32_t> rows; triangle_woop_rows(*desc, rows); if (!rows.empty()) std::memcpy(rows_out, rows.data(), rows.size() * 4); CTL_CATCH
+}
+int ctl_append_leaf_rows_host(const ctl_scene_desc* new_desc, uint32_t old_n_meshes, uint32_t old_n_tri_data, uint32_t old_n_woop, uint32_t old_n_bvh_nodes, uint32_t* tri_row, uint32_t* leaf_rows_out) {
+    CTL_REQUIRE(new_desc && tri_row, "null argument");
+    CTL_TRY mesh_set_plan P; plan_mesh_growth(old_n_meshes, old_n_tri_data, old_n_woop, old_n_bvh_nodes, *new_desc, "ctl_append_leaf_rows_host: ", P); append_leaf_rows_host(*new_desc, P, leaf_rows_out, tri_row); CTL_CATCH
 }
 int ctl_flat_bvh_levels(const ctl_flat_bvh* h, const uint32_t** level_start, uint32_t* n_levels, const uint32_t** level_nodes, uint64_t* n_level_nodes) {
     CTL_REQUIRE(h && level_start && n_levels && level_nodes && n_level_nodes, "null argument");

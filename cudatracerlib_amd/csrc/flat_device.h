@@ -13,6 +13,12 @@ namespace ctl {
 template <typename T> void swap_buffers(dbuf<T>& a, dbuf<T>& b) { std::swap(a.p, b.p); std::swap(a.n, b.n); }
 inline dim3 blocks_for(size_t n) { return dim3((unsigned)((n + 255u) / 256u)); }
 
+// what the node-set stages (flat_rebuilder::apply_node_set, flat_nodes.hip) read of the two-level geometry: the scene's own arrays (Scene::update_nodes) or grown ones that are not
+// the scene's yet (flat_rebuilder::update_meshes).  Counts in elements of the pointer's type; tri_row may be null (see apply_node_set)
+struct node_set_view { const float4* leaf_tris; size_t n_leaf_tris; const uint4* tri_data; const uint32_t* tri_row; size_t n_tri_row; };
+// the geometry arrays of a scene with appended meshes (flat_meshes.hip), in buffers of their own until apply_node_set swaps them in; tri_row: null on a two-level scene
+struct mesh_growth { dbuf<uint4> tri_data; dbuf<float4> bot_nodes, leaf_tris; dbuf<uint32_t> tri_row; };
+
 // The rebuild of flat_rebuild.h on the device over n entries (and the closing entry behind them) that need not be the scene's own: ctl_scene_rebuild_flat runs it over
 // flat_leaves_, ctl_scene_update_nodes over the entries it has just assembled.  Three steps, so that a caller can put its own work between them:
 //   allocate   every buffer of the new tree; nothing of the scene is written (the scratch that has no meaning between calls — rocPRIM's storage, the entry boxes, the carry
@@ -32,6 +38,14 @@ struct flat_rebuilder {
     void run(Scene& A);
     void commit(Scene& A);
     void report(ctl_scene_rebuild_stats& st) const;
+    // The node-set stages behind Scene::update_nodes' checks (flat_nodes.hip), and ctl_scene_update_meshes (flat_meshes.hip): the growth of the geometry arrays for appended
+    // meshes in front of the same stages; with nothing appended it is Scene::update_nodes.  Both work on the scene's private buffers as the rebuild does.  They stand here,
+    // as static functions of the scene's friend, and not in class Scene: tracer.h is one of the sources of bench.py's traversal-kernel hash (KERNEL_BUILD), so a declaration
+    // there would retire the committed traffic profile for a change that touches no kernel the profile measures.
+    static void apply_node_set(Scene& A, const ctl_scene_desc& d, const uint32_t* old_of_new, const node_set_basis& basis, const node_set_plan& plan, const node_set_view& V, mesh_growth* grown,
+                               ctl_scene_nodes_stats* stats, const char* who);
+    static size_t read_tri_rows(Scene& A, uint32_t* rows_out, size_t capacity);   // ctl_scene_read_triangle_rows: the words of the scene's triangle -> row table (0: none yet)
+    static void update_meshes(Scene& A, const ctl_scene_desc& d, const uint32_t* old_of_new, uint32_t n_new_nodes, const node_set_basis& basis, ctl_scene_meshes_stats* stats);
     flat_rebuilder() {}
     flat_rebuilder(const flat_rebuilder&) = delete; flat_rebuilder& operator=(const flat_rebuilder&) = delete;
     ~flat_rebuilder();

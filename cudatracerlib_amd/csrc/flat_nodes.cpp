@@ -2,11 +2,13 @@
 // (update_nodes_flat_scene, what ctl_flat_bvh_update_nodes runs): the functions of flat_nodes.h and flat_rebuild.h in the device's order, so the device tree equals this
 // one byte for byte (tests/test_gpu_node_set.py).
 #include "flat_nodes.h"
+#include "flat_meshes.h"
 #include "flatten.h"
 #include "flat_rebuild.h"
 #include "scene_checks.h"
 #include "mitsuba_loader.h"   // unsupported_error
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -20,7 +22,7 @@ void node_set_basis::fill(const ctl_scene_desc& d) {
 }
 
 void plan_node_set(const node_set_basis& old, const geometry_hashes& old_geom, const ctl_scene_desc& nd, const uint32_t* old_of_new, uint32_t n_new_nodes,
-                   const std::vector<uint8_t>* device_owned, node_set_plan& out, const char* who_) {
+                   const std::vector<uint8_t>* device_owned, node_set_plan& out, const char* who_, mesh_set_plan* grow) {
     const std::string who = std::string(who_) + ": ";
     if (!old.filled) throw std::runtime_error(who + "the description the tree was made from is not known");
     // the map
@@ -40,10 +42,15 @@ void plan_node_set(const node_set_basis& old, const geometry_hashes& old_geom, c
         last = o; out.new_of_old[o] = k;
     }
     out.identity = n_new_nodes == n_old && out.added.empty();
-    // the geometry side must be the tree's own
-    if (nd.n_meshes != old.meshes.size() || (nd.n_meshes && std::memcmp(nd.meshes, old.meshes.data(), (size_t)nd.n_meshes * sizeof(ctl_kernel_mesh)) != 0))
+    // the geometry side must be the tree's own — or, where the caller takes appended meshes, the tree's own plus tails (flat_meshes.cpp)
+    if (grow) {
+        plan_mesh_growth((uint32_t)old.meshes.size(), old.n_tri_data, old.n_woop, old.n_bvh_nodes, nd, who, *grow);   // (n_meshes is at least the held count from here on)
+        if (!old.meshes.empty() && std::memcmp(nd.meshes, old.meshes.data(), old.meshes.size() * sizeof(ctl_kernel_mesh)) != 0)
+            throw std::runtime_error(who + "a mesh the scene holds has another record: meshes can be appended, not changed; re-create the scene");
+        out.identity = out.identity && !grow->grown();
+    } else if (nd.n_meshes != old.meshes.size() || (nd.n_meshes && std::memcmp(nd.meshes, old.meshes.data(), (size_t)nd.n_meshes * sizeof(ctl_kernel_mesh)) != 0))
         throw std::runtime_error(who + "the set of meshes differs: only meshes the scene already holds can be instanced; re-create the scene");
-    if (nd.n_tri_data != old.n_tri_data || nd.n_woop != old.n_woop || nd.n_bvh_nodes != old.n_bvh_nodes) throw std::runtime_error(who + "the geometry arrays have other sizes; re-create the scene");
+    if (!grow && (nd.n_tri_data != old.n_tri_data || nd.n_woop != old.n_woop || nd.n_bvh_nodes != old.n_bvh_nodes)) throw std::runtime_error(who + "the geometry arrays have other sizes; re-create the scene");
     if (nd.n_images != old.images.size() || (nd.rough_transmittance != nullptr) != old.rough_transmittance) throw std::runtime_error(who + "the images or transmittance tables differ; re-create the scene");
     for (uint32_t i = 0; i < nd.n_images; i++) {
         const ctl_mipmap &x = old.images[i], &y = nd.images[i];
@@ -59,7 +66,22 @@ void plan_node_set(const node_set_basis& old, const geometry_hashes& old_geom, c
             throw std::runtime_error(who + "kept node " + std::to_string(k) + " (was " + std::to_string(old_of_new[k]) + ") has another mesh or material assignment");
     }
     check_scene_desc(nd, kCheckAllParts, who_);   // what ctl_scene_desc_check refuses
-    if (!old_geom.empty()) {
+    if (!old_geom.empty() && grow && grow->grown()) {
+        // the held part: the same pointers under the old counts must hash to what the tree holds; then the whole description's hashes, which the tree holds from now on
+        const auto t0 = std::chrono::steady_clock::now();
+        const uint32_t n_held = (uint32_t)old.meshes.size();
+        if (device_owned && device_owned->size() != n_held) device_owned = nullptr;
+        ctl_scene_desc held = nd; held.n_meshes = n_held; held.n_tri_data = old.n_tri_data; held.n_woop = old.n_woop; held.n_bvh_nodes = old.n_bvh_nodes;
+        geometry_hashes hg; hash_geometry(held, hg, device_owned);
+        std::vector<uint8_t> owned_all; if (device_owned) { owned_all = *device_owned; owned_all.resize(nd.n_meshes, 0); }
+        hash_geometry(nd, out.geom, device_owned ? &owned_all : nullptr);
+        if (device_owned && hg.values.size() == old_geom.values.size())
+            for (uint32_t m = 0; m < n_held; m++) if ((*device_owned)[m]) { hg.values[2 * m] = out.geom.values[2 * m] = old_geom.values[2 * m]; hg.values[2 * m + 1] = out.geom.values[2 * m + 1] = old_geom.values[2 * m + 1]; }
+        grow->hash_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (!hg.same_structure(old_geom)) throw std::runtime_error(who + "the structure of the geometry arrays the scene holds (woop_index, mesh BVH links, texels, transmittance tables) differs; re-create the scene");
+        for (uint32_t m = 0; m < n_held; m++) if (!hg.same_values(old_geom, m))
+            throw std::runtime_error(who + "mesh " + std::to_string(m) + " has other vertex values than the scene holds: apply them with ctl_scene_update first");
+    } else if (!old_geom.empty()) {
         if (device_owned && device_owned->size() != nd.n_meshes) device_owned = nullptr;
         hash_geometry(nd, out.geom, device_owned);
         if (device_owned && out.geom.values.size() == old_geom.values.size())
@@ -86,6 +108,11 @@ void update_nodes_flat_scene(flat_scene& F, const node_set_basis& old, const ctl
     rebuild_refuse(F.format, F.refit.ready() && F.refit.part_index.size() == F.leaves.size(), F.compact_links, F.leaves.size(), who);
     node_set_plan plan;
     plan_node_set(old, F.refit.geom, nd, old_of_new, n_new_nodes, nullptr, plan, who);
+    apply_node_set_flat(F, old, nd, old_of_new, n_new_nodes, plan, extra_missing, builder, who);
+}
+
+void apply_node_set_flat(flat_scene& F, const node_set_basis& old, const ctl_scene_desc& nd, const uint32_t* old_of_new, uint32_t n_new_nodes, const node_set_plan& plan,
+                         std::vector<uint32_t>& extra_missing, int builder, const char* who) {
     if (old.nodes.size() != F.refit.xf0.size()) throw std::runtime_error(std::string(who) + ": the handle's description has another number of nodes than its tree");
     if (plan.identity) {   // as ctl_scene_update: a refit where a node has moved, else nothing (the geometry values are the tree's own: plan_node_set)
         bool moved = false;

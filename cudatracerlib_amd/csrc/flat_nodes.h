@@ -71,11 +71,18 @@ struct node_set_plan {
 };
 // Everything both callers refuse before anything is written (std::runtime_error -> CTL_ERR_INVALID): the map, the kept nodes' mesh / material assignment, the mesh set,
 // counts, images and tables, the geometry structure and — outside device-owned meshes — values, check_scene_desc of the new description.
+// grow (null: the rules above, unchanged): the description may APPEND meshes (flat_meshes.h; ctl_scene_update_meshes) — n_meshes and the three geometry counts at least the
+// held ones, the held mesh records a byte-equal prefix, every appended mesh wholly behind the old ends of the arrays, the hashes of the description restricted to the old
+// counts equal to the held ones; `*grow` receives what is appended.  `identity` then also needs nothing appended.  device_owned holds one byte per HELD mesh.
+struct mesh_set_plan;
 void plan_node_set(const node_set_basis& old, const geometry_hashes& old_geom, const ctl_scene_desc& nd, const uint32_t* old_of_new, uint32_t n_new_nodes,
-                   const std::vector<uint8_t>* device_owned, node_set_plan& out, const char* who);
+                   const std::vector<uint8_t>* device_owned, node_set_plan& out, const char* who, mesh_set_plan* grow = nullptr);
 // the host yardstick (ctl_flat_bvh_update_nodes): steps 1 - 4 on a host handle, the Woop rows from `nd`.  extra_missing: the triangles step 2 skipped are merged in
 // (ascending, unique).  Refusals leave F as it was; an identity map is refit_flat_scene(F, nd) where a node has moved, else nothing.
 struct flat_scene;
 void update_nodes_flat_scene(flat_scene& F, const node_set_basis& old, const ctl_scene_desc& nd, const uint32_t* old_of_new, uint32_t n_new_nodes, std::vector<uint32_t>& extra_missing, int builder = 0);   // builder: CTL_REBUILD_LBVH (0) or CTL_REBUILD_PLOC
+// the same after the checks: `plan` is plan_node_set's answer for these arguments (update_meshes_flat_scene, flat_meshes.cpp, comes here with a plan that appends meshes)
+void apply_node_set_flat(flat_scene& F, const node_set_basis& old, const ctl_scene_desc& nd, const uint32_t* old_of_new, uint32_t n_new_nodes, const node_set_plan& plan,
+                         std::vector<uint32_t>& extra_missing, int builder, const char* who);
 
 }  // namespace ctl

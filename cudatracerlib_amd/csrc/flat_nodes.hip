@@ -107,22 +107,31 @@ void Scene::update_nodes(const ctl_scene_desc& d, const uint32_t* old_of_new, ui
     const std::vector<uint8_t> device_owned = device_owned_meshes();
     node_set_plan plan;
     plan_node_set(basis, snap_->geom, d, old_of_new, n_new_nodes, device_owned.empty() ? nullptr : &device_owned, plan, who);
-    const uint32_t n_old_nodes = snap_->d.n_nodes;
-    if (basis.nodes.size() != n_old_nodes || (flat && refit_.xf0.size() != n_old_nodes)) throw std::runtime_error(std::string(who) + ": the scene's description has another number of nodes than its tree");
-    ctl_scene_nodes_stats st{}; st.entries_before = st.entries_after = flat ? (uint32_t)flat_n_entries_ : 0u;
+    const node_set_view V{ leaf_tris_.p, leaf_tris_.n, tri_data_.p, refit_tri_row_.p, refit_tri_row_.n };
+    flat_rebuilder::apply_node_set(*this, d, old_of_new, basis, plan, V, nullptr, stats, who);
+}
+
+// the stages behind the checks.  V: the two-level arrays the stages read — the scene's own, or grown ones (`grown`, flat_meshes.hip) that become the scene's where the new tree
+// is committed; V.tri_row null on a flattened scene: the scene has no triangle -> row table yet and gets one from `d` here
+void flat_rebuilder::apply_node_set(Scene& A, const ctl_scene_desc& d, const uint32_t* old_of_new, const node_set_basis& basis, const node_set_plan& plan, const node_set_view& V, mesh_growth* grown,
+                           ctl_scene_nodes_stats* stats, const char* who) {
+    const bool flat = A.flattened();
+    const uint32_t n_old_nodes = A.snap_->d.n_nodes;
+    if (basis.nodes.size() != n_old_nodes || (flat && A.refit_.xf0.size() != n_old_nodes)) throw std::runtime_error(std::string(who) + ": the scene's description has another number of nodes than its tree");
+    ctl_scene_nodes_stats st{}; st.entries_before = st.entries_after = flat ? (uint32_t)A.flat_n_entries_ : 0u;
     if (plan.identity) {   // nothing of the node set changes: ctl_scene_update, no rebuild
-        update(d, nullptr);
+        A.update(d, nullptr);
         if (stats) *stats = st;
         return;
     }
     // host work before the device is touched: the instance records, the creation poses, the carry matrices
     const shading_state shade = derive_shading_state(d);
     std::vector<float4> inst, fwd; std::vector<uint4> ninfo;
-    pack_instances(d, inst, fwd, ninfo);
+    Scene::pack_instances(d, inst, fwd, ninfo);
     std::vector<ctl_float4x4> xf0(d.n_nodes); std::vector<double> P;
     if (flat) {
-        for (uint32_t k = 0; k < d.n_nodes; k++) xf0[k] = old_of_new[k] == kNodesNone ? d.node_transforms[k] : refit_.xf0[old_of_new[k]];
-        P = carry_matrices(d, xf0, who);
+        for (uint32_t k = 0; k < d.n_nodes; k++) xf0[k] = old_of_new[k] == kNodesNone ? d.node_transforms[k] : A.refit_.xf0[old_of_new[k]];
+        P = Scene::carry_matrices(d, xf0, who);
     }
     CTL_HIP(hipDeviceSynchronize());   // no trace reads the arrays any more
     dbuf<float4> inst_new, fwd_new; dbuf<uint4> ninfo_new;
@@ -133,7 +142,7 @@ void Scene::update_nodes(const ctl_scene_desc& d, const uint32_t* old_of_new, ui
     rebuild_last_rounds() = 0u;
     flat_rebuilder B; B.builder = rebuild_builder_choice();   // what the C entry point asked for (rebuild_builder_scope, flat_rebuild.h)
     if (flat) {
-        const uint32_t n_old = (uint32_t)flat_n_entries_, n_added = (uint32_t)plan.added.size(), G = plan.added_base.back();
+        const uint32_t n_old = (uint32_t)A.flat_n_entries_, n_added = (uint32_t)plan.added.size(), G = plan.added_base.back();
         // ---- scratch of this call; the scene's tri_row table and rocPRIM storage are caches without a meaning of their own
         dbuf<uint32_t> map_dev, flags, pos, base_dev, tri0_dev, added_dev, gflags, gpos, part_mid; dbuf<float4> leaves_mid; dbuf<ctl_material> mats_tmp; dbuf<unsigned char> temp;
         map_dev.alloc(n_old_nodes); flags.alloc((size_t)n_old + 1); pos.alloc((size_t)n_old + 1); gflags.alloc((size_t)G + 1); gpos.alloc((size_t)G + 1);
@@ -141,27 +150,29 @@ void Scene::update_nodes(const ctl_scene_desc& d, const uint32_t* old_of_new, ui
         CTL_HIP(hipMemcpy(map_dev.p, plan.new_of_old.data(), (size_t)n_old_nodes * 4, hipMemcpyHostToDevice));
         CTL_HIP(hipMemcpy(base_dev.p, plan.added_base.data(), plan.added_base.size() * 4, hipMemcpyHostToDevice));
         if (n_added) { CTL_HIP(hipMemcpy(tri0_dev.p, plan.added_tri0.data(), (size_t)n_added * 4, hipMemcpyHostToDevice)); CTL_HIP(hipMemcpy(added_dev.p, plan.added.data(), (size_t)n_added * 4, hipMemcpyHostToDevice)); }
-        if (!refit_tri_row_.p) {   // triangle -> row of the leaf stream; woop_index is structure (the hashes matched): the table holds for every later update
+        const uint32_t* tri_row = V.tri_row; size_t n_tri_row = V.n_tri_row;
+        if (!tri_row) {   // triangle -> row of the leaf stream; woop_index is structure (the hashes matched): the table holds for every later update
             std::vector<uint32_t> rows; triangle_woop_rows(d, rows);
-            refit_tri_row_.upload(rows.data(), rows.size()); CTL_HIP(hipStreamSynchronize(nullptr));
+            A.refit_tri_row_.upload(rows.data(), rows.size()); CTL_HIP(hipStreamSynchronize(nullptr));
+            tri_row = A.refit_tri_row_.p; n_tri_row = A.refit_tri_row_.n;
         }
         size_t scan_bytes = 0;
         CTL_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, flags.p, pos.p, 0u, (size_t)std::max(n_old, G) + 1, rocprim::plus<uint32_t>(), (hipStream_t) nullptr));
-        if (rebuild_temp_.n < std::max<size_t>(scan_bytes, 16)) { temp.alloc(std::max<size_t>(scan_bytes, 16)); swap_buffers(rebuild_temp_, temp); temp.free(); }
+        if (A.rebuild_temp_.n < std::max<size_t>(scan_bytes, 16)) { temp.alloc(std::max<size_t>(scan_bytes, 16)); swap_buffers(A.rebuild_temp_, temp); temp.free(); }
         event_set ev;
         CTL_HIP(hipEventRecord(ev.e[0], nullptr));
         // 1. which entries stay, 2. which triangles of the added nodes get an entry; the two scans
-        hipLaunchKernelGGL(k_nodes_flag, blocks_for((size_t)n_old + 1), dim3(256), 0, nullptr, flat_leaves_.p, n_old, map_dev.p, n_old_nodes, flags.p);
-        const nodes_added D{ base_dev.p, tri0_dev.p, added_dev.p, n_added, G, refit_tri_row_.p, (uint32_t)refit_tri_row_.n, leaf_tris_.p, (uint32_t)(leaf_tris_.n / 4) };
+        hipLaunchKernelGGL(k_nodes_flag, blocks_for((size_t)n_old + 1), dim3(256), 0, nullptr, A.flat_leaves_.p, n_old, map_dev.p, n_old_nodes, flags.p);
+        const nodes_added D{ base_dev.p, tri0_dev.p, added_dev.p, n_added, G, tri_row, (uint32_t)n_tri_row, V.leaf_tris, (uint32_t)(V.n_leaf_tris / 4) };
         hipLaunchKernelGGL(k_nodes_candidates, blocks_for((size_t)G + 1), dim3(256), 0, nullptr, D, gflags.p);
         CTL_HIP(hipGetLastError());
-        exclusive_scan_u32(rebuild_temp_, flags.p, pos.p, (size_t)n_old + 1, who);
-        exclusive_scan_u32(rebuild_temp_, gflags.p, gpos.p, (size_t)G + 1, who);
+        exclusive_scan_u32(A.rebuild_temp_, flags.p, pos.p, (size_t)n_old + 1, who);
+        exclusive_scan_u32(A.rebuild_temp_, gflags.p, gpos.p, (size_t)G + 1, who);
         uint32_t n_kept = 0, n_gen = 0;
         CTL_HIP(hipMemcpy(&n_kept, pos.p + n_old, 4, hipMemcpyDeviceToHost)); CTL_HIP(hipMemcpy(&n_gen, gpos.p + G, 4, hipMemcpyDeviceToHost));
         if (n_kept > n_old || n_gen > G) throw std::runtime_error(std::string(who) + ": the positions handed out exceed the entry count");
         const uint64_t n_new64 = (uint64_t)n_kept + n_gen;
-        rebuild_refuse(S.flat_format, true, true, (size_t)n_new64, who);
+        rebuild_refuse(A.S.flat_format, true, true, (size_t)n_new64, who);
         const uint32_t n_new = (uint32_t)n_new64;
         if (n_gen < G) {   // the triangles without an entry join the scene's list (flat_missing_triangles)
             std::vector<uint32_t> f(G);
@@ -171,39 +182,44 @@ void Scene::update_nodes(const ctl_scene_desc& d, const uint32_t* old_of_new, ui
         // every allocation before the first entry is written
         leaves_mid.alloc(((size_t)n_new + 1) * 8); part_mid.alloc(n_new); mats_tmp.alloc(std::max<uint32_t>(1u, d.n_materials));
         B.who = who; B.n = n_new; B.src_leaves = leaves_mid.p; B.src_part = part_mid.p;
-        B.allocate(*this, P);
+        B.allocate(A, P);
         if (d.n_materials) CTL_HIP(hipMemcpy(mats_tmp.p, d.materials, (size_t)d.n_materials * sizeof(ctl_material), hipMemcpyHostToDevice));
-        const nodes_move M{ flat_leaves_.p, refit_part_index_.p, flags.p, pos.p, map_dev.p, n_old_nodes, n_old, n_new, leaves_mid.p, part_mid.p };
+        const nodes_move M{ A.flat_leaves_.p, A.refit_part_index_.p, flags.p, pos.p, map_dev.p, n_old_nodes, n_old, n_new, leaves_mid.p, part_mid.p };
         hipLaunchKernelGGL(k_nodes_move, blocks_for((size_t)n_old * 8), dim3(256), 0, nullptr, M);
         if (G) hipLaunchKernelGGL(k_nodes_generate, blocks_for(G), dim3(256), 0, nullptr, D, gflags.p, gpos.p, inst_new.p, d.n_nodes, n_kept, n_new, leaves_mid.p, part_mid.p);
         CTL_HIP(hipGetLastError());
-        CTL_HIP(hipMemcpyAsync(leaves_mid.p + (size_t)n_new * 8, flat_leaves_.p + (size_t)n_old * 8, 128, hipMemcpyDeviceToDevice, nullptr));   // the closing entry
+        CTL_HIP(hipMemcpyAsync(leaves_mid.p + (size_t)n_new * 8, A.flat_leaves_.p + (size_t)n_old * 8, 128, hipMemcpyDeviceToDevice, nullptr));   // the closing entry
         CTL_HIP(hipEventRecord(ev.e[1], nullptr));
         // the re-stamp, the entry boxes and 4. the rebuild, with the NEW instance records and materials (the scene still holds the old ones)
-        B.R.inst = inst_new.p; B.R.inst_fwd = fwd_new.p; B.R.restamp = (int)d.n_materials; B.R.leaf_keys = S.flat_leaf_keys; B.R.alpha_maps = (int)shade.alpha_maps;
-        B.R.tri_data = tri_data_.p; B.R.node_info = ninfo_new.p; B.R.mats = mats_tmp.p;
-        B.run(*this);   // (synchronises) a tree too deep is refused here: the scene as it was
+        B.R.inst = inst_new.p; B.R.inst_fwd = fwd_new.p; B.R.restamp = (int)d.n_materials; B.R.leaf_keys = A.S.flat_leaf_keys; B.R.alpha_maps = (int)shade.alpha_maps;
+        B.R.tri_data = V.tri_data; B.R.node_info = ninfo_new.p; B.R.mats = mats_tmp.p;
+        B.run(A);   // (synchronises) a tree too deep is refused here: the scene as it was
         CTL_HIP(hipEventRecord(ev.e[2], nullptr)); CTL_HIP(hipEventSynchronize(ev.e[2]));
         CTL_HIP(hipEventElapsedTime(&st.edit_ms, ev.e[0], ev.e[1])); CTL_HIP(hipEventElapsedTime(&st.total_ms, ev.e[0], ev.e[2]));
         st.entries_after = n_new; st.entries_dropped = n_old - n_kept; st.entries_generated = n_gen; st.degenerate_skipped = G - n_gen; st.rebuilt = 1u;
         B.report(st.rebuild);
         // ---- from here on the scene is written
-        B.commit(*this);
-        refit_.xf0 = xf0;
+        B.commit(A);
+        A.refit_.xf0 = xf0;
         if (!skipped.empty()) {
-            flat_missing_tris_.insert(flat_missing_tris_.end(), skipped.begin(), skipped.end());
-            std::sort(flat_missing_tris_.begin(), flat_missing_tris_.end()); flat_missing_tris_.erase(std::unique(flat_missing_tris_.begin(), flat_missing_tris_.end()), flat_missing_tris_.end());
+            A.flat_missing_tris_.insert(A.flat_missing_tris_.end(), skipped.begin(), skipped.end());
+            std::sort(A.flat_missing_tris_.begin(), A.flat_missing_tris_.end()); A.flat_missing_tris_.erase(std::unique(A.flat_missing_tris_.begin(), A.flat_missing_tris_.end()), A.flat_missing_tris_.end());
         }
     }
+    // appended meshes (flat_meshes.hip): the grown geometry arrays become the scene's — A.bind() below hands their addresses to the tracers, a bound skin reads them at its next pose
+    if (grown) {
+        swap_buffers(A.tri_data_, grown->tri_data); swap_buffers(A.bot_nodes_, grown->bot_nodes); swap_buffers(A.leaf_tris_, grown->leaf_tris);
+        if (grown->tri_row.p) swap_buffers(A.refit_tri_row_, grown->tri_row);
+    }
     // the rest of the description, block by block as ctl_scene_update applies it; the instance records go in by a swap of buffers
-    swap_buffers(inst_, inst_new); swap_buffers(inst_fwd_, fwd_new); swap_buffers(node_info_, ninfo_new);
-    set_shading_state(shade);
-    upload_materials(d); upload_lights(d); upload_top_level(d);
-    lights_stale_ = false; run_shape_sets(d);   // the lights of emissive skins: node indices by the new description, the pose stays (shape_set.hip)
-    if (flat) S.inst_w_one = inverse_transforms_have_w_one(d);
+    swap_buffers(A.inst_, inst_new); swap_buffers(A.inst_fwd_, fwd_new); swap_buffers(A.node_info_, ninfo_new);
+    A.set_shading_state(shade);
+    A.upload_materials(d); A.upload_lights(d); A.upload_top_level(d);
+    A.lights_stale_ = false; A.run_shape_sets(d);   // the lights of emissive skins: node indices by the new description, the pose stays (shape_set.hip)
+    if (flat) A.S.inst_w_one = inverse_transforms_have_w_one(d);
     CTL_HIP(hipDeviceSynchronize());
-    bind(d); n_nodes = d.n_nodes; set_camera(d);
-    snapshot(d, plan.geom.empty() ? nullptr : &plan.geom);
+    A.bind(d); A.n_nodes = d.n_nodes; A.set_camera(d);
+    A.snapshot(d, plan.geom.empty() ? nullptr : &plan.geom);
     if (stats) *stats = st;
 }
 

@@ -659,6 +659,41 @@ int ctl_flat_bvh_update_nodes(ctl_flat_bvh* h, const ctl_scene_desc* new_desc, c
  * refitted tree to fall back on, so the builder is the whole choice: INTEGRATION.md says which to ask for. */
 int ctl_scene_update_nodes_ex(ctl_scene* scene, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes, int builder, ctl_scene_nodes_stats* stats_out);
 int ctl_flat_bvh_update_nodes_ex(ctl_flat_bvh* h, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes, int builder);
+/* ---- NEW MESHES on a live scene (csrc/flat_meshes.h, flat_meshes.hip, flat_meshes.cpp; INTEGRATION.md "Adding meshes").  ctl_scene_update and ctl_scene_update_nodes
+ * refuse a description with another mesh set, and keep doing so; ctl_scene_update_meshes takes one that APPENDS meshes: new_desc is the scene's description after further
+ * ctl_builder_add_mesh calls (the builder only ever appends to tri_data, woop, woop_index, bvh_nodes and meshes) and any node-set edit ctl_scene_update_nodes takes —
+ * added nodes may instance held or appended meshes, an appended mesh may have no node.  old_of_new, n_new_nodes: as for ctl_scene_update_nodes.
+ * Accepted when: n_meshes, n_tri_data, n_woop and n_bvh_nodes are at least the held counts; the held mesh records are a byte-equal prefix of meshes; every appended mesh
+ * lies wholly behind the old ends of the arrays (tri_offset >= the held n_tri_data; bvh_tri_offset / 3 and bvh_index_offset >= the held n_woop; bvh_node_offset / 4 >= the
+ * held n_bvh_nodes) and inside the new ones, the first appended mesh starting, in each of the three arrays, exactly where the held elements end; the geometry hashes of new_desc restricted to the held
+ * counts equal the scene's (other VALUES in a held mesh that is not device-owned: ctl_scene_update first); images, transmittance tables, materials and kept nodes follow the
+ * rules of ctl_scene_update_nodes (a new mesh's materials may only name images the scene has); ctl_scene_desc_check accepts new_desc, the two-level stack depth with the
+ * new meshes' BVHs included.  Nothing appended: the call is ctl_scene_update_nodes, the append part of the stats zero.
+ * On the device: tri_data, the mesh BVH nodes, the two-level leaf stream and — where the scene has one — the triangle -> row table grow into NEW buffers: the old contents
+ * are copied device to device (deformed and posed values live nowhere else), the tails are uploaded in creation's layouts, k_append_leaf_rows interleaves the appended
+ * Woop rows with their index words and extends the table (the first row in stream order that names a triangle).  The node-set stages of ctl_scene_update_nodes then read
+ * the grown buffers, and the buffers become the scene's only after the new tree stands.  Any growth rebuilds the flattened tree, an identity node map included.
+ * During the call HBM holds a second copy of the three geometry arrays.  Tracers follow the new arrays; start the next pass with new_trace.  Bound meshes stay bound.
+ * Refusals leave the scene as it was: CTL_ERR_NO_DEVICE first; CTL_ERR_INVALID for wrong arguments and every rule above; CTL_ERR_UNSUPPORTED exactly where
+ * ctl_scene_update_nodes answers so.  A failed allocation leaves the scene as it was.  Removing meshes, new images and new tables still need a new scene.
+ * ctl_flat_bvh_update_meshes is the host yardstick (no GPU): the same acceptance, then ctl_flat_bvh_update_nodes' stages, which read the Woop rows from new_desc. */
+typedef struct {
+    uint32_t meshes_added, triangles_added, rows_added, bvh_nodes_added;   /* rows: of the two-level leaf stream (n_woop) */
+    float append_ms, hash_ms;      /* HIP events around the growth copies, the uploads and k_append_leaf_rows; host time hashing new_desc (twice: the held part, the whole) */
+    ctl_scene_nodes_stats nodes;   /* the stages that follow */
+} ctl_scene_meshes_stats;
+int ctl_scene_update_meshes(ctl_scene* scene, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes, ctl_scene_meshes_stats* stats_out);
+int ctl_scene_update_meshes_ex(ctl_scene* scene, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes, int builder, ctl_scene_meshes_stats* stats_out);
+int ctl_flat_bvh_update_meshes(ctl_flat_bvh* h, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes);
+int ctl_flat_bvh_update_meshes_ex(ctl_flat_bvh* h, const ctl_scene_desc* new_desc, const uint32_t* old_of_new, uint32_t n_new_nodes, int builder);
+/* test hooks (no GPU).  ctl_triangle_woop_rows: per triangle of desc->tri_data the first row of the leaf stream that names it, UINT32_MAX for none (n_tri_data words).
+ * ctl_append_leaf_rows_host: k_append_leaf_rows' arithmetic on the host for the rows new_desc appends to held counts — tri_row holds new_desc->n_tri_data words, the first
+ * old_n_tri_data of them the held table; leaf_rows_out (may be NULL) receives 16 words per appended row. */
+int ctl_triangle_woop_rows(const ctl_scene_desc* desc, uint32_t* rows_out);
+/* ctl_scene_read_triangle_rows (test hook): the triangle -> row table as HBM holds it.  *count_out = its words (0: the scene has none yet — the first geometry update,
+ * skin binding or node-set change makes it); rows_out (may be NULL) receives them when capacity is at least that. */
+int ctl_scene_read_triangle_rows(ctl_scene* scene, uint32_t* rows_out, size_t capacity, size_t* count_out);
+int ctl_append_leaf_rows_host(const ctl_scene_desc* new_desc, uint32_t old_n_meshes, uint32_t old_n_tri_data, uint32_t old_n_woop, uint32_t old_n_bvh_nodes, uint32_t* tri_row, uint32_t* leaf_rows_out);
 /* The flattened tree of a CTL_SCENE_FLATTEN scene copied back from HBM into a handle for ctl_flat_bvh_arrays, with the BSDF-model bits (28..31 of the index word)
  * and the alpha bit (31 of the node word) that ctl_scene_create_ex stamps into the device copy removed: the arrays the test oracle traverses. */
 int ctl_scene_read_flat_bvh(ctl_scene* scene, ctl_flat_bvh** out);

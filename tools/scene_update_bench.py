@@ -27,6 +27,9 @@ Per workload, on one GPU, in one process:
   7. (--only nodes) ctl_scene_update_nodes: one more instance of the moved node's mesh added (at the M3 place), then one node removed, each timed once — wall
      time around the (synchronous) call with the stage times of ctl_scene_nodes_stats — against the warm-cache re-creation of the same description in the same run,
      and the Mrays/s of the updated scene (an LBVH, the added instance with whole-triangle entries) against the freshly created one.
+  8. (--only meshes) ctl_scene_update_meshes: one mesh appended — a copy of the moved node's mesh — with one node of it (at the M3 place), timed once: wall time around
+     the (synchronous) call, the host hashing, the append stage and the stage times of ctl_scene_nodes_stats, against the warm-cache re-creation of the same
+     description in the same run, and the rays/s of the updated scene against the fresh one's.
 One JSON line per workload is appended to --out; --results appends a section to that Markdown file.  bench.py is not involved.
 """
 import argparse
@@ -272,6 +275,36 @@ def node_set(workload, args, sc, scene, node, X0, size, rec):
     one("remove", lambda: sc.DeleteNode(node))
 
 
+def mesh_set(workload, args, sc, scene, node, X0, size, rec):
+    """--only meshes: one mesh appended — a copy of the middle node's mesh, its triangles taken back from the Woop rows — and one node of it at the M3 place"""
+    d = sc.desc
+    mesh = int(d.view("nodes", np.uint32, d.n_nodes, 6)[node, 0])
+    P = mesh_soup(d, mesh)
+    t = time.perf_counter(); new_mesh = sc.add_mesh(P, np.arange(len(P), dtype=np.uint32).reshape(-1, 3), materials=[api.diffuse((0.6, 0.5, 0.4))]); compile_ms = (time.perf_counter() - t) * 1e3
+    sc.CreateNode(new_mesh, motion(X0, size, "M3"))
+    t = time.perf_counter(); st = scene.update_meshes(sc.UpdateScene(), builder=args.builder); wall = (time.perf_counter() - t) * 1e3
+    b = dict(wall_ms=wall, add_mesh_ms=compile_ms, stats=st, updated_mrays=mrays(scene, args))
+    with tempfile.TemporaryDirectory() as cache:
+        api.set_cache_dir(cache)
+        s2 = ctl.Scene(sc.desc, flatten=True); del s2     # warms the cache for exactly this description
+        t = time.perf_counter(); fresh = ctl.Scene(sc.UpdateScene(), flatten=True); b["recreate_warmcache_ms"] = (time.perf_counter() - t) * 1e3
+        api.set_cache_dir(None)
+    b["fresh_mrays"] = mrays(fresh, args); del fresh
+    rec["meshes_add"] = b
+
+
+def markdown_meshes(recs):
+    out = ["", "## Adding meshes in place (tools/scene_update_bench.py --only meshes)", "",
+           "| workload | appended (triangles / rows / BVH nodes) | entries | generated | ctl_scene_update_meshes, wall | hashing (host) | append (copies + uploads + kernel) | drop + generate | rebuild (key + sort / topology + gather / boxes) | node-set stages, device total | re-creation, warm cache | updated scene | fresh scene | ratio |",
+           "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    for r in recs:
+        b = r["meshes_add"]; st = b["stats"]; n = st["nodes"]; rb = n["rebuild"]
+        out.append("| %s | %d / %d / %d | %d -> %d | %d | %.1f ms | %.1f ms | %.2f ms | %.2f ms | %.2f ms (%.2f / %.2f / %.2f) | %.2f ms | %.0f ms | %.0f Mrays/s | %.0f Mrays/s | %.3f |" % (r["workload"], st["triangles_added"], st["rows_added"],
+                   st["bvh_nodes_added"], n["entries_before"], n["entries_after"], n["entries_generated"], b["wall_ms"], st["hash_ms"], st["append_ms"], n["edit_ms"], rb["total_ms"], rb["sort_ms"], rb["topology_ms"], rb["refit_ms"],
+                   n["total_ms"], b["recreate_warmcache_ms"], b["updated_mrays"], b["fresh_mrays"], b["updated_mrays"] / b["fresh_mrays"]))
+    return "\n".join(out) + "\n"
+
+
 def markdown_nodes(recs):
     out = ["", "## Adding and removing nodes in place (tools/scene_update_bench.py --only nodes)", "",
            "| workload | edit | entries | dropped | generated | ctl_scene_update_nodes, wall | drop + generate | rebuild (key + sort / topology + gather / boxes) | device total | re-creation, warm cache | updated scene | fresh scene | ratio |",
@@ -348,6 +381,9 @@ def run(workload, args):
     if args.only == "nodes":
         node_set(workload, args, sc, scene, node, X0, size, rec)
         return rec
+    if args.only == "meshes":
+        mesh_set(workload, args, sc, scene, node, X0, size, rec)
+        return rec
 
     def material(k):
         sc.desc.materials[0].tex[0].value[0] = 0.3 + 0.01 * k; assert scene.update(sc.desc) == api.DIFF_MATERIALS
@@ -409,6 +445,8 @@ def markdown(recs):
         return markdown_rebuild(recs)
     if "nodes_add" in recs[0]:
         return markdown_nodes(recs)
+    if "meshes_add" in recs[0]:
+        return markdown_meshes(recs)
     if "update_transform_ms" not in recs[0]:
         return markdown_deform(recs)
     out = ["", "## In-place scene updates (tools/scene_update_bench.py)", "",
@@ -431,7 +469,7 @@ def main():
     ap.add_argument("--depth", type=int, default=8); ap.add_argument("--passes", type=int, default=4)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scene_update.jsonl"))
     ap.add_argument("--results", default=None)
-    ap.add_argument("--only", default=None, choices=["deform", "skin", "rebuild", "nodes"], help="nodes: the camera update and ctl_scene_update_nodes adding and removing one node against the re-creation of the same description; rebuild: the camera update and ctl_scene_rebuild_flat after M3 and after D1 against the re-creation of the same pose; deform: the camera update and the one-mesh deformation alone; skin: the camera update and the pose change of a bound mesh against the host path")
+    ap.add_argument("--only", default=None, choices=["deform", "skin", "rebuild", "nodes", "meshes"], help="meshes: the camera update and ctl_scene_update_meshes appending one mesh the size of the middle node's, with one node of it, against the re-creation of the same description; nodes: the camera update and ctl_scene_update_nodes adding and removing one node against the re-creation of the same description; rebuild: the camera update and ctl_scene_rebuild_flat after M3 and after D1 against the re-creation of the same pose; deform: the camera update and the one-mesh deformation alone; skin: the camera update and the pose change of a bound mesh against the host path")
     ap.add_argument("--builder", default="lbvh", choices=["lbvh", "ploc"], help="the builder of --only rebuild and --only nodes (csrc/flat_ploc.h); the record carries it")
     ap.add_argument("--tag", default=None, help="a word for the record: which library ran (an A/B against another commit's library through $CTL_AMD_LIB)")
     args = ap.parse_args()
@@ -440,7 +478,7 @@ def main():
     recs = []
     for w in args.workloads.split(","):
         rec = run(w, args)
-        if args.only in ("rebuild", "nodes"):
+        if args.only in ("rebuild", "nodes", "meshes"):
             rec["builder"] = args.builder
         if args.tag:
             rec["tag"] = args.tag
