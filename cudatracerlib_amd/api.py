@@ -321,6 +321,17 @@ class FlatBvh:
         _check(lib.ctl_flat_bvh_arrays(self._h, C.byref(self.desc)))
         return self
 
+    def update_mesh_set(self, desc, mesh_map=None, node_map=None, builder="lbvh"):
+        """ctl_flat_bvh_update_mesh_set: as update_meshes, for a description that also REMOVES meshes (csrc/flat_mesh_set.h) — the yardstick of Scene.update_mesh_set.
+        mesh_map / node_map None: from the mesh / node ids of `desc` and of the description the handle was last given.  A refusal leaves the handle as it was.  Returns self."""
+        held = getattr(self, "_keepalive", None)
+        mesh_map, node_map = _maps_from_ids("update_mesh_set", desc, getattr(held, "mesh_ids", None), getattr(held, "node_ids", None), mesh_map, node_map)
+        MM = np.ascontiguousarray(mesh_map, dtype=np.uint32); M = np.ascontiguousarray(node_map, dtype=np.uint32)
+        _check(lib.ctl_flat_bvh_update_mesh_set(self._h, C.byref(desc), MM.ctypes.data, u32(len(MM)), M.ctypes.data, u32(len(M)), rebuild_builder(builder)))
+        self._keepalive = desc
+        _check(lib.ctl_flat_bvh_arrays(self._h, C.byref(self.desc)))
+        return self
+
     def levels(self):
         """ctl_flat_bvh_levels: (level_start (n_levels + 1,), level_nodes (n_nodes,)) uint32 copies — the nodes by depth as a refit walks them"""
         ls, ln = C.POINTER(u32)(), C.POINTER(u32)(); nl, nn = u32(), u64()
@@ -774,6 +785,8 @@ class DynamicScene:
         self.mesh_inputs = {}   # mesh index -> dict(positions, indices, normals, uvs) as add_mesh / UpdateMesh last took them: what a caller deforms
         self._node_ids = []     # per node, in index order: its id — assigned at CreateNode, never reused, kept by DeleteNode's shift (node_ids, Scene.update_nodes)
         self._next_node_id = 0
+        self._mesh_ids = []     # per mesh, in index order: its id — assigned at add_mesh, never reused, kept by RemoveMesh's shift (mesh_ids, Scene.update_mesh_set)
+        self._next_mesh_id = 0
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -796,7 +809,31 @@ class DynamicScene:
                                         None if N is None else _fp(N), None if UV is None else _fp(UV),
                                         None if TM is None else TM.ctypes.data_as(C.c_void_p), arr, u32(len(mats)), C.byref(out)))
         self.mesh_inputs[out.value] = dict(positions=P, indices=I, normals=N, uvs=UV)
+        self._sync_mesh_ids(out.value)
+        self._mesh_ids.append(self._next_mesh_id); self._next_mesh_id += 1
         return out.value
+
+    def _sync_mesh_ids(self, n):
+        """meshes the builder made without add_mesh (ParseMitsubaScene) get their ids now"""
+        while len(self._mesh_ids) < n:
+            self._mesh_ids.append(self._next_mesh_id); self._next_mesh_id += 1
+
+    def RemoveMesh(self, mesh):
+        """ctl_builder_remove_mesh — what DynamicScene::UpdateScene does to a mesh without users (DynamicScene.cpp:483-507, Mesh::Free): the mesh's ranges leave the geometry
+        arrays, the meshes behind it move down by one index (their ids stay: mesh_ids()) and by the erased sizes; its standard materials stay in the builder, unreferenced.
+        CtlError(ERR_INVALID), the builder unchanged, for a bad index or a mesh a node still instances (DeleteNode first).  UpdateScene() then gives the new description,
+        which Scene.update_mesh_set applies in place."""
+        n = u32()
+        _check(lib.ctl_builder_mesh_count(self._h, C.byref(n)))
+        self._sync_mesh_ids(n.value)       # meshes a loader made get their ids BEFORE the shift, so that the ids a live Scene holds keep naming the same meshes
+        _check(lib.ctl_builder_remove_mesh(self._h, u32(mesh)))
+        if mesh < len(self._mesh_ids):
+            del self._mesh_ids[mesh]
+        self.mesh_inputs = {(k if k < mesh else k - 1): v for k, v in self.mesh_inputs.items() if k != mesh}
+
+    def mesh_ids(self):
+        """the stable id of every mesh, in index order (also on the description UpdateScene returns, as desc.mesh_ids)"""
+        return tuple(self._mesh_ids)
 
     def UpdateMesh(self, mesh, positions, indices=None, normals=None, uvs=None):
         """ctl_builder_update_mesh — DynamicScene::AnimateMesh (DynamicScene.cpp:450-456) for a caller that supplies the positions: new vertex arrays for `mesh`, same
@@ -986,6 +1023,8 @@ class DynamicScene:
         _check(lib.ctl_builder_finalize(self._h, C.byref(self.desc)))
         self._sync_node_ids(self.desc.n_nodes)
         self.desc.node_ids = self.node_ids()   # (a Python attribute next to the C fields) what Scene.update_nodes computes its map from
+        self._sync_mesh_ids(self.desc.n_meshes)
+        self.desc.mesh_ids = self.mesh_ids()   # likewise, for Scene.update_mesh_set
         return self.desc
 
     def getKernelSceneData(self):
@@ -1009,6 +1048,7 @@ class Scene:
         self._skins = {}   # mesh -> dict(n_vert, n_bones) of the bound meshes
         self._light_counts = (int(desc.n_lights_buf), int(desc.n_anim_bytes))   # the sizes read_lights' buffers must have
         self._node_ids = getattr(desc, "node_ids", None)   # of the description the scene holds (DynamicScene.UpdateScene), or None
+        self._mesh_ids = getattr(desc, "mesh_ids", None)   # likewise
         self._image_dims = [(int(desc.images[i].width), int(desc.images[i].height)) for i in range(desc.n_images)]   # an update keeps them (read_image)
 
     def update(self, desc):
@@ -1085,10 +1125,40 @@ class Scene:
         self._node_ids = getattr(desc, "node_ids", None)
         self._light_counts = (int(desc.n_lights_buf), int(desc.n_anim_bytes))
         self._mesh_counts = mesh_counts(desc)
+        self._mesh_ids = getattr(desc, "mesh_ids", None)
         out = {k: getattr(st, k) for k, _ in st._fields_ if k != "nodes"}
         out["nodes"] = {k: getattr(st.nodes, k) for k, _ in st.nodes._fields_ if k != "rebuild"}
         out["nodes"]["rebuild"] = {k: getattr(st.nodes.rebuild, k) for k, _ in st.nodes.rebuild._fields_}
         out["nodes"]["rebuild"]["rounds"] = _last_rounds() if st.nodes.rebuilt else 0
+        return out
+
+    def update_mesh_set(self, sc_or_desc, mesh_map=None, node_map=None, builder="lbvh"):
+        """ctl_scene_update_mesh_set: meshes REMOVED in place — after DynamicScene.RemoveMesh (and any add_mesh, CreateNode, DeleteNode) on a builder whose description the
+        scene holds, and UpdateScene().  The kept meshes' ranges of the geometry arrays are compacted on the device into new, smaller buffers (csrc/flat_mesh_set.hip:
+        deformed and posed meshes keep their shape), appended tails follow, then the stages of update_nodes run with the kept entries' triangle words lowered; any removal
+        rebuilds the tree.  With nothing removed the call is update_meshes.
+        mesh_map: per new mesh its index in the description the scene holds or 0xffffffff (appended); node_map: as update_nodes' old_of_new.  None: computed from the stable
+        mesh / node ids of the two descriptions (DynamicScene.UpdateScene sets them).
+        Returns the stats dict: meshes_removed, triangles_removed, rows_removed, bvh_nodes_removed, runs, bytes_moved, bytes_freed, compact_ms, hash_ms, meshes = the
+        update_meshes dict.  CtlError(ERR_INVALID / ERR_UNSUPPORTED) leaves the scene as it was.  Bound meshes stay bound under their new indices.  Start the next pass
+        with new_trace."""
+        desc = sc_or_desc.getKernelSceneData() if isinstance(sc_or_desc, DynamicScene) else sc_or_desc
+        mesh_map, node_map = _maps_from_ids("update_mesh_set", desc, self._mesh_ids, self._node_ids, mesh_map, node_map)
+        MM = np.ascontiguousarray(mesh_map, dtype=np.uint32); M = np.ascontiguousarray(node_map, dtype=np.uint32)
+        st = ctl_scene_mesh_set_stats()
+        _check(lib.ctl_scene_update_mesh_set(self._h, C.byref(desc), MM.ctypes.data, u32(len(MM)), M.ctypes.data, u32(len(M)), rebuild_builder(builder), C.addressof(st)))
+        self._keepalive = desc
+        self._node_ids = getattr(desc, "node_ids", None); self._mesh_ids = getattr(desc, "mesh_ids", None)
+        self._light_counts = (int(desc.n_lights_buf), int(desc.n_anim_bytes))
+        self._mesh_counts = mesh_counts(desc)
+        new_of_old = {int(o): m for m, o in enumerate(MM) if o != 0xffffffff}
+        self._skins = {new_of_old[m]: v for m, v in self._skins.items() if m in new_of_old}
+        out = {k: getattr(st, k) for k, _ in st._fields_ if k not in ("meshes", "reserved")}
+        ms = st.meshes
+        out["meshes"] = {k: getattr(ms, k) for k, _ in ms._fields_ if k != "nodes"}
+        out["meshes"]["nodes"] = {k: getattr(ms.nodes, k) for k, _ in ms.nodes._fields_ if k != "rebuild"}
+        out["meshes"]["nodes"]["rebuild"] = {k: getattr(ms.nodes.rebuild, k) for k, _ in ms.nodes.rebuild._fields_}
+        out["meshes"]["nodes"]["rebuild"]["rounds"] = _last_rounds() if ms.nodes.rebuilt else 0
         return out
 
     def update_stats(self):
@@ -1250,6 +1320,28 @@ class ctl_scene_meshes_stats(C.Structure):
     _fields_ = [("meshes_added", u32), ("triangles_added", u32), ("rows_added", u32), ("bvh_nodes_added", u32), ("append_ms", f32), ("hash_ms", f32), ("nodes", ctl_scene_nodes_stats)]
 
 
+class ctl_scene_mesh_set_stats(C.Structure):
+    _fields_ = [("meshes_removed", u32), ("triangles_removed", u32), ("rows_removed", u32), ("bvh_nodes_removed", u32), ("runs", u32), ("reserved", u32),
+                ("bytes_moved", u64), ("bytes_freed", u64), ("compact_ms", f32), ("hash_ms", f32), ("meshes", ctl_scene_meshes_stats)]
+
+
+def _maps_from_ids(who, desc, held_mesh_ids, held_node_ids, mesh_map, node_map):
+    """the mesh and node maps of update_mesh_set where the caller gave none: from the stable ids on the two descriptions"""
+    if mesh_map is None:
+        new_ids = getattr(desc, "mesh_ids", None)
+        if new_ids is None or held_mesh_ids is None:
+            raise ValueError(who + ": no mesh ids on the descriptions (DynamicScene.UpdateScene sets them): pass mesh_map")
+        index = {i: k for k, i in enumerate(held_mesh_ids)}
+        mesh_map = [index.get(i, 0xffffffff) for i in new_ids]
+    if node_map is None:
+        new_ids = getattr(desc, "node_ids", None)
+        if new_ids is None or held_node_ids is None:
+            raise ValueError(who + ": no node ids on the descriptions (DynamicScene.UpdateScene sets them): pass node_map")
+        index = {i: k for k, i in enumerate(held_node_ids)}
+        node_map = [index.get(i, 0xffffffff) for i in new_ids]
+    return mesh_map, node_map
+
+
 # (declared only where the library has them: tools/ab_bench.py loads the parent commit's library through $CTL_AMD_LIB for a same-box A/B of bench.py, which calls none
 # of them; calling one on such a library raises AttributeError)
 for _n, _a in (("ctl_scene_rebuild_flat", [C.c_void_p, C.c_void_p]), ("ctl_flat_bvh_rebuild", [C.c_void_p, C.c_void_p]), ("ctl_flat_bvh_levels", [C.c_void_p] * 5),
@@ -1267,6 +1359,10 @@ for _n, _a in (("ctl_scene_rebuild_flat", [C.c_void_p, C.c_void_p]), ("ctl_flat_
                ("ctl_scene_read_image", [C.c_void_p, u32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
                ("ctl_scene_update_meshes", [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_void_p]), ("ctl_scene_update_meshes_ex", [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_int, C.c_void_p]),
                ("ctl_flat_bvh_update_meshes", [C.c_void_p, C.c_void_p, C.c_void_p, u32]), ("ctl_flat_bvh_update_meshes_ex", [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_int]),
+               ("ctl_builder_remove_mesh", [C.c_void_p, u32]), ("ctl_builder_mesh_count", [C.c_void_p, C.c_void_p]),
+               ("ctl_scene_update_mesh_set", [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_void_p, u32, C.c_int, C.c_void_p]),
+               ("ctl_flat_bvh_update_mesh_set", [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_void_p, u32, C.c_int]),
+               ("ctl_compact_tri_rows_host", [C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p, C.c_void_p]),
                ("ctl_triangle_woop_rows", [C.c_void_p, C.c_void_p]), ("ctl_scene_read_triangle_rows", [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]), ("ctl_append_leaf_rows_host", [C.c_void_p, u32, u32, u32, u32, C.c_void_p, C.c_void_p])):
     if hasattr(lib, _n):
         getattr(lib, _n).argtypes = _a
@@ -1368,6 +1464,15 @@ def append_leaf_rows_host(new_desc, old_desc, old_rows):
     leaf = np.zeros((new_desc.n_woop - old_desc.n_woop, 16), np.uint32)
     _check(lib.ctl_append_leaf_rows_host(C.byref(new_desc), u32(old_desc.n_meshes), u32(old_desc.n_tri_data), u32(old_desc.n_woop), u32(old_desc.n_bvh_nodes), table.ctypes.data, leaf.ctypes.data))
     return table, leaf
+
+
+def compact_tri_rows_host(old_desc, mesh_map, old_rows):
+    """ctl_compact_tri_rows_host: the arithmetic of k_compact_tri_rows (csrc/flat_mesh_set.h) on the host — the triangle -> row table of the meshes that mesh_map (per new
+    mesh its index in old_desc, 0xffffffff = appended) keeps, from old_desc's table"""
+    MM = np.ascontiguousarray(mesh_map, dtype=np.uint32); R = np.ascontiguousarray(old_rows, dtype=np.uint32)
+    out = np.zeros(max(1, old_desc.n_tri_data), np.uint32); n = u32()
+    _check(lib.ctl_compact_tri_rows_host(C.byref(old_desc), MM.ctypes.data, u32(len(MM)), R.ctypes.data, out.ctypes.data, C.byref(n)))
+    return out[:n.value].copy()
 
 
 def mesh_counts(desc):

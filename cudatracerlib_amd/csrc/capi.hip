@@ -11,6 +11,7 @@
 #include "flat_rebuild.h"
 #include "flat_nodes.h"
 #include "flat_meshes.h"
+#include "flat_mesh_set.h"
 #include "flat_device.h"
 #include "mesh_skin.h"
 #include "shape_set.h"
@@ -549,6 +550,31 @@ int ctl_triangle_woop_rows(const ctl_scene_desc* desc, uint32_t* rows_out) {
 int ctl_append_leaf_rows_host(const ctl_scene_desc* new_desc, uint32_t old_n_meshes, uint32_t old_n_tri_data, uint32_t old_n_woop, uint32_t old_n_bvh_nodes, uint32_t* tri_row, uint32_t* leaf_rows_out) {
     CTL_REQUIRE(new_desc && tri_row, "null argument");
     CTL_TRY mesh_set_plan P; plan_mesh_growth(old_n_meshes, old_n_tri_data, old_n_woop, old_n_bvh_nodes, *new_desc, "ctl_append_leaf_rows_host: ", P); append_leaf_rows_host(*new_desc, P, leaf_rows_out, tri_row); CTL_CATCH
+}
+// ---- removed meshes (flat_mesh_set.hip, flat_mesh_set.cpp)
+int ctl_builder_mesh_count(const ctl_builder* b, uint32_t* count_out) { CTL_REQUIRE(b && count_out, "null argument"); *count_out = (uint32_t)b->b.meshes.size(); return CTL_OK; }
+int ctl_builder_remove_mesh(ctl_builder* b, uint32_t mesh_index) { CTL_REQUIRE(b, "null argument"); CTL_TRY b->b.remove_mesh(mesh_index); CTL_CATCH }
+int ctl_scene_update_mesh_set(ctl_scene* scene, const ctl_scene_desc* new_desc, const uint32_t* old_mesh_of_new, uint32_t n_new_meshes, const uint32_t* old_of_new, uint32_t n_new_nodes,
+                              int builder, ctl_scene_mesh_set_stats* stats_out) {
+    if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
+    CTL_REQUIRE(scene && new_desc, "null argument");
+    CTL_REQUIRE(old_of_new, "ctl_scene_update_mesh_set: null node map");
+    CTL_REQUIRE(old_mesh_of_new || !n_new_meshes, "ctl_scene_update_mesh_set: null mesh map");
+    CTL_REQUIRE(known_builder(builder), "ctl_scene_update_mesh_set: unknown builder");
+    const int rc = [&]() -> int { CTL_TRY rebuild_builder_scope use(builder); flat_rebuilder::update_mesh_set(scene->s, *new_desc, old_mesh_of_new, n_new_meshes, old_of_new, n_new_nodes, scene->basis, stats_out); CTL_CATCH }();
+    if (rc == CTL_OK) { scene->n_materials = new_desc->n_materials; scene->n_images = new_desc->n_images; scene->basis.fill(*new_desc); }
+    return rc;
+}
+int ctl_flat_bvh_update_mesh_set(ctl_flat_bvh* h, const ctl_scene_desc* new_desc, const uint32_t* old_mesh_of_new, uint32_t n_new_meshes, const uint32_t* old_of_new, uint32_t n_new_nodes, int builder) {
+    CTL_REQUIRE(h && new_desc, "null argument");
+    CTL_REQUIRE(known_builder(builder), "ctl_flat_bvh_update_mesh_set: unknown builder");
+    CTL_TRY update_mesh_set_flat_scene(h->f, h->basis, *new_desc, old_mesh_of_new, n_new_meshes, old_of_new, n_new_nodes, h->extra_missing, builder); h->basis.fill(*new_desc); CTL_CATCH
+}
+int ctl_compact_tri_rows_host(const ctl_scene_desc* old_desc, const uint32_t* old_mesh_of_new, uint32_t n_new_meshes, const uint32_t* held_rows, uint32_t* rows_out, uint32_t* count_out) {
+    CTL_REQUIRE(old_desc && held_rows && rows_out && count_out, "null argument");
+    CTL_TRY node_set_basis basis; basis.fill(*old_desc); mesh_compaction cut; plan_mesh_compaction(basis, old_mesh_of_new, n_new_meshes, "ctl_compact_tri_rows_host: ", cut);
+    if (cut.removes()) compact_tri_rows_host(cut, held_rows, old_desc->n_tri_data, rows_out); else if (old_desc->n_tri_data) std::memcpy(rows_out, held_rows, (size_t)old_desc->n_tri_data * 4);
+    *count_out = cut.kept_tris; CTL_CATCH
 }
 int ctl_flat_bvh_levels(const ctl_flat_bvh* h, const uint32_t** level_start, uint32_t* n_levels, const uint32_t** level_nodes, uint64_t* n_level_nodes) {
     CTL_REQUIRE(h && level_start && n_levels && level_nodes && n_level_nodes, "null argument");

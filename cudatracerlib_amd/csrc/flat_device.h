@@ -18,6 +18,13 @@ inline dim3 blocks_for(size_t n) { return dim3((unsigned)((n + 255u) / 256u)); }
 struct node_set_view { const float4* leaf_tris; size_t n_leaf_tris; const uint4* tri_data; const uint32_t* tri_row; size_t n_tri_row; };
 // the geometry arrays of a scene with appended meshes (flat_meshes.hip), in buffers of their own until apply_node_set swaps them in; tri_row: null on a two-level scene
 struct mesh_growth { dbuf<uint4> tri_data; dbuf<float4> bot_nodes, leaf_tris; dbuf<uint32_t> tri_row; };
+// the staging of appended tails and their layout into such buffers (flat_meshes.hip): alloc, then run once the front part of the buffers is on its way
+struct mesh_tail_stage {
+    dbuf<float4> raw; dbuf<uint32_t> words, first, index_offset, tri_offset;
+    void alloc(const mesh_set_plan& grow);
+    void run(mesh_growth& Gr, const ctl_scene_desc& d, const mesh_set_plan& grow);
+};
+struct mesh_set_change;   // flat_mesh_set.h
 
 // The rebuild of flat_rebuild.h on the device over n entries (and the closing entry behind them) that need not be the scene's own: ctl_scene_rebuild_flat runs it over
 // flat_leaves_, ctl_scene_update_nodes over the entries it has just assembled.  Three steps, so that a caller can put its own work between them:
@@ -46,6 +53,13 @@ struct flat_rebuilder {
                                ctl_scene_nodes_stats* stats, const char* who);
     static size_t read_tri_rows(Scene& A, uint32_t* rows_out, size_t capacity);   // ctl_scene_read_triangle_rows: the words of the scene's triangle -> row table (0: none yet)
     static void update_meshes(Scene& A, const ctl_scene_desc& d, const uint32_t* old_of_new, uint32_t n_new_nodes, const node_set_basis& basis, ctl_scene_meshes_stats* stats);
+    static void apply_mesh_growth(Scene& A, const ctl_scene_desc& d, const uint32_t* old_of_new, const node_set_basis& basis, const node_set_plan& plan, const mesh_set_plan& grow,
+                                  ctl_scene_meshes_stats* stats, const char* who);   // update_meshes behind its checks
+    // ctl_scene_update_mesh_set (flat_mesh_set.hip): meshes removed — the geometry arrays compacted on the device into new buffers —, meshes appended and the node set changed in
+    // one call; with nothing removed it is update_meshes.  remap_skins (mesh_skin.hip): the bound meshes under their new indices, called where the compacted buffers become the scene's
+    static void update_mesh_set(Scene& A, const ctl_scene_desc& d, const uint32_t* old_mesh_of_new, uint32_t n_new_meshes, const uint32_t* old_of_new, uint32_t n_new_nodes,
+                                const node_set_basis& basis, ctl_scene_mesh_set_stats* stats);
+    static void remap_skins(Scene& A, const mesh_compaction& cut, const ctl_scene_desc& d);
     flat_rebuilder() {}
     flat_rebuilder(const flat_rebuilder&) = delete; flat_rebuilder& operator=(const flat_rebuilder&) = delete;
     ~flat_rebuilder();

@@ -66,6 +66,32 @@ size_t flat_rebuilder::read_tri_rows(Scene& A, uint32_t* rows_out, size_t capaci
     return n;
 }
 
+// the appended tails of `d` into grown buffers whose front part already stands (device to device copies or compaction, both on the null stream): tri_data and the mesh BVH
+// nodes uploaded, the appended range of the table "no row", then k_append_leaf_rows.  alloc() first: every allocation before the first copy
+void mesh_tail_stage::alloc(const mesh_set_plan& grow) {
+    const uint32_t n_appended = (uint32_t)grow.first.size();
+    raw.alloc((size_t)grow.rows_added * 3); words.alloc(grow.rows_added);
+    first.alloc(std::max(1u, n_appended)); index_offset.alloc(std::max(1u, n_appended)); tri_offset.alloc(std::max(1u, n_appended));
+}
+void mesh_tail_stage::run(mesh_growth& Gr, const ctl_scene_desc& d, const mesh_set_plan& grow) {
+    static_assert(sizeof(ctl_woop_tri) == 48 && sizeof(ctl_woop_index) == 4 && sizeof(ctl_bvh_node) == 64 && sizeof(ctl_triangle_data) == 32, "the staged layouts");
+    const uint32_t n_appended = (uint32_t)grow.first.size();
+    if ((size_t)d.n_tri_data * 2 > Gr.tri_data.n || (size_t)d.n_bvh_nodes * 4 > Gr.bot_nodes.n || (size_t)d.n_woop * 4 > Gr.leaf_tris.n || (Gr.tri_row.p && Gr.tri_row.n < d.n_tri_data))
+        throw std::runtime_error("the grown geometry arrays are smaller than the new description");
+    if (grow.triangles_added) CTL_HIP(hipMemcpy(Gr.tri_data.p + (size_t)grow.old_tri_data * 2, d.tri_data + grow.old_tri_data, (size_t)grow.triangles_added * sizeof(ctl_triangle_data), hipMemcpyHostToDevice));
+    if (grow.bvh_nodes_added) CTL_HIP(hipMemcpy(Gr.bot_nodes.p + (size_t)grow.old_bvh_nodes * 4, d.bvh_nodes + grow.old_bvh_nodes, (size_t)grow.bvh_nodes_added * sizeof(ctl_bvh_node), hipMemcpyHostToDevice));
+    if (Gr.tri_row.p && grow.triangles_added) CTL_HIP(hipMemsetAsync(Gr.tri_row.p + grow.old_tri_data, 0xff, (size_t)grow.triangles_added * 4, nullptr));
+    if (grow.rows_added) {
+        CTL_HIP(hipMemcpy(raw.p, d.woop + grow.old_woop, (size_t)grow.rows_added * sizeof(ctl_woop_tri), hipMemcpyHostToDevice));
+        CTL_HIP(hipMemcpy(words.p, d.woop_index + grow.old_woop, (size_t)grow.rows_added * sizeof(ctl_woop_index), hipMemcpyHostToDevice));
+        CTL_HIP(hipMemcpy(first.p, grow.first.data(), (size_t)n_appended * 4, hipMemcpyHostToDevice)); CTL_HIP(hipMemcpy(index_offset.p, grow.index_offset.data(), (size_t)n_appended * 4, hipMemcpyHostToDevice));
+        CTL_HIP(hipMemcpy(tri_offset.p, grow.tri_offset.data(), (size_t)n_appended * 4, hipMemcpyHostToDevice));
+        const append_rows K{ raw.p, words.p, grow.old_woop, d.n_woop, first.p, index_offset.p, tri_offset.p, n_appended, Gr.leaf_tris.p, (uint32_t)(Gr.leaf_tris.n / 4), Gr.tri_row.p, d.n_tri_data };
+        hipLaunchKernelGGL(k_append_leaf_rows, blocks_for(grow.rows_added), dim3(256), 0, nullptr, K);
+        CTL_HIP(hipGetLastError());
+    }
+}
+
 void flat_rebuilder::update_meshes(Scene& A, const ctl_scene_desc& d, const uint32_t* old_of_new, uint32_t n_new_nodes, const node_set_basis& basis, ctl_scene_meshes_stats* stats) {
     require_device();
     const char* who = "ctl_scene_update_meshes";
@@ -75,6 +101,13 @@ void flat_rebuilder::update_meshes(Scene& A, const ctl_scene_desc& d, const uint
     const std::vector<uint8_t> device_owned = A.device_owned_meshes();
     node_set_plan plan; mesh_set_plan grow;
     plan_node_set(basis, A.snap_->geom, d, old_of_new, n_new_nodes, device_owned.empty() ? nullptr : &device_owned, plan, who, &grow);
+    apply_mesh_growth(A, d, old_of_new, basis, plan, grow, stats, who);
+}
+
+// behind the checks (ctl_scene_update_mesh_set comes here too when its map removes nothing: flat_mesh_set.hip)
+void flat_rebuilder::apply_mesh_growth(Scene& A, const ctl_scene_desc& d, const uint32_t* old_of_new, const node_set_basis& basis, const node_set_plan& plan, const mesh_set_plan& grow,
+                                       ctl_scene_meshes_stats* stats, const char* who) {
+    const bool flat = A.flattened();
     ctl_scene_meshes_stats st{}; st.hash_ms = grow.hash_ms;
     if (!grow.grown()) {   // nothing appended: ctl_scene_update_nodes
         const node_set_view V{ A.leaf_tris_.p, A.leaf_tris_.n, A.tri_data_.p, A.refit_tri_row_.p, A.refit_tri_row_.n };
@@ -86,35 +119,20 @@ void flat_rebuilder::update_meshes(Scene& A, const ctl_scene_desc& d, const uint
     const size_t old_tri = (size_t)grow.old_tri_data * 2, old_bot = std::max<size_t>(4, (size_t)grow.old_bvh_nodes * 4), old_leaf = std::max<size_t>(4, (size_t)grow.old_woop * 4);
     if (A.tri_data_.n != old_tri || A.bot_nodes_.n != old_bot || A.leaf_tris_.n != old_leaf || (A.refit_tri_row_.p && A.refit_tri_row_.n != grow.old_tri_data))
         throw std::runtime_error(std::string(who) + ": the scene's geometry arrays have other sizes than the description it holds");
-    static_assert(sizeof(ctl_woop_tri) == 48 && sizeof(ctl_woop_index) == 4 && sizeof(ctl_bvh_node) == 64 && sizeof(ctl_triangle_data) == 32, "the staged layouts");
-    const uint32_t n_appended = (uint32_t)grow.first.size();
     CTL_HIP(hipDeviceSynchronize());   // no trace reads the arrays any more; a pose or a deformation has finished (those calls are synchronous)
     // every allocation before the first copy
-    mesh_growth Gr; dbuf<float4> raw; dbuf<uint32_t> words, first, index_offset, tri_offset;
-    raw.alloc((size_t)grow.rows_added * 3); words.alloc(grow.rows_added);
-    first.alloc(std::max(1u, n_appended)); index_offset.alloc(std::max(1u, n_appended)); tri_offset.alloc(std::max(1u, n_appended));
+    mesh_growth Gr; mesh_tail_stage tails; tails.alloc(grow);
     event_pair ev; CTL_HIP(hipEventCreate(&ev.a)); CTL_HIP(hipEventCreate(&ev.b));
     CTL_HIP(hipEventRecord(ev.a, nullptr));
     // ---- grow: old contents device to device, the tails from the description
     grow_copy(Gr.tri_data, (size_t)d.n_tri_data * 2, A.tri_data_);
     grow_copy(Gr.bot_nodes, std::max<size_t>(4, (size_t)d.n_bvh_nodes * 4), A.bot_nodes_);
     grow_copy(Gr.leaf_tris, std::max<size_t>(4, (size_t)d.n_woop * 4), A.leaf_tris_);
-    if (grow.triangles_added) CTL_HIP(hipMemcpy(Gr.tri_data.p + old_tri, d.tri_data + grow.old_tri_data, (size_t)grow.triangles_added * sizeof(ctl_triangle_data), hipMemcpyHostToDevice));
-    if (grow.bvh_nodes_added) CTL_HIP(hipMemcpy(Gr.bot_nodes.p + (size_t)grow.old_bvh_nodes * 4, d.bvh_nodes + grow.old_bvh_nodes, (size_t)grow.bvh_nodes_added * sizeof(ctl_bvh_node), hipMemcpyHostToDevice));
     if (flat && A.refit_tri_row_.p) {   // the device extension of the table
         Gr.tri_row.alloc(d.n_tri_data);
         if (grow.old_tri_data) CTL_HIP(hipMemcpyAsync(Gr.tri_row.p, A.refit_tri_row_.p, (size_t)grow.old_tri_data * 4, hipMemcpyDeviceToDevice, nullptr));
-        if (grow.triangles_added) CTL_HIP(hipMemsetAsync(Gr.tri_row.p + grow.old_tri_data, 0xff, (size_t)grow.triangles_added * 4, nullptr));
     }
-    if (grow.rows_added) {
-        CTL_HIP(hipMemcpy(raw.p, d.woop + grow.old_woop, (size_t)grow.rows_added * sizeof(ctl_woop_tri), hipMemcpyHostToDevice));
-        CTL_HIP(hipMemcpy(words.p, d.woop_index + grow.old_woop, (size_t)grow.rows_added * sizeof(ctl_woop_index), hipMemcpyHostToDevice));
-        CTL_HIP(hipMemcpy(first.p, grow.first.data(), (size_t)n_appended * 4, hipMemcpyHostToDevice)); CTL_HIP(hipMemcpy(index_offset.p, grow.index_offset.data(), (size_t)n_appended * 4, hipMemcpyHostToDevice));
-        CTL_HIP(hipMemcpy(tri_offset.p, grow.tri_offset.data(), (size_t)n_appended * 4, hipMemcpyHostToDevice));
-        const append_rows K{ raw.p, words.p, grow.old_woop, d.n_woop, first.p, index_offset.p, tri_offset.p, n_appended, Gr.leaf_tris.p, (uint32_t)(Gr.leaf_tris.n / 4), Gr.tri_row.p, d.n_tri_data };
-        hipLaunchKernelGGL(k_append_leaf_rows, blocks_for(grow.rows_added), dim3(256), 0, nullptr, K);
-        CTL_HIP(hipGetLastError());
-    }
+    tails.run(Gr, d, grow);
     if (flat && !Gr.tri_row.p) {   // no table yet: made as ctl_scene_update_nodes makes it, on the host from the whole new description (the same table: tests/test_mesh_set_host.py)
         std::vector<uint32_t> rows; triangle_woop_rows(d, rows);
         Gr.tri_row.upload(rows.data(), rows.size()); CTL_HIP(hipStreamSynchronize(nullptr));

@@ -3,6 +3,7 @@
 // one byte for byte (tests/test_gpu_node_set.py).
 #include "flat_nodes.h"
 #include "flat_meshes.h"
+#include "flat_mesh_set.h"
 #include "flatten.h"
 #include "flat_rebuild.h"
 #include "scene_checks.h"
@@ -129,6 +130,7 @@ void apply_node_set_flat(flat_scene& F, const node_set_basis& old, const ctl_sce
         const uint32_t k = nodes_new_of(F.leaves[i].node, plan.new_of_old.data(), n_old_nodes);
         if (k == kNodesNone) continue;
         T.leaves.push_back(F.leaves[i]); T.leaves.back().node = nodes_renumber(F.leaves[i].node, k);
+        if (!plan.node_tri_delta.empty()) T.leaves.back().index = mesh_set_entry_index(F.leaves[i].index, plan.node_tri_delta[F.leaves[i].node & ~kNodesStampBit]);
         T.refit.part_index.push_back(F.refit.part_index[i]);
     }
     // 2. generate
@@ -155,6 +157,7 @@ void apply_node_set_flat(flat_scene& F, const node_set_basis& old, const ctl_sce
     for (flat_leaf& L : T.leaves) { std::memcpy(L.inv, nd.node_inv_transforms[L.node].m, 48); L.w33 = nd.node_inv_transforms[L.node].m[15]; }
     rebuild_flat_entries(T, nd, builder);
     F = std::move(T);
+    if (plan.cut) mesh_set_rebase_triangles(extra_missing, *plan.cut);
     extra_missing.insert(extra_missing.end(), skipped.begin(), skipped.end());
     std::sort(extra_missing.begin(), extra_missing.end()); extra_missing.erase(std::unique(extra_missing.begin(), extra_missing.end()), extra_missing.end());
 }

@@ -5,7 +5,7 @@
 // change of the node set without the scene being made again:
 //   1. drop and renumber   per entry: its node word (bit 31 is the alpha stamp) through new_of_old[] (kNodesNone = the node was removed) -> kept or dropped; an exclusive
 //                          scan over the flags hands out the positions; the 128 B of every kept entry and its part_index word move there, the node word renumbered with
-//                          its stamp bit kept.  Stable, no atomic decides a position.  part_boxes stay as they are: a box no entry refers to is harmless
+//                          its stamp bit kept (and, where meshes were removed, the triangle word lowered: flat_mesh_set.h).  Stable, no atomic decides a position.  part_boxes stay as they are: a box no entry refers to is harmless
 //   2. generate            for every added node in index order, for every triangle of its mesh in mesh order: the triangle's Woop rows (through the triangle -> row table of
 //                          triangle_woop_rows, flatten.h); a triangle whose Woop matrix is singular (nodes_rows_regular — the rule gather_references applies at creation) or
 //                          that no row stands for gets NO entry; a scan over the regular flags gives the positions behind the kept entries; the entry in flat_leaf's layout:
@@ -60,6 +60,7 @@ struct node_set_basis {
     uint32_t n_materials = 0, n_tri_data = 0, n_woop = 0, n_bvh_nodes = 0; bool rough_transmittance = false, filled = false;
     void fill(const ctl_scene_desc& d);
 };
+struct mesh_compaction;   // flat_mesh_set.h
 // a checked change of the node set
 struct node_set_plan {
     bool identity = false;                 // same count, old_of_new[k] == k: nothing of this file runs
@@ -68,6 +69,10 @@ struct node_set_plan {
     std::vector<uint32_t> added_tri0;      // per added node: the first triangle of its mesh (global index) ...
     std::vector<uint32_t> added_base;      // ... and the candidates in front of it; one more element: the number of candidates
     geometry_hashes geom;                  // of the new description (values of device-owned meshes carried over)
+    // a plan that also REMOVES meshes (flat_mesh_set.h plan_mesh_set; empty / null on every other call, whose stages and bytes are unchanged): per old node the triangles
+    // removed in front of its mesh — step 1 lowers the triangle word of the node's kept entries by it —, and the compaction the lists of triangles follow
+    std::vector<uint32_t> node_tri_delta;
+    const mesh_compaction* cut = nullptr;
 };
 // Everything both callers refuse before anything is written (std::runtime_error -> CTL_ERR_INVALID): the map, the kept nodes' mesh / material assignment, the mesh set,
 // counts, images and tables, the geometry structure and — outside device-owned meshes — values, check_scene_desc of the new description.

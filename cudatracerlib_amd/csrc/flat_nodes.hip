@@ -14,6 +14,7 @@
 // Everything runs on the null stream between two synchronisations, like the refit.  Plain launches, plain stores; no atomic decides a position; every index is checked
 // against the size of the array it goes into.  The scene's own buffers are written only after the new tree stands: a refusal or a failed allocation leaves the scene as it was.
 #include "flat_device.h"
+#include "flat_mesh_set.h"
 #include "scene_checks.h"
 #include "mitsuba_loader.h"   // unsupported_error
 #include <rocprim/rocprim.hpp>
@@ -51,7 +52,8 @@ __global__ void __launch_bounds__(256) k_nodes_candidates(nodes_added D, uint32_
     flags[g] = regular;
 }
 
-struct nodes_move { const float4* old_leaves; const uint32_t* old_part; const uint32_t* flags; const uint32_t* pos; const uint32_t* new_of_old; uint32_t n_old_nodes, n_old, n_new; float4* new_leaves; uint32_t* new_part; };
+// tri_delta: null, or per old node the triangles removed in front of its mesh (flat_mesh_set.h): the entry's triangle word is lowered while it moves
+struct nodes_move { const float4* old_leaves; const uint32_t* old_part; const uint32_t* flags; const uint32_t* pos; const uint32_t* new_of_old; uint32_t n_old_nodes, n_old, n_new; float4* new_leaves; uint32_t* new_part; const uint32_t* tri_delta; };
 
 __global__ void __launch_bounds__(256) k_nodes_move(nodes_move M) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x, i = t >> 3, q = t & 7u;
@@ -59,7 +61,10 @@ __global__ void __launch_bounds__(256) k_nodes_move(nodes_move M) {
     const uint32_t p = M.pos[i];
     if (p >= M.n_new) return;   // cannot happen: the positions are the scan of the flags and n_new is at least their sum; never write outside the arrays
     float4 v = M.old_leaves[(size_t)i * 8 + q];
-    if (q == 3u) { const uint32_t w = __float_as_uint(v.y); v.y = __uint_as_float(nodes_renumber(w, nodes_new_of(w, M.new_of_old, M.n_old_nodes))); }
+    if (q == 3u) {
+        const uint32_t w = __float_as_uint(v.y); v.y = __uint_as_float(nodes_renumber(w, nodes_new_of(w, M.new_of_old, M.n_old_nodes)));
+        if (M.tri_delta && (w & ~kNodesStampBit) < M.n_old_nodes) v.x = __uint_as_float(mesh_set_entry_index(__float_as_uint(v.x), M.tri_delta[w & ~kNodesStampBit]));   // (a kept entry's node is always one of the old ones)
+    }
     M.new_leaves[(size_t)p * 8 + q] = v;
     if (q == 0u) M.new_part[p] = M.old_part[i];
 }
@@ -144,10 +149,11 @@ void flat_rebuilder::apply_node_set(Scene& A, const ctl_scene_desc& d, const uin
     if (flat) {
         const uint32_t n_old = (uint32_t)A.flat_n_entries_, n_added = (uint32_t)plan.added.size(), G = plan.added_base.back();
         // ---- scratch of this call; the scene's tri_row table and rocPRIM storage are caches without a meaning of their own
-        dbuf<uint32_t> map_dev, flags, pos, base_dev, tri0_dev, added_dev, gflags, gpos, part_mid; dbuf<float4> leaves_mid; dbuf<ctl_material> mats_tmp; dbuf<unsigned char> temp;
+        dbuf<uint32_t> map_dev, flags, pos, base_dev, tri0_dev, added_dev, gflags, gpos, part_mid, delta_dev; dbuf<float4> leaves_mid; dbuf<ctl_material> mats_tmp; dbuf<unsigned char> temp;
         map_dev.alloc(n_old_nodes); flags.alloc((size_t)n_old + 1); pos.alloc((size_t)n_old + 1); gflags.alloc((size_t)G + 1); gpos.alloc((size_t)G + 1);
         base_dev.alloc(plan.added_base.size()); tri0_dev.alloc(std::max<size_t>(1, n_added)); added_dev.alloc(std::max<size_t>(1, n_added));
         CTL_HIP(hipMemcpy(map_dev.p, plan.new_of_old.data(), (size_t)n_old_nodes * 4, hipMemcpyHostToDevice));
+        if (plan.node_tri_delta.size() == n_old_nodes) { delta_dev.alloc(n_old_nodes); CTL_HIP(hipMemcpy(delta_dev.p, plan.node_tri_delta.data(), (size_t)n_old_nodes * 4, hipMemcpyHostToDevice)); }
         CTL_HIP(hipMemcpy(base_dev.p, plan.added_base.data(), plan.added_base.size() * 4, hipMemcpyHostToDevice));
         if (n_added) { CTL_HIP(hipMemcpy(tri0_dev.p, plan.added_tri0.data(), (size_t)n_added * 4, hipMemcpyHostToDevice)); CTL_HIP(hipMemcpy(added_dev.p, plan.added.data(), (size_t)n_added * 4, hipMemcpyHostToDevice)); }
         const uint32_t* tri_row = V.tri_row; size_t n_tri_row = V.n_tri_row;
@@ -184,7 +190,7 @@ void flat_rebuilder::apply_node_set(Scene& A, const ctl_scene_desc& d, const uin
         B.who = who; B.n = n_new; B.src_leaves = leaves_mid.p; B.src_part = part_mid.p;
         B.allocate(A, P);
         if (d.n_materials) CTL_HIP(hipMemcpy(mats_tmp.p, d.materials, (size_t)d.n_materials * sizeof(ctl_material), hipMemcpyHostToDevice));
-        const nodes_move M{ A.flat_leaves_.p, A.refit_part_index_.p, flags.p, pos.p, map_dev.p, n_old_nodes, n_old, n_new, leaves_mid.p, part_mid.p };
+        const nodes_move M{ A.flat_leaves_.p, A.refit_part_index_.p, flags.p, pos.p, map_dev.p, n_old_nodes, n_old, n_new, leaves_mid.p, part_mid.p, delta_dev.p };
         hipLaunchKernelGGL(k_nodes_move, blocks_for((size_t)n_old * 8), dim3(256), 0, nullptr, M);
         if (G) hipLaunchKernelGGL(k_nodes_generate, blocks_for(G), dim3(256), 0, nullptr, D, gflags.p, gpos.p, inst_new.p, d.n_nodes, n_kept, n_new, leaves_mid.p, part_mid.p);
         CTL_HIP(hipGetLastError());
@@ -201,6 +207,7 @@ void flat_rebuilder::apply_node_set(Scene& A, const ctl_scene_desc& d, const uin
         // ---- from here on the scene is written
         B.commit(A);
         A.refit_.xf0 = xf0;
+        if (plan.cut) mesh_set_rebase_triangles(A.flat_missing_tris_, *plan.cut);   // removed meshes: the held list in the new numbering, before the new triangles join it
         if (!skipped.empty()) {
             A.flat_missing_tris_.insert(A.flat_missing_tris_.end(), skipped.begin(), skipped.end());
             std::sort(A.flat_missing_tris_.begin(), A.flat_missing_tris_.end()); A.flat_missing_tris_.erase(std::unique(A.flat_missing_tris_.begin(), A.flat_missing_tris_.end()), A.flat_missing_tris_.end());
@@ -211,6 +218,7 @@ void flat_rebuilder::apply_node_set(Scene& A, const ctl_scene_desc& d, const uin
         swap_buffers(A.tri_data_, grown->tri_data); swap_buffers(A.bot_nodes_, grown->bot_nodes); swap_buffers(A.leaf_tris_, grown->leaf_tris);
         if (grown->tri_row.p) swap_buffers(A.refit_tri_row_, grown->tri_row);
     }
+    if (plan.cut) remap_skins(A, *plan.cut, d);   // removed meshes (flat_mesh_set.hip): the bindings under their new mesh indices, before the shape sets of emissive skins run
     // the rest of the description, block by block as ctl_scene_update applies it; the instance records go in by a swap of buffers
     swap_buffers(A.inst_, inst_new); swap_buffers(A.inst_fwd_, fwd_new); swap_buffers(A.node_info_, ninfo_new);
     A.set_shading_state(shade);

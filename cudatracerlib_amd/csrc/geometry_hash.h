@@ -5,6 +5,10 @@
 //   images[i]   image i's size and level-0 texels.  Another texel is a difference of STRUCTURE as it always was (same_structure compares these words too); they are kept
 //               per image so that ctl_scene_update_image (scene_images.hip), which replaces one image's texels in place, can replace that image's words
 //   values[m]   mesh m's ranges of tri_data and woop, and the float boxes (the first 48 B) of its bvh_nodes
+//   mesh_structure[m]  mesh m's own share of the structure, from the same pass: its woop_index words and the links of its BVH nodes.  Both are MESH-RELATIVE (an index word
+//               names a triangle of the mesh, a link a node or a leaf row of the mesh; the offsets are added per instance, tracer.hip pack_instances), so the words
+//               survive a move of the mesh's ranges: what ctl_scene_update_mesh_set (flat_mesh_set.h) compares mesh by mesh, where the whole-array hash changes with any
+//               removal.  tables: the transmittance tables' share alone, for the same caller.  same_structure reads neither
 // A description whose structure hash (and counts, meshes, node -> mesh / material assignment) equals the scene's differs from it in geometry VALUES at most, and
 // the per-mesh hashes say in which meshes: the ones an update re-uploads and whose leaf entries it rewrites.
 #pragma once
@@ -25,6 +29,9 @@ struct geometry_hashes {
     uint64_t structure[2] = { 0, 0 };
     std::vector<uint64_t> values;   // two words per mesh
     std::vector<uint64_t> images;   // two words per image
+    std::vector<uint64_t> mesh_structure;   // two words per mesh
+    uint64_t tables[2] = { 0, 0 };
+    bool same_mesh_structure(size_t m, const geometry_hashes& o, size_t om) const { return mesh_structure.size() > 2 * m + 1 && o.mesh_structure.size() > 2 * om + 1 && mesh_structure[2 * m] == o.mesh_structure[2 * om] && mesh_structure[2 * m + 1] == o.mesh_structure[2 * om + 1]; }
     bool same_structure(const geometry_hashes& o) const { return structure[0] == o.structure[0] && structure[1] == o.structure[1] && values.size() == o.values.size() && images == o.images; }
     bool same_values(const geometry_hashes& o, size_t m) const { return values[2 * m] == o.values[2 * m] && values[2 * m + 1] == o.values[2 * m + 1]; }
     // a mesh whose values in HBM are no description's any more (ctl_scene_unbind_skin): the two words no digest is expected to give, so that every later comparison

@@ -14,6 +14,8 @@
 // Plain launches on the null stream, in order; 256-lane workgroups; no workgroup waits for another; no atomics.
 #include "tracer.h"
 #include "mesh_skin.h"
+#include "flat_device.h"
+#include "flat_mesh_set.h"
 #include "scene_builder.h"
 #include "geometry_hash.h"
 #include "mitsuba_loader.h"   // unsupported_error
@@ -246,6 +248,24 @@ void Scene::animate_mesh(uint32_t mesh, const ctl_float4x4* bones0, const ctl_fl
     float ms = 0; CTL_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
     last_skin_ms_ = ms; last_shape_set_ms_ = shape_ms; last_update_ = st; last_mask_ = st.mask;
     if (stats) *stats = st;
+}
+
+// ctl_scene_update_mesh_set removed meshes (flat_mesh_set.hip): the bindings under the new mesh indices, the offsets each one caches from the new description.  A bound mesh
+// is never removed (plan_mesh_set), so every binding has a new index.  Here, because skin_binding is this file's
+void flat_rebuilder::remap_skins(Scene& A, const mesh_compaction& cut, const ctl_scene_desc& d) {
+    if (A.skins_.empty() && A.skin_lights_.empty()) return;
+    const mesh_ranges R(d);
+    std::map<uint32_t, std::shared_ptr<skin_binding>> skins;
+    for (const auto& kv : A.skins_) {
+        const uint32_t k = kv.first < cut.new_of_old.size() ? cut.new_of_old[kv.first] : kNodesNone;
+        if (k == kNodesNone || k >= d.n_meshes) continue;
+        kv.second->tri0 = R.tri0[k]; kv.second->woop0 = R.woop0[k];
+        skins[k] = kv.second;
+    }
+    A.skins_.swap(skins);
+    std::set<uint32_t> lights;
+    for (uint32_t m : A.skin_lights_) { const uint32_t k = m < cut.new_of_old.size() ? cut.new_of_old[m] : kNodesNone; if (k != kNodesNone) lights.insert(k); }
+    A.skin_lights_.swap(lights);
 }
 
 void Scene::read_mesh_geometry(uint32_t mesh, float* positions_out, float* normals_out, ctl_triangle_data* tri_data_out, ctl_woop_tri* woop_out) {

@@ -581,6 +581,40 @@ void scene_builder::remove_node(uint32_t i) {
     for (auto& L : lights) if (L.type == CTL_LIGHT_DIFFUSE && L.node_idx != 0xffffffffu && L.node_idx > i) L.node_idx--;
 }
 
+// The counterpart of add_mesh for a mesh no node instances any more (the reference frees such a mesh's ranges, DynamicScene.cpp:483-507 / Mesh::Free; the arrays here are
+// dense, so the later meshes move down): the builder afterwards holds, in tri, woop, widx, bvh, meshes and mesh_info, what a builder holds that never added the mesh.
+// Everything that can refuse runs before the first byte is written.  mesh_materials (and with it every std_material_offset) stays as it is.
+void scene_builder::remove_mesh(uint32_t mesh_index) {
+    if (mesh_index >= mesh_info.size()) throw std::runtime_error("ctl_builder_remove_mesh: bad mesh index");
+    for (size_t k = 0; k < nodes.size(); k++) if (nodes[k].mesh_index == mesh_index)
+        throw std::runtime_error("ctl_builder_remove_mesh: node " + std::to_string(k) + " still instances mesh " + std::to_string(mesh_index) + " (ctl_builder_remove_node first)");
+    const mesh_rec mr = mesh_info[mesh_index];
+    if ((size_t)mr.tri_offset + mr.n_tris > tri.size() || (size_t)mr.woop_offset + mr.n_woop > woop.size() || woop.size() != widx.size() || (size_t)mr.node_offset + mr.n_nodes > bvh.size())
+        throw std::runtime_error("ctl_builder_remove_mesh: the mesh's ranges reach outside the builder's arrays");
+    tri.erase(tri.begin() + mr.tri_offset, tri.begin() + mr.tri_offset + mr.n_tris);
+    woop.erase(woop.begin() + mr.woop_offset, woop.begin() + mr.woop_offset + mr.n_woop);
+    widx.erase(widx.begin() + mr.woop_offset, widx.begin() + mr.woop_offset + mr.n_woop);
+    bvh.erase(bvh.begin() + mr.node_offset, bvh.begin() + mr.node_offset + mr.n_nodes);
+    mesh_info.erase(mesh_info.begin() + mesh_index); meshes.erase(meshes.begin() + mesh_index);
+    for (size_t m = mesh_index; m < mesh_info.size(); m++) {   // add_mesh only ever appends: every later mesh lies behind the erased ranges
+        mesh_rec& r = mesh_info[m];
+        r.tri_offset -= mr.n_tris; r.woop_offset -= mr.n_woop; r.node_offset -= mr.n_nodes;
+        ctl_kernel_mesh& km = meshes[m];
+        km.tri_offset = r.tri_offset; km.bvh_node_offset = r.node_offset * 4; km.bvh_tri_offset = r.woop_offset * 3; km.bvh_index_offset = r.woop_offset;
+    }
+    // the shape sets of area lights name global rows and triangles (i_dat, t_dat): those on nodes of later meshes follow, while the nodes still carry the old mesh indices
+    for (const ctl_light& L : lights) {
+        if (L.type != CTL_LIGHT_DIFFUSE || L.node_idx >= nodes.size() || nodes[L.node_idx].mesh_index <= mesh_index) continue;
+        if ((size_t)L.triangles_index + (size_t)L.count * sizeof(ctl_shape_tri) > anim.size()) continue;
+        for (uint32_t i = 0; i < L.count; i++) {
+            ctl_shape_tri s; std::memcpy(&s, anim.data() + L.triangles_index + (size_t)i * sizeof(ctl_shape_tri), sizeof(s));
+            s.i_dat -= mr.n_woop; s.t_dat -= mr.n_tris;
+            std::memcpy(anim.data() + L.triangles_index + (size_t)i * sizeof(ctl_shape_tri), &s, sizeof(s));
+        }
+    }
+    for (ctl_node& n : nodes) if (n.mesh_index > mesh_index) n.mesh_index--;
+}
+
 void scene_builder::finalize(ctl_scene_desc& out) {
     if (nodes.empty()) throw std::runtime_error("ctl_builder_finalize: scene has no nodes");
     if (!have_camera) throw std::runtime_error("ctl_builder_finalize: no camera set");

@@ -85,6 +85,9 @@ struct scene_builder {
     // DynamicScene::DeleteNode (Engine/DynamicScene.cpp:380-384) for a node without lights (the loader's medium-only shapes): the nodes behind it move up one index, the
     // area lights of those nodes follow; the node's material copies stay in the array, unreferenced
     void remove_node(uint32_t node_index);
+    // ctl_builder_remove_mesh: a mesh without nodes leaves tri, woop, widx, bvh, meshes and mesh_info; the later meshes' offsets, the mesh_index of their nodes and the
+    // i_dat / t_dat of their area lights move down.  mesh_materials is not compacted.  Refused (nothing changed) for a bad index or a mesh a node still instances
+    void remove_mesh(uint32_t mesh_index);
     void finalize(ctl_scene_desc& out);
 };
 

@@ -321,6 +321,17 @@ int ctl_builder_add_node(ctl_builder* b, uint32_t mesh_index, const ctl_float4x4
  * CTL_ERR_UNSUPPORTED for a node that carries area lights (their records and shape sets would have to leave the light tables), CTL_ERR_INVALID for an index that is no
  * node's and for the last node of the builder; a refusal leaves the builder untouched. */
 int ctl_builder_remove_node(ctl_builder* b, uint32_t node_index);
+/* The counterpart of ctl_builder_add_mesh for a mesh that no node instances any more (the reference frees such a mesh's ranges in DynamicScene::UpdateScene,
+ * Engine/DynamicScene.cpp:483-507; the arrays here are dense, so they are compacted): the mesh's ranges leave tri_data, woop, woop_index and bvh_nodes and its record
+ * leaves meshes; every later mesh moves down by one index and by the erased sizes in its offsets, the mesh_index of its nodes and the i_dat / t_dat of their area
+ * lights follow.  After ctl_builder_finalize those arrays equal, byte for byte, the ones of a builder that never added the mesh — except std_material_offset: the
+ * MATERIALS ARE NOT COMPACTED, the removed mesh's standard materials stay in the builder as unreferenced rows (384 B each), so std_material_offset and material_offset of
+ * everything kept are unchanged.  The compiled-mesh cache is not involved.  CTL_ERR_INVALID, the builder unchanged, for an index that is no mesh's and for a mesh a node
+ * still instances (the message names the first such node).  ctl_builder_remove_node refuses a node that carries area lights, so a mesh with an emissive node cannot be
+ * removed yet.  The next ctl_builder_finalize gives the description ctl_scene_update_mesh_set takes. */
+int ctl_builder_remove_mesh(ctl_builder* b, uint32_t mesh_index);
+/* the number of meshes the builder holds now, whoever added them (a loader included), without a ctl_builder_finalize */
+int ctl_builder_mesh_count(const ctl_builder* b, uint32_t* count_out);
 /* DynamicScene::CreateLight(node, matName, L) (DynamicScene.cpp:689-711): all triangles of the node whose local
  * material index is `local_material` become one DiffuseLight. */
 int ctl_builder_add_area_light(ctl_builder* b, uint32_t node_index, uint32_t local_material, const float radiance[3]);
@@ -675,7 +686,7 @@ int ctl_flat_bvh_update_nodes_ex(ctl_flat_bvh* h, const ctl_scene_desc* new_desc
  * the grown buffers, and the buffers become the scene's only after the new tree stands.  Any growth rebuilds the flattened tree, an identity node map included.
  * During the call HBM holds a second copy of the three geometry arrays.  Tracers follow the new arrays; start the next pass with new_trace.  Bound meshes stay bound.
  * Refusals leave the scene as it was: CTL_ERR_NO_DEVICE first; CTL_ERR_INVALID for wrong arguments and every rule above; CTL_ERR_UNSUPPORTED exactly where
- * ctl_scene_update_nodes answers so.  A failed allocation leaves the scene as it was.  Removing meshes, new images and new tables still need a new scene.
+ * ctl_scene_update_nodes answers so.  A failed allocation leaves the scene as it was.  New images and new tables still need a new scene.
  * ctl_flat_bvh_update_meshes is the host yardstick (no GPU): the same acceptance, then ctl_flat_bvh_update_nodes' stages, which read the Woop rows from new_desc. */
 typedef struct {
     uint32_t meshes_added, triangles_added, rows_added, bvh_nodes_added;   /* rows: of the two-level leaf stream (n_woop) */
@@ -694,6 +705,42 @@ int ctl_triangle_woop_rows(const ctl_scene_desc* desc, uint32_t* rows_out);
  * skin binding or node-set change makes it); rows_out (may be NULL) receives them when capacity is at least that. */
 int ctl_scene_read_triangle_rows(ctl_scene* scene, uint32_t* rows_out, size_t capacity, size_t* count_out);
 int ctl_append_leaf_rows_host(const ctl_scene_desc* new_desc, uint32_t old_n_meshes, uint32_t old_n_tri_data, uint32_t old_n_woop, uint32_t old_n_bvh_nodes, uint32_t* tri_row, uint32_t* leaf_rows_out);
+/* ---- REMOVED MESHES on a live scene (csrc/flat_mesh_set.h, flat_mesh_set.hip, flat_mesh_set.cpp; INTEGRATION.md "Removing meshes").  ctl_scene_update,
+ * ctl_scene_update_nodes and ctl_scene_update_meshes refuse a description with a mesh removed, and keep doing so; ctl_scene_update_mesh_set takes one: new_desc is the
+ * scene's description after ctl_builder_remove_mesh, further ctl_builder_add_mesh calls and any node-set edit — removal, append and node set in one call.
+ *   old_mesh_of_new[m]  the index new mesh m had in the description the scene holds, or UINT32_MAX for an appended mesh; n_new_meshes == new_desc->n_meshes.  The kept
+ *                       indices strictly increasing (no reordering), the appended meshes all behind the kept ones, as the builder appends
+ *   old_of_new          as for ctl_scene_update_nodes;   builder: CTL_REBUILD_LBVH or CTL_REBUILD_PLOC
+ * A map that removes nothing makes the call ctl_scene_update_meshes_ex (and one that appends nothing either, ctl_scene_update_nodes_ex), the removal part of the stats zero.
+ * Accepted when, besides the map's rules: no kept node (through old_of_new) instances a removed mesh, and a kept node's mesh is its old mesh through the map, its material
+ * assignment unchanged; no removed mesh is bound to a skin (ctl_scene_unbind_skin first); every kept mesh's record equals the held record with its offsets lowered by
+ * exactly the triangles, leaf rows and BVH nodes removed in front of it, std_material_offset equal; the appended meshes follow the compacted ends exactly, as in
+ * ctl_scene_update_meshes; structure (woop_index and mesh BVH links, which are mesh-relative: per-mesh hash words) and values of every kept mesh are unchanged — the values
+ * of a device-owned mesh are neither read nor compared —; images, transmittance tables and materials follow the rules of ctl_scene_update_nodes; ctl_scene_desc_check
+ * accepts new_desc.  Everything is checked before anything is written or a tracer is stalled.
+ * On the device the kept ranges of tri_data, the mesh BVH nodes, the two-level leaf stream and — where the scene has one — the triangle -> row table are COMPACTED into
+ * NEW, smaller buffers: k_compact_quads moves 16-B quads, one lane per destination quad, the source found through a table of runs (maximal groups of consecutive kept
+ * meshes); k_compact_tri_rows lowers the table's words by each run's row delta.  The source is what stands in HBM, so deformed and posed meshes keep their shape.  Nothing
+ * moves in place: DURING THE CALL HBM HOLDS THE OLD ARRAYS AND THE COMPACTED ONES, and the new buffers become the scene's only after the new tree stands.  The appended
+ * tails and the node-set stages follow as in ctl_scene_update_meshes; the leaf entries of kept nodes get their triangle words lowered while they move.  Any removal
+ * rebuilds the flattened tree, an identity node map included.  Bound meshes stay bound under their new indices; tracers follow the new arrays: start the next pass with
+ * new_trace.  Refusals leave the scene as it was: CTL_ERR_NO_DEVICE first; CTL_ERR_INVALID for wrong arguments and every rule above; CTL_ERR_UNSUPPORTED exactly where
+ * ctl_scene_update_nodes answers so.  The material table is not compacted; new images and new tables still need a new scene.
+ * ctl_flat_bvh_update_mesh_set is the host yardstick (no GPU): the same acceptance, then ctl_flat_bvh_update_nodes' stages with the triangle words lowered. */
+typedef struct {
+    uint32_t meshes_removed, triangles_removed, rows_removed, bvh_nodes_removed;   /* rows: of the two-level leaf stream (n_woop) */
+    uint32_t runs, reserved;                /* the runs of kept meshes the compaction kernels searched */
+    uint64_t bytes_moved, bytes_freed;      /* by the compaction kernels; what the scene's geometry arrays shrank by through the removal */
+    float compact_ms, hash_ms;              /* HIP events around the compaction launches; host time of the ONE hash pass over new_desc */
+    ctl_scene_meshes_stats meshes;          /* the append and the node-set stages that follow (its hash_ms repeats hash_ms) */
+} ctl_scene_mesh_set_stats;
+int ctl_scene_update_mesh_set(ctl_scene* scene, const ctl_scene_desc* new_desc, const uint32_t* old_mesh_of_new, uint32_t n_new_meshes,
+                              const uint32_t* old_of_new, uint32_t n_new_nodes, int builder, ctl_scene_mesh_set_stats* stats_out);
+int ctl_flat_bvh_update_mesh_set(ctl_flat_bvh* h, const ctl_scene_desc* new_desc, const uint32_t* old_mesh_of_new, uint32_t n_new_meshes,
+                                 const uint32_t* old_of_new, uint32_t n_new_nodes, int builder);
+/* test hook (no GPU): k_compact_tri_rows' arithmetic on the host.  held_rows: the table of old_desc (old_desc->n_tri_data words); rows_out (as many words of room) receives
+ * the compacted table of the kept meshes, *count_out its length. */
+int ctl_compact_tri_rows_host(const ctl_scene_desc* old_desc, const uint32_t* old_mesh_of_new, uint32_t n_new_meshes, const uint32_t* held_rows, uint32_t* rows_out, uint32_t* count_out);
 /* The flattened tree of a CTL_SCENE_FLATTEN scene copied back from HBM into a handle for ctl_flat_bvh_arrays, with the BSDF-model bits (28..31 of the index word)
  * and the alpha bit (31 of the node word) that ctl_scene_create_ex stamps into the device copy removed: the arrays the test oracle traverses. */
 int ctl_scene_read_flat_bvh(ctl_scene* scene, ctl_flat_bvh** out);

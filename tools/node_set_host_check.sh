@@ -8,7 +8,7 @@ OUT=${1:-${TMPDIR:-/tmp}}
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 cd "$ROOT/cudatracerlib_amd/csrc"
 SAN="-Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined"
-"$HIPCC" --offload-arch=gfx950 -std=c++17 -O1 -g -ffp-contract=off -pthread $SAN -I. -x hip ../../tools/node_set_host_check.cpp \
+"$HIPCC" --offload-arch=gfx950 -std=c++17 -O1 -g -ffp-contract=off -pthread $SAN -I. -x hip ../../tools/node_set_host_check.cpp flat_meshes.cpp \
     flat_nodes.cpp flat_rebuild.cpp flatten.cpp scene_builder.cpp scene_checks.cpp geometry_hash.cpp bvh_builder.cpp sbvh_builder.cpp scene_cache.cpp image_io.cpp jpeg_decode.cpp \
     -fsanitize=address,undefined -lz -ldl -o "$OUT/node_set_host_check"
 "$OUT/node_set_host_check"

@@ -30,6 +30,9 @@ Per workload, on one GPU, in one process:
   8. (--only meshes) ctl_scene_update_meshes: one mesh appended — a copy of the moved node's mesh — with one node of it (at the M3 place), timed once: wall time around
      the (synchronous) call, the host hashing, the append stage and the stage times of ctl_scene_nodes_stats, against the warm-cache re-creation of the same
      description in the same run, and the rays/s of the updated scene against the fresh one's.
+  9. (--only mesh-remove) ctl_scene_update_mesh_set: step 8's append, then the ORIGINAL mesh of the moved node — it stands in front of the copy — removed together with
+     its nodes, timed once: wall time, the host hashing, the compaction kernels between HIP events with the bytes they moved, a plain device-to-device copy of the same
+     byte count in the same run (warm-up, median of 10) as their yardstick, the node-set stages, warm-cache re-creation of the same description, rays/s, HBM freed.
 One JSON line per workload is appended to --out; --results appends a section to that Markdown file.  bench.py is not involved.
 """
 import argparse
@@ -293,6 +296,70 @@ def mesh_set(workload, args, sc, scene, node, X0, size, rec):
     rec["meshes_add"] = b
 
 
+def device_copy_gbs(n_bytes):
+    """(ms, GB/s read + written) of a plain device-to-device hipMemcpy of n_bytes: the yardstick of the compaction kernels.  Three warm-up copies, HIP events on the null
+    stream, median of 10.  The HIP runtime is the one the library has loaded"""
+    import ctypes as C
+    hip = C.CDLL("libamdhip64.so")
+    def ok(code):
+        if code != 0:
+            raise RuntimeError("HIP error %d in device_copy_gbs" % code)
+    n = max(1, int(n_bytes))
+    src, dst, a, b = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+    ok(hip.hipMalloc(C.byref(src), C.c_size_t(n))); ok(hip.hipMalloc(C.byref(dst), C.c_size_t(n)))
+    ok(hip.hipMemset(src, 0, C.c_size_t(n)))
+    ok(hip.hipEventCreate(C.byref(a))); ok(hip.hipEventCreate(C.byref(b)))
+    ts = []
+    for k in range(13):
+        ok(hip.hipEventRecord(a, None))
+        ok(hip.hipMemcpyAsync(dst, src, C.c_size_t(n), C.c_int(3), None))      # hipMemcpyDeviceToDevice
+        ok(hip.hipEventRecord(b, None)); ok(hip.hipEventSynchronize(b))
+        ms = C.c_float(0); ok(hip.hipEventElapsedTime(C.byref(ms), a, b))
+        if k >= 3:
+            ts.append(ms.value)
+    hip.hipEventDestroy(a); hip.hipEventDestroy(b); hip.hipFree(src); hip.hipFree(dst)
+    ms = float(np.median(ts))
+    return ms, 2.0 * n / (ms * 1e-3) / 1e9
+
+
+def mesh_remove(workload, args, sc, scene, node, X0, size, rec):
+    """--only mesh-remove: mesh_set's append (a copy of the middle node's mesh with one node), then the ORIGINAL mesh — it stands in front of the copy — removed together
+    with its nodes through ctl_scene_update_mesh_set.  Each call is timed once."""
+    mesh_set(workload, args, sc, scene, node, X0, size, rec)
+    d = sc.desc
+    nodes = d.view("nodes", np.uint32, d.n_nodes, 6)
+    mesh = int(nodes[node, 0])
+    mine = [k for k in range(d.n_nodes) if int(nodes[k, 0]) == mesh]
+    bytes_before = d.n_tri_data * 32 + (d.n_woop + d.n_bvh_nodes) * 64
+    for k in reversed(mine):
+        sc.DeleteNode(k)
+    sc.RemoveMesh(mesh)
+    t = time.perf_counter(); st = scene.update_mesh_set(sc.UpdateScene(), builder=args.builder); wall = (time.perf_counter() - t) * 1e3
+    b = dict(wall_ms=wall, nodes_removed=len(mine), stats=st, updated_mrays=mrays(scene, args), geometry_bytes_before=int(bytes_before))
+    b["compact_gbs"] = 2.0 * st["bytes_moved"] / (st["compact_ms"] * 1e-3) / 1e9 if st["compact_ms"] > 0 else 0.0
+    b["copy_ms"], b["copy_gbs"] = device_copy_gbs(int(st["bytes_moved"]))
+    with tempfile.TemporaryDirectory() as cache:
+        api.set_cache_dir(cache)
+        s2 = ctl.Scene(sc.desc, flatten=True); del s2     # warms the cache for exactly this description
+        t = time.perf_counter(); fresh = ctl.Scene(sc.UpdateScene(), flatten=True); b["recreate_warmcache_ms"] = (time.perf_counter() - t) * 1e3
+        api.set_cache_dir(None)
+    b["fresh_mrays"] = mrays(fresh, args); del fresh
+    rec["meshes_remove"] = b
+
+
+def markdown_mesh_remove(recs):
+    out = ["", "## Removing meshes in place (tools/scene_update_bench.py --only mesh-remove)", "",
+           "| workload | removed (meshes / triangles / rows / BVH nodes, nodes) | runs | entries | ctl_scene_update_mesh_set, wall | hashing (host) | compaction: bytes moved, time, read + written | plain device copy of the same bytes | drop + generate | rebuild | node-set stages, device total | re-creation, warm cache | HBM freed | updated scene | fresh scene | ratio |",
+           "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    for r in recs:
+        b = r["meshes_remove"]; st = b["stats"]; n = st["meshes"]["nodes"]; rb = n["rebuild"]
+        out.append("| %s | %d / %d / %d / %d, %d | %d | %d -> %d | %.1f ms | %.1f ms | %.1f MB, %.3f ms, %.0f GB/s | %.3f ms, %.0f GB/s | %.2f ms | %.2f ms | %.2f ms | %.0f ms | %.2f MB | %.0f Mrays/s | %.0f Mrays/s | %.3f |" % (
+                   r["workload"], st["meshes_removed"], st["triangles_removed"], st["rows_removed"], st["bvh_nodes_removed"], b["nodes_removed"], st["runs"], n["entries_before"], n["entries_after"], b["wall_ms"],
+                   st["hash_ms"], st["bytes_moved"] / 1e6, st["compact_ms"], b["compact_gbs"], b["copy_ms"], b["copy_gbs"], n["edit_ms"], rb["total_ms"], n["total_ms"], b["recreate_warmcache_ms"], st["bytes_freed"] / 1e6,
+                   b["updated_mrays"], b["fresh_mrays"], b["updated_mrays"] / b["fresh_mrays"]))
+    return "\n".join(out) + "\n"
+
+
 def markdown_meshes(recs):
     out = ["", "## Adding meshes in place (tools/scene_update_bench.py --only meshes)", "",
            "| workload | appended (triangles / rows / BVH nodes) | entries | generated | ctl_scene_update_meshes, wall | hashing (host) | append (copies + uploads + kernel) | drop + generate | rebuild (key + sort / topology + gather / boxes) | node-set stages, device total | re-creation, warm cache | updated scene | fresh scene | ratio |",
@@ -381,6 +448,9 @@ def run(workload, args):
     if args.only == "nodes":
         node_set(workload, args, sc, scene, node, X0, size, rec)
         return rec
+    if args.only == "mesh-remove":
+        mesh_remove(workload, args, sc, scene, node, X0, size, rec)
+        return rec
     if args.only == "meshes":
         mesh_set(workload, args, sc, scene, node, X0, size, rec)
         return rec
@@ -439,6 +509,8 @@ def markdown_deform(recs):
 
 
 def markdown(recs):
+    if "meshes_remove" in recs[0]:
+        return markdown_mesh_remove(recs) + markdown_meshes(recs)
     if "skin_animate_ms" in recs[0]:
         return markdown_skin(recs)
     if "rebuild_M3" in recs[0]:
@@ -469,7 +541,7 @@ def main():
     ap.add_argument("--depth", type=int, default=8); ap.add_argument("--passes", type=int, default=4)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scene_update.jsonl"))
     ap.add_argument("--results", default=None)
-    ap.add_argument("--only", default=None, choices=["deform", "skin", "rebuild", "nodes", "meshes"], help="meshes: the camera update and ctl_scene_update_meshes appending one mesh the size of the middle node's, with one node of it, against the re-creation of the same description; nodes: the camera update and ctl_scene_update_nodes adding and removing one node against the re-creation of the same description; rebuild: the camera update and ctl_scene_rebuild_flat after M3 and after D1 against the re-creation of the same pose; deform: the camera update and the one-mesh deformation alone; skin: the camera update and the pose change of a bound mesh against the host path")
+    ap.add_argument("--only", default=None, choices=["deform", "skin", "rebuild", "nodes", "meshes", "mesh-remove"], help="mesh-remove: the append of --only meshes, then the original mesh in front of the copy removed with its nodes through ctl_scene_update_mesh_set, against a plain device copy of the bytes the compaction moved and the re-creation of the same description; meshes: the camera update and ctl_scene_update_meshes appending one mesh the size of the middle node's, with one node of it, against the re-creation of the same description; nodes: the camera update and ctl_scene_update_nodes adding and removing one node against the re-creation of the same description; rebuild: the camera update and ctl_scene_rebuild_flat after M3 and after D1 against the re-creation of the same pose; deform: the camera update and the one-mesh deformation alone; skin: the camera update and the pose change of a bound mesh against the host path")
     ap.add_argument("--builder", default="lbvh", choices=["lbvh", "ploc"], help="the builder of --only rebuild and --only nodes (csrc/flat_ploc.h); the record carries it")
     ap.add_argument("--tag", default=None, help="a word for the record: which library ran (an A/B against another commit's library through $CTL_AMD_LIB)")
     args = ap.parse_args()
@@ -478,7 +550,7 @@ def main():
     recs = []
     for w in args.workloads.split(","):
         rec = run(w, args)
-        if args.only in ("rebuild", "nodes", "meshes"):
+        if args.only in ("rebuild", "nodes", "meshes", "mesh-remove"):
             rec["builder"] = args.builder
         if args.tag:
             rec["tag"] = args.tag
