@@ -787,6 +787,9 @@ class DynamicScene:
         self._next_node_id = 0
         self._mesh_ids = []     # per mesh, in index order: its id — assigned at add_mesh, never reused, kept by RemoveMesh's shift (mesh_ids, Scene.update_mesh_set)
         self._next_mesh_id = 0
+        self._image_ids = []    # per image, in index order: its id — assigned at add_image, never reused, kept by remove_image's shift; replace_image gives the index a new one
+        self._next_image_id = 0
+        self._image_sizes = {}  # image id -> (width, height) as add_image / replace_image took them
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -912,7 +915,58 @@ class DynamicScene:
         t = np.ascontiguousarray(texels, dtype=np.uint32)
         idx = u32()
         _check(lib.ctl_builder_add_image(self._h, t.ctypes.data_as(C.c_void_p), u32(t.shape[1]), u32(t.shape[0]), u32(texel_type), u32(wrap), u32(filter), C.byref(idx)))
+        self._sync_image_ids(idx.value)
+        self._image_ids.append(self._next_image_id); self._next_image_id += 1
+        self._image_sizes[self._image_ids[-1]] = (t.shape[1], t.shape[0])
         return idx.value
+
+    def _sync_image_ids(self, n):
+        """images the builder made without add_image (ParseMitsubaScene) get their ids now"""
+        while len(self._image_ids) < n:
+            self._image_ids.append(self._next_image_id); self._next_image_id += 1
+
+    def _image_count(self):
+        n = u32()
+        _check(lib.ctl_builder_image_count(self._h, C.byref(n)))
+        return n.value
+
+    def image_ids(self):
+        """the stable id of every image, in index order (also on the description UpdateScene returns, as desc.image_ids): what Scene.update_image_set computes its map
+        from.  An image replaced by another size carries a new id: to the scene it is a fresh image"""
+        return tuple(self._image_ids)
+
+    def remove_image(self, image):
+        """ctl_builder_remove_image: an image that no material row and no light references leaves the builder; the images behind it move down by one index (their ids stay:
+        image_ids()) and every texture that names one of them follows.  CtlError(ERR_INVALID), the builder unchanged, for a bad index or an image still referenced — the
+        message names the first referrer; rows orphaned by DeleteNode / RemoveMesh count (set_material repoints them).  UpdateScene() then gives the new description, which
+        Scene.update_image_set applies in place."""
+        self._sync_image_ids(self._image_count())      # images a loader made get their ids BEFORE the shift
+        _check(lib.ctl_builder_remove_image(self._h, u32(image)))
+        if image < len(self._image_ids):
+            del self._image_ids[image]
+
+    def replace_image(self, image, texels):
+        """ctl_builder_replace_image: new level-0 texels (h, w) uint32 of ANOTHER size at the same index; texel type, wrap and filter stay.  With the image's own size it is
+        update_image (and the id stays).  CtlError(ERR_INVALID) for a bad index and for the environment map's image: the builder is untouched."""
+        t = np.ascontiguousarray(texels, dtype=np.uint32)
+        if t.ndim != 2:
+            raise ValueError("replace_image: texels (h, w) uint32")
+        self._sync_image_ids(self._image_count())
+        _check(lib.ctl_builder_replace_image(self._h, u32(image), t.ctypes.data_as(C.c_void_p), u32(t.shape[1]), u32(t.shape[0])))
+        if self._image_sizes.get(self._image_ids[image]) != (t.shape[1], t.shape[0]):      # (a size this object never saw — a loader's image — counts as another)
+            self._image_ids[image] = self._next_image_id; self._next_image_id += 1
+        self._image_sizes[self._image_ids[image]] = (t.shape[1], t.shape[0])
+
+    def get_material(self, index):
+        """ctl_builder_get_material: a copy of row `index` of the material table — absolute, as desc.nodes[k].material_offset + local index or what add_material returned"""
+        m = ctl_material()
+        _check(lib.ctl_builder_get_material(self._h, u32(index), C.byref(m)))
+        return m
+
+    def set_material(self, index, material):
+        """ctl_builder_set_material — DynamicScene::getMaterials + Invalidate: replaces row `index` of the material table (absolute index) after the checks a new record
+        gets; a nested-material index that breaks the BSDFFirst rule is refused.  UpdateScene() then makes the derived sampling weights; Scene.update applies the result."""
+        _check(lib.ctl_builder_set_material(self._h, u32(index), C.byref(material)))
 
     def update_image(self, image, texels):
         """ctl_builder_update_image — DynamicScene::ReloadTextures for a caller that supplies the bitmap: new level-0 texels (h, w) uint32 for a registered image, same size.
@@ -1025,6 +1079,8 @@ class DynamicScene:
         self.desc.node_ids = self.node_ids()   # (a Python attribute next to the C fields) what Scene.update_nodes computes its map from
         self._sync_mesh_ids(self.desc.n_meshes)
         self.desc.mesh_ids = self.mesh_ids()   # likewise, for Scene.update_mesh_set
+        self._sync_image_ids(self.desc.n_images)
+        self.desc.image_ids = self.image_ids() # likewise, for Scene.update_image_set
         return self.desc
 
     def getKernelSceneData(self):
@@ -1049,6 +1105,7 @@ class Scene:
         self._light_counts = (int(desc.n_lights_buf), int(desc.n_anim_bytes))   # the sizes read_lights' buffers must have
         self._node_ids = getattr(desc, "node_ids", None)   # of the description the scene holds (DynamicScene.UpdateScene), or None
         self._mesh_ids = getattr(desc, "mesh_ids", None)   # likewise
+        self._image_ids = getattr(desc, "image_ids", None) # likewise
         self._image_dims = [(int(desc.images[i].width), int(desc.images[i].height)) for i in range(desc.n_images)]   # an update keeps them (read_image)
 
     def update(self, desc):
@@ -1260,6 +1317,35 @@ class Scene:
         _check(lib.ctl_scene_read_image(self._h, u32(image), T.ctypes.data, C.c_size_t(n), C.byref(levels), off))
         return dict(texels=T, levels=levels.value, offsets=np.array(off[:], np.uint32))
 
+    def update_image_set(self, sc_or_desc, image_map=None):
+        """ctl_scene_update_image_set: another SET of images in place — after DynamicScene.add_image, remove_image and replace_image (and whatever set_material and the light
+        calls changed beside them) on a builder whose description the scene holds, and UpdateScene().  The pyramids of the kept images move on the device into a new texel
+        pool laid out as a fresh scene's (csrc/scene_image_set.hip: texels written by update_image survive), fresh images are uploaded and their pyramids built there, then
+        the stages of update run over the rest of the description.  Another mesh or node set is refused: those go through their own calls.
+        image_map: per new image its index in the description the scene holds or 0xffffffff (fresh: added or replaced); None: computed from the stable image ids of the two
+        descriptions (DynamicScene.UpdateScene sets them).
+        Returns the stats dict: images_kept, images_fresh, images_removed, runs, texels_moved, texels_uploaded, bytes_freed, move_ms, pyramid_ms, hash_ms, total_ms, update =
+        the update_stats dict.  CtlError(ERR_INVALID / ERR_UNSUPPORTED) leaves the scene as it was.  Start the next pass with new_trace."""
+        desc = sc_or_desc.getKernelSceneData() if isinstance(sc_or_desc, DynamicScene) else sc_or_desc
+        if image_map is None:
+            new_ids = getattr(desc, "image_ids", None)
+            if new_ids is None or self._image_ids is None:
+                raise ValueError("update_image_set: no image ids on the descriptions (DynamicScene.UpdateScene sets them): pass image_map")
+            index = {i: k for k, i in enumerate(self._image_ids)}
+            image_map = [index.get(i, 0xffffffff) for i in new_ids]
+        M = np.ascontiguousarray(image_map, dtype=np.uint32)
+        st = ctl_scene_image_set_stats()
+        _check(lib.ctl_scene_update_image_set(self._h, C.byref(desc), M.ctypes.data if len(M) else None, u32(len(M)), C.addressof(st)))
+        self._keepalive = desc
+        self._image_ids = getattr(desc, "image_ids", None)
+        self._node_ids = getattr(desc, "node_ids", self._node_ids)
+        self._light_counts = (int(desc.n_lights_buf), int(desc.n_anim_bytes))
+        self._image_dims = [(int(desc.images[i].width), int(desc.images[i].height)) for i in range(desc.n_images)]
+        self.last_mask = st.update.mask
+        out = {k: getattr(st, k) for k, _ in st._fields_ if k != "update"}
+        out["update"] = {k: getattr(st.update, k) for k, _ in st.update._fields_}
+        return out
+
     def read_mesh_geometry(self, mesh, vertices=False):
         """ctl_scene_read_mesh_geometry: dict(tri (n_tri, 8) uint32, woop (n_rows, 12) uint32) as HBM holds them — any mesh of any scene — and, with vertices=True
         (a bound, posed mesh), positions and normals (n_vert, 3) float32 of the last pose"""
@@ -1304,6 +1390,11 @@ class ctl_scene_update_stats(C.Structure):
 class ctl_scene_image_stats(C.Structure):
     _fields_ = [("levels", u32), ("texels_written", u32), ("materials_patched", u32), ("env_tables", u32),
                 ("upload_ms", f32), ("pyramid_ms", f32), ("env_ms", f32), ("hash_ms", f32), ("total_ms", f32)]
+
+
+class ctl_scene_image_set_stats(C.Structure):
+    _fields_ = [("images_kept", u32), ("images_fresh", u32), ("images_removed", u32), ("runs", u32), ("texels_moved", u64), ("texels_uploaded", u64), ("bytes_freed", u64),
+                ("move_ms", f32), ("pyramid_ms", f32), ("hash_ms", f32), ("total_ms", f32), ("update", ctl_scene_update_stats)]
 
 
 class ctl_scene_rebuild_stats(C.Structure):
@@ -1363,6 +1454,11 @@ for _n, _a in (("ctl_scene_rebuild_flat", [C.c_void_p, C.c_void_p]), ("ctl_flat_
                ("ctl_scene_update_mesh_set", [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_void_p, u32, C.c_int, C.c_void_p]),
                ("ctl_flat_bvh_update_mesh_set", [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_void_p, u32, C.c_int]),
                ("ctl_compact_tri_rows_host", [C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p, C.c_void_p]),
+               ("ctl_builder_image_count", [C.c_void_p, C.c_void_p]), ("ctl_builder_remove_image", [C.c_void_p, u32]), ("ctl_builder_replace_image", [C.c_void_p, u32, C.c_void_p, u32, u32]),
+               ("ctl_builder_get_material", [C.c_void_p, u32, C.c_void_p]), ("ctl_builder_set_material", [C.c_void_p, u32, C.c_void_p]),
+               ("ctl_scene_update_image_set", [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_void_p]),
+               ("ctl_image_set_plan_host", [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+               ("ctl_move_texels_host", [C.c_void_p, u64, C.c_void_p, u32, C.c_void_p, u64]),
                ("ctl_triangle_woop_rows", [C.c_void_p, C.c_void_p]), ("ctl_scene_read_triangle_rows", [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]), ("ctl_append_leaf_rows_host", [C.c_void_p, u32, u32, u32, u32, C.c_void_p, C.c_void_p])):
     if hasattr(lib, _n):
         getattr(lib, _n).argtypes = _a
@@ -1448,6 +1544,27 @@ def mip_pyramid_host(texels, texel_type=TEXEL_RGBCOL):
     T = np.zeros(n, np.uint32)
     _check(lib.ctl_mip_pyramid_host(C.addressof(m), T.ctypes.data, C.c_size_t(n), C.byref(levels), off))
     return dict(texels=T, levels=levels.value, offsets=np.array(off[:], np.uint32))
+
+
+def image_set_plan_host(old_desc, new_desc, image_map):
+    """ctl_image_set_plan_host (no GPU): the acceptance check of Scene.update_image_set for a scene made from old_desc, and its plan — dict(offsets (n,) uint64: the texel
+    offset of every image's level 0 in the new pool; total: the pool's texels; runs (n_runs + 1, 4) uint64: per run first destination texel, first source texel, length,
+    kept texels in front of it, then the sentinel; n_runs).  CtlError(ERR_INVALID) names the rule broken."""
+    M = np.ascontiguousarray(image_map, dtype=np.uint32)
+    off = np.zeros(len(M), np.uint64); runs = np.zeros((len(M) + 1, 4), np.uint64); total = u64(); n_runs = u32()
+    _check(lib.ctl_image_set_plan_host(C.byref(old_desc), C.byref(new_desc), M.ctypes.data if len(M) else None, u32(len(M)), off.ctypes.data if len(M) else None,
+                                       C.addressof(total), runs.ctypes.data, C.addressof(n_runs)))
+    return dict(offsets=off, total=int(total.value), runs=runs[:n_runs.value + 1].copy(), n_runs=int(n_runs.value))
+
+
+def move_texels_host(old_pool, runs, new_pool):
+    """ctl_move_texels_host (no GPU): k_move_texels' arithmetic on the host — the kept texels of old_pool into new_pool (uint32, written in place) through the run table of
+    image_set_plan_host; words no run covers are untouched"""
+    O = np.ascontiguousarray(old_pool, np.uint32); R = np.ascontiguousarray(runs, np.uint64).reshape(-1, 4)
+    if new_pool.dtype != np.uint32 or not new_pool.flags.c_contiguous:
+        raise ValueError("move_texels_host: new_pool must be a contiguous uint32 array")
+    _check(lib.ctl_move_texels_host(O.ctypes.data if len(O) else None, u64(len(O)), R.ctypes.data, u32(len(R) - 1), new_pool.ctypes.data if len(new_pool) else None, u64(len(new_pool))))
+    return new_pool
 
 
 def triangle_woop_rows(desc):

@@ -10,7 +10,7 @@ import hashlib, os, subprocess, sys, glob, tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libctl_amd.so")
-SRCS = ["kernels.hip", "shade_basic.hip", "shade_full.hip", "shade_class_a.hip", "shade_class_b.hip", "shade_class_c.hip", "shade_class_p.hip", "shade_class_g.hip", "shade_class_g_wf.hip", "shade_class_p_wf.hip", "shade_class_a_wf.hip", "shade_class_b_wf.hip", "shade_class_c_wf.hip", "shade_basic_wf.hip", "shade_full_wf.hip", "shade_full_media.hip", "shade_full_media_grid.hip", "shade_full_partials.hip", "medium_stage.hip", "megakernel.hip", "prim_tracer.hip", "traversal_probe.hip", "shading_eval_basic.hip", "shading_eval_full.hip", "shading_eval_partials.hip", "image_pipeline.hip", "nlm_filter.hip", "block_sampler.hip", "tracer.hip", "scene_update.hip", "flat_refit.hip", "flat_rebuild.hip", "flat_nodes.hip", "flat_meshes.hip", "flat_mesh_set.hip", "mesh_skin.hip", "shape_set.hip", "scene_images.hip", "volume_eval.hip", "capi.hip", "scene_builder.cpp", "scene_checks.cpp", "geometry_hash.cpp", "bvh_builder.cpp", "sbvh_builder.cpp", "flatten.cpp", "flat_rebuild.cpp", "flat_nodes.cpp", "flat_meshes.cpp", "flat_mesh_set.cpp", "mitsuba_loader.cpp", "image_io.cpp", "jpeg_decode.cpp", "mesh_io.cpp", "scene_cache.cpp", "comm.cpp"]
+SRCS = ["kernels.hip", "shade_basic.hip", "shade_full.hip", "shade_class_a.hip", "shade_class_b.hip", "shade_class_c.hip", "shade_class_p.hip", "shade_class_g.hip", "shade_class_g_wf.hip", "shade_class_p_wf.hip", "shade_class_a_wf.hip", "shade_class_b_wf.hip", "shade_class_c_wf.hip", "shade_basic_wf.hip", "shade_full_wf.hip", "shade_full_media.hip", "shade_full_media_grid.hip", "shade_full_partials.hip", "medium_stage.hip", "megakernel.hip", "prim_tracer.hip", "traversal_probe.hip", "shading_eval_basic.hip", "shading_eval_full.hip", "shading_eval_partials.hip", "image_pipeline.hip", "nlm_filter.hip", "block_sampler.hip", "tracer.hip", "scene_update.hip", "flat_refit.hip", "flat_rebuild.hip", "flat_nodes.hip", "flat_meshes.hip", "flat_mesh_set.hip", "mesh_skin.hip", "shape_set.hip", "scene_images.hip", "scene_image_set.hip", "volume_eval.hip", "capi.hip", "scene_builder.cpp", "scene_checks.cpp", "geometry_hash.cpp", "bvh_builder.cpp", "sbvh_builder.cpp", "flatten.cpp", "flat_rebuild.cpp", "flat_nodes.cpp", "flat_meshes.cpp", "flat_mesh_set.cpp", "scene_image_set.cpp", "mitsuba_loader.cpp", "image_io.cpp", "jpeg_decode.cpp", "mesh_io.cpp", "scene_cache.cpp", "comm.cpp"]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-munsafe-fp-atomics",
          "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-pthread",
          # device code without the SLP vectoriser: on gfx950 a packed f32 multiply / add issues no faster than the two scalar ones, and the register pairs it needs cost v_mov

@@ -13,6 +13,7 @@
 #include "flat_meshes.h"
 #include "flat_mesh_set.h"
 #include "flat_device.h"
+#include "scene_image_set.h"
 #include "mesh_skin.h"
 #include "shape_set.h"
 #include "material_factory.h"
@@ -435,6 +436,41 @@ int ctl_scene_read_image(ctl_scene* scene, uint32_t image_index, uint32_t* texel
     if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
     CTL_REQUIRE(scene, "null scene");
     CTL_TRY scene->s.read_image(image_index, texels_out, capacity, levels_out, level_offsets_out); CTL_CATCH
+}
+// ---- another set of images (scene_image_set.hip, scene_image_set.cpp)
+int ctl_builder_image_count(const ctl_builder* b, uint32_t* count_out) { CTL_REQUIRE(b && count_out, "null argument"); *count_out = (uint32_t)b->b.images.size(); return CTL_OK; }
+int ctl_builder_remove_image(ctl_builder* b, uint32_t image_index) { CTL_REQUIRE(b, "null argument"); CTL_TRY b->b.remove_image(image_index); CTL_CATCH }
+int ctl_builder_replace_image(ctl_builder* b, uint32_t image_index, const uint32_t* texels, uint32_t width, uint32_t height) {
+    CTL_REQUIRE(b, "null argument");
+    CTL_TRY b->b.replace_image(image_index, texels, width, height); CTL_CATCH
+}
+int ctl_builder_get_material(const ctl_builder* b, uint32_t absolute_index, ctl_material* out) { CTL_REQUIRE(b && out, "null argument"); CTL_TRY *out = b->b.material(absolute_index); CTL_CATCH }
+int ctl_builder_set_material(ctl_builder* b, uint32_t absolute_index, const ctl_material* material) { CTL_REQUIRE(b && material, "null argument"); CTL_TRY b->b.set_material(absolute_index, *material); CTL_CATCH }
+int ctl_scene_update_image_set(ctl_scene* scene, const ctl_scene_desc* new_desc, const uint32_t* old_image_of_new, uint32_t n_new_images, ctl_scene_image_set_stats* stats_out) {
+    if (device_count() <= 0) return fail(CTL_ERR_NO_DEVICE, kNoDevice);
+    CTL_REQUIRE(scene && new_desc, "null argument");
+    CTL_REQUIRE(old_image_of_new || !n_new_images, "ctl_scene_update_image_set: null image map");
+    const int rc = [&]() -> int { CTL_TRY flat_rebuilder::update_image_set(scene->s, *new_desc, old_image_of_new, n_new_images, scene->basis, stats_out); CTL_CATCH }();
+    if (rc == CTL_OK) { scene->n_materials = new_desc->n_materials; scene->n_images = new_desc->n_images; scene->basis.fill(*new_desc); }
+    return rc;
+}
+static_assert(sizeof(image_run) == 4 * sizeof(uint64_t), "a run is four words of the table ctl_image_set_plan_host hands out");
+int ctl_image_set_plan_host(const ctl_scene_desc* old_desc, const ctl_scene_desc* new_desc, const uint32_t* old_image_of_new, uint32_t n_new_images,
+                            uint64_t* offsets_out, uint64_t* total_out, uint64_t* run_table_out, uint32_t* n_runs_out) {
+    CTL_REQUIRE(old_desc && new_desc, "null argument");
+    CTL_TRY
+        node_set_basis basis; basis.fill(*old_desc);
+        geometry_hashes held; hash_geometry(*old_desc, held);
+        image_set_plan plan; plan_image_set(basis, held, *new_desc, old_image_of_new, n_new_images, nullptr, plan, "ctl_image_set_plan_host");
+        if (offsets_out && !plan.offsets.empty()) std::memcpy(offsets_out, plan.offsets.data(), plan.offsets.size() * 8);
+        if (total_out) *total_out = plan.total;
+        if (run_table_out) std::memcpy(run_table_out, plan.runs.data(), plan.runs.size() * sizeof(image_run));
+        if (n_runs_out) *n_runs_out = plan.n_runs();
+    CTL_CATCH
+}
+int ctl_move_texels_host(const uint32_t* old_pool, uint64_t n_old_texels, const uint64_t* run_table, uint32_t n_runs, uint32_t* new_pool, uint64_t n_new_texels) {
+    CTL_REQUIRE(run_table && (old_pool || !n_old_texels) && (new_pool || !n_new_texels), "null argument");
+    CTL_TRY move_texels_host(old_pool, n_old_texels, reinterpret_cast<const image_run*>(run_table), n_runs, new_pool, n_new_texels); CTL_CATCH
 }
 int ctl_shape_sets_host(const ctl_scene_desc* desc, uint32_t mesh_index, const ctl_triangle_data* tri_data, const ctl_woop_tri* woop, ctl_light* lights_out, uint8_t* anim_out) {
     CTL_REQUIRE(desc, "null description");

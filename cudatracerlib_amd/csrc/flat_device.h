@@ -25,6 +25,9 @@ struct mesh_tail_stage {
     void run(mesh_growth& Gr, const ctl_scene_desc& d, const mesh_set_plan& grow);
 };
 struct mesh_set_change;   // flat_mesh_set.h
+// scene_images.hip: the pyramid of one image from its level 0, in place in the pool — one k_mip_level launch per level on the null stream, nothing waited for.  level0: the
+// image's first texel (device); width, height, type: the image's; L: its level table
+void launch_mip_levels(uint32_t* level0, uint32_t width, uint32_t height, uint32_t type, const dev_mip_levels& L);
 
 // The rebuild of flat_rebuild.h on the device over n entries (and the closing entry behind them) that need not be the scene's own: ctl_scene_rebuild_flat runs it over
 // flat_leaves_, ctl_scene_update_nodes over the entries it has just assembled.  Three steps, so that a caller can put its own work between them:
@@ -60,6 +63,11 @@ struct flat_rebuilder {
     static void update_mesh_set(Scene& A, const ctl_scene_desc& d, const uint32_t* old_mesh_of_new, uint32_t n_new_meshes, const uint32_t* old_of_new, uint32_t n_new_nodes,
                                 const node_set_basis& basis, ctl_scene_mesh_set_stats* stats);
     static void remap_skins(Scene& A, const mesh_compaction& cut, const ctl_scene_desc& d);
+    // ctl_scene_update behind its diff (scene_update.hip): Scene::update is scene_desc_diff + this; ctl_scene_update_image_set comes here with the mask of scene_desc_diff_small
+    static uint32_t apply_update(Scene& A, const ctl_scene_desc& d, uint32_t mask, const geometry_hashes& geom, ctl_scene_update_stats* stats);
+    // ctl_scene_update_image_set (scene_image_set.hip): images removed, added and replaced by ones of another size — the kept pyramids moved on the device into a new texel
+    // pool, the fresh ones uploaded and built there —, then the stages of ctl_scene_update over the rest of d; with an identity map it is Scene::update
+    static void update_image_set(Scene& A, const ctl_scene_desc& d, const uint32_t* old_image_of_new, uint32_t n_new_images, const node_set_basis& basis, ctl_scene_image_set_stats* stats);
     flat_rebuilder() {}
     flat_rebuilder(const flat_rebuilder&) = delete; flat_rebuilder& operator=(const flat_rebuilder&) = delete;
     ~flat_rebuilder();

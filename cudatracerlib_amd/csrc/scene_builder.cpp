@@ -12,6 +12,7 @@
 #include "shape_set.h"
 #include "env_tables.h"
 #include "volume_eval.h"
+#include "device_scene.h"   // the BSDF model classifiers
 #include <cstring>
 #include <algorithm>
 #include <stdexcept>
@@ -613,6 +614,81 @@ void scene_builder::remove_mesh(uint32_t mesh_index) {
         }
     }
     for (ctl_node& n : nodes) if (n.mesh_index > mesh_index) n.mesh_index--;
+}
+
+// ---- the image set and the material table edited after the fact (ctl_builder_remove_image, _replace_image, _get_material, _set_material)
+namespace {
+const char* const kTextureSlots[6] = { "tex[0]", "tex[1]", "tex[2]", "tex[3]", "map_tex", "alpha_tex" };
+ctl_texture& texture_slot(ctl_material& m, int k) { return k < 4 ? m.tex[k] : (k == 4 ? m.map_tex : m.alpha_tex); }
+const ctl_texture& texture_slot(const ctl_material& m, int k) { return k < 4 ? m.tex[k] : (k == 4 ? m.map_tex : m.alpha_tex); }
+bool names_image(const ctl_texture& t, uint32_t image) { return t.type == CTL_TEX_IMAGE && t.image == image; }
+void lower_image(ctl_texture& t, uint32_t removed) { if (t.type == CTL_TEX_IMAGE && t.image != 0xffffffffu && t.image > removed) t.image--; }
+}  // namespace
+
+// The counterpart of add_image for an image nothing reads any more: the builder afterwards holds, in images, image_texels, mats and lights, what a builder holds that never
+// added the image.  Everything that can refuse runs before the first byte is written.  A referrer is any texture slot of type CTL_TEX_IMAGE of any row of `mats` — a row
+// orphaned by remove_node / remove_mesh included: the table is not compacted, and the row would reach a scene with a dangling index —, a DiffuseLight's radiance texture
+// and the environment light's map.  mesh_materials, which only a later add_node copies from, follow the shift; a slot there that names the removed image becomes "no
+// image" (0xffffffff, black: Texture.cu:33-34), for the host to set on the node's copy
+void scene_builder::remove_image(uint32_t image) {
+    const std::string who = "ctl_builder_remove_image: ";
+    if (image >= images.size()) throw std::runtime_error(who + "bad image index " + std::to_string(image) + " of " + std::to_string(images.size()));
+    for (size_t i = 0; i < mats.size(); i++) for (int k = 0; k < 6; k++) if (names_image(texture_slot(mats[i], k), image))
+        throw std::runtime_error(who + "material " + std::to_string(i) + " (" + kTextureSlots[k] + ") still references image " + std::to_string(image) + " (ctl_builder_set_material first)");
+    for (size_t i = 0; i < lights.size(); i++) {
+        if (lights[i].type == CTL_LIGHT_DIFFUSE && names_image(lights[i].rad_texture, image)) throw std::runtime_error(who + "the radiance texture of light " + std::to_string(i) + " still references image " + std::to_string(image));
+        if (lights[i].type == CTL_LIGHT_INFINITE && lights[i].env_image == image) throw std::runtime_error(who + "light " + std::to_string(i) + " (the environment map) still references image " + std::to_string(image));
+    }
+    images.erase(images.begin() + image); image_texels.erase(image_texels.begin() + image);
+    for (ctl_material& m : mats) for (int k = 0; k < 6; k++) lower_image(texture_slot(m, k), image);
+    for (ctl_material& m : mesh_materials) for (int k = 0; k < 6; k++) { ctl_texture& t = texture_slot(m, k); if (names_image(t, image)) t.image = 0xffffffffu; else lower_image(t, image); }
+    for (ctl_light& L : lights) {
+        if (L.type == CTL_LIGHT_DIFFUSE) lower_image(L.rad_texture, image);
+        if (L.type == CTL_LIGHT_INFINITE && L.env_image > image) L.env_image--;
+    }
+}
+
+// new level-0 texels of ANOTHER size at the same index; texel type, wrap and filter mode stay.  With the image's own size it is update_image.  The environment map's image
+// is refused: its tables were laid out in the anim blob by set_environment_map for its size
+void scene_builder::replace_image(uint32_t image, const uint32_t* texels, uint32_t w, uint32_t h) {
+    const std::string who = "ctl_builder_replace_image: ";
+    if (image >= images.size()) throw std::runtime_error(who + "bad image index " + std::to_string(image) + " of " + std::to_string(images.size()));
+    if (!texels || w == 0 || h == 0) throw std::runtime_error(who + "empty image");
+    if (w == images[image].width && h == images[image].height) { update_image(image, texels, w, h); return; }
+    for (size_t i = 0; i < lights.size(); i++) if (lights[i].type == CTL_LIGHT_INFINITE && lights[i].env_image == image)
+        throw std::runtime_error(who + "image " + std::to_string(image) + " is the environment map of light " + std::to_string(i) + ": its tables in the anim blob were laid out for " +
+                                 std::to_string(images[image].width) + " x " + std::to_string(images[image].height));
+    image_texels[image].assign(texels, texels + (size_t)w * h);
+    images[image].width = w; images[image].height = h;
+}
+
+const ctl_material& scene_builder::material(uint32_t index) const {
+    if (index >= mats.size()) throw std::runtime_error("ctl_builder_get_material: bad material index " + std::to_string(index) + " of " + std::to_string(mats.size()));
+    return mats[index];
+}
+// DynamicScene::getMaterials + Invalidate for one row of the material table, addressed as the kernels address it (ctl_node::material_offset + local index, or what
+// add_aux_material returned).  The record is stored as given, node_light_index included (a host edits what get_material handed it); what can be judged of it without the
+// transmittance tables is judged here, the rest by ctl_scene_desc_check as for any description
+void scene_builder::set_material(uint32_t index, const ctl_material& m) {
+    const std::string who = "ctl_builder_set_material: ";
+    if (index >= mats.size()) throw std::runtime_error(who + "bad material index " + std::to_string(index) + " of " + std::to_string(mats.size()));
+    if (!is_simple_bsdf(m.bsdf_type) && !is_nesting_bsdf(m.bsdf_type)) throw std::runtime_error(who + "BSDF type " + std::to_string(m.bsdf_type) + " has no HIP implementation yet");
+    if (m.map_kind > CTL_MAP_HEIGHT) throw std::runtime_error(who + "unknown surface map kind");
+    if (m.alpha_state > CTL_ALPHA_REFLECTANCE_COLOR || m.alpha_state == 4) throw std::runtime_error(who + "unknown alpha blend state");
+    for (int k = 0; k < 6; k++) {
+        if ((k == 4 && m.map_kind == CTL_MAP_NONE) || (k == 5 && m.alpha_state == CTL_ALPHA_DISABLED)) continue;   // counted only where they are read, as check_scene_desc counts them
+        const ctl_texture& t = texture_slot(m, k);
+        if (t.type != CTL_TEX_CONSTANT && t.type != CTL_TEX_CHECKER && t.type != CTL_TEX_IMAGE && t.type != 0) throw std::runtime_error(who + "texture type " + std::to_string(t.type) + " has no HIP implementation yet");
+        if (t.type == CTL_TEX_IMAGE && t.image != 0xffffffffu && t.image >= images.size()) throw std::runtime_error(who + std::string(kTextureSlots[k]) + " references image " + std::to_string(t.image) + " of " + std::to_string(images.size()));
+    }
+    // BSDFFirst (SceneTypes/BSDF.h:102): a nested BSDF is one of the simple models — the rule add_aux_material holds a new row to, in both directions here
+    for (int k = 0; k < nested_bsdf_count(m.bsdf_type); k++) {
+        const uint32_t ni = m.u[2 + k];
+        if (ni >= mats.size() || ni == index || mats[ni].bsdf_type >= CTL_BSDF_HK) throw std::runtime_error(who + "nested material index " + std::to_string(ni) + " is out of range or names no simple BSDF (BSDFFirst)");
+    }
+    if (m.bsdf_type >= CTL_BSDF_HK) for (size_t i = 0; i < mats.size(); i++) for (int k = 0; k < nested_bsdf_count(mats[i].bsdf_type); k++) if (mats[i].u[2 + k] == index && i != index)
+        throw std::runtime_error(who + "material " + std::to_string(i) + " nests material " + std::to_string(index) + ", which must stay a simple BSDF (BSDFFirst)");
+    mats[index] = m;
 }
 
 void scene_builder::finalize(ctl_scene_desc& out) {

@@ -88,6 +88,13 @@ struct scene_builder {
     // ctl_builder_remove_mesh: a mesh without nodes leaves tri, woop, widx, bvh, meshes and mesh_info; the later meshes' offsets, the mesh_index of their nodes and the
     // i_dat / t_dat of their area lights move down.  mesh_materials is not compacted.  Refused (nothing changed) for a bad index or a mesh a node still instances
     void remove_mesh(uint32_t mesh_index);
+    // ctl_builder_remove_image: an image no material row and no light references leaves images / image_texels; every image index above it, in mats, mesh_materials and
+    // lights, moves down.  ctl_builder_replace_image: level-0 texels of another size at the same index (not the environment map's).  Refused: nothing changed
+    void remove_image(uint32_t image);
+    void replace_image(uint32_t image, const uint32_t* texels, uint32_t w, uint32_t h);
+    // one row of the material table by its absolute index (ctl_builder_get_material / _set_material): DynamicScene::getMaterials + Invalidate
+    const ctl_material& material(uint32_t index) const;
+    void set_material(uint32_t index, const ctl_material& m);
     void finalize(ctl_scene_desc& out);
 };
 

@@ -20,6 +20,7 @@
 #include "env_tables.h"
 #include "material_textures.h"
 #include "geometry_hash.h"
+#include "flat_device.h"
 #include <chrono>
 #include <cstddef>
 #include <memory>
@@ -100,6 +101,16 @@ float ms_since(clk::time_point t0) { return std::chrono::duration<float, std::mi
 
 }  // namespace
 
+void launch_mip_levels(uint32_t* level0, uint32_t width, uint32_t height, uint32_t type, const dev_mip_levels& L) {
+    const uint32_t* src = level0; uint32_t pw = width;
+    for (uint32_t l = 1, j = width / 2, k = height / 2; l < L.levels; l++, j >>= 1, k >>= 1) {
+        uint32_t* dst = level0 + L.offsets[l - 1];
+        const size_t n = (size_t)j * k;
+        hipLaunchKernelGGL(k_mip_level, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, nullptr, src, dst, pw, j, k, type); CTL_HIP(hipGetLastError());
+        src = dst; pw = j;
+    }
+}
+
 void Scene::read_image(uint32_t image, uint32_t* texels_out, size_t capacity, uint32_t* levels_out, uint32_t* level_offsets_out) {
     require_device();
     if (!snap_ || image >= snap_->images.size() || image >= image_off_.size()) throw std::runtime_error("ctl_scene_read_image: bad image index " + std::to_string(image));
@@ -155,15 +166,7 @@ void Scene::update_image(uint32_t image, const uint32_t* texels, uint32_t width,
     st.upload_ms = ms_since(t0);
     // ---- 2. the pyramid, level by level, and the one texel ImageTexture::Average() addresses
     t0 = clk::now();
-    {
-        const uint32_t* src = pool; uint32_t pw = M.width;
-        for (uint32_t l = 1, j = M.width / 2, k = M.height / 2; l < L.levels; l++, j >>= 1, k >>= 1) {
-            uint32_t* dst = pool + L.offsets[l - 1];
-            const size_t n = (size_t)j * k;
-            hipLaunchKernelGGL(k_mip_level, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, nullptr, src, dst, pw, j, k, M.texel_type); CTL_HIP(hipGetLastError());
-            src = dst; pw = j;
-        }
-    }
+    launch_mip_levels(pool, M.width, M.height, M.texel_type, L);
     uint32_t avg_texel = 0;
     {
         mip_level_table T; static_assert(sizeof(T) == sizeof(L), "one layout"); std::memcpy(&T, &L, sizeof(T));

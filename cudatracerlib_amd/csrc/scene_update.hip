@@ -10,6 +10,8 @@
 #include "scene_cache.h"
 #include "mitsuba_loader.h"   // unsupported_error
 #include "scene_volumes.h"
+#include "scene_image_set.h"
+#include "flat_device.h"
 #include <cstring>
 
 namespace ctl {
@@ -29,6 +31,27 @@ static bool volume_grids_same(const ctl_scene_desc& a, const ctl_scene_desc& b) 
         if (x.single_grid ? !cells_same(x.dim, x.data, y.dim, y.data) : !(cells_same(x.dim_a, x.data_a, y.dim_a, y.data_a) && cells_same(x.dim_s, x.data_s, y.dim_s, y.data_s))) return false;
     }
     return true;
+}
+
+// what ctl_scene_update applies, judged without the geometry arrays and the images (scene_image_set.h): the tail of scene_desc_diff, and the whole diff of
+// ctl_scene_update_image_set, whose plan has compared the rest through the hashes.  b may hold more materials than a (the table grows, it is never compacted)
+uint32_t scene_desc_diff_small(const ctl_scene_desc& a, const ctl_scene_desc& b) {
+    auto same = [](const void* x, const void* y, size_t bytes) { return bytes == 0 || (x && y && std::memcmp(x, y, bytes) == 0); };
+    uint32_t mask = 0;
+    for (uint32_t k = 0; k < a.n_nodes && k < b.n_nodes; k++) {
+        const ctl_node &x = a.nodes[k], &y = b.nodes[k];
+        if (x.lights[0] != y.lights[0] || x.lights[1] != y.lights[1] || x.n_lights != y.n_lights) mask |= CTL_DIFF_LIGHTS;
+    }
+    if (std::memcmp(&a.camera, &b.camera, sizeof(ctl_sensor)) != 0) mask |= CTL_DIFF_CAMERA;
+    if (a.n_materials != b.n_materials || !same(a.materials, b.materials, (size_t)a.n_materials * sizeof(ctl_material))) mask |= CTL_DIFF_MATERIALS;
+    if (a.n_lights_buf != b.n_lights_buf || !same(a.lights, b.lights, (size_t)a.n_lights_buf * sizeof(ctl_light)) || a.n_anim_bytes != b.n_anim_bytes || !same(a.anim, b.anim, a.n_anim_bytes) ||
+        a.num_lights != b.num_lights || a.env_map_index != b.env_map_index || std::memcmp(a.light_indices, b.light_indices, sizeof(a.light_indices)) != 0 ||
+        std::memcmp(a.light_cdf, b.light_cdf, sizeof(a.light_cdf)) != 0) mask |= CTL_DIFF_LIGHTS;
+    if (!same(a.node_transforms, b.node_transforms, (size_t)a.n_nodes * sizeof(ctl_float4x4)) || !same(a.node_inv_transforms, b.node_inv_transforms, (size_t)a.n_nodes * sizeof(ctl_float4x4)) ||
+        a.scene_start_node != b.scene_start_node || a.n_scene_bvh_nodes != b.n_scene_bvh_nodes || !same(a.scene_bvh_nodes, b.scene_bvh_nodes, (size_t)a.n_scene_bvh_nodes * sizeof(ctl_bvh_node)) ||
+        std::memcmp(a.box_min, b.box_min, 12) != 0 || std::memcmp(a.box_max, b.box_max, 12) != 0 || std::memcmp(&a.ray_trace_eps, &b.ray_trace_eps, 4) != 0) mask |= CTL_DIFF_TRANSFORMS;
+    if (a.n_volumes != b.n_volumes || !same(a.volumes, b.volumes, (size_t)a.n_volumes * sizeof(ctl_volume)) || !volume_grids_same(a, b)) mask |= CTL_DIFF_VOLUMES;
+    return mask;
 }
 
 uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const geometry_hashes* a_geometry, geometry_hashes* b_geometry, const std::vector<uint8_t>* ignore_values) {
@@ -61,15 +84,7 @@ uint32_t scene_desc_diff(const ctl_scene_desc& a, const ctl_scene_desc& b, const
         if (!hb.same_structure(ga)) mask |= CTL_DIFF_TOPOLOGY;
         else for (uint32_t m = 0; m < b.n_meshes; m++) if (!hb.same_values(ga, m)) { mask |= CTL_DIFF_GEOMETRY; break; }
     }
-    if (std::memcmp(&a.camera, &b.camera, sizeof(ctl_sensor)) != 0) mask |= CTL_DIFF_CAMERA;
-    if (!same(a.materials, b.materials, (size_t)a.n_materials * sizeof(ctl_material))) mask |= CTL_DIFF_MATERIALS;
-    if (a.n_lights_buf != b.n_lights_buf || !same(a.lights, b.lights, (size_t)a.n_lights_buf * sizeof(ctl_light)) || a.n_anim_bytes != b.n_anim_bytes || !same(a.anim, b.anim, a.n_anim_bytes) ||
-        a.num_lights != b.num_lights || a.env_map_index != b.env_map_index || std::memcmp(a.light_indices, b.light_indices, sizeof(a.light_indices)) != 0 ||
-        std::memcmp(a.light_cdf, b.light_cdf, sizeof(a.light_cdf)) != 0) mask |= CTL_DIFF_LIGHTS;
-    if (!same(a.node_transforms, b.node_transforms, (size_t)a.n_nodes * sizeof(ctl_float4x4)) || !same(a.node_inv_transforms, b.node_inv_transforms, (size_t)a.n_nodes * sizeof(ctl_float4x4)) ||
-        a.scene_start_node != b.scene_start_node || a.n_scene_bvh_nodes != b.n_scene_bvh_nodes || !same(a.scene_bvh_nodes, b.scene_bvh_nodes, (size_t)a.n_scene_bvh_nodes * sizeof(ctl_bvh_node)) ||
-        std::memcmp(a.box_min, b.box_min, 12) != 0 || std::memcmp(a.box_max, b.box_max, 12) != 0 || std::memcmp(&a.ray_trace_eps, &b.ray_trace_eps, 4) != 0) mask |= CTL_DIFF_TRANSFORMS;
-    if (a.n_volumes != b.n_volumes || !same(a.volumes, b.volumes, (size_t)a.n_volumes * sizeof(ctl_volume)) || !volume_grids_same(a, b)) mask |= CTL_DIFF_VOLUMES;
+    mask |= scene_desc_diff_small(a, b);
     return mask;
 }
 
@@ -213,12 +228,18 @@ uint32_t Scene::update(const ctl_scene_desc& d, ctl_scene_update_stats* stats) {
     const std::vector<uint8_t> device_owned = device_owned_meshes();
     // lights_stale_: an emissive skin was unbound (shape_set.hip) and HBM holds its last pose's shape sets — the light tables are uploaded whatever the descriptions say
     const uint32_t mask = scene_desc_diff(snap_->d, d, &snap_->geom, &geom, device_owned.empty() ? nullptr : &device_owned) | (lights_stale_ ? (uint32_t)CTL_DIFF_LIGHTS : 0u);
-    last_mask_ = mask;
-    if (mask == 0) { last_update_ = ctl_scene_update_stats{}; if (stats) *stats = last_update_; return 0; }   // nothing differs: no synchronisation, no tracer is stalled
+    return flat_rebuilder::apply_update(*this, d, mask, geom, stats);
+}
+
+// ctl_scene_update behind its diff: `mask` = what differs between the description the scene holds and d, geom = d's hashes.  ctl_scene_update_image_set (scene_image_set.hip)
+// comes here too, with the mask of scene_desc_diff_small — there d may hold more materials than the snapshot
+uint32_t flat_rebuilder::apply_update(Scene& A, const ctl_scene_desc& d, uint32_t mask, const geometry_hashes& geom, ctl_scene_update_stats* stats) {
+    A.last_mask_ = mask;
+    if (mask == 0) { A.last_update_ = ctl_scene_update_stats{}; if (stats) *stats = A.last_update_; return 0; }   // nothing differs: no synchronisation, no tracer is stalled
     if (mask & CTL_DIFF_TOPOLOGY) throw std::runtime_error("ctl_scene_update: the topology of the scene differs (geometry arrays, counts, node -> mesh / material assignment, images or transmittance tables): re-create the scene");
-    const bool refit = (mask & (CTL_DIFF_TRANSFORMS | CTL_DIFF_GEOMETRY)) && flattened();
-    if (refit && S.flat_format != kFlatQ4) throw unsupported_error("ctl_scene_update: the Q8 node format is not refitted; a transform or geometry change needs a scene in the default format (or a new scene)");
-    if (refit && refit_.level_start.size() < 2) throw unsupported_error("ctl_scene_update: the flattened tree carries no refit data");
+    const bool refit = (mask & (CTL_DIFF_TRANSFORMS | CTL_DIFF_GEOMETRY)) && A.flattened();
+    if (refit && A.S.flat_format != kFlatQ4) throw unsupported_error("ctl_scene_update: the Q8 node format is not refitted; a transform or geometry change needs a scene in the default format (or a new scene)");
+    if (refit && A.refit_.level_start.size() < 2) throw unsupported_error("ctl_scene_update: the flattened tree carries no refit data");
     // Everything that can refuse the new description runs before anything is written, and before a tracer is stalled.  A transform change brings a new scene BVH: its
     // links must stay inside the array (creation is more lenient there, scene_checks.h) and its depth fit next to the mesh BVHs of creation (the geometry hash matched)
     check_scene_desc(d, mask, "ctl_scene_update");
@@ -226,50 +247,51 @@ uint32_t Scene::update(const ctl_scene_desc& d, ctl_scene_update_stats* stats) {
     const mesh_ranges ranges(d);
     if (mask & CTL_DIFF_GEOMETRY) {
         mesh_changed.assign(d.n_meshes, 0);
-        for (uint32_t m = 0; m < d.n_meshes; m++) mesh_changed[m] = geom.same_values(snap_->geom, m) ? 0 : 1;
+        for (uint32_t m = 0; m < d.n_meshes; m++) mesh_changed[m] = geom.same_values(A.snap_->geom, m) ? 0 : 1;
         // the arrays were sized by creation and the counts agree; a range the re-upload writes must still lie inside them
-        for (uint32_t m = 0; m < d.n_meshes; m++) if (mesh_changed[m] && ((size_t)ranges.tri1[m] * 2 > tri_data_.n || (size_t)ranges.woop1[m] * 4 > leaf_tris_.n || (size_t)ranges.node1[m] * 4 > bot_nodes_.n))
+        for (uint32_t m = 0; m < d.n_meshes; m++) if (mesh_changed[m] && ((size_t)ranges.tri1[m] * 2 > A.tri_data_.n || (size_t)ranges.woop1[m] * 4 > A.leaf_tris_.n || (size_t)ranges.node1[m] * 4 > A.bot_nodes_.n))
             throw std::runtime_error("ctl_scene_update: mesh " + std::to_string(m) + " reaches outside the scene's geometry arrays");
-        if (flattened() && !flat_missing_tris_.empty()) {
+        if (A.flattened() && !A.flat_missing_tris_.empty()) {
             // a triangle that gather_references dropped at creation (singular Woop matrix) and that is regular now: the tree has no leaf entry to put it in
             std::vector<uint32_t> rows; triangle_woop_rows(d, rows);
-            const int m = mesh_gaining_a_triangle(d, flat_missing_tris_, rows, mesh_changed);
+            const int m = mesh_gaining_a_triangle(d, A.flat_missing_tris_, rows, mesh_changed);
             if (m >= 0) {
-                last_mask_ |= CTL_DIFF_TOPOLOGY;
+                A.last_mask_ |= CTL_DIFF_TOPOLOGY;
                 throw std::runtime_error("ctl_scene_update: mesh " + std::to_string(m) + " has a triangle that was degenerate when the scene was flattened and no longer is: the flattened tree has no leaf entry for it; re-create the scene");
             }
         }
     }
     ctl_scene_update_stats st{}; st.mask = mask;
     CTL_HIP(hipDeviceSynchronize());   // no trace reads the arrays any more
-    const uint32_t had_alpha_maps = S.alpha_maps;
-    if (mask & (CTL_DIFF_MATERIALS | CTL_DIFF_LIGHTS)) set_shading_state(derive_shading_state(d));
+    const uint32_t had_alpha_maps = A.S.alpha_maps;
+    if (mask & (CTL_DIFF_MATERIALS | CTL_DIFF_LIGHTS)) A.set_shading_state(derive_shading_state(d));
     bool restamp = false;
     if (mask & CTL_DIFF_MATERIALS) {
-        upload_materials(d);
+        A.upload_materials(d);
         // the entries of a flattened scene carry their material's BSDF model and "has an alpha map": re-stamped on the device where either changed
-        if (flattened() && d.n_materials) {
-            for (uint32_t i = 0; i < d.n_materials; i++) if (d.materials[i].bsdf_type != snap_->materials[i].bsdf_type || d.materials[i].alpha_state != snap_->materials[i].alpha_state) restamp = true;
-            if (had_alpha_maps != S.alpha_maps) restamp = true;
+        if (A.flattened() && d.n_materials) {
+            const std::vector<ctl_material>& held = A.snap_->materials;   // (a material behind the held table is no entry's yet)
+            for (uint32_t i = 0; i < d.n_materials && i < held.size(); i++) if (d.materials[i].bsdf_type != held[i].bsdf_type || d.materials[i].alpha_state != held[i].alpha_state) restamp = true;
+            if (had_alpha_maps != A.S.alpha_maps) restamp = true;
         }
     }
-    if (mask & CTL_DIFF_LIGHTS) { upload_lights(d); lights_stale_ = false; if (!(mask & CTL_DIFF_TRANSFORMS)) upload_instances(d); }   // node_info carries the nodes' light slots
+    if (mask & CTL_DIFF_LIGHTS) { A.upload_lights(d); A.lights_stale_ = false; if (!(mask & CTL_DIFF_TRANSFORMS)) A.upload_instances(d); }   // node_info carries the nodes' light slots
     if (mask & CTL_DIFF_TRANSFORMS) {
-        upload_top_level(d); upload_instances(d);
-        if (flattened()) S.inst_w_one = inverse_transforms_have_w_one(d);
+        A.upload_top_level(d); A.upload_instances(d);
+        if (A.flattened()) A.S.inst_w_one = inverse_transforms_have_w_one(d);
     }
     if (mask & CTL_DIFF_GEOMETRY) {
-        for (uint32_t m = 0; m < d.n_meshes; m++) if (mesh_changed[m]) upload_mesh_geometry(d, ranges, m);
-        if (flattened()) restamp = true;   // the entries' model / alpha bits come from tri_data: re-stamped from the new one
+        for (uint32_t m = 0; m < d.n_meshes; m++) if (mesh_changed[m]) A.upload_mesh_geometry(d, ranges, m);
+        if (A.flattened()) restamp = true;   // the entries' model / alpha bits come from tri_data: re-stamped from the new one
     }
     // the shape sets of the lights on emissive skins are the device's: d's own were made from rest-pose rows (and have just been uploaded, or its transforms have moved the node)
-    if (mask & (CTL_DIFF_LIGHTS | CTL_DIFF_TRANSFORMS | CTL_DIFF_GEOMETRY)) run_shape_sets(d);
+    if (mask & (CTL_DIFF_LIGHTS | CTL_DIFF_TRANSFORMS | CTL_DIFF_GEOMETRY)) A.run_shape_sets(d);
     CTL_HIP(hipDeviceSynchronize());
-    bind(d);
-    if (mask & CTL_DIFF_CAMERA) set_camera(d);
-    if (refit || restamp) { refit_flat(d, refit, restamp, (mask & CTL_DIFF_GEOMETRY) ? &mesh_changed : nullptr, &st); st.restamped = restamp ? 1u : 0u; }
-    last_update_ = st;
-    snapshot(d, &geom);
+    A.bind(d);
+    if (mask & CTL_DIFF_CAMERA) A.set_camera(d);
+    if (refit || restamp) { A.refit_flat(d, refit, restamp, (mask & CTL_DIFF_GEOMETRY) ? &mesh_changed : nullptr, &st); st.restamped = restamp ? 1u : 0u; }
+    A.last_update_ = st;
+    A.snapshot(d, &geom);
     if (stats) *stats = st;
     return mask;
 }

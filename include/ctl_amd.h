@@ -399,8 +399,29 @@ int ctl_builder_update_mesh(ctl_builder* b, uint32_t mesh_index, const float* po
  * in the anim blob and its `normalization` in its record (rowWeights depends on the height only and stays).  The sampling weights of the materials that read the image's
  * average (plastic, roughplastic, phong, ward, coating, roughcoating) are made by the next ctl_builder_finalize, as always.  This is the host yardstick of
  * ctl_scene_update_image (below), and what a host that keeps its builder calls beside it, so that the next ctl_scene_update finds no difference.
- * CTL_ERR_INVALID (a null builder or texels, a bad index, another width or height) leaves the builder untouched. */
+ * CTL_ERR_INVALID (a null builder or texels, a bad index, another width or height: ctl_builder_replace_image) leaves the builder untouched. */
 int ctl_builder_update_image(ctl_builder* b, uint32_t image_index, const uint32_t* texels, uint32_t width, uint32_t height);
+/* The counterpart of ctl_builder_add_image for an image nothing reads any more: the image and its texels leave the builder, every later image moves down by one, and every
+ * ctl_texture::image above it is lowered by one — the materials' tex[0..3], map_tex and alpha_tex (textures of type CTL_TEX_IMAGE), the lights' rad_texture and the
+ * environment light's env_image.  After ctl_builder_finalize the images, materials, lights and anim blob equal, byte for byte, those of a builder that never added the image.
+ * CTL_ERR_INVALID, the builder untouched, for an index that is no image's and for an image that any row of the material table or any light still references;
+ * ctl_last_error() names the first referrer.  The material table is never compacted, so rows orphaned by ctl_builder_remove_node / ctl_builder_remove_mesh count: the host
+ * repoints them first (ctl_builder_set_material).  A mesh's standard materials, which only a later ctl_builder_add_node copies, follow the shift; a texture there that named
+ * the removed image names none afterwards (0xffffffff: black).  The next ctl_builder_finalize gives the description ctl_scene_update_image_set takes. */
+int ctl_builder_remove_image(ctl_builder* b, uint32_t image_index);
+/* New level-0 texels of ANOTHER size for image `image_index`; texel type, wrap and filter mode stay (for ctl_scene_update_image_set the image is a fresh one).  Called with the
+ * image's current size it is ctl_builder_update_image.  CTL_ERR_INVALID, the builder untouched, for a bad index, null texels, an empty size, and for the environment map's
+ * image: its tables were laid out in the anim blob by ctl_builder_set_environment_map, for its size. */
+int ctl_builder_replace_image(ctl_builder* b, uint32_t image_index, const uint32_t* texels, uint32_t width, uint32_t height);
+/* the number of images the builder holds now, whoever added them (a loader included), without a ctl_builder_finalize */
+int ctl_builder_image_count(const ctl_builder* b, uint32_t* count_out);
+/* DynamicScene::getMaterials + Invalidate (Engine/DynamicScene.h) for one row of the material table: absolute_index as the kernels address it (ctl_node::material_offset +
+ * the triangle's local index, or what ctl_builder_add_material returned).  ctl_builder_set_material stores the record as given — node_light_index included: a host edits what
+ * ctl_builder_get_material handed it — after the checks a new record gets: a known BSDF model, map kind and alpha state, known texture types, image indices the builder
+ * holds, and BSDFFirst in both directions (a nested index in u[2] / u[3] names another row that is a simple BSDF; a row some coating or blend nests stays simple).  The next
+ * ctl_builder_finalize makes the derived sampling weights, as always; ctl_scene_update applies the result (CTL_DIFF_MATERIALS).  CTL_ERR_INVALID leaves the builder untouched. */
+int ctl_builder_get_material(const ctl_builder* b, uint32_t absolute_index, ctl_material* out);
+int ctl_builder_set_material(ctl_builder* b, uint32_t absolute_index, const ctl_material* material);
 /* The pyramid a scene keeps of an image (MIPMap::CompileToBinary, Engine/MIPMap.cpp:41-95), host only: level 0 followed by levels 1 .. into texels_out[capacity]
  * (may be NULL: the level table alone), *levels_out = 1 + floor(log2(min(width, height))), level_offsets_out[l - 1] = the texel offset of level l >= 1; level l is
  * (width >> l) x (height >> l).  CTL_ERR_INVALID: a null or empty image, an unknown texel type, a capacity below the pyramid's texel count. */
@@ -551,13 +572,53 @@ int ctl_skin_mesh_host(const ctl_scene_desc* desc, uint32_t mesh_index, const fl
  * Synchronous, like ctl_scene_update: call it between passes and start the next pass with new_trace.  ctl_scene_desc_diff and ctl_scene_update still call another texel in a
  * description CTL_DIFF_TOPOLOGY.  stats_out (may be NULL): wall-clock times of the steps, each ended by a device synchronisation (env_ms includes the read-back of the tables).
  *   CTL_ERR_NO_DEVICE    no device (checked first)
- *   CTL_ERR_INVALID      a null scene or texels, a bad image index, another width or height, an unknown flag bit: before the device is touched, the scene stays as it was
+ *   CTL_ERR_INVALID      a null scene or texels, a bad image index, another width or height (ctl_scene_update_image_set takes a replaced image), an unknown flag bit: before the
+ *                        device is touched, the scene stays as it was
  * ctl_scene_read_image copies back level 0 and the pyramid of an image as the pool holds them, with the arguments and the layout of ctl_mip_pyramid_host. */
 enum { CTL_IMAGE_TEXELS_DEVICE = 1 };   /* `texels` is a device pointer */
 typedef struct { uint32_t levels, texels_written, materials_patched, env_tables;
                  float upload_ms, pyramid_ms, env_ms, hash_ms, total_ms; } ctl_scene_image_stats;
 int ctl_scene_update_image(ctl_scene* scene, uint32_t image_index, const uint32_t* texels, uint32_t width, uint32_t height, uint32_t flags, ctl_scene_image_stats* stats_out);
 int ctl_scene_read_image(ctl_scene* scene, uint32_t image_index, uint32_t* texels_out, size_t capacity, uint32_t* levels_out, uint32_t level_offsets_out[15]);
+/* ---- ANOTHER SET OF IMAGES on a live scene (csrc/scene_image_set.h, scene_image_set.hip, scene_image_set.cpp; INTEGRATION.md "Editing the image set").  ctl_scene_update and
+ * the node- and mesh-set calls refuse a description with another image set, and keep doing so; ctl_scene_update_image keeps an image's size.  ctl_scene_update_image_set takes
+ * one: new_desc is the scene's description after ctl_builder_add_image, ctl_builder_remove_image and ctl_builder_replace_image, with whatever ctl_builder_set_material and
+ * the light calls changed beside them.
+ *   old_image_of_new[j]  the index image j had in the description the scene holds, or UINT32_MAX for a FRESH image (added, or replaced by another size);
+ *                        n_new_images == new_desc->n_images; the kept indices strictly increasing (images are not reordered), fresh images anywhere
+ * Accepted when, besides the map's rules: a kept image has the held width, height, texel type, wrap and filter mode and the held digest (texels written through
+ * ctl_scene_update_image are fine when the host mirrored them with ctl_builder_update_image; after an update from a device pointer it reads them back with
+ * ctl_scene_read_image first); every image has texels; everything else in new_desc is what ctl_scene_update applies — camera, the contents of the materials (n_materials may
+ * grow, not shrink), lights and anim blob (a scene may gain its first environment map this way), transforms, volumes.  Another mesh set, node set, geometry structure or
+ * values, or other transmittance tables are refused: those edits go through their own calls, before or after, each on its own finalized description.  ONE hash pass runs over
+ * new_desc (hash_ms).  Everything is checked before the device is touched and before a tracer is stalled.
+ * On the device the texel pool is laid out anew, in image order, exactly as ctl_scene_create lays it out: afterwards ctl_scene_read_image of every image equals a fresh
+ * scene's, word for word.  The pyramids of the kept images MOVE, whole, by one kernel launch (k_move_texels: one lane per kept texel, the source found through a table of
+ * runs — maximal groups of kept images consecutive in both pools), so their levels are not recomputed and what stands in HBM is what survives; a fresh image's level 0 is
+ * uploaded into its slot and its pyramid built there, level by level, all fresh images before one synchronisation.  Nothing moves in place: DURING THE CALL HBM HOLDS THE OLD
+ * POOL AND THE NEW ONE, and the new one (with the image and level tables at the new counts) becomes the scene's only at the commit.  Then the ordinary stages of
+ * ctl_scene_update run over the rest of new_desc (a flattened tree is re-stamped where a material gained or lost an alpha map, refitted where a node moved; no tree is
+ * rebuilt).  Two-level and flattened scenes, Q4 and Q8, every plugin; tracers follow the new arrays: start the next pass with new_trace.  An identity map over the same
+ * count makes the call ctl_scene_update.  Synchronous.  Only the rough-transmittance tables still need a new scene.
+ *   CTL_ERR_NO_DEVICE    no device (checked first)
+ *   CTL_ERR_INVALID      every rule above, ctl_last_error() naming it; the scene stays as it was.  A failed allocation leaves the scene as it was too
+ *   CTL_ERR_UNSUPPORTED  a transform change in new_desc on a CTL_FLAT_Q8 scene or a tree without refit data, as ctl_scene_update answers
+ * stats_out (may be NULL): the counts of the map, the runs, the texels moved (whole pyramids) and uploaded (level 0 of fresh images), what the pool shrank by; HIP-event
+ * times of the move and of the fresh images' uploads + pyramids; host time of the hash pass and of the whole call; the ctl_scene_update_stats of the stages that follow. */
+typedef struct {
+    uint32_t images_kept, images_fresh, images_removed, runs;
+    uint64_t texels_moved, texels_uploaded, bytes_freed;
+    float move_ms, pyramid_ms, hash_ms, total_ms;
+    ctl_scene_update_stats update;
+} ctl_scene_image_set_stats;
+int ctl_scene_update_image_set(ctl_scene* scene, const ctl_scene_desc* new_desc, const uint32_t* old_image_of_new, uint32_t n_new_images, ctl_scene_image_set_stats* stats_out);
+/* test hooks (no GPU).  ctl_image_set_plan_host: the whole acceptance check of ctl_scene_update_image_set for a scene made from old_desc, and its plan — offsets_out
+ * [n_new_images]: the texel offset of every image's level 0 in the new pool; *total_out: the pool's texels; run_table_out[4 * (n_new_images + 1)] (may be NULL): per run
+ * { first destination texel, first source texel, length, kept texels in front of it }, then the sentinel { *total_out, texels of the old pool, 0, texels moved };
+ * *n_runs_out: the runs without the sentinel.  ctl_move_texels_host: k_move_texels' arithmetic on the host over such a table; words of new_pool no run covers are untouched. */
+int ctl_image_set_plan_host(const ctl_scene_desc* old_desc, const ctl_scene_desc* new_desc, const uint32_t* old_image_of_new, uint32_t n_new_images,
+                            uint64_t* offsets_out, uint64_t* total_out, uint64_t* run_table_out, uint32_t* n_runs_out);
+int ctl_move_texels_host(const uint32_t* old_pool, uint64_t n_old_texels, const uint64_t* run_table, uint32_t n_runs, uint32_t* new_pool, uint64_t n_new_texels);
 /* On-disk cache of compiled geometry — the role of the reference's .xmsh files (Engine/Mesh.cpp:46-98,199-290; DynamicScene::CreateNode
  * compiles a mesh only when its .xmsh is missing).  With a directory set, ctl_builder_add_mesh stores / reloads a compiled mesh
  * (TriangleData, BVH nodes, Woop rows) and CTL_SCENE_FLATTEN stores / reloads the flattened BVH, both keyed by a hash of their
@@ -686,7 +747,7 @@ int ctl_flat_bvh_update_nodes_ex(ctl_flat_bvh* h, const ctl_scene_desc* new_desc
  * the grown buffers, and the buffers become the scene's only after the new tree stands.  Any growth rebuilds the flattened tree, an identity node map included.
  * During the call HBM holds a second copy of the three geometry arrays.  Tracers follow the new arrays; start the next pass with new_trace.  Bound meshes stay bound.
  * Refusals leave the scene as it was: CTL_ERR_NO_DEVICE first; CTL_ERR_INVALID for wrong arguments and every rule above; CTL_ERR_UNSUPPORTED exactly where
- * ctl_scene_update_nodes answers so.  A failed allocation leaves the scene as it was.  New images and new tables still need a new scene.
+ * ctl_scene_update_nodes answers so.  A failed allocation leaves the scene as it was.  New images go through ctl_scene_update_image_set, on a description of its own; new tables still need a new scene.
  * ctl_flat_bvh_update_meshes is the host yardstick (no GPU): the same acceptance, then ctl_flat_bvh_update_nodes' stages, which read the Woop rows from new_desc. */
 typedef struct {
     uint32_t meshes_added, triangles_added, rows_added, bvh_nodes_added;   /* rows: of the two-level leaf stream (n_woop) */
@@ -725,7 +786,7 @@ int ctl_append_leaf_rows_host(const ctl_scene_desc* new_desc, uint32_t old_n_mes
  * tails and the node-set stages follow as in ctl_scene_update_meshes; the leaf entries of kept nodes get their triangle words lowered while they move.  Any removal
  * rebuilds the flattened tree, an identity node map included.  Bound meshes stay bound under their new indices; tracers follow the new arrays: start the next pass with
  * new_trace.  Refusals leave the scene as it was: CTL_ERR_NO_DEVICE first; CTL_ERR_INVALID for wrong arguments and every rule above; CTL_ERR_UNSUPPORTED exactly where
- * ctl_scene_update_nodes answers so.  The material table is not compacted; new images and new tables still need a new scene.
+ * ctl_scene_update_nodes answers so.  The material table is not compacted; another image set goes through ctl_scene_update_image_set (a removed mesh's textures: INTEGRATION.md "Editing the image set"); new tables still need a new scene.
  * ctl_flat_bvh_update_mesh_set is the host yardstick (no GPU): the same acceptance, then ctl_flat_bvh_update_nodes' stages with the triangle words lowered. */
 typedef struct {
     uint32_t meshes_removed, triangles_removed, rows_removed, bvh_nodes_removed;   /* rows: of the two-level leaf stream (n_woop) */
